@@ -13,10 +13,18 @@ all-gathered over RCCL after the timed region, as they would be before fusion.
 127.0.0.1) unless it is already running under a launcher (WORLD_SIZE set); it refuses to run when fewer than N devices are
 visible instead of quietly measuring fewer.
 
-The same line carries a `workloads` block: every other BASELINE.json config timed in this process after the headline (SUB_WORKLOADS:
-configs[1] at 6 and 3 iterations, configs[2] with adaptive patches and K9/K10's roofline, the configs[4] shape, 1080p frames, a
-pass of the sharded scheduler with its depth exchange inside the timed region) and whole `apd_run` passes (PASS_WORKLOADS: K1..K15
-with K14 / K15 against their own counter profile).
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) measures the headline alone: set-up, W warm-up iterations, the K
+timed ones, the roofline of the dominant kernel from those launches and the committed counter profiles, the outputs with
+--dump-outputs, the line.  With --full the same process goes on as the default run did before --full existed: the post-loop kernels
+(K11..K13), the depth check against the analytic scene and the all-gather of the final maps, then a `workloads` block -- every other
+BASELINE.json config timed after the headline (SUB_WORKLOADS: configs[1] at 6 and 3 iterations, configs[2] with adaptive patches and
+K9/K10's roofline, the configs[4] shape, 1080p frames, a pass of the sharded scheduler with its depth exchange inside the timed
+region) and whole `apd_run` passes (PASS_WORKLOADS: K1..K15 with K14 / K15 against their own counter profile) -- and the CPU
+baselines.
+
+--dump-outputs DIR writes what a caller of the timed sweep receives after its last step (the maps of apd_download, APD.cu:2490-2492)
+as DIR/<name>.npy: a fixed, seeded sample of at most DUMP_MAX_PIXELS pixels of rank 0's reference view, the same pixels in every run
+of the same workload, so that two builds can be compared array for array.
 
 Prints ONE JSON line on rank 0.
 """
@@ -107,14 +115,21 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD,
                     help="one of %s, or custom_<W>x<H>_<N>src[_apd]" % ", ".join(sorted(WORKLOADS)))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", default="1024x768", help="WxH of the CPU-baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: post-loop kernels + depth check + all-gather of the final maps, the `workloads` block "
+                         "and the CPU baselines (off by default: a plain run measures the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the sweep's caller receives (planes, weak_info, selected_views) as "
+                         "DIR/<name>.npy, float32 / float64, a seeded sample of at most %d pixels" % DUMP_MAX_PIXELS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--cpu-sample", default="1024x768", help="WxH of the CPU-baseline sample (--full)")
     ap.add_argument("--seed", type=int, default=12345)
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="apd_set_option on the handle (A/B runs), e.g. --opt k67_windows=0; names: fast_rcp early_out source_quads "
                          "tiled_copy k67_windows k1415_windows.  Reported in config.options")
-    ap.add_argument("--no-workloads", action="store_true", help="headline only: skip the `workloads` block (the other BASELINE configs)")
-    ap.add_argument("--only-workloads", action="append", default=[], metavar="KEY", help="restrict the `workloads` block to these keys")
+    ap.add_argument("--no-workloads", action="store_true", help="with --full: skip the `workloads` block (the other BASELINE configs)")
+    ap.add_argument("--only-workloads", action="append", default=[], metavar="KEY",
+                    help="with --full: restrict the `workloads` block to these keys")
     ap.add_argument("--full-line", action="store_true",
                     help="tooling only (tools/ab.sh, tools/profile_round.sh): print the full block as the stdout line instead of the compact one")
     ap.add_argument("--selftest-cpu", action="store_true",
@@ -260,10 +275,12 @@ class SweepWorkload:
         self.pass_inputs, self.geom = None, None
         self.ctx.torch.cuda.empty_cache()
 
-    def measure(self, steps, warmup, pass_exchange=False):
+    def measure(self, steps, warmup, pass_exchange=False, post=True, dump_dir=None):
         """Times `steps` iterations of the sweep on every owned view (barrier + synchronize on both sides, MAX over ranks).
         pass_exchange: the timed region also holds what ends a pass of the sharded scheduler -- K11..K13, the depth export and
-        the all-gather of every view's depth map (the exchange the reference does through depths.dmb, APD.cpp:497-500)."""
+        the all-gather of every view's depth map (the exchange the reference does through depths.dmb, APD.cpp:497-500).
+        post: after the timed region, K11..K13, the depth check against the analytic scene and the all-gather of the final maps.
+        dump_dir: the first owned view's maps after the last timed step go there (dump_outputs)."""
         ctx, pkg, torch = self.ctx, self.ctx.pkg, self.ctx.torch
         W, H, N = self.W, self.H, self.N
         hs = self.handles
@@ -320,41 +337,45 @@ class SweepWorkload:
         prof = hs[0].profile()
         for h in hs:
             h.profile_enable(False)
+        if dump_dir is not None:
+            dump_outputs(dump_dir, hs[0], ctx.np)
 
         # after the timed region: post-loop kernels + all-gather of depth/normal maps (before fusion)
-        allgather_ms = None
-        t_post0 = time.perf_counter()
-        if not pass_exchange:
-            for kid in (pkg.K11, pkg.K12, pkg.K13):
-                hs[0].run_kernel(kid)
-            d0 = torch.empty((H, W), device=ctx.dev, dtype=torch.float32)
-            n0 = torch.empty((H, W, 3), device=ctx.dev, dtype=torch.float32)
-            hs[0].export_depth_normal(d0, n0)
-            torch.cuda.synchronize()
-            if ctx.distributed and len(hs) == 1:
-                from apd_mvs_amd import sharding
-                ta = time.perf_counter()
-                gathered_d = sharding.allgather_maps({ctx.rank: d0.view(H, W, 1)}, ctx.world)   # view index == rank here
+        allgather_ms = within = post_ms = None
+        if post or pass_exchange:
+            t_post0 = time.perf_counter()
+            if not pass_exchange:
+                for kid in (pkg.K11, pkg.K12, pkg.K13):
+                    hs[0].run_kernel(kid)
+                d0 = torch.empty((H, W), device=ctx.dev, dtype=torch.float32)
+                n0 = torch.empty((H, W, 3), device=ctx.dev, dtype=torch.float32)
+                hs[0].export_depth_normal(d0, n0)
                 torch.cuda.synchronize()
-                pass_allgather_ms = (time.perf_counter() - ta) * 1e3   # what every pass ends with: the sources' depth maps for the next one
-                gathered_n = sharding.allgather_maps({ctx.rank: n0}, ctx.world)
-                torch.cuda.synchronize()
-                allgather_ms = (time.perf_counter() - ta) * 1e3
-                assert gathered_d.shape[0] == ctx.world and torch.equal(gathered_d[ctx.rank, :, :, 0], d0)
-                assert gathered_n.shape[0] == ctx.world
-                del gathered_d, gathered_n
-            del n0
-        else:
-            d0 = depth[0]
-            views = len(hs) * ctx.world
-            assert gathered.shape[0] == views
-            for slot, d in enumerate(depth):   # every rank holds every view's map, its own ones bit for bit
-                assert torch.equal(gathered[ctx.rank + slot * ctx.world, :, :, 0], d)
-        gt = self.gt[0]
-        err = (d0 - gt).abs() / gt
-        within = float((err[8:-8, 8:-8] < 0.01).float().mean().item())
-        post_ms = (time.perf_counter() - t_post0) * 1e3
-        del d0, depth, gathered
+                if ctx.distributed and len(hs) == 1:
+                    from apd_mvs_amd import sharding
+                    ta = time.perf_counter()
+                    gathered_d = sharding.allgather_maps({ctx.rank: d0.view(H, W, 1)}, ctx.world)   # view index == rank here
+                    torch.cuda.synchronize()
+                    pass_allgather_ms = (time.perf_counter() - ta) * 1e3   # what every pass ends with: the sources' depth maps for the next one
+                    gathered_n = sharding.allgather_maps({ctx.rank: n0}, ctx.world)
+                    torch.cuda.synchronize()
+                    allgather_ms = (time.perf_counter() - ta) * 1e3
+                    assert gathered_d.shape[0] == ctx.world and torch.equal(gathered_d[ctx.rank, :, :, 0], d0)
+                    assert gathered_n.shape[0] == ctx.world
+                    del gathered_d, gathered_n
+                del n0
+            else:
+                d0 = depth[0]
+                views = len(hs) * ctx.world
+                assert gathered.shape[0] == views
+                for slot, d in enumerate(depth):   # every rank holds every view's map, its own ones bit for bit
+                    assert torch.equal(gathered[ctx.rank + slot * ctx.world, :, :, 0], d)
+            gt = self.gt[0]
+            err = (d0 - gt).abs() / gt
+            within = float((err[8:-8, 8:-8] < 0.01).float().mean().item())
+            post_ms = (time.perf_counter() - t_post0) * 1e3
+            del d0
+        del depth, gathered
 
         mpix = W * H / 1e6
         views_total = ctx.world * len(hs)
@@ -384,11 +405,11 @@ class SweepWorkload:
                            "note": "timed region = iterations 0..K-1 of a freshly initialised pass; iteration 0 starts from random planes"},
             "rank_ms_per_step": [round(v, 3) for v in rank_ms_per_step],
             "kernel_ms_timed_region": kernel_ms,
-            "post_loop_ms": round(post_ms, 1),
+            "post_loop_ms": None if post_ms is None else round(post_ms, 1),
             "allgather_ms": None if allgather_ms is None else round(allgather_ms, 3),
             "pass_allgather_ms": None if pass_allgather_ms is None else round(pass_allgather_ms, 3),
             "pass_allgather_inside_timed_region": bool(pass_exchange),
-            "quality_within_1pct_depth": round(within, 4),
+            "quality_within_1pct_depth": None if within is None else round(within, 4),
             "setup_s": round(self.setup_s, 2),
         }
 
@@ -791,6 +812,12 @@ def main():
     if args.gpus < 1:
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        sys.stderr.write("bench.py: --steps must be >= 1 and --warmup >= 0\n")
+        return 2
+    if args.only_workloads and not args.full:
+        sys.stderr.write("bench.py: --only-workloads restricts the `workloads` block of --full; a plain run has none\n")
+        return 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)
 
@@ -823,12 +850,12 @@ def main():
     ctx = Ctx(pkg, synth, np, torch, dev, rank, world, distributed, dist)
 
     # ---- headline: BASELINE.json configs[1] (or --workload) at the command line's --steps / --warmup ----
-    # the `workloads` block belongs to the default line (the driver's command); tuning runs (--workload X, --opt) time one thing
-    subs = [] if (args.no_workloads or args.opt or (args.workload != DEFAULT_WORKLOAD and not args.only_workloads)) else \
+    # the `workloads` block belongs to the default line with --full; tuning runs (--workload X, --opt) time one thing
+    subs = [] if (not args.full or args.no_workloads or args.opt or (args.workload != DEFAULT_WORKLOAD and not args.only_workloads)) else \
         [s for s in SUB_WORKLOADS if not args.only_workloads or s[0] in args.only_workloads]
     same = [s for s in subs if s[1] == args.workload and s[5] == 1]
     wl = SweepWorkload(ctx, args.workload, max([max(args.warmup, args.steps)] + [max(s[2], s[3]) for s in same]), args.opt, args.seed)
-    head = wl.measure(args.steps, args.warmup)
+    head = wl.measure(args.steps, args.warmup, post=args.full, dump_dir=args.dump_outputs if rank == 0 else None)
     head_apd = wl.apd_mode
     N_head = wl.N
 
@@ -885,7 +912,7 @@ def main():
     subs_s = time.perf_counter() - t_subs
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # reported at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # reported at N=1 only
         cpu_baseline = run_cpu_baseline(args, N_head, np)
         if workloads.get(CONFIGS0_KEY, {}).get("value") is not None:   # configs[0] names the CPU path: its own shape on the CPU, same line
             c0 = run_cpu_configs0(args)
@@ -906,6 +933,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": args.full,
             "config": head["config"],
             "roofline": head["roofline"],
             "strong_path": head["strong_path"] if head_apd else None,
@@ -1046,6 +1074,26 @@ def apply_options(h, opts):
     for o in opts:
         name, _, value = o.partition("=")
         h.set_option(name, int(value))
+
+
+DUMP_MAX_PIXELS = 1 << 20   # 16 + 4 + 8 bytes per pixel: 28 MiB of .npy at most
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir, h, np):
+    """--dump-outputs: the three maps apd_download hands a caller (APD.cu:2490-2492) -- planes (normal xyz, depth) as float32 [P, 4],
+    weak_info as float32 [P], selected_views as float64 [P] (32-bit view masks, exact) -- over P pixels in row-major order: the whole
+    frame up to DUMP_MAX_PIXELS, above that a sample drawn with DUMP_SAMPLE_SEED (the same pixels for every run of the same shape)."""
+    planes, weak, views = h.download()
+    n = planes.shape[0] * planes.shape[1]
+    if n > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=DUMP_MAX_PIXELS, replace=False))
+    else:
+        idx = np.arange(n)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "planes.npy"), planes.reshape(n, 4)[idx])
+    np.save(os.path.join(out_dir, "weak_info.npy"), weak.reshape(n)[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "selected_views.npy"), views.reshape(n)[idx].astype(np.float64))
 
 
 def selftest_cpu(args, world, rank):

@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 ARGS="${@:---steps 6 --warmup 1 --no-cpu-baseline}"
-echo "== bench (default flags)"; python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json
+echo "== bench (default flags)"; python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json
 echo "== kernel trace"; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python bench.py --no-workloads $ARGS > $OUT/bench_trace.json 2> $OUT/trace.err
 echo "== pmc FETCH_SIZE"; timeout 300 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pmc -- python bench.py --no-workloads $ARGS > $OUT/bench_pmc_fetch.json 2> $OUT/pmc_fetch.err
 echo "== pmc WRITE_SIZE"; timeout 300 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $OUT/pmc_write -o pmc -- python bench.py --no-workloads $ARGS > $OUT/bench_pmc_write.json 2> $OUT/pmc_write.err

@@ -81,7 +81,7 @@ def main():
         _, workload, n_timed, _, pass_kind = [e for e in bench.PASS_WORKLOADS if e[0] == pass_key][0]
         sweep_key = [e[0] for e in bench.SUB_WORKLOADS if e[1] == workload and e[5] == 1 and e[2] == bench.PASS_ITERATIONS][0]
         flags = ["--steps", "1", "--warmup", "0"]   # the headline before the sub-lines: one iteration of the default workload
-        tail = ["--no-cpu-baseline", "--only-workloads", sweep_key, "--only-workloads", pass_key]
+        tail = ["--full", "--no-cpu-baseline", "--only-workloads", sweep_key, "--only-workloads", pass_key]
         kernels_of_interest = PASS_KERNELS
         tag = "%s_p%d%s" % (workload, n_timed, "" if pass_kind == "photometric" else "_" + pass_kind)
     os.makedirs(out_dir, exist_ok=True)

@@ -24,11 +24,11 @@ done
 mkdir -p profiles/$ROUND && cp "$OUT"/pmc_bench_*.json "$OUT"/pmc_pass_*.json profiles/$ROUND/   # where they will be committed; bench.py looks under profiles/*/
 # the two lines of the round: the default command and the driver's; each carries the `workloads` block (every BASELINE config)
 # stdout of each command = the compact line the driver parses (line_*.json, <= 2000 bytes); the full block is bench_workloads.json
-python bench.py > "$OUT/line_default.json" 2> "$OUT/bench_default.err"; cp bench_workloads.json "$OUT/bench_default.json"
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/line_driver_s20_w5.json" 2>/dev/null; cp bench_workloads.json "$OUT/bench_driver_s20_w5.json"
+python bench.py --full > "$OUT/line_default.json" 2> "$OUT/bench_default.err"; cp bench_workloads.json "$OUT/bench_default.json"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/line_driver_s20_w5.json" 2>/dev/null; cp bench_workloads.json "$OUT/bench_driver_s20_w5.json"
 wc -c "$OUT"/line_*.json
 # the rocprofv3 --kernel-trace --stats summary of the driver's command, workloads block included
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/apd_trace_driver -o trace -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_driver_traced.json" 2> "$OUT/trace_driver.err"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/apd_trace_driver -o trace -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_driver_traced.json" 2> "$OUT/trace_driver.err"
 find /tmp/apd_trace_driver -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats_bench_driver_s20_w5_with_workloads.csv" \;
 rm -rf /tmp/apd_trace_driver
 

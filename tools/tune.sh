@@ -7,7 +7,7 @@ export APD_ALLOW_STALE_LIBRARY=1   # lab builds with ad-hoc flags: the build-id 
 for f in "$@"; do
   APD_EXTRA_FLAGS="$f" python apd-mvs_amd/build.py --force > /tmp/build.log 2>&1 || { echo "BUILD FAILED for $f"; tail -5 /tmp/build.log; continue; }
   echo "== flags: [$f] workload $WL"
-  timeout 600 python bench.py --full-line --no-workloads $ARGS 2>/dev/null | python -c "
+  timeout 600 python bench.py --full --full-line --no-workloads $ARGS 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.readline())
 w=d.get('weak_path') or {}
 it=d.get('iterations') or {}
