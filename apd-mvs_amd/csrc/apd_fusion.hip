@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/apd_mi355x.h"
+#include "apd_fusion_device.h"
 #include "apd_fusion_math.h"
 
 namespace {
@@ -212,72 +213,8 @@ __global__ __launch_bounds__(256) void k_fusion_emit(const DevView *__restrict__
     }
 }
 
-// exclusive scan of the block counts (one workgroup; a view has at most a few hundred thousand blocks)
-__global__ __launch_bounds__(1024) void k_fusion_scan(int *__restrict__ counts, int nblocks, int *__restrict__ total)
-{
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int per = (nblocks + 1023) / 1024;
-    const int b0 = t * per, b1 = min(b0 + per, nblocks);
-    int sum = 0;
-    for (int b = b0; b < b1; ++b) {
-        sum += counts[b];
-    }
-    part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - sum;
-    for (int b = b0; b < b1; ++b) {
-        const int c = counts[b];
-        counts[b] = run;
-        run += c;
-    }
-    if (t == 1023) {
-        *total = part[1023];
-    }
-}
-
-// Packs the accepted points of a view in raster order as the 15-byte records of the PLY body (x y z float, diffuse_blue /
-// green / red uchar, APD.cpp:214-254): one download per view straight into the file image, no per-point loop on the host.
-__global__ __launch_bounds__(256) void k_fusion_compact(RefTask task, int n, const float *__restrict__ xyz_sparse,
-                                                         const uint8_t *__restrict__ bgr_sparse, const int *__restrict__ block_offsets,
-                                                         uint8_t *__restrict__ records)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    const bool acc = p < n && task.state[p] == kAccepted;
-    const unsigned long long m = __ballot(acc);
-    __shared__ int wave_counts[4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-        wave_counts[wave] = __popcll(m);
-    }
-    __syncthreads();
-    if (acc) {
-        int pos = block_offsets[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) {
-            pos += wave_counts[w];
-        }
-        uint8_t *rec = records + (size_t)pos * 15;
-        for (int k = 0; k < 3; ++k) {
-            const uint32_t bits = __float_as_uint(xyz_sparse[3 * (size_t)p + k]);  // little endian, as the host's memcpy wrote them
-            rec[4 * k + 0] = (uint8_t)(bits & 0xFFu);
-            rec[4 * k + 1] = (uint8_t)((bits >> 8) & 0xFFu);
-            rec[4 * k + 2] = (uint8_t)((bits >> 16) & 0xFFu);
-            rec[4 * k + 3] = (uint8_t)(bits >> 24);
-        }
-        rec[12] = bgr_sparse[3 * (size_t)p + 0];
-        rec[13] = bgr_sparse[3 * (size_t)p + 1];
-        rec[14] = bgr_sparse[3 * (size_t)p + 2];
-    }
-}
-
-thread_local std::string g_fusion_error;
-thread_local double g_fusion_ms[3] = {0.0, 0.0, 0.0};  // last apd_fuse_views: set-up (allocations, uploads), views (kernels + point downloads), PLY file
+using apd_fusion::g_fusion_error;
+using apd_fusion::g_fusion_ms;
 
 int fusion_fail(int code, const char *what, hipError_t e)
 {
@@ -297,6 +234,33 @@ int fusion_fail(int code, const char *what, hipError_t e)
     } while (0)
 
 }  // namespace
+
+namespace apd_fusion {
+
+thread_local std::string g_fusion_error;
+thread_local double g_fusion_ms[3] = {0.0, 0.0, 0.0};
+
+int write_ply(const char *who, const char *ply_path, long long count, const std::vector<std::vector<uint8_t>> &body)
+{
+    FILE *f = fopen(ply_path, "wb");
+    if (!f) {
+        g_fusion_error = std::string(who) + ": cannot write " + ply_path;
+        return APD_ERR_IO;
+    }
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+               "property uchar diffuse_blue\nproperty uchar diffuse_green\nproperty uchar diffuse_red\nend_header\n", (int)count);
+    bool ok = true;
+    for (const std::vector<uint8_t> &part : body) {
+        ok = ok && (part.empty() || fwrite(part.data(), 1, part.size(), f) == part.size());
+    }
+    if (fclose(f) != 0 || !ok) {
+        g_fusion_error = std::string(who) + ": short write to " + ply_path;
+        return APD_ERR_IO;
+    }
+    return APD_OK;
+}
+
+}  // namespace apd_fusion
 
 extern "C" const char *apd_fusion_last_error(void) { return g_fusion_error.c_str(); }
 
@@ -496,7 +460,7 @@ extern "C" int apd_fuse_views(int device, int num_views, const apd_camera *camer
         hipLaunchKernelGGL(k_fusion_emit, dim3(blocks), dim3(256), 0, 0, dviews, task, (float *)xyz_sparse, (uint8_t *)grey_sparse,
                            (int *)block_counts);
         hipLaunchKernelGGL(k_fusion_scan, dim3(1), dim3(1024), 0, 0, (int *)block_counts, blocks, (int *)total);
-        hipLaunchKernelGGL(k_fusion_compact, dim3(blocks), dim3(256), 0, 0, task, n, (const float *)xyz_sparse,
+        hipLaunchKernelGGL(k_fusion_compact, dim3(blocks), dim3(256), 0, 0, (const uint8_t *)task.state, (uint8_t)kAccepted, n, (const float *)xyz_sparse,
                            (const uint8_t *)grey_sparse, (const int *)block_counts, (uint8_t *)records);
         FUS_TRY(hipGetLastError());
         int npts = 0;
@@ -516,20 +480,9 @@ extern "C" int apd_fuse_views(int device, int num_views, const apd_camera *camer
     g_fusion_ms[1] = ms_since(t_views);
     const auto t_file = std::chrono::steady_clock::now();
     cleanup();
-    FILE *f = fopen(ply_path, "wb");
-    if (!f) {
-        g_fusion_error = std::string("apd_fuse_views: cannot write ") + ply_path;
-        return APD_ERR_IO;
-    }
-    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-               "property uchar diffuse_blue\nproperty uchar diffuse_green\nproperty uchar diffuse_red\nend_header\n", (int)count);
-    bool ok = true;
-    for (const std::vector<uint8_t> &part : body) {
-        ok = ok && (part.empty() || fwrite(part.data(), 1, part.size(), f) == part.size());
-    }
-    if (fclose(f) != 0 || !ok) {
-        g_fusion_error = std::string("apd_fuse_views: short write to ") + ply_path;
-        return APD_ERR_IO;
+    const int written = apd_fusion::write_ply("apd_fuse_views", ply_path, count, body);
+    if (written != APD_OK) {
+        return written;
     }
     *num_points = count;
     g_fusion_ms[2] = ms_since(t_file);

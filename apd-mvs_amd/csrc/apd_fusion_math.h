@@ -150,23 +150,32 @@ APD_HD bool vote_target(const View &src, const float P[3], int &sc, int &sr)
     return sc >= 0 && sc < src.cols && sr >= 0 && sr < src.rows;
 }
 
-// Backward check of reference pixel (c, r) against source pixel (sc, sr) with depth src_depth and normal src_n:
-// thresholds 2 px, 1 % depth, 10 degrees (APD.cpp:905-925).  `weight` is exp(-score), the term added to the consistency.
-APD_HD bool vote_check(const View &ref, const View &src, int c, int r, float ref_depth, const float ref_n[3], int sc, int sr,
-                       float src_depth, const float src_n[3], float &weight)
+// Reference pixel (c, r) against source pixel (sc, sr) with depth src_depth and normal src_n: reprojection error, relative
+// depth difference and normal angle, the three costs of all three fusion loops (APD.cpp:937-939, :1101-1103, :1267-1269).
+APD_HD void measure(const View &ref, const View &src, int c, int r, float ref_depth, const float ref_n[3], int sc, int sr,
+                    float src_depth, const float src_n[3], float &reproj_error, float &relative_depth_diff, float &angle)
 {
     float Q[3];
     lift(src, sc, sr, src_depth, Q);
     float bu, bw, back_depth;
     drop(ref, Q, bu, bw, back_depth);
     const double ex = (double)(c - bu), ey = (double)(r - bw);  // float differences, double pow(., 2) and sqrt
-    const float reproj_error = (float)sqrt(ex * ex + ey * ey);
-    const float relative_depth_diff = fabsf(back_depth - ref_depth) / ref_depth;
+    reproj_error = (float)sqrt(ex * ex + ey * ey);
+    relative_depth_diff = fabsf(back_depth - ref_depth) / ref_depth;
     const float dot = ref_n[0] * src_n[0] + ref_n[1] * src_n[1] + ref_n[2] * src_n[2];
-    float angle = acos_c9(dot);
+    angle = acos_c9(dot);
     if (angle != angle) {  // acos of a dot product just above 1 is NaN and counts as 0 (APD.cpp:817-824)
         angle = 0.0f;
     }
+}
+
+// Backward check of reference pixel (c, r) against source pixel (sc, sr) with depth src_depth and normal src_n:
+// thresholds 2 px, 1 % depth, 10 degrees (APD.cpp:905-925).  `weight` is exp(-score), the term added to the consistency.
+APD_HD bool vote_check(const View &ref, const View &src, int c, int r, float ref_depth, const float ref_n[3], int sc, int sr,
+                       float src_depth, const float src_n[3], float &weight)
+{
+    float reproj_error, relative_depth_diff, angle;
+    measure(ref, src, c, r, ref_depth, ref_n, sc, sr, src_depth, src_n, reproj_error, relative_depth_diff, angle);
     if (!(reproj_error < 2.0f && relative_depth_diff < 0.01f && angle < 0.174533f)) {
         return false;
     }

@@ -1,0 +1,514 @@
+// apd_fusion_tat.hip -- the Tanks and Temples fusions (RunFusion_TAT_Intermediate, APD.cpp:979-1147, and RunFusion_TAT_advanced,
+// APD.cpp:1149-1296) on the device: apd_fuse_views_variant of include/apd_mi355x.h.
+//
+// Both loops walk the views in order and the pixels of a view in raster order, like the ETH loop (apd_fusion.hip), but they
+// depend on that order in another way.  They never consume source pixels: they read `masks` of the sources only and set
+// `masks` of the reference pixels they emit, so a view depends on earlier views through the masks and the pixels of one view
+// do not depend on each other's decisions.  What they do depend on is `diff`, one entry per source that is declared once per
+// view (APD.cpp:1069, :1233) and overwritten only where the source is valid (in bounds, not masked, depth > 0): a pixel at
+// which source j is not valid sees the values of the last earlier pixel of the view, in raster order, at which j was.  That
+// pixel is an inclusive max-scan over raster order of `valid_j(p) ? p : -1`, exact under any association.  Per view:
+//
+//   k_tat_valid   one lane per pixel: valid_j for every source (bit j of a 32-bit word per pixel), and per 256-pixel block
+//                 and source the last valid pixel (wave ballots);
+//   k_tat_scan    one workgroup per source: exclusive max-scan of the block values over the blocks of the view;
+//   k_tat_decide  one lane per pixel: the last valid pixel q_j <= p of every source (own wave's ballot, the earlier waves of
+//                 the block, then the block prefix), the costs recomputed at q_j (apd_fusion_math.h: the very arithmetic of the
+//                 scan's pixel, so the same bits the reference stored in diff[j]), the k loop, and the point;
+//   k_fusion_scan + k_fusion_compact (apd_fusion_device.h): the points in raster order as PLY records.
+//
+// Memory per view of n pixels and S sources: 4 n (validity words) + 8 S n / 256 (block values) + 1 n (emitted) + 30 n (the
+// points before and after compaction, as in the ETH fusion) bytes, about 36 bytes per pixel, plus one mask byte per pixel
+// of every view for the whole run.  No (pixel, source) record is stored: at 6200 x 4130 with 10 sources the records would be
+// ~4 GB, this layout is ~0.9 GB.
+#include <hip/hip_runtime.h>
+
+#include <float.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "../../include/apd_mi355x.h"
+#include "apd_fusion_device.h"
+#include "apd_fusion_math.h"
+
+namespace {
+
+using apd_fusion::View;
+using apd_fusion::g_fusion_error;
+using apd_fusion::g_fusion_ms;
+
+constexpr int kMaxSrc = APD_MAX_IMAGES;
+
+struct TatView {
+    View geo;
+    const float *image;   // rows*cols*channels, 0..255; channels 1 (grey) or 3 (blue, green, red)
+    const float *depth;   // <= 0: no estimate
+    const float *normal;  // 3 per pixel, world frame
+    const uint8_t *block; // optional `blocks/mask_<id>.jpg`: pixels < 128 are not fused as reference pixels
+    uint8_t *mask;        // the reference's `masks`: 1 = emitted as a reference pixel
+};
+
+struct TatTask {
+    int ref;                 // index of the reference view
+    int num_src;
+    int n;                   // pixels of the reference view
+    int channels;            // of the images
+    int intermediate;        // 1: RunFusion_TAT_Intermediate (angle test, averaged colour), 0: RunFusion_TAT_advanced
+    int src[kMaxSrc];
+    // thresholds of round k (index k = 2 .. num_src), computed on the host in float like the reference's `k * dist_base`,
+    // `k * depth_base`, `k * angle_grad + angle_base`
+    float max_dist[kMaxSrc + 1], max_depth[kMaxSrc + 1], max_angle[kMaxSrc + 1];
+    uint32_t *valid;         // [pixel]: bit j = source j valid at the pixel
+    int *block_last;         // [block][num_src]: last valid pixel of the block (-1: none); after k_tat_scan, of the blocks before it
+    uint8_t *emitted;        // [pixel]: 1 = the pixel is a point
+    float *xyz;              // [pixel][3]
+    uint8_t *bgr;            // [pixel][3]
+    int *block_counts;       // points per block
+};
+
+__device__ __forceinline__ bool is_reference_pixel(const TatView &rv, int p)
+{
+    return !(rv.block && rv.block[p] < 128) && !(rv.depth[p] <= 0.0f);  // APD.cpp:1072-1078 (:1236-1242)
+}
+
+// valid(j) of APD.cpp:1086-1096 (:1252-1262): the pixel that world point P projects to in source sv, if any and usable
+__device__ __forceinline__ bool source_pixel(const TatView &sv, const float P[3], int &sc, int &sr)
+{
+    if (!apd_fusion::vote_target(sv.geo, P, sc, sr)) {
+        return false;
+    }
+    const int s = sr * sv.geo.cols + sc;
+    return sv.mask[s] != 1 && !(sv.depth[s] <= 0.0f);
+}
+
+__global__ __launch_bounds__(256) void k_tat_valid(const TatView *__restrict__ views, TatTask task)
+{
+    const TatView &rv = views[task.ref];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    uint32_t bits = 0;
+    if (p < task.n) {
+        if (is_reference_pixel(rv, p)) {
+            const int r = p / rv.geo.cols, c = p - r * rv.geo.cols;
+            float P[3];
+            apd_fusion::lift(rv.geo, c, r, rv.depth[p], P);
+            for (int j = 0; j < task.num_src; ++j) {
+                int sc, sr;
+                if (source_pixel(views[task.src[j]], P, sc, sr)) {
+                    bits |= 1u << j;
+                }
+            }
+        }
+        task.valid[p] = bits;
+    }
+    __shared__ int wave_last[4][kMaxSrc];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int j = 0; j < task.num_src; ++j) {
+        const unsigned long long m = __ballot((bits >> j) & 1u);
+        if (lane == 0) {
+            wave_last[wave][j] = m ? (int)(blockIdx.x * 256 + wave * 64 + 63 - __clzll(m)) : -1;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < task.num_src) {
+        const int j = threadIdx.x;
+        const int last = max(max(wave_last[0][j], wave_last[1][j]), max(wave_last[2][j], wave_last[3][j]));
+        task.block_last[(size_t)blockIdx.x * task.num_src + j] = last;
+    }
+}
+
+// exclusive max-scan of block_last over the blocks of the view, for source j = blockIdx.x
+__global__ __launch_bounds__(1024) void k_tat_scan(TatTask task, int nblocks)
+{
+    __shared__ int part[1024];
+    const int j = blockIdx.x, t = threadIdx.x, S = task.num_src;
+    const int per = (nblocks + 1023) / 1024;
+    const int b0 = t * per, b1 = min(b0 + per, nblocks);
+    int m = -1;
+    for (int b = b0; b < b1; ++b) {
+        m = max(m, task.block_last[(size_t)b * S + j]);
+    }
+    part[t] = m;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = (t >= off) ? part[t - off] : -1;
+        __syncthreads();
+        part[t] = max(part[t], v);
+        __syncthreads();
+    }
+    int run = t > 0 ? part[t - 1] : -1;
+    for (int b = b0; b < b1; ++b) {
+        const int v = task.block_last[(size_t)b * S + j];
+        task.block_last[(size_t)b * S + j] = run;
+        run = max(run, v);
+    }
+}
+
+// Last pixel <= this lane's of the view at which source j was valid, -1 if none: this wave's ballot up to the lane, else the
+// last one of an earlier wave of the block, else the scanned prefix of the earlier blocks.
+__device__ __forceinline__ int last_valid(const unsigned long long (*wave_mask)[kMaxSrc], const TatTask &task, int j, int wave,
+                                          unsigned long long lanes_le)
+{
+    const unsigned long long mine = wave_mask[wave][j] & lanes_le;
+    if (mine) {
+        return (int)(blockIdx.x * 256 + wave * 64 + 63 - __clzll(mine));
+    }
+    for (int w = wave - 1; w >= 0; --w) {
+        const unsigned long long m = wave_mask[w][j];
+        if (m) {
+            return (int)(blockIdx.x * 256 + w * 64 + 63 - __clzll(m));
+        }
+    }
+    return task.block_last[(size_t)blockIdx.x * task.num_src + j];
+}
+
+// dynamic LDS: num_src * 256 bytes (first round each source passes at, per lane)
+__global__ __launch_bounds__(256) void k_tat_decide(const TatView *__restrict__ views, TatTask task)
+{
+    extern __shared__ uint8_t first_round[];  // [j][lane of the block]
+    __shared__ unsigned long long wave_mask[4][kMaxSrc];
+    const TatView &rv = views[task.ref];
+    const int S = task.num_src;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t bits = p < task.n ? task.valid[p] : 0u;
+    for (int j = 0; j < S; ++j) {
+        const unsigned long long m = __ballot((bits >> j) & 1u);
+        if (lane == 0) {
+            wave_mask[wave][j] = m;
+        }
+    }
+    __syncthreads();
+    const unsigned long long lanes_le = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+    bool emit = false;
+    if (p < task.n && is_reference_pixel(rv, p)) {
+        // diff[j] (APD.cpp:1097-1107): the costs at the last pixel q <= p where j was valid; FLT_MAX (never passes) if none
+        for (int j = 0; j < S; ++j) {
+            const TatView &sv = views[task.src[j]];
+            const int q = last_valid(wave_mask, task, j, wave, lanes_le);
+            int first = S + 1;
+            int sc, sr;
+            if (q >= 0) {
+                const int rq = q / rv.geo.cols, cq = q - rq * rv.geo.cols;
+                const float depth_q = rv.depth[q];
+                float P[3];
+                apd_fusion::lift(rv.geo, cq, rq, depth_q, P);
+                if (apd_fusion::vote_target(sv.geo, P, sc, sr)) {  // always true: j was valid at q
+                    const int s = sr * sv.geo.cols + sc;
+                    const float ref_n[3] = {rv.normal[3 * (size_t)q], rv.normal[3 * (size_t)q + 1], rv.normal[3 * (size_t)q + 2]};
+                    const float src_n[3] = {sv.normal[3 * (size_t)s], sv.normal[3 * (size_t)s + 1], sv.normal[3 * (size_t)s + 2]};
+                    float dist, depth, angle;
+                    apd_fusion::measure(rv.geo, sv.geo, cq, rq, depth_q, ref_n, sc, sr, sv.depth[s], src_n, dist, depth, angle);
+                    // the thresholds grow with k, so "j is used in round k" is "k >= first round j passes"
+                    for (int k = 2; k <= S; ++k) {
+                        if (dist < task.max_dist[k] && depth < task.max_depth[k] && (!task.intermediate || angle < task.max_angle[k])) {
+                            first = k;
+                            break;
+                        }
+                    }
+                }
+            }
+            first_round[j * 256 + threadIdx.x] = (uint8_t)first;
+        }
+        // the k loop (APD.cpp:1111-1144, :1277-1293): the first k with at least k sources used emits
+        int count = 0, round = 0;
+        for (int k = 2; k <= S && round == 0; ++k) {
+            count = 0;
+            for (int j = 0; j < S; ++j) {
+                count += first_round[j * 256 + threadIdx.x] <= k;
+            }
+            if (count >= k) {
+                round = k;
+            }
+        }
+        if (round > 0) {
+            emit = true;
+            const int r = p / rv.geo.cols, c = p - r * rv.geo.cols;
+            float P[3];
+            apd_fusion::lift(rv.geo, c, r, rv.depth[p], P);
+            const int nc = task.channels;
+            float colour[3];
+            for (int k = 0; k < 3; ++k) {
+                colour[k] = rv.image[(size_t)p * nc + (nc == 3 ? k : 0)];
+            }
+            if (task.intermediate) {  // + the colours at diff[j].src_r / src_c of the used sources, in source order
+                for (int j = 0; j < S; ++j) {
+                    if (first_round[j * 256 + threadIdx.x] > round) {
+                        continue;
+                    }
+                    const TatView &sv = views[task.src[j]];
+                    const int q = last_valid(wave_mask, task, j, wave, lanes_le);
+                    const int rq = q / rv.geo.cols, cq = q - rq * rv.geo.cols;
+                    float Q[3];
+                    int sc, sr;
+                    apd_fusion::lift(rv.geo, cq, rq, rv.depth[q], Q);
+                    if (!apd_fusion::vote_target(sv.geo, Q, sc, sr)) {  // never: the pixel k_tat_valid found at q
+                        continue;
+                    }
+                    const size_t s = (size_t)sr * sv.geo.cols + sc;
+                    for (int k = 0; k < 3; ++k) {
+                        colour[k] += sv.image[s * nc + (nc == 3 ? k : 0)];
+                    }
+                }
+                for (int k = 0; k < 3; ++k) {
+                    colour[k] /= (count + 1.0f);
+                }
+            }
+            task.xyz[3 * (size_t)p + 0] = P[0];
+            task.xyz[3 * (size_t)p + 1] = P[1];
+            task.xyz[3 * (size_t)p + 2] = P[2];
+            for (int k = 0; k < 3; ++k) {
+                task.bgr[3 * (size_t)p + k] = static_cast<uint8_t>(colour[k]);
+            }
+            rv.mask[p] = 1;
+        }
+    }
+    if (p < task.n) {
+        task.emitted[p] = emit ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(emit);
+    __shared__ int wave_counts[4];
+    if (lane == 0) {
+        wave_counts[wave] = __popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        task.block_counts[blockIdx.x] = wave_counts[0] + wave_counts[1] + wave_counts[2] + wave_counts[3];
+    }
+}
+
+int tat_fail(int code, const char *what, hipError_t e)
+{
+    char buf[256];
+    snprintf(buf, sizeof(buf), "apd_fuse_views_variant: %s: %s", what, hipGetErrorString(e));
+    g_fusion_error = buf;
+    return code;
+}
+
+#define TAT_TRY(expr)                                        \
+    do {                                                     \
+        hipError_t e_ = (expr);                              \
+        if (e_ != hipSuccess) {                              \
+            cleanup();                                       \
+            return tat_fail(APD_ERR_HIP, #expr, e_);         \
+        }                                                    \
+    } while (0)
+
+int fuse_tat(bool intermediate, int device, int num_views, const apd_camera *cameras, const float *const *images, int image_channels,
+             const float *const *depths, const float *const *normals, const uint8_t *const *blocks, const int *rows, const int *cols,
+             const int *pair_offsets, const int *pair_indices, int maps_on_device, const char *ply_path, long long *num_points)
+{
+    const auto t_begin = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    std::vector<void *> owned;
+    std::vector<TatView> hv(num_views);
+    void *staging = nullptr;  // page-locked buffer of the point downloads
+    auto cleanup = [&]() {
+        for (void *p : owned) {
+            hipFree(p);
+        }
+        owned.clear();
+        if (staging) {
+            hipHostFree(staging);
+            staging = nullptr;
+        }
+    };
+    auto dev_alloc = [&](size_t bytes, void **out) -> hipError_t {
+        hipError_t e = hipMalloc(out, bytes > 0 ? bytes : 1);
+        if (e == hipSuccess) {
+            owned.push_back(*out);
+        }
+        return e;
+    };
+    TAT_TRY(hipSetDevice(device));
+    size_t max_px = 0;
+    int max_src = 1;
+    for (int i = 0; i < num_views; ++i) {
+        const size_t n = (size_t)rows[i] * cols[i];
+        max_px = std::max(max_px, n);
+        max_src = std::max(max_src, pair_offsets[i + 1] - pair_offsets[i]);
+        TatView &v = hv[i];
+        const apd_camera &c = cameras[i];
+        memcpy(v.geo.K, c.K, sizeof(v.geo.K));
+        memcpy(v.geo.R, c.R, sizeof(v.geo.R));
+        memcpy(v.geo.t, c.t, sizeof(v.geo.t));
+        // -R^T t in float, term order of Get3DPointonWorld (APD.cpp:795-798)
+        v.geo.centre[0] = -(c.R[0] * c.t[0] + c.R[3] * c.t[1] + c.R[6] * c.t[2]);
+        v.geo.centre[1] = -(c.R[1] * c.t[0] + c.R[4] * c.t[1] + c.R[7] * c.t[2]);
+        v.geo.centre[2] = -(c.R[2] * c.t[0] + c.R[5] * c.t[1] + c.R[8] * c.t[2]);
+        v.geo.rows = rows[i];
+        v.geo.cols = cols[i];
+        if (maps_on_device) {
+            v.image = images[i];
+            v.depth = depths[i];
+            v.normal = normals[i];
+            v.block = blocks ? blocks[i] : nullptr;
+        } else {
+            void *g, *d, *nm;
+            TAT_TRY(dev_alloc(n * 4 * image_channels, &g));
+            TAT_TRY(dev_alloc(n * 4, &d));
+            TAT_TRY(dev_alloc(n * 12, &nm));
+            TAT_TRY(hipMemcpy(g, images[i], n * 4 * image_channels, hipMemcpyHostToDevice));
+            TAT_TRY(hipMemcpy(d, depths[i], n * 4, hipMemcpyHostToDevice));
+            TAT_TRY(hipMemcpy(nm, normals[i], n * 12, hipMemcpyHostToDevice));
+            v.image = (const float *)g;
+            v.depth = (const float *)d;
+            v.normal = (const float *)nm;
+            v.block = nullptr;
+            if (blocks && blocks[i]) {
+                void *b;
+                TAT_TRY(dev_alloc(n, &b));
+                TAT_TRY(hipMemcpy(b, blocks[i], n, hipMemcpyHostToDevice));
+                v.block = (const uint8_t *)b;
+            }
+        }
+        void *mask;
+        TAT_TRY(dev_alloc(n, &mask));
+        TAT_TRY(hipMemset(mask, 0, n));  // APD.cpp:1038, :1205: one zeroed mask per view
+        v.mask = (uint8_t *)mask;
+    }
+    TatView *dviews = nullptr;
+    {
+        void *p;
+        TAT_TRY(dev_alloc(sizeof(TatView) * num_views, &p));
+        dviews = (TatView *)p;
+        TAT_TRY(hipMemcpy(dviews, hv.data(), sizeof(TatView) * num_views, hipMemcpyHostToDevice));
+    }
+    const int max_blocks = (int)((max_px + 255) / 256);
+    void *valid, *block_last, *emitted, *xyz, *bgr, *block_counts, *total, *records;
+    TAT_TRY(dev_alloc(max_px * 4, &valid));
+    TAT_TRY(dev_alloc((size_t)max_blocks * max_src * 4, &block_last));
+    TAT_TRY(dev_alloc(max_px, &emitted));
+    TAT_TRY(dev_alloc(max_px * 12, &xyz));
+    TAT_TRY(dev_alloc(max_px * 3, &bgr));
+    TAT_TRY(dev_alloc((size_t)max_blocks * 4, &block_counts));
+    TAT_TRY(dev_alloc(sizeof(int), &total));
+    TAT_TRY(dev_alloc(max_px * 15, &records));
+    std::vector<std::vector<uint8_t>> body((size_t)num_views);
+    if (hipHostMalloc(&staging, max_px * 15 > 0 ? max_px * 15 : 1, hipHostMallocDefault) != hipSuccess) {
+        staging = nullptr;  // pageable downloads then
+    }
+    // APD.cpp:984-989, :1154-1155
+    const float dist_base = 0.25f;
+    const float depth_base = intermediate ? 1.0f / 3500.0f : 1.0f / 3000.0f;
+    const float angle_base = 0.06981317007977318f;  // 4 degrees
+    const float angle_grad = 0.05235987755982988f;  // 3 degrees
+    g_fusion_ms[0] = ms_since(t_begin);
+    const auto t_views = std::chrono::steady_clock::now();
+    long long count = 0;
+    for (int i = 0; i < num_views; ++i) {
+        const int n = rows[i] * cols[i];
+        const int S = pair_offsets[i + 1] - pair_offsets[i];
+        if (n == 0 || S < 2) {
+            continue;  // the k loop runs from 2 to the number of sources: nothing to emit
+        }
+        const int nblocks = (n + 255) / 256;
+        TatTask task;
+        memset(&task, 0, sizeof(task));
+        task.ref = i;
+        task.num_src = S;
+        task.n = n;
+        task.channels = image_channels;
+        task.intermediate = intermediate ? 1 : 0;
+        for (int j = 0; j < S; ++j) {
+            task.src[j] = pair_indices[pair_offsets[i] + j];
+        }
+        for (int k = 2; k <= S; ++k) {
+            task.max_dist[k] = k * dist_base;
+            task.max_depth[k] = k * depth_base;
+            task.max_angle[k] = k * angle_grad + angle_base;  // two roundings: the library is built without contraction
+        }
+        task.valid = (uint32_t *)valid;
+        task.block_last = (int *)block_last;
+        task.emitted = (uint8_t *)emitted;
+        task.xyz = (float *)xyz;
+        task.bgr = (uint8_t *)bgr;
+        task.block_counts = (int *)block_counts;
+        hipLaunchKernelGGL(k_tat_valid, dim3(nblocks), dim3(256), 0, 0, dviews, task);
+        hipLaunchKernelGGL(k_tat_scan, dim3(S), dim3(1024), 0, 0, task, nblocks);
+        hipLaunchKernelGGL(k_tat_decide, dim3(nblocks), dim3(256), (size_t)S * 256, 0, dviews, task);
+        hipLaunchKernelGGL(k_fusion_scan, dim3(1), dim3(1024), 0, 0, (int *)block_counts, nblocks, (int *)total);
+        hipLaunchKernelGGL(k_fusion_compact, dim3(nblocks), dim3(256), 0, 0, (const uint8_t *)emitted, (uint8_t)1, n, (const float *)xyz,
+                           (const uint8_t *)bgr, (const int *)block_counts, (uint8_t *)records);
+        TAT_TRY(hipGetLastError());
+        int npts = 0;
+        TAT_TRY(hipMemcpy(&npts, total, sizeof(int), hipMemcpyDeviceToHost));
+        if (npts > 0) {
+            body[i].resize((size_t)npts * 15);
+            if (staging) {
+                TAT_TRY(hipMemcpy(staging, records, (size_t)npts * 15, hipMemcpyDeviceToHost));
+                memcpy(body[i].data(), staging, (size_t)npts * 15);
+            } else {
+                TAT_TRY(hipMemcpy(body[i].data(), records, (size_t)npts * 15, hipMemcpyDeviceToHost));
+            }
+            count += npts;
+        }
+    }
+    g_fusion_ms[1] = ms_since(t_views);
+    const auto t_file = std::chrono::steady_clock::now();
+    cleanup();
+    const int written = apd_fusion::write_ply("apd_fuse_views_variant", ply_path, count, body);
+    if (written != APD_OK) {
+        return written;
+    }
+    *num_points = count;
+    g_fusion_ms[2] = ms_since(t_file);
+    return APD_OK;
+}
+
+}  // namespace
+
+extern "C" int apd_fuse_views_variant(int variant, int device, int num_views, const apd_camera *cameras, const float *const *images,
+                                      int image_channels, const float *const *depths, const float *const *normals,
+                                      const uint8_t *const *weaks, const uint8_t *const *blocks, const int *rows, const int *cols,
+                                      const int *pair_offsets, const int *pair_indices, int maps_on_device, const char *ply_path,
+                                      long long *num_points)
+{
+    if (variant == APD_FUSION_ETH) {
+        return apd_fuse_views(device, num_views, cameras, images, image_channels, depths, normals, weaks, blocks, rows, cols, pair_offsets,
+                              pair_indices, maps_on_device, ply_path, num_points);
+    }
+    g_fusion_error.clear();
+    if (variant != APD_FUSION_TAT_INTERMEDIATE && variant != APD_FUSION_TAT_ADVANCED) {
+        g_fusion_error = "apd_fuse_views_variant: unknown variant " + std::to_string(variant);
+        return APD_ERR_INVALID;
+    }
+    if (num_views <= 0 || !cameras || !images || !depths || !normals || !rows || !cols || !pair_offsets || !pair_indices || !ply_path ||
+        !num_points) {
+        g_fusion_error = "apd_fuse_views_variant: null argument";
+        return APD_ERR_INVALID;
+    }
+    if (image_channels != 1 && image_channels != 3) {
+        g_fusion_error = "apd_fuse_views_variant: images have 1 (grey) or 3 (blue, green, red) channels";
+        return APD_ERR_INVALID;
+    }
+    for (int i = 0; i < num_views; ++i) {
+        const int ns = pair_offsets[i + 1] - pair_offsets[i];
+        if (ns < 0 || ns > kMaxSrc) {
+            g_fusion_error = "apd_fuse_views_variant: a view has more than APD_MAX_IMAGES sources";
+            return APD_ERR_INVALID;
+        }
+        if (rows[i] < 0 || cols[i] < 0 || (long long)rows[i] * cols[i] > 0x7fffff00LL) {
+            g_fusion_error = "apd_fuse_views_variant: view size out of range";
+            return APD_ERR_INVALID;
+        }
+        for (int k = pair_offsets[i]; k < pair_offsets[i + 1]; ++k) {
+            if (pair_indices[k] < 0 || pair_indices[k] >= num_views) {
+                g_fusion_error = "apd_fuse_views_variant: source index out of range";
+                return APD_ERR_INVALID;
+            }
+            if (pair_indices[k] == i) {  // the view would read the masks it writes: order dependent inside a view
+                g_fusion_error = "apd_fuse_views_variant: a view lists itself as a source";
+                return APD_ERR_INVALID;
+            }
+        }
+    }
+    return fuse_tat(variant == APD_FUSION_TAT_INTERMEDIATE, device, num_views, cameras, images, image_channels, depths, normals, blocks, rows,
+                    cols, pair_offsets, pair_indices, maps_on_device, ply_path, num_points);
+}

@@ -143,6 +143,9 @@ void ResizeLinear(const Mat &src, Mat &dst, int new_cols, int new_rows);
 // APD.h:34 -- consistency check + merge of the final depth maps into <dense>/APD/APD.ply (device fusion apd_fuse_views)
 void RunFusion(const path &dense_folder, const std::vector<Problem> &problems);
 void SetFusionDevice(int device);  // additive: HIP device of the fusion (default 0)
+// additive: which of the reference's fusion loops RunFusion and the in-memory paths run: APD_FUSION_ETH (RunFusion, the default),
+// APD_FUSION_TAT_INTERMEDIATE or APD_FUSION_TAT_ADVANCED (APD.cpp:979-1296; the reference switches by editing main.cpp:219)
+void SetFusionVariant(int variant);
 
 class APD {
 public:

@@ -1,7 +1,8 @@
-// fusion.cpp -- depth-map fusion of the drop-in host: what the reference's RunFusion (ETH variant, APD.cpp:826-977) and
-// ExportPointCloud (APD.cpp:214-254) produce, i.e. <dense>/APD/APD.ply.
+// fusion.cpp -- depth-map fusion of the drop-in host: what the reference's RunFusion (ETH variant, APD.cpp:826-977) or, after
+// SetFusionVariant, RunFusion_TAT_Intermediate / RunFusion_TAT_advanced (APD.cpp:979-1296), and ExportPointCloud
+// (APD.cpp:214-254) produce, i.e. <dense>/APD/APD.ply.
 //
-// The fusion itself runs on the GPU (apd_fuse_views, csrc/apd_fusion.hip); this file is the drop-in entry point
+// The fusion itself runs on the GPU (apd_fuse_views_variant, csrc/apd_fusion.hip and csrc/apd_fusion_tat.hip); this file is the drop-in entry point
 // RunFusion, which reads the maps the way the reference does and hands them over.  There is no host fallback: a failing
 // device fusion ends the program like any other device error.  (The reference's sequential loop lives in
 // oracle/fusion_oracle.cpp as the checker of the device fusion.)
@@ -26,6 +27,7 @@
 namespace {
 
 int g_fusion_device = 0;
+int g_fusion_variant = APD_FUSION_ETH;  // which of the reference's loops (APD_FUSION_*, include/apd_mi355x.h)
 
 struct FusionView {
     Camera cam;
@@ -50,7 +52,7 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
         imgs[i] = views[i].image.ptr<float>();
         deps[i] = views[i].depth.ptr<float>();
         nors[i] = views[i].normal.ptr<float>();
-        weaks[i] = views[i].weak.ptr<uint8_t>();
+        weaks[i] = views[i].weak.empty() ? nullptr : views[i].weak.ptr<uint8_t>();
         if (!views[i].block.empty()) {
             blocks[i] = views[i].block.ptr<uint8_t>();
             any_block = true;
@@ -65,8 +67,9 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
     }
     long long n = 0;
     const int channels = (V > 0 && views[0].image.type == MAT_32FC3) ? 3 : 1;
-    const int st = apd_fuse_views(g_fusion_device, V, cams.data(), imgs.data(), channels, deps.data(), nors.data(), weaks.data(),
-                                  any_block ? blocks.data() : nullptr, rows.data(), cols.data(), offs.data(), idx.data(), 0, ply_path.string().c_str(), &n);
+    const int st = apd_fuse_views_variant(g_fusion_variant, g_fusion_device, V, cams.data(), imgs.data(), channels, deps.data(), nors.data(),
+                                          weaks.data(), any_block ? blocks.data() : nullptr, rows.data(), cols.data(), offs.data(), idx.data(), 0,
+                                          ply_path.string().c_str(), &n);
     if (st != APD_OK) {
         std::cerr << apd_fusion_last_error() << std::endl;
         return -1;
@@ -77,6 +80,8 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
 }  // namespace
 
 void SetFusionDevice(int device) { g_fusion_device = device; }
+
+void SetFusionVariant(int variant) { g_fusion_variant = variant; }
 
 // Reads every view's final maps from <dense>/APD/<id>/ and fuses them into APD/APD.ply (APD.cpp:826-977).
 void RunFusion(const path &dense_folder, const std::vector<Problem> &problems) { RunFusionWithMaps(dense_folder, problems, nullptr); }
@@ -123,9 +128,11 @@ bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> 
             } else {
                 ReadBinMat(problem.result_folder / path("depths.dmb"), v.depth);
                 ReadBinMat(problem.result_folder / path("normals.dmb"), v.normal);
-                ReadBinMat(problem.result_folder / path("weak.bin"), v.weak);
+                if (g_fusion_variant == APD_FUSION_ETH) {  // the T&T loops read depths and normals only (APD.cpp:1023-1024, :1190-1191)
+                    ReadBinMat(problem.result_folder / path("weak.bin"), v.weak);
+                }
             }
-            if (v.depth.empty() || v.normal.empty() || v.weak.empty()) {
+            if (v.depth.empty() || v.normal.empty() || (v.weak.empty() && g_fusion_variant == APD_FUSION_ETH)) {
                 std::cerr << "Missing maps of view " << problem.ref_image_id << " in " << problem.result_folder << std::endl;
                 failed[i] = 1;
                 return;
@@ -156,7 +163,7 @@ bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> 
         }
         v.cam.width = cols;
         v.cam.height = rows;
-        if (!on_device) {  // device maps: the weak map already has the size of the depth map
+        if (!on_device && !v.weak.empty()) {  // device maps: the weak map already has the size of the depth map
             RescaleMatToTargetSize<uint8_t>(v.weak, v.weak, cols, rows);
         }
         if (use_block) {  // blocks/mask_<id>.jpg, read as grey (APD.cpp:871-875); must have the size of the depth map
@@ -385,8 +392,9 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
     std::cout << "Fusion inputs ready: prepared in " << f->prepare_ms << " ms behind the passes, waited "
               << std::chrono::duration_cast<std::chrono::milliseconds>(t_fuse - t_wait).count() << " ms" << std::endl;
     long long count = 0;
-    const int st = apd_fuse_views(f->device, V, cams.data(), f->imgs.data(), f->channels, depths.data(), normals.data(), weaks.data(),
-                                  f->any_block ? f->blocks.data() : nullptr, rws.data(), cls.data(), offs.data(), idx.data(), 1, ply_path.string().c_str(), &count);
+    const int st = apd_fuse_views_variant(g_fusion_variant, f->device, V, cams.data(), f->imgs.data(), f->channels, depths.data(), normals.data(),
+                                          weaks.data(), f->any_block ? f->blocks.data() : nullptr, rws.data(), cls.data(), offs.data(), idx.data(), 1,
+                                          ply_path.string().c_str(), &count);
     double ms_setup = 0, ms_views = 0, ms_file = 0;
     apd_fusion_last_timing(&ms_setup, &ms_views, &ms_file);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms (set-up "

@@ -132,4 +132,7 @@ int apdhost_schedule(int round_num, int single_level, int *rows, int cap_rows)
 // HIP device of the fusion started by apdhost_fuse / RunFusion (default 0)
 void apdhost_set_fusion_device(int device) { SetFusionDevice(device); }
 
+// Fusion loop of apdhost_fuse / RunFusion: APD_FUSION_ETH (default), APD_FUSION_TAT_INTERMEDIATE, APD_FUSION_TAT_ADVANCED
+void apdhost_set_fusion_variant(int variant) { SetFusionVariant(variant); }
+
 }  // extern "C"

@@ -1,7 +1,7 @@
 // main.cpp -- drop-in driver of the PatchMatch path.
 //
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
-//       [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl]
+//       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl]
 //
 // One device index: the reference's driver.  A device LIST (or --jacobi): host/multi_device.cpp -- views sharded over the
 // devices, state resident on them, depth maps all-gathered after every pass (RCCL when there is more than one rank -- its set-up takes seconds
@@ -65,6 +65,18 @@ bool ParseOptions(int argc, char **argv, Options &o)
             o.keep_maps = true;
         } else if (a == "--no-fusion") {
             o.no_fusion = true;
+        } else if (a == "--fusion") {
+            const std::string name = i + 1 < argc ? argv[++i] : "";
+            if (name == "eth") {
+                o.fusion_variant = APD_FUSION_ETH;
+            } else if (name == "tat-intermediate") {
+                o.fusion_variant = APD_FUSION_TAT_INTERMEDIATE;
+            } else if (name == "tat-advanced") {
+                o.fusion_variant = APD_FUSION_TAT_ADVANCED;
+            } else {
+                fprintf(stderr, "bad fusion '%s': eth, tat-intermediate or tat-advanced\n", name.c_str());
+                return false;
+            }
         } else if (a == "--late-fusion-inputs") {
             o.late_fusion_inputs = true;
         } else if (a == "--scheduler-free-gb" && i + 1 < argc) {
@@ -242,7 +254,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -256,6 +268,7 @@ int main(int argc, char **argv)
     }
     APD::SetDevice(opt.gpu_index);
     SetFusionDevice(opt.gpu_index);
+    SetFusionVariant(opt.fusion_variant);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

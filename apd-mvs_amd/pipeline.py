@@ -444,16 +444,24 @@ def load_colour_images(folder, ids):
         return list(pool.map(load, ids))
 
 
-def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None):
+FUSION_VARIANTS = {"eth": 0, "tat_intermediate": 1, "tat_advanced": 2}  # APD_FUSION_* of include/apd_mi355x.h
+
+
+def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth"):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
-    (apd_fuse_views, csrc/apd_fusion.hip).  Every view must be at one resolution per view; images are
+    (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
+    Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
+    the weak maps).  Every view must be at one resolution per view; images are
     resampled to the depth-map size if it differs (RescaleImageAndCamera, APD.cpp:729-750).  colour_images: optional
     float32 [H, W, 3] arrays (blue, green, red, as load_colour_images returns them) for the point colours; the grey
     images of the scene otherwise (blue = green = red).  block_masks: optional uint8 [H, W] arrays (or None per view), the
     `blocks/mask_<id>.jpg` of APD.cpp:849-853: reference pixels below 128 are not fused.  Returns the number of points."""
     import ctypes as C
+    if variant not in FUSION_VARIANTS:
+        raise ValueError("unknown fusion variant %r: one of %s" % (variant, ", ".join(sorted(FUSION_VARIANTS))))
     L = host_lib()
     L.apdhost_set_fusion_device(int(device))
+    L.apdhost_set_fusion_variant(FUSION_VARIANTS[variant])
     V = scene.num_views
     cam_t = type(scene.cameras[0])
     cams = (cam_t * V)()
@@ -500,5 +508,5 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     n = L.apdhost_fuse(V, C.byref(cams), ptrs(imgs), channels, ptrs(deps), ptrs(nors), ptrs(weaks), blocks, rows, cols, offs, idx,
                        str(ply_path).encode())
     if n < 0:
-        raise RuntimeError("device fusion failed (apd_fuse_views): see stderr")
+        raise RuntimeError("device fusion failed (apd_fuse_views_variant, %s): see stderr" % variant)
     return int(n)

@@ -325,6 +325,20 @@ const char *apd_fusion_last_error(void);
  * consumption rounds, download of the points), the PLY file (release of the buffers + write). */
 int apd_fusion_last_timing(double *setup_ms, double *views_ms, double *file_ms);
 
+/* The reference's three fusion loops: RunFusion (ETH, APD.cpp:826-977), RunFusion_TAT_Intermediate (APD.cpp:979-1147) and
+ * RunFusion_TAT_advanced (APD.cpp:1149-1296, Tanks and Temples). */
+enum { APD_FUSION_ETH = 0, APD_FUSION_TAT_INTERMEDIATE = 1, APD_FUSION_TAT_ADVANCED = 2 };
+/* apd_fuse_views with a choice of loop.  APD_FUSION_ETH is apd_fuse_views itself.  The two T&T variants read no weak maps
+ * (`weaks` may be NULL), never consume source pixels (they mark only the reference pixels they emit), and keep the reference's
+ * per-view `diff` entries: a source that is not valid at a pixel keeps the values of the last earlier pixel of the view, in
+ * raster order, at which it was.  The point list is the one the sequential host loop writes.  An unknown variant or a view
+ * that lists itself as a source is refused (APD_ERR_INVALID) and nothing is written.  apd_fusion_last_error /
+ * apd_fusion_last_timing report on it like on apd_fuse_views. */
+int apd_fuse_views_variant(int variant, int device, int num_views, const apd_camera *cameras, const float *const *images,
+                           int image_channels, const float *const *depths, const float *const *normals, const uint8_t *const *weaks,
+                           const uint8_t *const *blocks, const int *rows, const int *cols, const int *pair_offsets,
+                           const int *pair_indices, int maps_on_device, const char *ply_path, long long *num_points);
+
 /* Host-side constant of K3 (GenNeighbours, APD.cu:1911 / :1946): its inlier test `dist / (depth_max - depth_min) <
  * ransac_threshold` (dist >= 0) is evaluated on the device as `dist < cut`, the same predicate for every binary32 dist because
  * x -> RN(x / d) is monotone.  Returns 1 and the cut, or 0 when the parameters admit none (the kernel then divides).  Needs

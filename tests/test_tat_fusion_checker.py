@@ -1,0 +1,142 @@
+"""The Tanks and Temples fusion checker (tests/helpers/tat_fusion_ref.cpp: RunFusion_TAT_Intermediate / RunFusion_TAT_advanced,
+APD.cpp:979-1296, as the sequential loops they are) against answers derived by hand on tiny scenes, and the C ABI of the device
+fusion (apd_fuse_views_variant) where it needs no device.  No GPU needed."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import tat_checker
+
+W, H, F, Z = 8, 6, 10.0, 10.0
+
+
+@pytest.fixture(scope="module")
+def checker(ob, tmp_path_factory):
+    return tat_checker.build(ob, tmp_path_factory.mktemp("tat_checker"))
+
+
+def _scene(pkg, shifts, tilt_deg=None):
+    """Fronto-parallel plane at depth Z seen by cameras R = I, t = (-s, 0, 0): pixel (r, c) of view 0 is pixel (r, c - s) of
+    a view with shift s, exactly (f = Z).  Normals face the cameras; tilt_deg[v] tilts view v's normals about the y axis."""
+    K = [F, 0, 3.5, 0, F, 2.5, 0, 0, 1]
+    cams = [pkg.make_camera(K, np.eye(3), [-s, 0.0, 0.0], W, H, 1.0, 100.0) for s in shifts]
+    depths, normals, images = [], [], []
+    for v in range(len(shifts)):
+        depths.append(np.full((H, W), Z, np.float32))
+        a = np.deg2rad((tilt_deg or {}).get(v, 0.0))
+        n = np.zeros((H, W, 3), np.float32)
+        n[..., 0], n[..., 2] = np.sin(a), -np.cos(a)
+        normals.append(n)
+        images.append((np.arange(H * W, dtype=np.float32).reshape(H, W) * 3 + 40 * v) % 256)
+    return (type(cams[0]) * len(cams))(*cams), images, depths, normals
+
+
+def _pixels(xyz):
+    """(row, col) of view 0's pixels the points were lifted from: world x = c - 3.5, y = r - 2.5."""
+    return [(int(round(p[1] + 2.5)), int(round(p[0] + 3.5))) for p in xyz]
+
+
+@pytest.mark.parametrize("variant", ["tat_intermediate", "tat_advanced"])
+def test_stale_entries_emit_and_never_valid_sources_do_not(pkg, checker, tmp_path, variant):
+    """Pixel (r, c) of view 0 is (r, c + 1) of source 1 and (r, c + 2) of source 2; source 2 has no depth in row 0.  Row 0: source 2
+    is never valid -> no point, even at (0, 7) where both sources are out of bounds.  Rows >= 1: (r, 6) has source 2 out of bounds
+    and its entry stale from (r, 5), (r, 7) has both out of bounds and both entries stale -> points all the same."""
+    cams, images, depths, normals = _scene(pkg, [0, -1, -2])
+    depths[2][0] = 0.0
+    n, stale = tat_checker.fuse(checker, variant, cams, images, depths, normals, [[1, 2], [], []], tmp_path / "a.ply")
+    xyz, bgr = tat_checker.read_ply(tmp_path / "a.ply")
+    assert n == len(xyz) == W * (H - 1)
+    assert _pixels(xyz) == [(r, c) for r in range(1, H) for c in range(W)]
+    assert stale == 2 * (H - 1)
+    assert np.array_equal(xyz[:, 2], np.full(n, Z, np.float32))
+    ref = images[0].reshape(-1)[W:]
+    if variant == "tat_advanced":  # the reference pixel's colour alone
+        assert np.array_equal(bgr, np.repeat(ref.astype(np.uint8)[:, None], 3, 1))
+    else:  # (ref + the colours at the entries' source pixels) / (count + 1)
+        for (r, c), (r1, c1), (r2, c2) in (((1, 7), (1, 7), (1, 7)),   # stale: source 1 from (1, 6), source 2 from (1, 5)
+                                           ((2, 4), (2, 5), (2, 6))):  # fresh
+            want = np.uint8(np.float32(np.float32(images[0][r, c] + images[1][r1, c1]) + images[2][r2, c2]) / np.float32(3.0))
+            assert (bgr[_pixels(xyz).index((r, c))] == want).all()
+        assert not np.array_equal(bgr[:, 0], ref.astype(np.uint8))
+
+
+def test_one_source_emits_nothing(pkg, checker, tmp_path):
+    cams, images, depths, normals = _scene(pkg, [0, 1, 2])
+    for variant in ("tat_intermediate", "tat_advanced"):
+        n, stale = tat_checker.fuse(checker, variant, cams, images, depths, normals, [[1], [0], [0]], tmp_path / "a.ply")
+        assert (n, stale) == (0, 0)
+        assert tat_checker.read_ply(tmp_path / "a.ply")[0].shape == (0, 3)
+
+
+@pytest.mark.parametrize("tilt,kept", [(9.0, True), (11.0, False)])
+def test_intermediate_rejects_normals_tilted_past_k_times_3_plus_4_degrees_and_advanced_ignores_them(pkg, checker, tmp_path, tilt, kept):
+    """Two sources: only k = 2, angle threshold 2 * 3 + 4 = 10 degrees.  Source 1's normals tilted by 9 degrees still count, by
+    11 they do not and no pixel has two sources; the advanced loop has no angle test."""
+    cams, images, depths, normals = _scene(pkg, [0, -1, 1], tilt_deg={1: tilt})
+    pairs = [[1, 2], [], []]
+    n_int, _ = tat_checker.fuse(checker, "tat_intermediate", cams, images, depths, normals, pairs, tmp_path / "i.ply")
+    n_adv, _ = tat_checker.fuse(checker, "tat_advanced", cams, images, depths, normals, pairs, tmp_path / "a.ply")
+    flat = _scene(pkg, [0, -1, 1])
+    n_flat, _ = tat_checker.fuse(checker, "tat_advanced", flat[0], flat[1], flat[2], flat[3], pairs, tmp_path / "f.ply")
+    assert n_flat > 0 and n_adv == n_flat
+    assert n_int == (n_flat if kept else 0)
+
+
+def test_masks_of_emitted_reference_pixels_invalidate_them_as_sources(pkg, checker, tmp_path):
+    """View 0 emits every pixel it can and marks it; view 1 then finds every source pixel in view 0 masked (never valid: no
+    entry, no point) but those view 0 could not emit."""
+    cams, images, depths, normals = _scene(pkg, [0, 0, 0])
+    n0, _ = tat_checker.fuse(checker, "tat_advanced", cams, images, depths, normals, [[1, 2], [], []], tmp_path / "a.ply")
+    assert n0 == W * H
+    n, _ = tat_checker.fuse(checker, "tat_advanced", cams, images, depths, normals, [[1, 2], [0, 2], []], tmp_path / "b.ply")
+    assert n == W * H  # view 1: source 0 is masked everywhere, so one source at most
+    n, _ = tat_checker.fuse(checker, "tat_advanced", cams, images, depths, normals, [[1, 2], [2, 0], [0, 1]], tmp_path / "c.ply")
+    assert n == W * H  # view 2 has source 1 unmasked (view 1 emitted nothing) and source 0 masked
+
+
+def _abi_args(pkg, pairs):
+    cams = (pkg.Camera * 2)()
+    img = np.zeros((4, 4), np.float32)
+    nrm = np.zeros((4, 4, 3), np.float32)
+    keep = (img, nrm)
+    fptr = (C.c_void_p * 2)(img.ctypes.data, img.ctypes.data)
+    nptr = (C.c_void_p * 2)(nrm.ctypes.data, nrm.ctypes.data)
+    rows, cols = (C.c_int * 2)(4, 4), (C.c_int * 2)(4, 4)
+    flat = pairs[0] + pairs[1]
+    offs, idx = (C.c_int * 3)(0, len(pairs[0]), len(flat)), (C.c_int * len(flat))(*flat)
+    return keep, (cams, fptr, 1, fptr, nptr, None, None, rows, cols, offs, idx, 0)
+
+
+def test_variant_entry_is_exported_and_refuses_bad_arguments_before_touching_a_device(pkg, tmp_path):
+    """An unknown variant and a view that is its own source are refused (APD_ERR_INVALID) and nothing is written, with or without
+    a device."""
+    L = pkg.lib()
+    assert hasattr(L, "apd_fuse_views_variant")
+    L.apd_fusion_last_error.restype = C.c_char_p
+    n = C.c_longlong(0)
+    out = tmp_path / "x.ply"
+    keep, args = _abi_args(pkg, [[1, 1], [0, 0]])
+    for variant in (3, -1, 99):
+        assert L.apd_fuse_views_variant(variant, 0, 2, *args, str(out).encode(), C.byref(n)) == -1
+        assert not out.exists() and b"unknown variant" in L.apd_fusion_last_error()
+    keep, args = _abi_args(pkg, [[1, 0], [0]])
+    for variant in (1, 2):
+        assert L.apd_fuse_views_variant(variant, 0, 2, *args, str(out).encode(), C.byref(n)) == -1
+        assert not out.exists() and b"itself" in L.apd_fusion_last_error()
+    del keep
+
+
+def test_no_gpu_means_the_tat_fusions_fail_loudly(pkg, tmp_path):
+    """No host fallback: without a device the T&T variants return an error and write nothing."""
+    if pkg.device_count() > 0:
+        pytest.skip("a GPU is visible")
+    L = pkg.lib()
+    L.apd_fusion_last_error.restype = C.c_char_p
+    n = C.c_longlong(0)
+    out = tmp_path / "x.ply"
+    keep, args = _abi_args(pkg, [[1, 1], [0, 0]])
+    for variant in (1, 2):
+        st = L.apd_fuse_views_variant(variant, 0, 2, *args, str(out).encode(), C.byref(n))
+        assert st != 0 and not out.exists() and L.apd_fusion_last_error()
+    del keep

@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--single-level", action="store_true")
     ap.add_argument("--max-src", type=int, default=0, help="keep only the first N source views of pair.txt")
     ap.add_argument("--no-fusion", action="store_true")
+    ap.add_argument("--fusion", choices=["eth", "tat-intermediate", "tat-advanced"], default="eth",
+                    help="which of the reference's fusion loops writes APD/APD.ply (as the drop-in binary's --fusion)")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -50,7 +52,8 @@ def main():
         if not args.no_fusion:
             tf = time.time()
             colour = pipeline.load_colour_images(args.dense_folder, getattr(scene, "ids", list(range(scene.num_views)))[:scene.num_views])
-            n = pipeline.fuse(scene, results, os.path.join(args.dense_folder, "APD", "APD.ply"), device=local_rank, colour_images=colour)
+            n = pipeline.fuse(scene, results, os.path.join(args.dense_folder, "APD", "APD.ply"), device=local_rank, colour_images=colour,
+                              variant=args.fusion.replace("-", "_"))
             print("fused %d points into APD/APD.ply in %.2f s" % (n, time.time() - tf), flush=True)
         print("PatchMatch passes done in %.1f s; maps written under %s" % (time.time() - t0, os.path.join(args.dense_folder, "APD")), flush=True)
     if world > 1:
