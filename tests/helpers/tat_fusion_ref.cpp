@@ -7,6 +7,7 @@
 // tests/test_tat_fusion_checker.py.  It includes nothing from the product; the helpers below restate the reference lines they
 // cite.  acosf is the fusion oracle's orc_fusion_acos (oracle/fusion_oracle.cpp), which tests/test_fusion_oracle.py pins to
 // libm and to the product's kernel.
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -83,18 +84,20 @@ struct CostData {  // APD.cpp:1045-1064 (Intermediate), :1212-1225 (advanced)
     float dist = FLT_MAX, depth = FLT_MAX, angle = FLT_MAX;
     int src_r = 0, src_c = 0;
     bool use = false;
-    bool fresh = false;  // not in the reference: written at the current pixel (else stale), for the tests' statistic
+    bool fresh = false;  // not in the reference: written at the current pixel (else stale), for the tests' statistics
+    long long writer = -1;  // not in the reference: the pixel (raster index) that wrote the entry last, for the tests' statistics
 };
 
 }  // namespace
 
 // variant 1: RunFusion_TAT_Intermediate, 2: RunFusion_TAT_advanced.  Same flat arguments as apd_fuse_views_variant with host
 // pointers (no weak maps).  Returns the number of points written, -1 on I/O failure or an unknown variant; *stale_points: how
-// many of them used at least one diff entry written at an earlier pixel.
+// many of them used at least one diff entry written at an earlier pixel; *max_gap: the largest (pixel - writer) over the
+// entries the points used, in raster pixels of the view (0: every used entry was fresh or there is no point).
 extern "C" long long tat_fuse(int variant, int num_views, const void *cameras_v, const float *const *images, int image_channels,
                               const float *const *depths, const float *const *normals, const uint8_t *const *blocks, const int *rows_of,
                               const int *cols_of, const int *pair_offsets, const int *pair_indices, const char *ply_path,
-                              long long *stale_points)
+                              long long *stale_points, long long *max_gap)
 {
     if (variant != 1 && variant != 2) {
         return -1;
@@ -112,7 +115,7 @@ extern "C" long long tat_fuse(int variant, int num_views, const void *cameras_v,
     const int nc = image_channels;
     auto colour_at = [&](int view, size_t px, int k) { return images[view][px * nc + (nc == 3 ? k : 0)]; };
     std::vector<uint8_t> cloud;  // 15 bytes per point: x y z float, blue green red uchar (APD.cpp:236-247)
-    long long count_points = 0, stale = 0;
+    long long count_points = 0, stale = 0, gap = 0;
     for (int ref_index = 0; ref_index < num_views; ++ref_index) {
         const int cols = cols_of[ref_index], rows = rows_of[ref_index];
         const int num_ngb = pair_offsets[ref_index + 1] - pair_offsets[ref_index];
@@ -162,6 +165,7 @@ extern "C" long long tat_fuse(int variant, int num_views, const void *cameras_v,
                         diff[j].src_r = src_r;
                         diff[j].src_c = src_c;
                         diff[j].fresh = true;
+                        diff[j].writer = (long long)ref_px;
                     }
                 }
                 for (int k = 2; k <= num_ngb; ++k) {
@@ -185,6 +189,7 @@ extern "C" long long tat_fuse(int variant, int num_views, const void *cameras_v,
                                 continue;
                             }
                             used_stale = used_stale || !diff[j].fresh;
+                            gap = std::max(gap, (long long)ref_px - diff[j].writer);
                             if (intermediate) {
                                 const int src_index = src_of[j];
                                 const size_t src_px = (size_t)diff[j].src_r * cols_of[src_index] + diff[j].src_c;
@@ -215,6 +220,9 @@ extern "C" long long tat_fuse(int variant, int num_views, const void *cameras_v,
     }
     if (stale_points) {
         *stale_points = stale;
+    }
+    if (max_gap) {
+        *max_gap = gap;
     }
     FILE *f = fopen(ply_path, "wb");  // ExportPointCloud, APD.cpp:214-254
     if (!f) {

@@ -26,15 +26,19 @@ def build(ob, out_dir):
     return L
 
 
-def fuse(L, variant, cameras, images, depths, normals, pairs, ply_path, blocks=None):
-    """variant "tat_intermediate" / "tat_advanced"; arguments as oracle.binding.fuse without the weak maps.
-    Returns (points, points that used a stale diff entry)."""
+def fuse(L, variant, cameras, images, depths, normals, pairs, ply_path, blocks=None, stats=None):
+    """variant "tat_intermediate" / "tat_advanced"; arguments as oracle.binding.fuse without the weak maps (blocks: a list of
+    uint8 arrays, None for a view without a block mask).  Returns (points, points that used a stale diff entry).  stats: a
+    dict that receives "max_gap", the largest (pixel - pixel that wrote the entry) in raster pixels over the diff entries the
+    points used."""
     V = len(images)
     keep = []
 
     def ptrs(arrs, dt):
         out = (C.c_void_p * V)()
         for i, a in enumerate(arrs):
+            if a is None:
+                continue
             a = np.ascontiguousarray(a, dt)
             keep.append(a)
             out[i] = a.ctypes.data
@@ -50,12 +54,14 @@ def fuse(L, variant, cameras, images, depths, normals, pairs, ply_path, blocks=N
     offs[V] = len(flat)
     idx = (C.c_int * max(len(flat), 1))(*flat)
     channels = 3 if np.asarray(images[0]).ndim == 3 else 1
-    stale = C.c_longlong(0)
+    stale, gap = C.c_longlong(0), C.c_longlong(0)
     n = L.tat_fuse(VARIANTS[variant], V, C.byref(cameras), ptrs(images, np.float32), channels, ptrs(depths, np.float32),
                    ptrs(normals, np.float32), None if blocks is None else ptrs(blocks, np.uint8), rows, cols, offs, idx,
-                   str(ply_path).encode(), C.byref(stale))
+                   str(ply_path).encode(), C.byref(stale), C.byref(gap))
     if n < 0:
         raise IOError("cannot write " + str(ply_path))
+    if stats is not None:
+        stats["max_gap"] = int(gap.value)
     return int(n), int(stale.value)
 
 

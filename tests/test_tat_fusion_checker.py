@@ -61,6 +61,22 @@ def test_stale_entries_emit_and_never_valid_sources_do_not(pkg, checker, tmp_pat
         assert not np.array_equal(bgr[:, 0], ref.astype(np.uint8))
 
 
+@pytest.mark.parametrize("variant", ["tat_intermediate", "tat_advanced"])
+def test_gap_statistic_of_the_stale_entries(pkg, checker, tmp_path, variant):
+    """The scene above: (r, 6) uses source 2's entry from (r, 5) (gap 1), (r, 7) uses source 1's from (r, 6) (gap 1) and
+    source 2's from (r, 5) (gap 2); every other point uses fresh entries (gap 0) -> the largest gap is 2."""
+    cams, images, depths, normals = _scene(pkg, [0, -1, -2])
+    depths[2][0] = 0.0
+    stats = {}
+    n, stale = tat_checker.fuse(checker, variant, cams, images, depths, normals, [[1, 2], [], []], tmp_path / "a.ply", stats=stats)
+    assert (n, stale) == (W * (H - 1), 2 * (H - 1))
+    assert stats == {"max_gap": 2}
+    # source 2 keeps depth in rows 0 (zeroed above) and 1 only: every pixel of rows >= 2 carries its entry from (1, 5)
+    depths[2][2:] = 0.0
+    n, _ = tat_checker.fuse(checker, variant, cams, images, depths, normals, [[1, 2], [], []], tmp_path / "b.ply", stats=stats)
+    assert n == W * (H - 1) and stats["max_gap"] == (H - 1) * W + 7 - (W + 5)
+
+
 def test_one_source_emits_nothing(pkg, checker, tmp_path):
     cams, images, depths, normals = _scene(pkg, [0, 1, 2])
     for variant in ("tat_intermediate", "tat_advanced"):
