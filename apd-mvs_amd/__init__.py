@@ -128,6 +128,8 @@ def lib():
     L.apd_run_before_depths.argtypes = [H]
     L.apd_run_after_depths.argtypes = [H]
     L.apd_upload_prior.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.apd_upload_mask.argtypes = [H, C.c_void_p]
+    L.apd_masked_count.argtypes = [H]
     L.apd_run.argtypes = [H]
     L.apd_run_kernel.argtypes = [H, C.c_int, C.c_int]
     L.apd_run_sweeps.argtypes = [H, C.c_int, C.c_int]
@@ -138,6 +140,7 @@ def lib():
     L.apd_state_bytes.argtypes = [H, C.c_int]
     L.apd_state_bytes.restype = C.c_size_t
     L.apd_export_depth_normal_device.argtypes = [H, C.c_void_p, C.c_void_p]
+    L.apd_export_state_device.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for n in ("apd_width", "apd_height", "apd_weak_count"):
         getattr(L, n).argtypes = [H]
     for n in ("apd_depth_min", "apd_depth_max"):
@@ -334,6 +337,23 @@ class Handle:
         self._keep_prior = (p, v, w)
         _check(lib().apd_upload_prior(self._h, _ptr(p), _ptr(v), _ptr(w)))
 
+    def upload_mask(self, mask):
+        """apd_upload_mask: uint8 (or bool) [H, W] numpy array or torch tensor (host or device), non-zero = process,
+        zero = masked out; None clears the mask.  Before the first kernel of the pass."""
+        if mask is None:
+            m = None
+        elif hasattr(mask, "data_ptr"):
+            import torch
+            m = mask.to(torch.uint8).contiguous()
+            assert m.numel() == self.W * self.H
+        else:
+            m = np.ascontiguousarray(mask).astype(np.uint8, copy=False)
+            assert m.size == self.W * self.H
+        _check(lib().apd_upload_mask(self._h, _ptr(m)))
+
+    def masked_count(self):
+        return lib().apd_masked_count(self._h)
+
     def run(self):
         _check(lib().apd_run(self._h))
         self.synchronize()
@@ -389,6 +409,10 @@ class Handle:
     def export_depth_normal(self, depth_dev, normal_dev=None):
         """depth_dev / normal_dev: torch CUDA tensors ([H,W] and [H,W,3] float32)."""
         _check(lib().apd_export_depth_normal_device(self._h, _ptr(depth_dev), _ptr(normal_dev)))
+
+    def export_state(self, planes_dev=None, weak_dev=None, views_dev=None, depth_dev=None):
+        """apd_export_state_device: torch CUDA tensors ([H,W,4] float32, [H,W] uint8, [H,W] int32, [H,W] float32) or None."""
+        _check(lib().apd_export_state_device(self._h, _ptr(planes_dev), _ptr(weak_dev), _ptr(views_dev), _ptr(depth_dev)))
 
     @property
     def weak_count(self):

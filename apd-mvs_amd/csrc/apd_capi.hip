@@ -23,6 +23,9 @@ size_t weak_list_scratch_ints(int W, int H);
 hipError_t build_weak_lists(const FrameArgs &fa, bool all_rows, int *const list[2], int *scratch, int counts[2], hipStream_t s);
 hipError_t launch_export_depth_normal(const FrameArgs &fa, float *depth, float *normal, hipStream_t s);
 hipError_t launch_export_state(const FrameArgs &fa, float4 *planes4, uint8_t *weak, uint32_t *views, float *depth, hipStream_t s);
+hipError_t launch_masked_download(const FrameArgs &fa, float4 *planes4, uint8_t *weak, uint32_t *views, hipStream_t s);
+hipError_t launch_mask_weak_info(const uint8_t *mask, uint8_t *weak, int n, hipStream_t s);
+hipError_t launch_mask_count(const uint8_t *mask, int n, int *count, hipStream_t s);
 hipError_t launch_check_u8(const float *img, int n, int *flag, hipStream_t s);
 hipError_t launch_weak_index_map(const uint8_t *weak, size_t n, int *map, int *scratch, hipStream_t s);
 hipError_t launch_pack_quads(const float *img, int W, int H, quad_t *quad, hipStream_t s);
@@ -109,6 +112,15 @@ struct apd_context {
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     hipEvent_t export_event = nullptr;   // recorded behind the kernel of the last export (apd_export_event)
+    // per-view pixel mask (apd_upload_mask): the buffer is kept across apd_reset, the mask is not
+    uint8_t *mask = nullptr;
+    bool have_mask = false;
+    int masked_count = 0;
+    bool pass_started = false;        // a kernel of this pass has been launched: the mask can no longer change
+    int *mask_scratch = nullptr;      // masked-pixel count / block sums of the weak index map rebuilt under a mask
+    float4 *dl_planes = nullptr;      // apd_download under a mask: the arrays with the masked pixels cleared
+    uint32_t *dl_views = nullptr;
+    uint8_t *dl_weak = nullptr;
 };
 
 static int record_export(apd_context *c)
@@ -237,6 +249,7 @@ static void refresh_frame_args(apd_context *c)
     fa.neighbours_map = c->neighbours_map;
     fa.neighbours = c->neighbours;
     fa.early_out = c->options[APD_OPT_EARLY_OUT];
+    fa.mask = c->have_mask ? c->mask : nullptr;
 }
 
 extern "C" {
@@ -396,6 +409,9 @@ int apd_reset(apd_handle c, const apd_params *params)
     c->weak_lists_valid = false;
     c->weak_map_stale = false;
     c->first_half_done = false;
+    c->have_mask = false;
+    c->masked_count = 0;
+    c->pass_started = false;
     const int st = initial_state(c);
     if (st != APD_OK) {
         return st;
@@ -443,6 +459,11 @@ int apd_destroy(apd_handle c)
     hipFree(c->weak_list_scratch);
     hipFree(c->neighbours_map);
     hipFree(c->neighbours);
+    hipFree(c->mask);
+    hipFree(c->mask_scratch);
+    hipFree(c->dl_planes);
+    hipFree(c->dl_views);
+    hipFree(c->dl_weak);
     if (c->export_event) {
         hipEventDestroy(c->export_event);
     }
@@ -841,6 +862,43 @@ int apd_upload_depths(apd_handle c, int num_images, const float *const *depths)
     return APD_OK;
 }
 
+static int ensure_mask_scratch(apd_context *c);
+
+int apd_upload_mask(apd_handle c, const uint8_t *mask)
+{
+    if (!c) {
+        return fail(APD_ERR_INVALID, "apd_upload_mask: null handle");
+    }
+    if (c->pass_started) {
+        return fail(APD_ERR_STATE, "apd_upload_mask: a kernel of this pass has already run; the mask is set after apd_create / apd_reset "
+                                   "and before the first kernel");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    c->have_mask = false;
+    c->masked_count = 0;
+    if (mask) {
+        const size_t n = (size_t)c->W * c->H;
+        if (!c->mask) {
+            HIP_TRY(hipMalloc(&c->mask, n));
+        }
+        if (int rc = ensure_mask_scratch(c)) {
+            return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(c->mask, mask, n, hipMemcpyDefault, c->stream));
+        HIP_TRY(hipMemsetAsync(c->mask_scratch, 0, sizeof(int), c->stream));
+        HIP_TRY(apd::launch_mask_count(c->mask, (int)n, c->mask_scratch, c->stream));
+        int count = 0;
+        HIP_TRY(hipMemcpyAsync(&count, c->mask_scratch, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->masked_count = count;
+        c->have_mask = true;
+    }
+    refresh_frame_args(c);
+    return APD_OK;
+}
+
+int apd_masked_count(apd_handle c) { return c ? c->masked_count : 0; }
+
 int apd_upload_prior(apd_handle c, const float *planes4, const uint32_t *selected_views, const uint8_t *weak_info)
 {
     if (!c) {
@@ -886,6 +944,7 @@ int apd_upload_prior(apd_handle c, const float *planes4, const uint32_t *selecte
     c->weak_lists_valid = false;
     c->weak_map_stale = false;
     c->first_half_done = false;
+    c->pass_started = false;   // a mask (apd_upload_mask, before or after this call) is applied to the new weak map by the first kernel
     if (need > c->weak_list_cap) {  // one colour holds at most every WEAK pixel of the map uploaded above (K4 only removes some)
         for (int k = 0; k < 2; ++k) {
             hipFree(c->weak_list[k]);
@@ -905,6 +964,43 @@ int apd_upload_prior(apd_handle c, const float *planes4, const uint32_t *selecte
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->prior_uploaded = true;
     refresh_frame_args(c);
+    return APD_OK;
+}
+
+static size_t mask_scratch_ints(size_t n) { return (n + 4095) / 4096 + 2; }
+
+static int ensure_mask_scratch(apd_context *c)
+{
+    if (!c->mask_scratch) {
+        HIP_TRY(hipMalloc(&c->mask_scratch, mask_scratch_ints((size_t)c->W * c->H) * sizeof(int)));
+    }
+    return APD_OK;
+}
+
+// Before the first kernel of a pass: the masked pixels of weak_info become APD_UNKNOWN, and the weak index map and the WEAK
+// count are what apd_upload_prior would have built from that map (APD.cpp:526-537).  Done here, not in the uploads, so that
+// apd_upload_mask and apd_upload_prior may come in either order and apd_upload_mask(NULL) leaves nothing behind.
+static int begin_pass(apd_context *c)
+{
+    if (c->pass_started) {
+        return APD_OK;
+    }
+    if (c->have_mask) {
+        const size_t n = (size_t)c->W * c->H;
+        HIP_TRY(apd::launch_mask_weak_info(c->mask, c->weak_info, (int)n, c->stream));
+        if (c->weak_count > 0) {
+            if (int rc = ensure_mask_scratch(c)) {
+                return rc;
+            }
+            HIP_TRY(apd::launch_weak_index_map(c->weak_info, n, c->neighbours_map, c->mask_scratch, c->stream));
+            int count = 0;
+            HIP_TRY(hipMemcpyAsync(&count, c->mask_scratch + (n + 4095) / 4096, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            c->weak_count = count;
+        }
+        c->weak_lists_valid = false;
+    }
+    c->pass_started = true;
     return APD_OK;
 }
 
@@ -1024,6 +1120,9 @@ int apd_run_kernel(apd_handle c, int kernel_id, int iter)
     if (kernel_id < 1 || kernel_id >= APD_KERNEL_COUNT) {
         return fail(APD_ERR_INVALID, "apd_run_kernel: unknown kernel %d", kernel_id);
     }
+    if ((rc = begin_pass(c))) {
+        return rc;
+    }
     return launch_one(c, kernel_id, iter);
 }
 
@@ -1031,6 +1130,9 @@ int apd_run_sweeps(apd_handle c, int first_iter, int iters)
 {
     int rc = check_ready(c, "apd_run_sweeps");
     if (rc) {
+        return rc;
+    }
+    if ((rc = begin_pass(c))) {
         return rc;
     }
     for (int i = first_iter; i < first_iter + iters; ++i) {  // APD.cu:2443-2457
@@ -1126,6 +1228,9 @@ int apd_run(apd_handle c)
     if (c->first_half_done) {
         return fail(APD_ERR_STATE, "apd_run: apd_run_before_depths already ran on this upload; finish the pass with apd_run_after_depths");
     }
+    if ((rc = begin_pass(c))) {
+        return rc;
+    }
     return run_schedule(c, true, true);
 }
 
@@ -1137,6 +1242,9 @@ int apd_run_before_depths(apd_handle c)
     }
     if (c->first_half_done) {
         return fail(APD_ERR_STATE, "apd_run_before_depths: already ran on this upload");
+    }
+    if ((rc = begin_pass(c))) {
+        return rc;
     }
     rc = run_schedule(c, true, false);
     c->first_half_done = rc == APD_OK;
@@ -1178,6 +1286,31 @@ int apd_download(apd_handle c, float *planes4, uint8_t *weak_info, uint32_t *sel
     }
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->W * c->H;
+    if (c->have_mask) {  // masked pixels leave as plane 0, UNKNOWN, views 0: cleared on the device, then the same three copies
+        if (planes4 && !c->dl_planes) {
+            HIP_TRY(hipMalloc(&c->dl_planes, n * sizeof(float4)));
+        }
+        if (weak_info && !c->dl_weak) {
+            HIP_TRY(hipMalloc(&c->dl_weak, n));
+        }
+        if (selected_views && !c->dl_views) {
+            HIP_TRY(hipMalloc(&c->dl_views, n * sizeof(uint32_t)));
+        }
+        HIP_TRY(apd::launch_masked_download(c->fa, planes4 ? c->dl_planes : nullptr, weak_info ? c->dl_weak : nullptr,
+                                            selected_views ? c->dl_views : nullptr, c->stream));
+        if (planes4) {
+            HIP_TRY(hipMemcpyAsync(planes4, c->dl_planes, n * sizeof(float4), hipMemcpyDefault, c->stream));
+        }
+        if (weak_info) {
+            HIP_TRY(hipMemcpyAsync(weak_info, c->dl_weak, n, hipMemcpyDefault, c->stream));
+        }
+        if (selected_views) {
+            HIP_TRY(hipMemcpyAsync(selected_views, c->dl_views, n * sizeof(uint32_t), hipMemcpyDefault, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        drain_profile(c);
+        return APD_OK;
+    }
     // APD.cu:2490-2492
     if (planes4) {
         HIP_TRY(hipMemcpyAsync(planes4, c->planes, n * sizeof(float4), hipMemcpyDefault, c->stream));

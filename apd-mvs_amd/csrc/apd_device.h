@@ -124,7 +124,15 @@ struct FrameArgs {
     short2 *neighbours;      // 9 per weak pixel
     int early_out;           // 1 (default): the exact early-outs of the refinement loops, K14 and K15; APD_OPT_EARLY_OUT = 0
                              // evaluates every NCC the reference evaluates (A/B runs and the parity test; same results)
+    const uint8_t *mask;     // apd_upload_mask: W*H bytes, 0 = masked out (K6..K8, K11..K15 and the WEAK lists of K3, K9, K10 leave the pixel alone); nullptr: no mask
 };
+
+// Per-view pixel mask (apd_upload_mask).  The pointer is a kernel argument, so the test for "no mask" is wave-uniform (a scalar
+// branch) and the byte is only loaded when a mask exists.
+__device__ __forceinline__ bool masked_out(const FrameArgs &fa, int center)
+{
+    return fa.mask != nullptr && fa.mask[center] == 0;
+}
 
 // The per-view constants are read-only for every kernel and the view index is wave-uniform wherever it is used: reading the
 // table through the constant address space lets the compiler use scalar loads (s_load_dword*) into SGPRs.  Through the

@@ -67,6 +67,12 @@ __global__ __launch_bounds__(256) void k_export_state(FrameArgs fa, float4 *plan
         pl.w = 0.0f;
         w = APD_UNKNOWN;
     }
+    uint32_t sv = fa.selected_views[center];
+    if (masked_out(fa, center)) {  // apd_upload_mask: a masked pixel carries no estimate
+        pl = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        w = APD_UNKNOWN;
+        sv = 0;
+    }
     if (planes4) {
         planes4[center] = pl;
     }
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(256) void k_export_state(FrameArgs fa, float4 *plan
         weak[center] = w;
     }
     if (views) {
-        views[center] = fa.selected_views[center];
+        views[center] = sv;
     }
     if (depth) {
         depth[center] = pl.w;
@@ -84,6 +90,66 @@ __global__ __launch_bounds__(256) void k_export_state(FrameArgs fa, float4 *plan
 hipError_t launch_export_state(const FrameArgs &fa, float4 *planes4, uint8_t *weak, uint32_t *views, float *depth, hipStream_t s)
 {
     hipLaunchKernelGGL(k_export_state, dim3((fa.W * fa.H + 255) / 256), dim3(256), 0, s, fa, planes4, weak, views, depth);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-view pixel masks (apd_upload_mask)
+// ------------------------------------------------------------------------------------------------
+
+// apd_download of a handle with a mask: the three state arrays as they are, except at masked pixels (plane 0, UNKNOWN, views 0).
+__global__ __launch_bounds__(256) void k_masked_download(FrameArgs fa, float4 *planes4, uint8_t *weak, uint32_t *views)
+{
+    const int center = blockIdx.x * 256 + threadIdx.x;
+    if (center >= fa.W * fa.H) {
+        return;
+    }
+    const bool out = masked_out(fa, center);
+    if (planes4) {
+        planes4[center] = out ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : fa.planes[center];
+    }
+    if (weak) {
+        weak[center] = out ? (uint8_t)APD_UNKNOWN : fa.weak_info[center];
+    }
+    if (views) {
+        views[center] = out ? 0u : fa.selected_views[center];
+    }
+}
+
+hipError_t launch_masked_download(const FrameArgs &fa, float4 *planes4, uint8_t *weak, uint32_t *views, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_masked_download, dim3((fa.W * fa.H + 255) / 256), dim3(256), 0, s, fa, planes4, weak, views);
+    return hipGetLastError();
+}
+
+// Masked pixels become APD_UNKNOWN before the schedule starts: never WEAK (no list entry, no neighbours), never a STRONG partner.
+__global__ __launch_bounds__(256) void k_mask_weak_info(const uint8_t *__restrict__ mask, uint8_t *__restrict__ weak, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n && mask[i] == 0) {
+        weak[i] = APD_UNKNOWN;
+    }
+}
+
+hipError_t launch_mask_weak_info(const uint8_t *mask, uint8_t *weak, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_mask_weak_info, dim3((n + 255) / 256), dim3(256), 0, s, mask, weak, n);
+    return hipGetLastError();
+}
+
+// *count += number of zero bytes of the mask (one atomic per wave)
+__global__ __launch_bounds__(256) void k_mask_count(const uint8_t *__restrict__ mask, int n, int *count)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long m = __ballot(i < n && mask[i] == 0);
+    if ((threadIdx.x & 63) == 0 && m != 0) {
+        atomicAdd(count, __popcll(m));
+    }
+}
+
+hipError_t launch_mask_count(const uint8_t *mask, int n, int *count, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_mask_count, dim3((n + 255) / 256), dim3(256), 0, s, mask, n, count);
     return hipGetLastError();
 }
 

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256, APD_K67_WAVES) void k67_update_strong(FrameArg
     }
     const int px = t.px, py = t.py;
     const int center = py * fa.W + px;
-    if (fa.weak_info[center] == APD_WEAK) {
+    if (fa.weak_info[center] == APD_WEAK || masked_out(fa, center)) {
         return;
     }
     // the 36 reference texels stay in the LDS tile (one ds_read per sample); only their moments live in registers
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(256, APD_K67_WAVES) void k67_update_strong(FrameArg
 __global__ __launch_bounds__(256) void k11_depth_and_normal(FrameArgs fa)
 {
     const int center = blockIdx.x * 256 + threadIdx.x;
-    if (center >= fa.W * fa.H) {
+    if (center >= fa.W * fa.H || masked_out(fa, center)) {
         return;
     }
     const int py = center / fa.W, px = center - py * fa.W;
@@ -434,7 +434,7 @@ __global__ __launch_bounds__(256) void k1213_filter_strong(FrameArgs fa, int col
     }
     const int px = t.px, py = t.py, W = fa.W;
     const int center = py * W + px;
-    if (fa.weak_info[center] == APD_WEAK) {
+    if (fa.weak_info[center] == APD_WEAK || masked_out(fa, center)) {
         return;
     }
     if (fa.costs[center] < 0.001f) {
@@ -528,6 +528,9 @@ __global__ __launch_bounds__(256) void k14_depth_to_weak(FrameArgs fa)
     const int W = fa.W, H = fa.H;
     const int min_margin = 6;
     const int center = px + py * W;
+    if (masked_out(fa, center)) {
+        return;
+    }
     if (px < min_margin || py < min_margin || px >= W - min_margin || py >= H - min_margin) {
         fa.weak_info[center] = APD_UNKNOWN;
         return;
@@ -608,6 +611,9 @@ __global__ __launch_bounds__(256) void k15_local_refine(FrameArgs fa)
     }
     const int W = fa.W;
     const int center = px + py * W;
+    if (masked_out(fa, center)) {
+        return;
+    }
     const float4 origin = normal_world_to_cam(fa, fa.planes[center]);
     const float origin_depth = origin.w;
     if (origin_depth == 0) {

@@ -133,6 +133,7 @@ __global__ __launch_bounds__(256, kQuad ? APD_K14W_WAVES : APD_K1415W_WAVES_F32)
 
     // lanes without depth samples to score stay in the wave: every lane helps to stage the windows
     bool alive = px < W && py < H;
+    alive = alive && !masked_out(fa, center);
     float4 origin = make_float4(0.0f, 0.0f, 1.0f, 1.0f);
     uint32_t sel = 0;
     ViewWeights<32> vw;
@@ -428,6 +429,7 @@ __global__ __launch_bounds__(256, kQuad ? APD_K15W_WAVES : APD_K1415W_WAVES_F32)
     constexpr int RADIUS = 5, NP = 2 * RADIUS + 1;
 
     bool alive = px < W && py < H;
+    alive = alive && !masked_out(fa, center);
     float4 origin = make_float4(0.0f, 0.0f, 1.0f, 1.0f);
     uint32_t sel = 0;
     ViewWeights<32> vw;

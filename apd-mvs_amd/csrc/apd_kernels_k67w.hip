@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256, kQuad ? APD_K67W_WAVES : APD_K67W_WAVES_F32) v
     const int px = t.px, py = t.py;
     const int center = py * fa.W + px;
     // lanes without a pixel to update stay in the wave: every lane helps to stage the windows
-    const bool alive = checkerboard_active(fa, t) && fa.weak_info[center] != APD_WEAK;
+    const bool alive = checkerboard_active(fa, t) && fa.weak_info[center] != APD_WEAK && !masked_out(fa, center);
     if (__builtin_amdgcn_ballot_w64(alive) == 0) {
         return;
     }

@@ -380,7 +380,7 @@ __global__ __launch_bounds__(256) void k8_ransac_fit_plane(FrameArgs fa)
     const int lane = threadIdx.x;
     const int center = blockIdx.x * 256 + threadIdx.x;
     const int W = fa.W;
-    if (center >= W * fa.H) {
+    if (center >= W * fa.H || masked_out(fa, center)) {  // a masked pixel is never WEAK, and its fit plane stays what K5 left
         return;
     }
     const float4 pl = fa.planes[center];
@@ -739,7 +739,7 @@ __device__ __forceinline__ bool weak_pixel_of_lane(const FrameArgs &fa, const Ti
     const int py = ty * kListTileH + (lane >> 3);
     const int px = tx * kListTileW + 2 * (lane & 7) + ((py + colour) & 1);
     center = py * fa.W + px;
-    return tx < o.tiles_x && ty < o.tiles_y && px < fa.W && py < row_limit && fa.weak_info[center] == APD_WEAK;
+    return tx < o.tiles_x && ty < o.tiles_y && px < fa.W && py < row_limit && fa.weak_info[center] == APD_WEAK && !masked_out(fa, center);
 }
 
 // pass 1: WEAK pixels of `colour` per ordered tile -> exclusive offsets inside a block of 64 tiles + the block's total
@@ -1304,9 +1304,13 @@ __global__ __launch_bounds__(256) void k_export_depth_normal(FrameArgs fa, float
     if (center >= fa.W * fa.H) {
         return;
     }
-    const float4 pl = fa.planes[center];
+    float4 pl = fa.planes[center];
     float d = pl.w;
     if (d < fa.depth_min || d > fa.depth_max) {
+        d = 0.0f;
+    }
+    if (masked_out(fa, center)) {  // apd_upload_mask: depth 0, normal (0,0,0)
+        pl = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         d = 0.0f;
     }
     depth[center] = d;

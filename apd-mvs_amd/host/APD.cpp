@@ -296,6 +296,38 @@ static bool read_gray_image_uncached(const path &stem, Mat &image_float)
     return false;
 }
 
+int ReadMaskFile(const path &stem, Mat &mask, std::string &file)
+{
+    path p = stem;
+    p += ".jpg";
+    if (!std::filesystem::exists(p)) {
+        p = stem;
+        p += ".pgm";
+        if (!std::filesystem::exists(p)) {
+            file = stem.string() + ".{jpg,pgm}";
+            return 0;
+        }
+    }
+    file = p.string();
+    Mat grey;
+    if (!ReadGrayImageShared(stem, grey) || grey.empty()) {
+        return -1;
+    }
+    mask.create(grey.rows, grey.cols, MAT_8UC1);
+    const float *g = grey.ptr<float>();
+    uint8_t *m = mask.ptr<uint8_t>();
+    for (size_t k = 0, n = (size_t)grey.rows * grey.cols; k < n; ++k) {
+        m[k] = g[k] < 128.0f ? 0 : 255;   // the threshold of the reference's block masks (APD.cpp:875)
+    }
+    return 1;
+}
+
+void LevelMask(const Mat &full, Mat &level, int width, int height)
+{
+    level = full.clone();
+    RescaleMatToTargetSize<uint8_t>(level, level, width, height);   // returns at once when the size already fits
+}
+
 // cv::imread(IMREAD_COLOR) of `images/%08d.jpg` as the fusion reads it (APD.cpp:859): 3 x float per pixel, blue first.
 // `.pgm` (grey: B = G = R) and binary `.ppm` (P6) are accepted too.
 bool ReadColorImage(const path &stem, Mat &image_bgr)
@@ -473,6 +505,30 @@ void APD::InuputInitialization()
     LoadGeometricDepths();
     LoadWeakMap();
     LoadPriorState();
+    LoadMask();
+}
+
+// The view's pixel mask (additive, Problem::masks_dir) at this pyramid level.  main() has checked every mask file against its
+// image before the first pass; a caller that drives the class directly gets the same refusal here.
+void APD::LoadMask()
+{
+    mask_host = Mat();
+    if (problem.masks_dir.empty()) {
+        return;
+    }
+    Mat full;
+    std::string file;
+    const int rc = ReadMaskFile(problem.dense_folder / path(problem.masks_dir) / path(ToFormatIndex(problem.ref_image_id)), full, file);
+    if (rc == 0) {
+        return;
+    }
+    Mat ref_full;
+    if (rc < 0 || !ReadGrayImageShared(problem.dense_folder / path("images") / path(ToFormatIndex(problem.ref_image_id)), ref_full) ||
+        full.cols != ref_full.cols || full.rows != ref_full.rows) {
+        std::cerr << "Mask " << file << " is unreadable or not of the size of its image\n";
+        exit(EXIT_FAILURE);
+    }
+    LevelMask(full, mask_host, width, height);
 }
 
 // Reference image first, then the sources in pair.txt order, with their cameras (APD.cpp:409-461); the depth search range
@@ -710,6 +766,9 @@ void APD::CudaSpaceInitialization()
                                      has_prior ? selected_views_host.ptr<uint32_t>() : nullptr,
                                      params_host.use_APD ? weak_info_host.ptr<uint8_t>() : nullptr),
                     "apd_upload_prior");
+    }
+    if (!mask_host.empty()) {
+        ApdSafeCall(apd_upload_mask(handle, mask_host.ptr<uint8_t>()), "apd_upload_mask");
     }
 }
 

@@ -67,6 +67,9 @@ struct Problem {
     PatchMatchParams params;
     bool show_medium_result = false;
     int iteration = 0;
+    // additive: per-view pixel masks <dense_folder>/<masks_dir>/<%08d>.jpg|pgm (grey < 128 = masked out of PatchMatch,
+    // apd_upload_mask); empty: no masks, nothing is read
+    std::string masks_dir;
 };
 
 // OpenCV type codes used by the .dmb/.bin files (APD.cpp:3-49)
@@ -134,6 +137,12 @@ bool ReadGrayImage(const path &image_path_without_ext, Mat &image_float);
 bool ReadGrayImageShared(const path &image_path_without_ext, Mat &image_float);  // the process cache's own matrix: read only
 // the same file as cv::imread(IMREAD_COLOR) returns it (fusion colours, APD.cpp:859): MAT_32FC3, blue first
 bool ReadColorImage(const path &image_path_without_ext, Mat &image_bgr);
+// Per-view pixel masks (--masks, apd_upload_mask; the reference's only mask is the fusion's blocks/mask_<id>.jpg, APD.cpp:849-853).
+// ReadMaskFile: <stem>.jpg / .pgm as MAT_8UC1 with 0 where the grey value is below 128 (masked out) and 255 elsewhere; returns 1,
+// 0 when there is no such file (the view is unmasked) and -1 when the file cannot be decoded; `file` names the file looked at.
+// LevelMask: the full-resolution mask at a pyramid level, resampled like the state maps (RescaleMatToTargetSize).
+int ReadMaskFile(const path &mask_path_without_ext, Mat &mask, std::string &file);
+void LevelMask(const Mat &full, Mat &level, int width, int height);
 // host-side helpers of the drop-in (not in the reference): a small thread pool and a parallel warm-up of the image cache
 void ParallelFor(size_t count, const std::function<void(size_t)> &job, unsigned max_threads = 0);
 void PrefetchGrayImages(const path &image_folder, const std::vector<int> &ids);
@@ -177,6 +186,7 @@ private:
     void LoadGeometricDepths();
     void LoadWeakMap();
     void LoadPriorState();
+    void LoadMask();
 
     int num_images = 0;
     int width = 0;
@@ -191,6 +201,7 @@ private:
     std::vector<float4> plane_hypotheses_host;
     PatchMatchParams params_host;
     Mat selected_views_host;
+    Mat mask_host;   // the view's pixel mask at this level (Problem::masks_dir); empty: unmasked
     bool has_prior = false;
     apd_handle handle = nullptr;
 };

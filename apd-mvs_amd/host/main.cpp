@@ -1,7 +1,11 @@
 // main.cpp -- drop-in driver of the PatchMatch path.
 //
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
-//       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl]
+//       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
+//
+// --masks [DIR] (default DIR: masks): <dense_folder>/DIR/<%08d>.jpg|pgm are per-view pixel masks, grey < 128 = masked out of
+// PatchMatch (apd_upload_mask: the pixels cost no NCC and leave as depth 0 / UNKNOWN); a view without a file is unmasked, a file
+// of another size than its image is refused before anything is written.  Every driver takes it and writes the same bytes.
 //
 // One device index: the reference's driver.  A device LIST (or --jacobi): host/multi_device.cpp -- views sharded over the
 // devices, state resident on them, depth maps all-gathered after every pass (RCCL when there is more than one rank -- its set-up takes seconds
@@ -75,6 +79,11 @@ bool ParseOptions(int argc, char **argv, Options &o)
                 o.fusion_variant = APD_FUSION_TAT_ADVANCED;
             } else {
                 fprintf(stderr, "bad fusion '%s': eth, tat-intermediate or tat-advanced\n", name.c_str());
+                return false;
+            }
+        } else if (a == "--masks") {
+            o.masks_dir = (i + 1 < argc && argv[i + 1][0] != '-') ? argv[++i] : "masks";
+            if (o.masks_dir.empty()) {
                 return false;
             }
         } else if (a == "--late-fusion-inputs") {
@@ -254,7 +263,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -275,6 +284,28 @@ int main(int argc, char **argv)
     if (!why.empty()) {
         fprintf(stderr, "%s\n", why.c_str());
         return EXIT_FAILURE;
+    }
+    if (!opt.masks_dir.empty()) {   // every mask file against its image, before a result folder exists
+        for (Problem &p : problems) {
+            p.masks_dir = opt.masks_dir;
+            Mat mask, image;
+            std::string file;
+            const int rc = ReadMaskFile(opt.dense_folder / opt.masks_dir / ToFormatIndex(p.ref_image_id), mask, file);
+            if (rc == 0) {
+                continue;
+            }
+            if (rc < 0) {
+                fprintf(stderr, "cannot read mask %s\n", file.c_str());
+                return EXIT_FAILURE;
+            }
+            if (!ReadGrayImageShared(opt.dense_folder / "images" / ToFormatIndex(p.ref_image_id), image)) {
+                return EXIT_FAILURE;
+            }
+            if (mask.cols != image.cols || mask.rows != image.rows) {
+                fprintf(stderr, "mask %s is %dx%d, its image is %dx%d\n", file.c_str(), mask.cols, mask.rows, image.cols, image.rows);
+                return EXIT_FAILURE;
+            }
+        }
     }
     std::vector<int> ids;  // every image any pass will read
     for (Problem &p : problems) {

@@ -111,6 +111,7 @@ struct Rank {
     DeviceBuffer send, recv;             // depth blocks of the all-gather (float): this pass's own maps / every view's of the pass before
     DeviceBuffer zero_depth;             // a source-only view has no estimate
     std::unordered_map<int, ResidentView> state;
+    std::unordered_map<int, DeviceBuffer> mask;   // --masks: the level's pixel mask of every owned view that has one (1 B per pixel)
     std::atomic<int> next{0};            // next entry of `own` to hand to a lane
 };
 
@@ -177,12 +178,12 @@ int DefaultLanes(size_t pixels)
 // fusion_prefetch: the colour images (3 floats per pixel and view) and block masks (1 B) of the fusion are uploaded to the first
 // device WHILE the passes run (StartFusionInputs), so they count towards the passes' footprint, not only the final stage's.
 double InMemoryBytesPerPixel(int num_images, int num_views, int num_ranks, int lanes, int max_sources, double *passes_out, double *final_out,
-                             bool fusion_prefetch)
+                             bool fusion_prefetch, bool masks)
 {
     const double slots = (double)((num_views + num_ranks - 1) / num_ranks);
     const double m = (double)max_sources;
     const double passes = 8.5 * num_images + 4.0 * slots * (1.0 + num_ranks) + 4.0 + 21.0 * slots + lanes * (21.0 + 107.0 + 25.0 + 4.0 * (m + 1.0)) +
-                          (fusion_prefetch ? 13.0 * num_views : 0.0);
+                          (fusion_prefetch ? 13.0 * num_views : 0.0) + (masks ? 1.0 * slots + 1.0 * lanes : 0.0);   // + a handle's own copy
     const double final_stage = 21.0 * slots + (num_ranks > 1 ? 17.0 * slots * num_ranks : 0.0) + 16.0 * num_views + 21.0 * num_views + 8.0 * m + 40.0;
     if (passes_out) {
         *passes_out = passes;
@@ -217,7 +218,7 @@ InMemoryFit TestInMemoryFit(const Options &opt, int device, int width, int heigh
     double per_px_passes = 0, per_px_final = 0;
     const double pixels = (double)width * (double)height;
     const bool prefetch = !(opt.no_fusion || opt.late_fusion_inputs);
-    fit.need_bytes = pixels * InMemoryBytesPerPixel(num_images, num_views, num_ranks, lanes, max_sources, &per_px_passes, &per_px_final, prefetch);
+    fit.need_bytes = pixels * InMemoryBytesPerPixel(num_images, num_views, num_ranks, lanes, max_sources, &per_px_passes, &per_px_final, prefetch, !opt.masks_dir.empty());
     fit.have_memory = apd_device_memory(device, &free_bytes, &total_bytes) == APD_OK;
     if (fit.have_memory && opt.scheduler_free_gb > 0) {
         free_bytes = std::min(free_bytes, (size_t)(opt.scheduler_free_gb * 1e9));
@@ -275,6 +276,17 @@ int RunMultiDevice(const Options &opt, std::vector<Problem> &problems)
         if (failed[i] || full[i].cols != full[0].cols || full[i].rows != full[0].rows) {
             fprintf(stderr, "Images may error, check it! (image %d)\n", ids[i]);  // main.cpp:158
             return EXIT_FAILURE;
+        }
+    }
+    std::vector<Mat> full_mask(V);   // --masks: full-resolution masks of the reference views (empty: unmasked)
+    if (!opt.masks_dir.empty()) {
+        for (int v = 0; v < V; ++v) {
+            std::string file;
+            const int rc = ReadMaskFile(opt.dense_folder / opt.masks_dir / ToFormatIndex(ids[v]), full_mask[v], file);
+            if (rc < 0 || (rc > 0 && (full_mask[v].cols != full[v].cols || full_mask[v].rows != full[v].rows))) {
+                fprintf(stderr, "mask %s is unreadable or not of the size of its image\n", file.c_str());
+                return EXIT_FAILURE;
+            }
         }
     }
     ms_load = stage.lap();
@@ -347,6 +359,9 @@ int RunMultiDevice(const Options &opt, std::vector<Problem> &problems)
                 l.scratch_views.alloc(k.device, pix0 * 4);
             }
             for (int v : k.own) {
+                if (!full_mask[v].empty()) {
+                    k.mask[v].alloc(k.device, pix0);
+                }
                 ResidentView &s = k.state[v];
                 s.planes.alloc(k.device, pix0 * 16);
                 s.weak.alloc(k.device, pix0);
@@ -431,6 +446,13 @@ int RunMultiDevice(const Options &opt, std::vector<Problem> &problems)
                     apd_host_unregister(level[i].data());
                 }
             }
+            for (Rank &k : ranks) {   // the masks of the level, resident beside the level images
+                for (auto &entry : k.mask) {
+                    Mat level_mask;
+                    LevelMask(full_mask[entry.first], level_mask, LW, LH);
+                    Check(apd_device_memcpy(k.device, entry.second.p, level_mask.data(), (size_t)LW * LH), "upload of a level mask");
+                }
+            }
             if (failure.failed) {
                 throw std::runtime_error(failure.what);
             }
@@ -509,6 +531,12 @@ int RunMultiDevice(const Options &opt, std::vector<Problem> &problems)
                 }
                 Check(apd_upload_prior(lane.handle, s.planes.as<float>(), s.views.as<uint32_t>(), pass.use_APD ? s.weak.as<uint8_t>() : nullptr),
                       "apd_upload_prior");
+            }
+            {
+                const auto m = k.mask.find(v);
+                if (m != k.mask.end()) {   // apd_reset has forgotten the mask of the handle's previous (view, pass)
+                    Check(apd_upload_mask(lane.handle, m->second.as<uint8_t>()), "apd_upload_mask");
+                }
             }
             Check(apd_run_before_depths(lane.handle), "apd_run_before_depths");
             if (pass.geom_consistency) {

@@ -31,6 +31,7 @@ struct Options {
     bool clean_exit = false;          // --clean-exit: return from main() instead of _Exit (exit handlers run: profilers)
     double scheduler_free_gb = 0;     // --scheduler-free-gb X: RunMultiDevice's own fit test counts at most X GB of free device memory (main()'s
                                       // choice of scheduler still uses the device's figure: this is how a test reaches the fall-back to files)
+    std::string masks_dir;            // --masks [DIR]: per-view pixel masks <dense_folder>/DIR/<%08d>.jpg|pgm (default DIR: masks); empty: none
     bool late_fusion_inputs = false;  // --late-fusion-inputs: colour decode + upload after the passes instead of behind them (A/B measurements)
 };
 
@@ -123,7 +124,7 @@ int RunMultiDevice(const Options &opt, std::vector<Problem> &problems);
 int DefaultLanes(size_t pixels);
 int InMemoryLanes(const Options &opt, int width, int height, int num_views, int num_ranks, bool distinct_devices);
 double InMemoryBytesPerPixel(int num_images, int num_views, int num_ranks, int lanes, int max_sources, double *passes_out = nullptr,
-                             double *final_out = nullptr, bool fusion_prefetch = false);
+                             double *final_out = nullptr, bool fusion_prefetch = false, bool masks = false);
 // The scheduler's fit test, ONE function for main()'s choice of scheduler and for RunMultiDevice's own check: bytes the run keeps resident on
 // `device` (its busiest one) against 90 % of the free device memory, the latter capped by --scheduler-free-gb.
 struct InMemoryFit {

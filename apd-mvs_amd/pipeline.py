@@ -33,10 +33,13 @@ class MvsScene:
     Views 0 .. num_views-1 are reference views (one pair.txt entry each).  Further cameras / images, if any, are SOURCE-ONLY
     views: images that pair.txt lists as sources but that have no entry of their own (a subset run).  The reference simply
     loads them (APD.cpp:419-452); they are never processed, contribute no depth map to the geometric term (the reference
-    reads a file that does not exist there, APD.cpp:497-500) and take no part in the fusion."""
+    reads a file that does not exist there, APD.cpp:497-500) and take no part in the fusion.
+    masks[i], optional: uint8 [H, W] at full resolution, non-zero = process, zero = masked out (apd_upload_mask); None for a
+    view without a mask, and `masks` itself may be None."""
     cameras: list
     images: list
     pairs: list
+    masks: list = None
 
     @property
     def num_views(self):
@@ -138,6 +141,19 @@ def rescale_nearest(src, target_width, target_height):
     return out
 
 
+MASK_THRESHOLD = 128   # grey value below which a pixel of a mask file is masked out (the reference's block masks, APD.cpp:849-853)
+
+
+def mask_from_grey(grey):
+    """Mask file -> uint8 mask: 255 where the grey value is >= 128 (process), 0 below (masked out)."""
+    return np.where(np.asarray(grey) < MASK_THRESHOLD, 0, 255).astype(np.uint8)
+
+
+def level_mask(mask, width, height):
+    """The full-resolution mask of a view at a pyramid level of width x height: RescaleMatToTargetSize, one byte per pixel."""
+    return np.ascontiguousarray(rescale_nearest(np.ascontiguousarray(mask, np.uint8), width, height))
+
+
 def level_inputs(scene, scale_size, camera_type):
     """Scaled images and intrinsics of one pyramid level (APD.cpp:464-488): every image by its own rounded size."""
     cams, imgs = [], []
@@ -181,7 +197,7 @@ class HipBackend:
     def camera_type(self):
         return self.pkg.Camera
 
-    def run_pass(self, width, height, params, cameras, images, depths, prior):
+    def run_pass(self, width, height, params, cameras, images, depths, prior, mask=None):
         import torch
         # the inputs were produced on torch's stream, the handle copies and computes on its own: hand over on the host
         torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
@@ -197,6 +213,8 @@ class HipBackend:
         h.upload_views(cameras, images, depths)
         if prior is not None:
             h.upload_prior(*prior)
+        if mask is not None:   # apd_reset has forgotten the mask of the handle's previous (view, pass)
+            h.upload_mask(mask)
         h.run()
         return h.download_device()
 
@@ -231,25 +249,30 @@ def run_pipeline(scene, backend, iters=3, seed=12345, single_level=False, group=
             t = t.to(dtype)
         return t.to(device)
 
-    def call_backend(W, H, p, cams_, imgs_, depths_, prior_):
+    def call_backend(W, H, p, cams_, imgs_, depths_, prior_, mask_=None):
+        # the mask travels as a keyword, and only for a view that has one: a backend without masks keeps working for unmasked scenes
+        kw = {} if mask_ is None else {"mask": mask_ if tensors_in else mask_.contiguous().numpy()}
         if tensors_in:
-            return backend.run_pass(W, H, p, cams_, imgs_, depths_, prior_)
+            return backend.run_pass(W, H, p, cams_, imgs_, depths_, prior_, **kw)
         # numpy backend (the CPU oracle in the tests): zero-copy views of the CPU tensors
         npy = lambda t: None if t is None else t.contiguous().numpy()
         pr = None if prior_ is None else (npy(prior_[0]), None if prior_[1] is None else npy(prior_[1]).view(np.uint32), npy(prior_[2]))
         planes, weak, views = backend.run_pass(W, H, p, cams_, [npy(t) for t in imgs_],
-                                               None if depths_ is None else [npy(t) for t in depths_], pr)
+                                               None if depths_ is None else [npy(t) for t in depths_], pr, **kw)
         return to_dev(planes), to_dev(weak), to_dev(views.view(np.int32))
 
     state = {}        # own views: (planes4 = world normal xyz + depth w, weak, views as int32 bits) at the level last written
     depth_store = {}  # every view's depth map as this rank knows it
     level_cache = {}
+    masks = getattr(scene, "masks", None) or [None] * V
     for spec in schedule:
         if spec.scale_size not in level_cache:
             level_cache.clear()
             cams, imgs = level_inputs(scene, spec.scale_size, backend.camera_type)
-            level_cache[spec.scale_size] = (cams, [to_dev(im) for im in imgs])
-        cams, imgs = level_cache[spec.scale_size]
+            # the masks of the level: nearest-neighbour like the state maps (RescaleMatToTargetSize, APD.cpp:752-774)
+            lmasks = [None if masks[v] is None else to_dev(level_mask(masks[v], cams[v].width, cams[v].height)) for v in range(V)]
+            level_cache[spec.scale_size] = (cams, [to_dev(im) for im in imgs], lmasks)
+        cams, imgs, lmasks = level_cache[spec.scale_size]
         for idx in mine:
             order = [idx] + list(scene.pairs[idx])
             W, H = cams[idx].width, cams[idx].height
@@ -269,7 +292,7 @@ def run_pipeline(scene, backend, iters=3, seed=12345, single_level=False, group=
                 planes0, weak0, views0 = state[idx]
                 prior = (rescale_nearest(planes0, W, H).contiguous(), rescale_nearest(views0, W, H).contiguous(),
                          rescale_nearest(weak0, W, H).contiguous() if p["use_APD"] else None)
-            planes, weak, views = call_backend(W, H, p, [cams[j] for j in order], [imgs[j] for j in order], depths, prior)
+            planes, weak, views = call_backend(W, H, p, [cams[j] for j in order], [imgs[j] for j in order], depths, prior, lmasks[idx])
             d = planes[..., 3]
             bad = (d < p["depth_min"]) | (d > p["depth_max"])   # main.cpp:109-112 (float32 comparisons)
             d.masked_fill_(bad, 0)      # in place on the strided view; no host synchronisation (unlike d[bad] = 0)
@@ -346,9 +369,30 @@ def host_lib():
     return _host
 
 
-def load_dense_folder(folder, camera_type):
+def read_mask_file(stem, rows, cols):
+    """<stem>.jpg / .pgm as a mask of rows x cols, None if there is no such file; a file of another size is refused."""
+    import ctypes as C
+    import os
+    if not any(os.path.exists(stem + ext) for ext in (".jpg", ".pgm")):
+        return None
+    L = host_lib()
+    name = stem + (".jpg" if os.path.exists(stem + ".jpg") else ".pgm")
+    r, c = C.c_int(), C.c_int()
+    if L.apdhost_read_gray_image(stem.encode(), C.byref(r), C.byref(c), None, 0) != 0:
+        raise IOError("cannot read mask %s" % name)
+    if (r.value, c.value) != (rows, cols):
+        raise ValueError("mask %s is %dx%d, its image is %dx%d" % (name, c.value, r.value, cols, rows))
+    grey = np.empty((rows, cols), np.float32)
+    L.apdhost_read_gray_image(stem.encode(), C.byref(r), C.byref(c), grey.ctypes.data_as(C.POINTER(C.c_float)), grey.size)
+    return mask_from_grey(grey)
+
+
+def load_dense_folder(folder, camera_type, masks_dir=None):
     """pair.txt (main.cpp:6-49: sources with score <= 0 dropped), cams/%08d_cam.txt, images/%08d.{jpg,pgm}.
-    View i of the returned scene is the i-th entry of pair.txt; `ids` maps it back to the image id."""
+    View i of the returned scene is the i-th entry of pair.txt; `ids` maps it back to the image id.
+    masks_dir (e.g. "masks"): <folder>/<masks_dir>/%08d.{jpg,pgm} become scene.masks for the reference views (grey < 128 =
+    masked out; a view without a file is unmasked; a file of another size than its image raises ValueError).  None: nothing
+    is read, even if the directory exists."""
     import ctypes as C
     import os
     L = host_lib()
@@ -399,6 +443,8 @@ def load_dense_folder(folder, camera_type):
     imgs = [im for _, im in loaded]
     scene = MvsScene(cams, imgs, [[index_of[s] for s in srcs] for srcs in src_ids])
     scene.ids = ids + extra   # image id of every loaded view; the first scene.num_views are the reference views
+    if masks_dir is not None:
+        scene.masks = [read_mask_file(os.path.join(folder, masks_dir, "%08d" % v), *imgs[i].shape) for i, v in enumerate(ids)]
     return scene
 
 

@@ -173,6 +173,25 @@ int apd_upload_views_shared(apd_handle h, int num_images, const apd_camera *came
  * (APD.cpp:541-547).  Builds the weak index map of APD.cpp:526-537. */
 int apd_upload_prior(apd_handle h, const float *planes4, const uint32_t *selected_views, const uint8_t *weak_info);
 
+/* Per-view pixel mask of this (view, pass): W*H bytes, host or device pointer, non-zero = process, zero = masked out; NULL
+ * clears it.  The reference knows one mask, `blocks/mask_<id>.jpg`, and only its fusion reads it (APD.cpp:849-853): PatchMatch
+ * has by then spent its time on those pixels and used their depths as geometric partners of other views.  Here the mask
+ * reaches the kernels:
+ *   - before the first kernel of the pass the masked pixels of the weak map (apd_upload_prior's, or the all-STRONG default)
+ *     become APD_UNKNOWN: never WEAK, so in no WEAK list and without neighbours (K2..K4), never an anchor of K3 or a tap of
+ *     K12/K13; the weak index map and apd_weak_count are those of that map;
+ *   - K1..K5 run on masked pixels as on any other; K6..K15 write no state array at a masked pixel (a wave whose pixels are
+ *     all masked leaves at its first ballot), and live pixels read masked neighbours like any neighbour;
+ *   - apd_download, apd_export_state_device and apd_export_depth_normal_device give a masked pixel depth 0, normal (0,0,0),
+ *     plane (0,0,0,0), APD_UNKNOWN, selected views 0 -- "no estimate" for the geometric term and for every fusion loop
+ *     (apd_download_state stays a raw copy).
+ * Without a mask, or with one that is non-zero everywhere, every bit is what an unmasked handle computes.  Valid after
+ * apd_create / apd_reset and before the first kernel of the pass (APD_ERR_STATE afterwards), before or after
+ * apd_upload_prior and the view uploads; forgotten by apd_reset like them.  Copied on the handle's stream; returns when the
+ * copy is done.  apd_masked_count: zero bytes of the current mask (0 without one). */
+int apd_upload_mask(apd_handle h, const uint8_t *mask);
+int apd_masked_count(apd_handle h);
+
 /* APD::RunPatchMatch (APD.cu:2386-2495), without the final device->host copies.  One handle is one (view, pass), like one
  * APD object: K14 rewrites the weak map the WEAK lists, the neighbour table and its index map were sized for, so a second
  * apd_run -- or K3 / K8 / K9 / K10 through apd_run_kernel after K14 or after apd_upload_state(APD_STATE_WEAK_INFO) -- returns

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Multi-GPU driver of the PatchMatch passes over a dense folder (the reference's layout: pair.txt, cams/, images/).
 
-  one GPU :  python tools/mvs_pipeline.py <dense_folder> [--iters 3] [--seed 12345] [--single-level]
+  one GPU :  python tools/mvs_pipeline.py <dense_folder> [--iters 3] [--seed 12345] [--single-level] [--masks [DIR]]
   N GPUs  :  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/mvs_pipeline.py <dense_folder>
 
 Reference views are sharded round-robin over the ranks (one process per GPU, RCCL over xGMI); depth maps are all-gathered
@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--no-fusion", action="store_true")
     ap.add_argument("--fusion", choices=["eth", "tat-intermediate", "tat-advanced"], default="eth",
                     help="which of the reference's fusion loops writes APD/APD.ply (as the drop-in binary's --fusion)")
+    ap.add_argument("--masks", nargs="?", const="masks", default=None, metavar="DIR",
+                    help="per-view pixel masks <dense_folder>/DIR/%%08d.jpg|pgm (default DIR: masks): grey < 128 is masked out of PatchMatch")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -39,7 +41,7 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local_rank)
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
-    scene = pipeline.load_dense_folder(args.dense_folder, pkg.Camera)
+    scene = pipeline.load_dense_folder(args.dense_folder, pkg.Camera, masks_dir=args.masks)
     if args.max_src > 0:
         scene.pairs = [p[:args.max_src] for p in scene.pairs]
     if rank == 0:
