@@ -322,6 +322,28 @@ int ReadMaskFile(const path &stem, Mat &mask, std::string &file)
     return 1;
 }
 
+int ReadViewMask(const path &dense_folder, const std::string &masks_dir, int image_id, Mat &mask)
+{
+    std::string file;
+    const int rc = ReadMaskFile(dense_folder / path(masks_dir) / path(ToFormatIndex(image_id)), mask, file);
+    if (rc == 0) {
+        return 0;
+    }
+    if (rc < 0) {
+        fprintf(stderr, "cannot read mask %s\n", file.c_str());
+        return -1;
+    }
+    Mat image;
+    if (!ReadGrayImageShared(dense_folder / path("images") / path(ToFormatIndex(image_id)), image)) {
+        return -1;
+    }
+    if (mask.cols != image.cols || mask.rows != image.rows) {
+        fprintf(stderr, "mask %s is %dx%d, its image is %dx%d\n", file.c_str(), mask.cols, mask.rows, image.cols, image.rows);
+        return -1;
+    }
+    return 1;
+}
+
 void LevelMask(const Mat &full, Mat &level, int width, int height)
 {
     level = full.clone();
@@ -517,18 +539,13 @@ void APD::LoadMask()
         return;
     }
     Mat full;
-    std::string file;
-    const int rc = ReadMaskFile(problem.dense_folder / path(problem.masks_dir) / path(ToFormatIndex(problem.ref_image_id)), full, file);
-    if (rc == 0) {
-        return;
-    }
-    Mat ref_full;
-    if (rc < 0 || !ReadGrayImageShared(problem.dense_folder / path("images") / path(ToFormatIndex(problem.ref_image_id)), ref_full) ||
-        full.cols != ref_full.cols || full.rows != ref_full.rows) {
-        std::cerr << "Mask " << file << " is unreadable or not of the size of its image\n";
+    const int rc = ReadViewMask(problem.dense_folder, problem.masks_dir, problem.ref_image_id, full);
+    if (rc < 0) {
         exit(EXIT_FAILURE);
     }
-    LevelMask(full, mask_host, width, height);
+    if (rc > 0) {
+        LevelMask(full, mask_host, width, height);
+    }
 }
 
 // Reference image first, then the sources in pair.txt order, with their cameras (APD.cpp:409-461); the depth search range

@@ -140,8 +140,11 @@ bool ReadColorImage(const path &image_path_without_ext, Mat &image_bgr);
 // Per-view pixel masks (--masks, apd_upload_mask; the reference's only mask is the fusion's blocks/mask_<id>.jpg, APD.cpp:849-853).
 // ReadMaskFile: <stem>.jpg / .pgm as MAT_8UC1 with 0 where the grey value is below 128 (masked out) and 255 elsewhere; returns 1,
 // 0 when there is no such file (the view is unmasked) and -1 when the file cannot be decoded; `file` names the file looked at.
+// ReadViewMask: <dense_folder>/<masks_dir>/<%08d of image_id> checked against images/<%08d>: 1 with the mask, 0 when the view has
+// none, -1 after saying on stderr what is wrong with the file (unreadable, or not of the size of its image).
 // LevelMask: the full-resolution mask at a pyramid level, resampled like the state maps (RescaleMatToTargetSize).
 int ReadMaskFile(const path &mask_path_without_ext, Mat &mask, std::string &file);
+int ReadViewMask(const path &dense_folder, const std::string &masks_dir, int image_id, Mat &mask);
 void LevelMask(const Mat &full, Mat &level, int width, int height);
 // host-side helpers of the drop-in (not in the reference): a small thread pool and a parallel warm-up of the image cache
 void ParallelFor(size_t count, const std::function<void(size_t)> &job, unsigned max_threads = 0);

@@ -4,6 +4,7 @@
 
 #include "APD.h"
 #include "schedule.h"
+#include "wavefront.h"
 #include "../csrc/apd_fusion_math.h"
 
 bool DecodeJpegGray(const uint8_t *data, size_t size, std::vector<uint8_t> &gray, int &width, int &height);
@@ -128,6 +129,35 @@ int apdhost_schedule(int round_num, int single_level, int *rows, int cap_rows)
     }
     return (int)plan.size();
 }
+
+// The task queue of a wavefront level (host/wavefront.h), as the in-memory scheduler drives it.  iterations / geom: per pass of the
+// level; view v's sources (reconstructed views only) are src_index[src_begin[v] .. src_begin[v + 1]); lanes_per_pass <= 0: the
+// scheduler's own cap.  take: 0 with a task in *pass_index / *view, 1 wait, 2 every task is handed out.  finish: 1 when the task was
+// the last of its pass.
+void *apdhost_wavefront_create(int num_passes, const int *iterations, const int *geom, int num_views, const int *src_begin, const int *src_index,
+                               int gauss_seidel, int lanes_per_pass)
+{
+    std::vector<WavefrontQueue::PassInfo> passes;
+    for (int p = 0; p < num_passes; ++p) {
+        passes.push_back({iterations[p], geom[p] != 0});
+    }
+    std::vector<std::vector<int>> sources(num_views);
+    for (int v = 0; v < num_views; ++v) {
+        sources[v].assign(src_index + src_begin[v], src_index + src_begin[v + 1]);
+    }
+    return new WavefrontQueue(std::move(passes), std::move(sources), gauss_seidel != 0, lanes_per_pass > 0 ? lanes_per_pass : APD_GS_LANES_PER_PASS);
+}
+
+int apdhost_wavefront_take(void *queue, int *pass_index, int *view) { return (int)static_cast<WavefrontQueue *>(queue)->Take(*pass_index, *view); }
+void apdhost_wavefront_publish(void *queue, int pass_index, int view) { static_cast<WavefrontQueue *>(queue)->Publish(pass_index, view); }
+int apdhost_wavefront_finish(void *queue, int pass_index, int view) { return static_cast<WavefrontQueue *>(queue)->Finish(pass_index, view) ? 1 : 0; }
+int apdhost_wavefront_published(void *queue, int view) { return static_cast<WavefrontQueue *>(queue)->Published(view); }
+int apdhost_wavefront_source_iteration(void *queue, int pass_index, int view, int source)
+{
+    return static_cast<WavefrontQueue *>(queue)->SourceIteration(pass_index, view, source);
+}
+int apdhost_wavefront_lanes_per_pass(void) { return APD_GS_LANES_PER_PASS; }
+void apdhost_wavefront_destroy(void *queue) { delete static_cast<WavefrontQueue *>(queue); }
 
 // HIP device of the fusion started by apdhost_fuse / RunFusion (default 0)
 void apdhost_set_fusion_device(int device) { SetFusionDevice(device); }

@@ -238,14 +238,10 @@ void ProcessProblem(const Problem &problem)
             n[c] = Vec3f{{h.x, h.y, h.z}};
         }
     });
-    const Mat *maps[4] = {&depth, &normal, &states, nullptr};
-    const Mat views = apd.GetSelectedViews();
-    maps[3] = &views;
-    for (int k = 0; k < 4; ++k) {
-        if (!WriteBinMat(problem.result_folder / kStateFiles[k], *maps[k])) {
-            fprintf(stderr, "cannot write %s\n", (problem.result_folder / kStateFiles[k]).string().c_str());
-            exit(EXIT_FAILURE);
-        }
+    const std::string unwritten = WriteStateFiles(problem.result_folder, depth, normal, states, apd.GetSelectedViews());
+    if (!unwritten.empty()) {
+        fprintf(stderr, "cannot write %s\n", unwritten.c_str());
+        exit(EXIT_FAILURE);
     }
     const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
     printf("Processing image: %08d done!\nCost time: %lld ms\n", problem.ref_image_id, (long long)ms);
@@ -288,21 +284,8 @@ int main(int argc, char **argv)
     if (!opt.masks_dir.empty()) {   // every mask file against its image, before a result folder exists
         for (Problem &p : problems) {
             p.masks_dir = opt.masks_dir;
-            Mat mask, image;
-            std::string file;
-            const int rc = ReadMaskFile(opt.dense_folder / opt.masks_dir / ToFormatIndex(p.ref_image_id), mask, file);
-            if (rc == 0) {
-                continue;
-            }
-            if (rc < 0) {
-                fprintf(stderr, "cannot read mask %s\n", file.c_str());
-                return EXIT_FAILURE;
-            }
-            if (!ReadGrayImageShared(opt.dense_folder / "images" / ToFormatIndex(p.ref_image_id), image)) {
-                return EXIT_FAILURE;
-            }
-            if (mask.cols != image.cols || mask.rows != image.rows) {
-                fprintf(stderr, "mask %s is %dx%d, its image is %dx%d\n", file.c_str(), mask.cols, mask.rows, image.cols, image.rows);
+            Mat mask;
+            if (ReadViewMask(opt.dense_folder, opt.masks_dir, p.ref_image_id, mask) < 0) {
                 return EXIT_FAILURE;
             }
         }

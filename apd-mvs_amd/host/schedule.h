@@ -1,6 +1,8 @@
 // schedule.h -- what the two schedulers of the drop-in host share: the command-line options, the pass table of the
 // reference driver (main.cpp:168-215) and the per-pass parameters of a problem.  host/main.cpp runs the table view by view
-// through files like the reference (Gauss-Seidel over views); host/multi_device.cpp runs it in memory on several devices.
+// through files like the reference (Gauss-Seidel over views); host/multi_device.cpp runs it in memory on several devices
+// (RunMultiDevice: a Scheduler whose lanes take the (pass, view) tasks of a level from host/wavefront.h's queue on one rank,
+// in order with an all-gather after every pass on several).
 #ifndef APD_MI355X_HOST_SCHEDULE_H_
 #define APD_MI355X_HOST_SCHEDULE_H_
 
@@ -35,9 +37,6 @@ struct Options {
     bool late_fusion_inputs = false;  // --late-fusion-inputs: colour decode + upload after the passes instead of behind them (A/B measurements)
 };
 
-
-// One pass over all views.  round_num pyramid levels, coarse to fine; per level one photometric pass and three
-// geometric ones (main.cpp:168-215).
 // true when a run over this device list sets RCCL up (several physical devices, or --rccl); the set-up blocks before the first pass
 // (round 5's --async-rccl measured slower and is gone: profiles/r05/ab_rccl_async_tt24.txt)
 inline bool WantsRccl(const Options &opt)
@@ -49,6 +48,8 @@ inline bool WantsRccl(const Options &opt)
     return opt.use_rccl && (several || opt.force_rccl);
 }
 
+// One pass over all views.  round_num pyramid levels, coarse to fine; per level one photometric pass and three
+// geometric ones (main.cpp:168-215).
 struct Pass {
     int level = 0;             // i of main.cpp:168
     int iteration = 0;         // Problem::iteration, counts passes
@@ -114,6 +115,17 @@ inline void Configure(Problem &problem, const Pass &pass, const Options &o)
 
 static const char *const kStateFiles[4] = {"depths.dmb", "normals.dmb", "weak.bin", "selected_views.bin"};
 
+// The four state files of a view (main.cpp:117-124) into its result folder.  Returns an empty string, or the file that could not be written.
+inline std::string WriteStateFiles(const path &result_folder, const Mat &depth, const Mat &normal, const Mat &weak, const Mat &views)
+{
+    const Mat *maps[4] = {&depth, &normal, &weak, &views};
+    for (int k = 0; k < 4; ++k) {
+        if (!WriteBinMat(result_folder / kStateFiles[k], *maps[k])) {
+            return (result_folder / kStateFiles[k]).string();
+        }
+    }
+    return std::string();
+}
 
 // host/multi_device.cpp: every pass on all listed devices (views round-robin), state resident on the devices, depth maps
 // all-gathered after every pass.  Returns the process exit code.
