@@ -4,7 +4,6 @@
 
 #include <math.h>
 #include <cmath>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +14,7 @@
 #include <vector>
 
 #include "apd_device.h"
+#include "apd_host_error.h"
 
 namespace apd {
 hipError_t launch_kernel(const FrameArgs &fa, int kernel_id, int iter, hipStream_t s);
@@ -35,27 +35,14 @@ hipError_t launch_pack_fquads(const float *img, int W, int H, fquad_t *fq, hipSt
 
 using apd::FrameArgs;
 using apd::ViewConst;
+using apd::set_error;
 
 static thread_local std::string g_last_error;
 
-static int fail(int code, const char *fmt, ...)
+static int hip_failed(const char *expr, hipError_t e, const char *file, int line)  // what HIP_TRY returns
 {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
+    return set_error(g_last_error, APD_ERR_HIP, "%s failed: %s (%s:%d)", expr, hipGetErrorString(e), file, line);
 }
-
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            return fail(APD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-        }                                                                                    \
-    } while (0)
 
 struct apd_context {
     int device = 0;
@@ -336,14 +323,14 @@ static int create_buffers(apd_context *c, int width, int height, const apd_param
 int apd_create(apd_handle *out, int device, int width, int height, const apd_params *params)
 {
     if (!out || !params || width <= 0 || height <= 0) {
-        return fail(APD_ERR_INVALID, "apd_create: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_create: bad argument");
     }
     if (width > 16384 || height > 16384) {  // pixel coordinates travel as short2 and through 24-bit multiply-adds
-        return fail(APD_ERR_UNSUPPORTED, "apd_create: image larger than 16384 x 16384 px");
+        return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_create: image larger than 16384 x 16384 px");
     }
     if (params->strong_radius != 5 || params->strong_increment != 2 || params->weak_radius != 5 || params->weak_increment != 5) {
         // the reference never changes these (main.h:84-87); the kernels are specialised for them
-        return fail(APD_ERR_UNSUPPORTED, "apd_create: only strong 5/2 and weak 5/5 patch geometry is built");
+        return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_create: only strong 5/2 and weak 5/5 patch geometry is built");
     }
     if (device >= 0) {
         HIP_TRY(hipSetDevice(device));
@@ -395,10 +382,10 @@ static int create_buffers(apd_context *c, int width, int height, const apd_param
 int apd_reset(apd_handle c, const apd_params *params)
 {
     if (!c || !params) {
-        return fail(APD_ERR_INVALID, "apd_reset: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_reset: bad argument");
     }
     if (params->strong_radius != 5 || params->strong_increment != 2 || params->weak_radius != 5 || params->weak_increment != 5) {
-        return fail(APD_ERR_UNSUPPORTED, "apd_reset: only strong 5/2 and weak 5/5 patch geometry is built");
+        return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_reset: only strong 5/2 and weak 5/5 patch geometry is built");
     }
     HIP_TRY(hipSetDevice(c->device));
     c->params = *params;
@@ -484,7 +471,7 @@ int apd_destroy(apd_handle c)
 int apd_set_stream(apd_handle c, void *hip_stream)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "apd_set_stream: null handle");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_set_stream: null handle");
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->own_stream) {
@@ -566,8 +553,8 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
     grow(c->fquads, (size_t)num_images);
     for (int i = 0; i < num_images; ++i) {
         if (cameras[i].width != c->W || cameras[i].height != c->H) {
-            return fail(APD_ERR_INVALID, "apd_upload_views: camera %d is %dx%d, handle is %dx%d", i, cameras[i].width, cameras[i].height,
-                        c->W, c->H);
+            return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_views: camera %d is %dx%d, handle is %dx%d", i, cameras[i].width, cameras[i].height,
+                             c->W, c->H);
         }
         if (!c->images[i]) {
             HIP_TRY(hipMalloc(&c->images[i], n * sizeof(float)));
@@ -591,7 +578,7 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
     for (int i = 0; i < num_images; ++i) {  // the reference view too: K9/K10 keep its sub-patch texels as bytes
         hipError_t e = apd::launch_check_u8(c->images[i], (int)n, c->flag_dev, c->stream);
         if (e != hipSuccess) {
-            return fail(APD_ERR_HIP, "k_check_u8 failed: %s", hipGetErrorString(e));
+            return set_error(g_last_error, APD_ERR_HIP, "k_check_u8 failed: %s", hipGetErrorString(e));
         }
     }
     int all_u8 = 0;
@@ -606,7 +593,7 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
             }
             hipError_t e = apd::launch_pack_fquads(c->images[i], c->W, c->H, c->fquads[i], c->stream);
             if (e != hipSuccess) {
-                return fail(APD_ERR_HIP, "k_pack_fquads failed: %s", hipGetErrorString(e));
+                return set_error(g_last_error, APD_ERR_HIP, "k_pack_fquads failed: %s", hipGetErrorString(e));
             }
         }
     }
@@ -618,7 +605,7 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
             }
             hipError_t e = apd::launch_pack_quads(c->images[i], c->W, c->H, c->quads[i], c->stream);
             if (e != hipSuccess) {
-                return fail(APD_ERR_HIP, "k_pack_quads failed: %s", hipGetErrorString(e));
+                return set_error(g_last_error, APD_ERR_HIP, "k_pack_quads failed: %s", hipGetErrorString(e));
             }
         }
         // the tiled copy serves the gathers of planes that are still random: the first iteration of a FIRST_INIT pass
@@ -633,7 +620,7 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
                 }
                 hipError_t e = apd::launch_pack_quads_tiled(c->images[i], c->W, c->H, c->quads_tiled[i], c->stream);
                 if (e != hipSuccess) {
-                    return fail(APD_ERR_HIP, "k_pack_quads_tiled failed: %s", hipGetErrorString(e));
+                    return set_error(g_last_error, APD_ERR_HIP, "k_pack_quads_tiled failed: %s", hipGetErrorString(e));
                 }
             }
         }
@@ -655,10 +642,10 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
 static int check_upload_args(apd_context *c, int num_images, const apd_camera *cameras, const float *const *images, const char *who)
 {
     if (!c || !cameras || !images || num_images < 2) {
-        return fail(APD_ERR_INVALID, "%s: bad argument", who);
+        return set_error(g_last_error, APD_ERR_INVALID, "%s: bad argument", who);
     }
     if (num_images > APD_MAX_IMAGES) {
-        return fail(APD_ERR_TOO_MANY, "Can't process so much images: %d", num_images);  // APD.cpp:428-431
+        return set_error(g_last_error, APD_ERR_TOO_MANY, "Can't process so much images: %d", num_images);  // APD.cpp:428-431
     }
     return APD_OK;
 }
@@ -670,7 +657,7 @@ int apd_upload_views(apd_handle c, int num_images, const apd_camera *cameras, co
         return rc;
     }
     if (c->params.geom_consistency && !depths) {
-        return fail(APD_ERR_INVALID, "apd_upload_views: geom_consistency needs depth maps");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_views: geom_consistency needs depth maps");
     }
     return upload_views_impl(c, num_images, cameras, images, depths, false);
 }
@@ -722,7 +709,7 @@ static int image_ensure(apd_image *im, int what /* 0 pairs, 1 tiled, 2 float qua
         void **made = what == 0 ? (void **)&im->pairs : what == 1 ? (void **)&im->tiled : (void **)&im->fquads;
         hipFree(*made);
         *made = nullptr;
-        return fail(APD_ERR_HIP, "packing a shared image failed: %s", hipGetErrorString(e));
+        return set_error(g_last_error, APD_ERR_HIP, "packing a shared image failed: %s", hipGetErrorString(e));
     }
     return APD_OK;
 }
@@ -730,7 +717,7 @@ static int image_ensure(apd_image *im, int what /* 0 pairs, 1 tiled, 2 float qua
 int apd_image_create(apd_image_t *out, int device, int width, int height, const float *pixels)
 {
     if (!out || !pixels || width <= 0 || height <= 0 || width > 16384 || height > 16384) {
-        return fail(APD_ERR_INVALID, "apd_image_create: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_image_create: bad argument");
     }
     if (device >= 0) {
         HIP_TRY(hipSetDevice(device));
@@ -752,7 +739,7 @@ int apd_image_create(apd_image_t *out, int device, int width, int height, const 
     hipFree(flag);
     if (e != hipSuccess) {
         apd_image_destroy(im);
-        return fail(APD_ERR_HIP, "apd_image_create: %s", hipGetErrorString(e));
+        return set_error(g_last_error, APD_ERR_HIP, "apd_image_create: %s", hipGetErrorString(e));
     }
     im->is_u8 = all_u8 != 0;
     const int rc = image_ensure(im, im->is_u8 ? 0 : 2, nullptr);
@@ -783,19 +770,19 @@ int apd_image_destroy(apd_image_t im)
 int apd_upload_views_shared(apd_handle c, int num_images, const apd_camera *cameras, const apd_image_t *images)
 {
     if (!c || !cameras || !images || num_images < 2) {
-        return fail(APD_ERR_INVALID, "apd_upload_views_shared: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_views_shared: bad argument");
     }
     if (num_images > APD_MAX_IMAGES) {
-        return fail(APD_ERR_TOO_MANY, "Can't process so much images: %d", num_images);  // APD.cpp:428-431
+        return set_error(g_last_error, APD_ERR_TOO_MANY, "Can't process so much images: %d", num_images);  // APD.cpp:428-431
     }
     HIP_TRY(hipSetDevice(c->device));
     bool all_u8 = true;
     for (int i = 0; i < num_images; ++i) {
         if (!images[i] || images[i]->W != c->W || images[i]->H != c->H || images[i]->device != c->device) {
-            return fail(APD_ERR_INVALID, "apd_upload_views_shared: image %d is missing, of another size or on another device than the handle", i);
+            return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_views_shared: image %d is missing, of another size or on another device than the handle", i);
         }
         if (cameras[i].width != c->W || cameras[i].height != c->H) {
-            return fail(APD_ERR_INVALID, "apd_upload_views_shared: camera %d is %dx%d, handle is %dx%d", i, cameras[i].width, cameras[i].height, c->W, c->H);
+            return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_views_shared: camera %d is %dx%d, handle is %dx%d", i, cameras[i].width, cameras[i].height, c->W, c->H);
         }
         all_u8 = all_u8 && images[i]->is_u8;
     }
@@ -844,13 +831,13 @@ int apd_upload_views_shared(apd_handle c, int num_images, const apd_camera *came
 int apd_upload_depths(apd_handle c, int num_images, const float *const *depths)
 {
     if (!c || !depths) {
-        return fail(APD_ERR_INVALID, "apd_upload_depths: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_depths: bad argument");
     }
     if (!c->views_uploaded || !c->depths_pending) {
-        return fail(APD_ERR_STATE, "apd_upload_depths: no apd_upload_views_split of a geometric pass is waiting for depth maps");
+        return set_error(g_last_error, APD_ERR_STATE, "apd_upload_depths: no apd_upload_views_split of a geometric pass is waiting for depth maps");
     }
     if (num_images != c->num_images) {
-        return fail(APD_ERR_INVALID, "apd_upload_depths: %d depth maps for %d views", num_images, c->num_images);
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_depths: %d depth maps for %d views", num_images, c->num_images);
     }
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->W * c->H;
@@ -867,11 +854,11 @@ static int ensure_mask_scratch(apd_context *c);
 int apd_upload_mask(apd_handle c, const uint8_t *mask)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "apd_upload_mask: null handle");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_mask: null handle");
     }
     if (c->pass_started) {
-        return fail(APD_ERR_STATE, "apd_upload_mask: a kernel of this pass has already run; the mask is set after apd_create / apd_reset "
-                                   "and before the first kernel");
+        return set_error(g_last_error, APD_ERR_STATE, "apd_upload_mask: a kernel of this pass has already run; the mask is set after apd_create / apd_reset "
+                                                      "and before the first kernel");
     }
     HIP_TRY(hipSetDevice(c->device));
     c->have_mask = false;
@@ -902,7 +889,7 @@ int apd_masked_count(apd_handle c) { return c ? c->masked_count : 0; }
 int apd_upload_prior(apd_handle c, const float *planes4, const uint32_t *selected_views, const uint8_t *weak_info)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "apd_upload_prior: null handle");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_prior: null handle");
     }
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->W * c->H;
@@ -1035,12 +1022,12 @@ static int launch_one(apd_context *c, int kernel_id, int iter)
     // refusals first: a refused launch must leave nothing behind (no event taken from the pool, nothing recorded on the stream)
     if (c->weak_map_stale && (kernel_id == APD_K3_GEN_NEIGHBOURS || kernel_id == APD_K8_RANSAC_FIT_PLANE ||
                               kernel_id == APD_K9_BLACK_UPDATE_WEAK || kernel_id == APD_K10_RED_UPDATE_WEAK)) {
-        return fail(APD_ERR_STATE, "kernel %d walks the WEAK lists / neighbour table of the last apd_upload_prior, but weak_info has been "
-                                   "rewritten since (K14 or apd_upload_state): call apd_upload_prior or apd_reset first", kernel_id);
+        return set_error(g_last_error, APD_ERR_STATE, "kernel %d walks the WEAK lists / neighbour table of the last apd_upload_prior, but weak_info has been "
+                                                      "rewritten since (K14 or apd_upload_state): call apd_upload_prior or apd_reset first", kernel_id);
     }
     if (c->depths_pending && (kernel_id == APD_K9_BLACK_UPDATE_WEAK || kernel_id == APD_K10_RED_UPDATE_WEAK ||
                               kernel_id == APD_K14_DEPTH_TO_WEAK || kernel_id == APD_K15_LOCAL_REFINE)) {
-        return fail(APD_ERR_STATE, "kernel %d reads the sources' depth maps (geometric term): call apd_upload_depths first", kernel_id);
+        return set_error(g_last_error, APD_ERR_STATE, "kernel %d reads the sources' depth maps (geometric term): call apd_upload_depths first", kernel_id);
     }
     apd_context::PendingEvent pe{kernel_id, nullptr, nullptr};
     if (c->profiling) {
@@ -1049,7 +1036,7 @@ static int launch_one(apd_context *c, int kernel_id, int iter)
         if (hipEventRecord(pe.start, c->stream) != hipSuccess) {
             c->event_pool.push_back(pe.start);
             c->event_pool.push_back(pe.stop);
-            return fail(APD_ERR_HIP, "hipEventRecord failed before kernel %d", kernel_id);
+            return set_error(g_last_error, APD_ERR_HIP, "hipEventRecord failed before kernel %d", kernel_id);
         }
     }
     hipError_t e;
@@ -1061,7 +1048,7 @@ static int launch_one(apd_context *c, int kernel_id, int iter)
             c->weak_lists_all_rows = kernel_id == APD_K3_GEN_NEIGHBOURS;
             e = apd::build_weak_lists(c->fa, c->weak_lists_all_rows, c->weak_list, c->weak_list_scratch, c->weak_list_count, c->stream);
             if (e != hipSuccess) {
-                return fail(APD_ERR_HIP, "building the WEAK pixel lists failed: %s", hipGetErrorString(e));
+                return set_error(g_last_error, APD_ERR_HIP, "building the WEAK pixel lists failed: %s", hipGetErrorString(e));
             }
             c->weak_lists_valid = true;
         }
@@ -1085,7 +1072,7 @@ static int launch_one(apd_context *c, int kernel_id, int iter)
         break;
     }
     if (e != hipSuccess) {
-        return fail(APD_ERR_HIP, "launch of kernel %d failed: %s", kernel_id, hipGetErrorString(e));
+        return set_error(g_last_error, APD_ERR_HIP, "launch of kernel %d failed: %s", kernel_id, hipGetErrorString(e));
     }
     if (c->profiling) {
         HIP_TRY(hipEventRecord(pe.stop, c->stream));
@@ -1097,16 +1084,16 @@ static int launch_one(apd_context *c, int kernel_id, int iter)
 static int check_ready(apd_context *c, const char *who)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "%s: null handle", who);
+        return set_error(g_last_error, APD_ERR_INVALID, "%s: null handle", who);
     }
     if (!c->views_uploaded) {
-        return fail(APD_ERR_STATE, "%s: apd_upload_views has not been called", who);
+        return set_error(g_last_error, APD_ERR_STATE, "%s: apd_upload_views has not been called", who);
     }
     if (c->params.state != APD_FIRST_INIT && !c->prior_uploaded) {
-        return fail(APD_ERR_STATE, "%s: state != FIRST_INIT needs apd_upload_prior", who);
+        return set_error(g_last_error, APD_ERR_STATE, "%s: state != FIRST_INIT needs apd_upload_prior", who);
     }
     if (hipSetDevice(c->device) != hipSuccess) {
-        return fail(APD_ERR_HIP, "%s: hipSetDevice failed", who);
+        return set_error(g_last_error, APD_ERR_HIP, "%s: hipSetDevice failed", who);
     }
     return APD_OK;
 }
@@ -1118,7 +1105,7 @@ int apd_run_kernel(apd_handle c, int kernel_id, int iter)
         return rc;
     }
     if (kernel_id < 1 || kernel_id >= APD_KERNEL_COUNT) {
-        return fail(APD_ERR_INVALID, "apd_run_kernel: unknown kernel %d", kernel_id);
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_run_kernel: unknown kernel %d", kernel_id);
     }
     if ((rc = begin_pass(c))) {
         return rc;
@@ -1209,8 +1196,8 @@ static int check_run(apd_context *c, const char *who)
         return rc;
     }
     if (c->weak_map_stale) {
-        return fail(APD_ERR_STATE, "%s: this handle already ran a pass (K14 rewrote weak_info): one handle is one (view, pass) like "
-                                   "one APD object; call apd_reset or apd_upload_prior first", who);
+        return set_error(g_last_error, APD_ERR_STATE, "%s: this handle already ran a pass (K14 rewrote weak_info): one handle is one (view, pass) like "
+                                                      "one APD object; call apd_reset or apd_upload_prior first", who);
     }
     return APD_OK;
 }
@@ -1222,11 +1209,11 @@ int apd_run(apd_handle c)
         return rc;
     }
     if (c->depths_pending) {   // refused up front: a whole pass would otherwise run K1..K8 and fail at the first kernel that reads a depth map
-        return fail(APD_ERR_STATE, "apd_run: the depth maps of this geometric pass are still pending (apd_upload_views_split / _shared): "
-                                   "call apd_upload_depths first, or drive the pass with apd_run_before_depths / apd_run_after_depths");
+        return set_error(g_last_error, APD_ERR_STATE, "apd_run: the depth maps of this geometric pass are still pending (apd_upload_views_split / _shared): "
+                                                      "call apd_upload_depths first, or drive the pass with apd_run_before_depths / apd_run_after_depths");
     }
     if (c->first_half_done) {
-        return fail(APD_ERR_STATE, "apd_run: apd_run_before_depths already ran on this upload; finish the pass with apd_run_after_depths");
+        return set_error(g_last_error, APD_ERR_STATE, "apd_run: apd_run_before_depths already ran on this upload; finish the pass with apd_run_after_depths");
     }
     if ((rc = begin_pass(c))) {
         return rc;
@@ -1241,7 +1228,7 @@ int apd_run_before_depths(apd_handle c)
         return rc;
     }
     if (c->first_half_done) {
-        return fail(APD_ERR_STATE, "apd_run_before_depths: already ran on this upload");
+        return set_error(g_last_error, APD_ERR_STATE, "apd_run_before_depths: already ran on this upload");
     }
     if ((rc = begin_pass(c))) {
         return rc;
@@ -1258,10 +1245,10 @@ int apd_run_after_depths(apd_handle c)
         return rc;
     }
     if (!c->first_half_done) {   // K9 / K10 / K14 / K15 on planes and random states nobody initialised
-        return fail(APD_ERR_STATE, "apd_run_after_depths: apd_run_before_depths has not run on this upload");
+        return set_error(g_last_error, APD_ERR_STATE, "apd_run_after_depths: apd_run_before_depths has not run on this upload");
     }
     if (c->depths_pending) {
-        return fail(APD_ERR_STATE, "apd_run_after_depths: the depth maps of this geometric pass have not been uploaded (apd_upload_depths)");
+        return set_error(g_last_error, APD_ERR_STATE, "apd_run_after_depths: the depth maps of this geometric pass have not been uploaded (apd_upload_depths)");
     }
     rc = run_schedule(c, false, true);
     c->first_half_done = false;   // the pass is complete (or failed): a second call is refused
@@ -1271,7 +1258,7 @@ int apd_run_after_depths(apd_handle c)
 int apd_synchronize(apd_handle c)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "apd_synchronize: null handle");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_synchronize: null handle");
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1282,7 +1269,7 @@ int apd_synchronize(apd_handle c)
 int apd_download(apd_handle c, float *planes4, uint8_t *weak_info, uint32_t *selected_views)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "apd_download: null handle");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_download: null handle");
     }
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->W * c->H;
@@ -1357,12 +1344,12 @@ size_t apd_state_bytes(apd_handle c, int which)
 int apd_download_state(apd_handle c, int which, void *dst, size_t bytes)
 {
     if (!c || !dst) {
-        return fail(APD_ERR_INVALID, "apd_download_state: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_download_state: bad argument");
     }
     size_t cap = 0;
     void *src = state_ptr(c, which, &cap);
     if (!src || bytes > cap) {
-        return fail(APD_ERR_INVALID, "apd_download_state: state %d has %zu bytes, asked for %zu", which, cap, bytes);
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_download_state: state %d has %zu bytes, asked for %zu", which, cap, bytes);
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, c->stream));
@@ -1374,12 +1361,12 @@ int apd_download_state(apd_handle c, int which, void *dst, size_t bytes)
 int apd_upload_state(apd_handle c, int which, const void *src, size_t bytes)
 {
     if (!c || !src) {
-        return fail(APD_ERR_INVALID, "apd_upload_state: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_state: bad argument");
     }
     size_t cap = 0;
     void *dst = state_ptr(c, which, &cap);
     if (!dst || bytes > cap) {
-        return fail(APD_ERR_INVALID, "apd_upload_state: state %d has %zu bytes, got %zu", which, cap, bytes);
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_state: state %d has %zu bytes, got %zu", which, cap, bytes);
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, c->stream));
@@ -1394,12 +1381,12 @@ int apd_upload_state(apd_handle c, int which, const void *src, size_t bytes)
 int apd_export_depth_normal_device(apd_handle c, float *depth_dev, float *normal_dev)
 {
     if (!c || !depth_dev) {
-        return fail(APD_ERR_INVALID, "apd_export_depth_normal_device: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_export_depth_normal_device: bad argument");
     }
     HIP_TRY(hipSetDevice(c->device));
     hipError_t e = apd::launch_export_depth_normal(c->fa, depth_dev, normal_dev, c->stream);
     if (e != hipSuccess) {
-        return fail(APD_ERR_HIP, "export kernel failed: %s", hipGetErrorString(e));
+        return set_error(g_last_error, APD_ERR_HIP, "export kernel failed: %s", hipGetErrorString(e));
     }
     if (int rc = record_export(c)) {
         return rc;
@@ -1411,12 +1398,12 @@ int apd_export_depth_normal_device(apd_handle c, float *depth_dev, float *normal
 int apd_export_state_device(apd_handle c, float *planes4_dev, uint8_t *weak_dev, uint32_t *views_dev, float *depth_dev)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "apd_export_state_device: null handle");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_export_state_device: null handle");
     }
     HIP_TRY(hipSetDevice(c->device));
     hipError_t e = apd::launch_export_state(c->fa, reinterpret_cast<float4 *>(planes4_dev), weak_dev, views_dev, depth_dev, c->stream);
     if (e != hipSuccess) {
-        return fail(APD_ERR_HIP, "export kernel failed: %s", hipGetErrorString(e));
+        return set_error(g_last_error, APD_ERR_HIP, "export kernel failed: %s", hipGetErrorString(e));
     }
     if (int rc = record_export(c)) {
         return rc;
@@ -1429,7 +1416,7 @@ int apd_export_state_device(apd_handle c, float *planes4_dev, uint8_t *weak_dev,
 int apd_export_event(apd_handle c, void **hip_event)
 {
     if (!c || !hip_event) {
-        return fail(APD_ERR_INVALID, "apd_export_event: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_export_event: bad argument");
     }
     *hip_event = (void *)c->export_event;
     return APD_OK;
@@ -1438,11 +1425,11 @@ int apd_export_event(apd_handle c, void **hip_event)
 int apd_set_option(apd_handle c, int option, int value)
 {
     if (!c || option < 0 || option >= APD_OPT_COUNT) {
-        return fail(APD_ERR_INVALID, "apd_set_option: bad handle or option %d", option);
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_set_option: bad handle or option %d", option);
     }
     const int hi = option == APD_OPT_TILED_COPY ? 2 : 1;
     if (value < 0 || value > hi) {
-        return fail(APD_ERR_INVALID, "apd_set_option: option %d takes 0..%d, got %d", option, hi, value);
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_set_option: option %d takes 0..%d, got %d", option, hi, value);
     }
     c->options[option] = value;
     refresh_frame_args(c);
@@ -1452,7 +1439,7 @@ int apd_set_option(apd_handle c, int option, int value)
 int apd_get_option(apd_handle c, int option, int *value)
 {
     if (!c || !value || option < 0 || option >= APD_OPT_COUNT) {
-        return fail(APD_ERR_INVALID, "apd_get_option: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_get_option: bad argument");
     }
     *value = c->options[option];
     return APD_OK;
@@ -1461,7 +1448,7 @@ int apd_get_option(apd_handle c, int option, int *value)
 int apd_get_stream(apd_handle c, void **hip_stream)
 {
     if (!c || !hip_stream) {
-        return fail(APD_ERR_INVALID, "apd_get_stream: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_get_stream: bad argument");
     }
     *hip_stream = (void *)c->stream;
     return APD_OK;
@@ -1476,7 +1463,7 @@ int apd_weak_count(apd_handle c) { return c ? c->weak_count : 0; }
 int apd_profile_enable(apd_handle c, int on)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "apd_profile_enable: null handle");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_profile_enable: null handle");
     }
     c->profiling = on != 0;
     return APD_OK;
@@ -1485,7 +1472,7 @@ int apd_profile_enable(apd_handle c, int on)
 int apd_profile_reset(apd_handle c)
 {
     if (!c) {
-        return fail(APD_ERR_INVALID, "apd_profile_reset: null handle");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_profile_reset: null handle");
     }
     hipStreamSynchronize(c->stream);
     drain_profile(c);
@@ -1497,7 +1484,7 @@ int apd_profile_reset(apd_handle c)
 int apd_profile_get(apd_handle c, int kernel_id, double *total_ms, int *launches)
 {
     if (!c || kernel_id < 0 || kernel_id >= APD_KERNEL_COUNT) {
-        return fail(APD_ERR_INVALID, "apd_profile_get: bad argument");
+        return set_error(g_last_error, APD_ERR_INVALID, "apd_profile_get: bad argument");
     }
     if (total_ms) {
         *total_ms = c->prof_ms[kernel_id];

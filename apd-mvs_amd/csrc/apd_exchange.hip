@@ -12,7 +12,6 @@
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -24,6 +23,7 @@
 #include <mutex>
 
 #include "apd_device.h"
+#include "apd_host_error.h"
 
 namespace apd {
 
@@ -157,24 +157,12 @@ hipError_t launch_mask_count(const uint8_t *mask, int n, int *count, hipStream_t
 
 static thread_local std::string g_exchange_error;
 
-static int xfail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_exchange_error = buf;
-    return code;
-}
+using apd::set_error;
 
-#define X_TRY(expr)                                                                                                        \
-    do {                                                                                                                   \
-        hipError_t e_ = (expr);                                                                                            \
-        if (e_ != hipSuccess) {                                                                                            \
-            return xfail(APD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);           \
-        }                                                                                                                  \
-    } while (0)
+static int hip_failed(const char *expr, hipError_t e, const char *file, int line)  // what HIP_TRY returns
+{
+    return set_error(g_exchange_error, APD_ERR_HIP, "%s failed: %s (%s:%d)", expr, hipGetErrorString(e), file, line);
+}
 
 // the six RCCL entry points, resolved with dlsym (signatures of rccl.h 2.2x)
 struct RcclApi {
@@ -280,11 +268,11 @@ const char *apd_exchange_last_error(void) { return g_exchange_error.c_str(); }
 int apd_device_malloc(int device, size_t bytes, void **out)
 {
     if (!out) {
-        return xfail(APD_ERR_INVALID, "apd_device_malloc: null result pointer");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_device_malloc: null result pointer");
     }
     *out = nullptr;
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipMalloc(out, bytes > 0 ? bytes : 1));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMalloc(out, bytes > 0 ? bytes : 1));
     return APD_OK;
 }
 
@@ -293,34 +281,34 @@ int apd_device_free(int device, void *p)
     if (!p) {
         return APD_OK;
     }
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipFree(p));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipFree(p));
     return APD_OK;
 }
 
 int apd_device_memcpy(int device, void *dst, const void *src, size_t bytes)
 {
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDefault));  // host / device on either side (unified addressing)
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDefault));  // host / device on either side (unified addressing)
     // a device-to-device hipMemcpy may return before the copy has run; callers hand `dst` to other streams (the exchange's
     // are non-blocking ones, which do not wait for the null stream) and to other threads
-    X_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
     return APD_OK;
 }
 
 int apd_device_memset(int device, void *dst, int value, size_t bytes)
 {
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipMemset(dst, value, bytes));
-    X_TRY(hipStreamSynchronize(nullptr));  // hipMemset of device memory is asynchronous
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemset(dst, value, bytes));
+    HIP_TRY(hipStreamSynchronize(nullptr));  // hipMemset of device memory is asynchronous
     return APD_OK;
 }
 
 int apd_device_memory(int device, size_t *free_bytes, size_t *total_bytes)
 {
     size_t f = 0, t = 0;
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipMemGetInfo(&f, &t));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemGetInfo(&f, &t));
     if (free_bytes) {
         *free_bytes = f;
     }
@@ -333,10 +321,10 @@ int apd_device_memory(int device, size_t *free_bytes, size_t *total_bytes)
 static int rescale_nearest_on(hipStream_t st, const void *src, int src_w, int src_h, void *dst, int dst_w, int dst_h, int elem_bytes, const char *who)
 {
     if (!src || !dst || src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) {
-        return xfail(APD_ERR_INVALID, "%s: bad argument", who);
+        return set_error(g_exchange_error, APD_ERR_INVALID, "%s: bad argument", who);
     }
     if (src_w == dst_w && src_h == dst_h) {  // the reference returns before touching dst (APD.cpp:754-756); callers want the copy
-        X_TRY(hipMemcpyAsync(dst, src, (size_t)src_w * src_h * elem_bytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dst, src, (size_t)src_w * src_h * elem_bytes, hipMemcpyDeviceToDevice, st));
         return APD_OK;
     }
     const dim3 grid((dst_w + 255) / 256, dst_h);
@@ -344,44 +332,44 @@ static int rescale_nearest_on(hipStream_t st, const void *src, int src_w, int sr
     case 1: hipLaunchKernelGGL(apd::k_rescale_nearest<uint8_t>, grid, dim3(256), 0, st, (const uint8_t *)src, src_w, src_h, (uint8_t *)dst, dst_w, dst_h); break;
     case 4: hipLaunchKernelGGL(apd::k_rescale_nearest<uint32_t>, grid, dim3(256), 0, st, (const uint32_t *)src, src_w, src_h, (uint32_t *)dst, dst_w, dst_h); break;
     case 16: hipLaunchKernelGGL(apd::k_rescale_nearest<apd::Bytes16>, grid, dim3(256), 0, st, (const apd::Bytes16 *)src, src_w, src_h, (apd::Bytes16 *)dst, dst_w, dst_h); break;
-    default: return xfail(APD_ERR_INVALID, "%s: element size %d (1, 4 or 16 bytes)", who, elem_bytes);
+    default: return set_error(g_exchange_error, APD_ERR_INVALID, "%s: element size %d (1, 4 or 16 bytes)", who, elem_bytes);
     }
-    X_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return APD_OK;
 }
 
 int apd_rescale_nearest_device(int device, const void *src, int src_w, int src_h, void *dst, int dst_w, int dst_h, int elem_bytes)
 {
-    X_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     const int rc = rescale_nearest_on(nullptr, src, src_w, src_h, dst, dst_w, dst_h, elem_bytes, "apd_rescale_nearest_device");
     if (rc != APD_OK) {
         return rc;
     }
-    X_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     return APD_OK;
 }
 
 int apd_rescale_nearest_async(int device, void *hip_stream, const void *src, int src_w, int src_h, void *dst, int dst_w, int dst_h, int elem_bytes)
 {
-    X_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     return rescale_nearest_on((hipStream_t)hip_stream, src, src_w, src_h, dst, dst_w, dst_h, elem_bytes, "apd_rescale_nearest_async");
 }
 
 int apd_device_memcpy_async(int device, void *hip_stream, void *dst, const void *src, size_t bytes)
 {
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)hip_stream));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)hip_stream));
     return APD_OK;
 }
 
 int apd_stream_create(int device, void **hip_stream)
 {
     if (!hip_stream) {
-        return xfail(APD_ERR_INVALID, "apd_stream_create: null result pointer");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_stream_create: null result pointer");
     }
     hipStream_t st = nullptr;
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     *hip_stream = (void *)st;
     return APD_OK;
 }
@@ -391,15 +379,15 @@ int apd_stream_destroy(int device, void *hip_stream)
     if (!hip_stream) {
         return APD_OK;
     }
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipStreamDestroy((hipStream_t)hip_stream));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamDestroy((hipStream_t)hip_stream));
     return APD_OK;
 }
 
 int apd_stream_synchronize(int device, void *hip_stream)
 {
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
     return APD_OK;
 }
 
@@ -420,13 +408,13 @@ __global__ __launch_bounds__(256) void k_split_planes(const float4 *__restrict__
 int apd_split_planes_async(int device, void *hip_stream, const float *planes4, size_t pixels, float *depth, float *normal3)
 {
     if (!planes4 || !depth || !normal3) {
-        return xfail(APD_ERR_INVALID, "apd_split_planes_async: null pointer");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_split_planes_async: null pointer");
     }
-    X_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     if (pixels > 0) {
         hipLaunchKernelGGL(apd::k_split_planes, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
                            reinterpret_cast<const float4 *>(planes4), pixels, depth, normal3);
-        X_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return APD_OK;
 }
@@ -434,19 +422,19 @@ int apd_split_planes_async(int device, void *hip_stream, const float *planes4, s
 int apd_host_register(void *p, size_t bytes)
 {
     if (!p || bytes == 0) {
-        return xfail(APD_ERR_INVALID, "apd_host_register: bad argument");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_host_register: bad argument");
     }
-    X_TRY(hipHostRegister(p, bytes, hipHostRegisterPortable));
+    HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterPortable));
     return APD_OK;
 }
 
 int apd_host_alloc(size_t bytes, void **out)
 {
     if (!out || bytes == 0) {
-        return xfail(APD_ERR_INVALID, "apd_host_alloc: bad argument");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_host_alloc: bad argument");
     }
     *out = nullptr;
-    X_TRY(hipHostMalloc(out, bytes, hipHostMallocPortable));
+    HIP_TRY(hipHostMalloc(out, bytes, hipHostMallocPortable));
     return APD_OK;
 }
 
@@ -455,7 +443,7 @@ int apd_host_free(void *p)
     if (!p) {
         return APD_OK;
     }
-    X_TRY(hipHostFree(p));
+    HIP_TRY(hipHostFree(p));
     return APD_OK;
 }
 
@@ -464,7 +452,7 @@ int apd_host_unregister(void *p)
     if (!p) {
         return APD_OK;
     }
-    X_TRY(hipHostUnregister(p));
+    HIP_TRY(hipHostUnregister(p));
     return APD_OK;
 }
 
@@ -499,17 +487,17 @@ __global__ __launch_bounds__(256) void k_gather_blocks(GatherArgs a, word4 *__re
 int apd_exchange_create(apd_exchange_t *out, int num_ranks, const int *devices, int prefer_rccl)
 {
     if (!out || num_ranks < 1 || !devices) {
-        return xfail(APD_ERR_INVALID, "apd_exchange_create: bad argument");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_exchange_create: bad argument");
     }
     int found = 0;
-    X_TRY(hipGetDeviceCount(&found));
+    HIP_TRY(hipGetDeviceCount(&found));
     apd_exchange *x = new apd_exchange();
     x->devices.assign(devices, devices + num_ranks);
     bool distinct = true;
     for (int i = 0; i < num_ranks; ++i) {
         if (devices[i] < 0 || devices[i] >= found) {
             delete x;
-            return xfail(APD_ERR_INVALID, "apd_exchange_create: device %d requested, %d found", devices[i], found);
+            return set_error(g_exchange_error, APD_ERR_INVALID, "apd_exchange_create: device %d requested, %d found", devices[i], found);
         }
         for (int j = 0; j < i; ++j) {
             distinct = distinct && devices[i] != devices[j];
@@ -521,7 +509,7 @@ int apd_exchange_create(apd_exchange_t *out, int num_ranks, const int *devices, 
         if (hipSetDevice(devices[i]) != hipSuccess || hipStreamCreateWithFlags(&x->streams[i], hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&x->done[i], hipEventDisableTiming) != hipSuccess) {
             apd_exchange_destroy(x);
-            return xfail(APD_ERR_HIP, "apd_exchange_create: cannot create a stream on device %d", devices[i]);
+            return set_error(g_exchange_error, APD_ERR_HIP, "apd_exchange_create: cannot create a stream on device %d", devices[i]);
         }
     }
     // the list's period: its first `period` entries are distinct and the rest repeats them in order
@@ -575,7 +563,7 @@ int apd_exchange_create(apd_exchange_t *out, int num_ranks, const int *devices, 
 int apd_exchange_setup_times(apd_exchange_t x, double *dlopen_ms, double *init_ms)
 {
     if (!x) {
-        return xfail(APD_ERR_INVALID, "apd_exchange_setup_times: null exchange");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_exchange_setup_times: null exchange");
     }
     if (dlopen_ms) {
         *dlopen_ms = g_rccl.loaded_ms();
@@ -598,7 +586,7 @@ const char *apd_exchange_backend(apd_exchange_t x)
 int apd_exchange_counts(apd_exchange_t x, int *with_rccl, int *with_copies)
 {
     if (!x) {
-        return xfail(APD_ERR_INVALID, "apd_exchange_counts: null exchange");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_exchange_counts: null exchange");
     }
     if (with_rccl) {
         *with_rccl = x->exchanges_rccl;
@@ -626,7 +614,7 @@ int apd_exchange_allgather_after(apd_exchange_t x, const void *const *send, void
                                  void *const *hip_events)
 {
     if (num_events < 0 || (num_events > 0 && !hip_events)) {
-        return xfail(APD_ERR_INVALID, "apd_exchange_allgather_after: bad event list");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_exchange_allgather_after: bad event list");
     }
     return exchange_allgather(x, send, recv, bytes_per_rank, false, num_events, hip_events);
 }
@@ -635,7 +623,7 @@ static int exchange_allgather(apd_exchange_t x, const void *const *send, void *c
                               void *const *hip_events)
 {
     if (!x || !send || !recv) {
-        return xfail(APD_ERR_INVALID, "apd_exchange_allgather: bad argument");
+        return set_error(g_exchange_error, APD_ERR_INVALID, "apd_exchange_allgather: bad argument");
     }
     const int n = (int)x->devices.size();
     // The send buffers were written on other streams (the handles' own, the null stream of the pack copies); the exchange's
@@ -645,14 +633,14 @@ static int exchange_allgather(apd_exchange_t x, const void *const *send, void *c
     // exchange waits for every writer's event -- an already completed event costs nothing, a pending one is honoured
     // (the contract used to rest on the callers having synchronised their streams).
     for (int r = 0; r < n && device_sync; ++r) {
-        X_TRY(hipSetDevice(x->devices[r]));
-        X_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipSetDevice(x->devices[r]));
+        HIP_TRY(hipDeviceSynchronize());
     }
     for (int r = 0; r < n && num_events > 0; ++r) {
-        X_TRY(hipSetDevice(x->devices[r]));
+        HIP_TRY(hipSetDevice(x->devices[r]));
         for (int e = 0; e < num_events; ++e) {
             if (hip_events[e]) {
-                X_TRY(hipStreamWaitEvent(x->streams[r], (hipEvent_t)hip_events[e], 0));
+                HIP_TRY(hipStreamWaitEvent(x->streams[r], (hipEvent_t)hip_events[e], 0));
             }
         }
     }
@@ -672,11 +660,11 @@ static int exchange_allgather(apd_exchange_t x, const void *const *send, void *c
         const int rc_end = g_rccl.GroupEnd();
         rc = rc ? rc : rc_end;
         if (rc != 0) {
-            return xfail(APD_ERR_HIP, "ncclAllGather failed: %s", g_rccl.GetErrorString(rc));
+            return set_error(g_exchange_error, APD_ERR_HIP, "ncclAllGather failed: %s", g_rccl.GetErrorString(rc));
         }
         for (int r = period; r < n; ++r) {  // the other ranks of a device: a copy of their leader's result, ordered behind the gather
-            X_TRY(hipSetDevice(x->devices[r]));
-            X_TRY(hipMemcpyAsync(recv[r], recv[r % period], (size_t)n * bytes_per_rank, hipMemcpyDeviceToDevice, x->streams[r % period]));
+            HIP_TRY(hipSetDevice(x->devices[r]));
+            HIP_TRY(hipMemcpyAsync(recv[r], recv[r % period], (size_t)n * bytes_per_rank, hipMemcpyDeviceToDevice, x->streams[r % period]));
         }
     } else {
         x->exchanges_copy++;
@@ -686,7 +674,7 @@ static int exchange_allgather(apd_exchange_t x, const void *const *send, void *c
         const size_t words = bytes_per_rank / 16, tail = bytes_per_rank % 16;
         const bool kernel_ok = n <= apd::kGatherMaxRanks && (tail == 0 || n == 1);
         for (int dst = 0; dst < n; ++dst) {
-            X_TRY(hipSetDevice(x->devices[dst]));
+            HIP_TRY(hipSetDevice(x->devices[dst]));
             int twin = -1;   // an earlier rank on the same device
             for (int q = 0; q < dst && twin < 0; ++q) {
                 twin = x->devices[q] == x->devices[dst] ? q : -1;
@@ -694,17 +682,17 @@ static int exchange_allgather(apd_exchange_t x, const void *const *send, void *c
             apd::GatherArgs ga;
             memset(&ga, 0, sizeof(ga));
             if (twin >= 0) {
-                X_TRY(hipStreamWaitEvent(x->streams[dst], x->done[twin], 0));
+                HIP_TRY(hipStreamWaitEvent(x->streams[dst], x->done[twin], 0));
                 const size_t all = (size_t)n * bytes_per_rank;
                 if (all % 16 == 0 && all > 0 && ((uintptr_t)recv[dst] % 16) == 0 && ((uintptr_t)recv[twin] % 16) == 0) {
                     ga.src[0] = reinterpret_cast<const apd::word4 *>(recv[twin]);   // the whole result as one block
                     const unsigned gx = (unsigned)std::min<size_t>((all / 16 + 255) / 256, 2048);
                     hipLaunchKernelGGL(apd::k_gather_blocks, dim3(gx, 1), dim3(256), 0, x->streams[dst], ga, reinterpret_cast<apd::word4 *>(recv[dst]), all / 16, (size_t)0);
-                    X_TRY(hipGetLastError());
+                    HIP_TRY(hipGetLastError());
                 } else {
-                    X_TRY(hipMemcpyAsync(recv[dst], recv[twin], all, hipMemcpyDeviceToDevice, x->streams[dst]));
+                    HIP_TRY(hipMemcpyAsync(recv[dst], recv[twin], all, hipMemcpyDeviceToDevice, x->streams[dst]));
                 }
-                X_TRY(hipEventRecord(x->done[dst], x->streams[dst]));
+                HIP_TRY(hipEventRecord(x->done[dst], x->streams[dst]));
                 continue;
             }
             int direct = 0;
@@ -715,22 +703,22 @@ static int exchange_allgather(apd_exchange_t x, const void *const *send, void *c
                     ga.src[src] = reinterpret_cast<const apd::word4 *>(send[src]);
                     ++direct;
                 } else if (x->devices[src] == x->devices[dst]) {
-                    X_TRY(hipMemcpyAsync(to, send[src], bytes_per_rank, hipMemcpyDeviceToDevice, x->streams[dst]));
+                    HIP_TRY(hipMemcpyAsync(to, send[src], bytes_per_rank, hipMemcpyDeviceToDevice, x->streams[dst]));
                 } else {
-                    X_TRY(hipMemcpyPeerAsync(to, x->devices[dst], send[src], x->devices[src], bytes_per_rank, x->streams[dst]));
+                    HIP_TRY(hipMemcpyPeerAsync(to, x->devices[dst], send[src], x->devices[src], bytes_per_rank, x->streams[dst]));
                 }
             }
             if (direct > 0) {
                 const unsigned gx = (unsigned)std::min<size_t>((words + 255) / 256 + 1, 2048 / (size_t)std::max(1, std::min(direct, 8)) + 1);
                 hipLaunchKernelGGL(apd::k_gather_blocks, dim3(gx, (unsigned)n), dim3(256), 0, x->streams[dst], ga, reinterpret_cast<apd::word4 *>(recv[dst]), words, tail);
-                X_TRY(hipGetLastError());
+                HIP_TRY(hipGetLastError());
             }
-            X_TRY(hipEventRecord(x->done[dst], x->streams[dst]));
+            HIP_TRY(hipEventRecord(x->done[dst], x->streams[dst]));
         }
     }
     for (int r = 0; r < n; ++r) {
-        X_TRY(hipSetDevice(x->devices[r]));
-        X_TRY(hipStreamSynchronize(x->streams[r]));
+        HIP_TRY(hipSetDevice(x->devices[r]));
+        HIP_TRY(hipStreamSynchronize(x->streams[r]));
     }
     return APD_OK;
 }

@@ -15,11 +15,11 @@
 // The first undecided pixel of a round always decides (everything before it is decided), so the iteration ends, and a
 // pixel's decision only ever depends on decisions of earlier pixels: same result as the raster-order loop, bit for bit.
 // Accepted pixels then consume their supports, and a block scan compacts the points in raster order.
+//
+// The second half of the file is the host driver of every device fusion (apd_fusion_device.h), the T&T ones included.
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <chrono>
@@ -31,6 +31,71 @@
 #include "apd_fusion_math.h"
 
 namespace {
+
+// exclusive scan of the block counts (one workgroup; a view has at most a few hundred thousand blocks)
+__global__ __launch_bounds__(1024) void k_fusion_scan(int *__restrict__ counts, int nblocks, int *__restrict__ total)
+{
+    __shared__ int part[1024];
+    const int t = threadIdx.x;
+    const int per = (nblocks + 1023) / 1024;
+    const int b0 = t * per, b1 = min(b0 + per, nblocks);
+    int sum = 0;
+    for (int b = b0; b < b1; ++b) {
+        sum += counts[b];
+    }
+    part[t] = sum;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = (t >= off) ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - sum;
+    for (int b = b0; b < b1; ++b) {
+        const int c = counts[b];
+        counts[b] = run;
+        run += c;
+    }
+    if (t == 1023) {
+        *total = part[1023];
+    }
+}
+
+// Packs the points of a view (pixels p < n with state[p] == accepted) in raster order as the 15-byte records of the PLY body
+// (x y z float, diffuse_blue / green / red uchar, APD.cpp:214-254): one download per view straight into the file image, no
+// per-point loop on the host.  block_offsets: k_fusion_scan of the per-256-pixel point counts.
+__global__ __launch_bounds__(256) void k_fusion_compact(const uint8_t *__restrict__ state, uint8_t accepted, int n,
+                                                         const float *__restrict__ xyz_sparse, const uint8_t *__restrict__ bgr_sparse,
+                                                         const int *__restrict__ block_offsets, uint8_t *__restrict__ records)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const bool acc = p < n && state[p] == accepted;
+    const unsigned long long m = __ballot(acc);
+    __shared__ int wave_counts[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+        wave_counts[wave] = __popcll(m);
+    }
+    __syncthreads();
+    if (acc) {
+        int pos = block_offsets[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) {
+            pos += wave_counts[w];
+        }
+        uint8_t *rec = records + (size_t)pos * 15;
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t bits = __float_as_uint(xyz_sparse[3 * (size_t)p + k]);  // little endian, as the host's memcpy wrote them
+            rec[4 * k + 0] = (uint8_t)(bits & 0xFFu);
+            rec[4 * k + 1] = (uint8_t)((bits >> 8) & 0xFFu);
+            rec[4 * k + 2] = (uint8_t)((bits >> 16) & 0xFFu);
+            rec[4 * k + 3] = (uint8_t)(bits >> 24);
+        }
+        rec[12] = bgr_sparse[3 * (size_t)p + 0];
+        rec[13] = bgr_sparse[3 * (size_t)p + 1];
+        rec[14] = bgr_sparse[3 * (size_t)p + 2];
+    }
+}
 
 using apd_fusion::View;
 
@@ -213,25 +278,84 @@ __global__ __launch_bounds__(256) void k_fusion_emit(const DevView *__restrict__
     }
 }
 
-using apd_fusion::g_fusion_error;
-using apd_fusion::g_fusion_ms;
 
-int fusion_fail(int code, const char *what, hipError_t e)
+struct EthFusion : apd_fusion::Call {
+    using Call::Call;
+    int run();
+};
+
+int EthFusion::run()
 {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "apd_fuse_views: %s: %s", what, hipGetErrorString(e));
-    g_fusion_error = buf;
-    return code;
+    if (const int rc = begin(true); rc != APD_OK) {
+        return rc;
+    }
+    std::vector<DevView> hv(a.num_views);
+    for (int i = 0; i < a.num_views; ++i) {
+        DevView &v = hv[i];
+        const size_t n = (size_t)pixels(i);
+        if (const int rc = fill_view(i, v); rc != APD_OK) {
+            return rc;
+        }
+        HIP_TRY(device_map(a.weaks[i], n, &v.weak));
+        if (const int rc = fill_block(i, v); rc != APD_OK) {
+            return rc;
+        }
+        HIP_TRY(alloc(n, &v.consumed));
+        HIP_TRY(alloc(n * 8, &v.claim));
+        HIP_TRY(hipMemset(v.consumed, 0, n));
+        HIP_TRY(hipMemset(v.claim, 0xFF, n * 8));
+    }
+    DevView *dviews = nullptr;
+    if (const int rc = upload_views(hv, &dviews); rc != APD_OK) {
+        return rc;
+    }
+    RefTask task;
+    task.channels = a.image_channels;
+    HIP_TRY(alloc(max_px * max_src * 4, &task.vote_idx));
+    HIP_TRY(alloc(max_px * max_src * 4, &task.vote_w));
+    HIP_TRY(alloc(max_px, &task.state));
+    HIP_TRY(alloc(sizeof(int), &task.flags));
+    if (const int rc = alloc_common(); rc != APD_OK) {
+        return rc;
+    }
+    unsigned epoch = 0;
+    for (int i = 0; i < a.num_views; ++i) {
+        const int n = pixels(i);
+        const int blocks = (n + 255) / 256;
+        if (n == 0) {
+            continue;
+        }
+        task.ref = i;
+        task.num_src = sources(i);
+        for (int j = 0; j < task.num_src; ++j) {
+            task.src[j] = a.pair_indices[a.pair_offsets[i] + j];
+        }
+        hipLaunchKernelGGL(k_fusion_votes, dim3(blocks), dim3(256), 0, 0, dviews, task);
+        HIP_TRY(hipGetLastError());
+        int rounds = 0;
+        for (;;) {
+            ++epoch;
+            ++rounds;
+            HIP_TRY(hipMemsetAsync(task.flags, 0, sizeof(int), 0));
+            hipLaunchKernelGGL(k_fusion_claim, dim3(blocks), dim3(256), 0, 0, dviews, task, epoch);
+            hipLaunchKernelGGL(k_fusion_decide, dim3(blocks), dim3(256), 0, 0, dviews, task, epoch);
+            HIP_TRY(hipGetLastError());
+            int undecided = 0;
+            HIP_TRY(hipMemcpy(&undecided, task.flags, sizeof(int), hipMemcpyDeviceToHost));
+            if (undecided == 0) {
+                break;
+            }
+            if (rounds > n) {  // cannot happen: the first undecided pixel decides in every round
+                return apd::set_error(apd_fusion::g_fusion_error, APD_ERR_STATE, "%s: consumption rounds did not converge", who);
+            }
+        }
+        hipLaunchKernelGGL(k_fusion_emit, dim3(blocks), dim3(256), 0, 0, dviews, task, xyz, bgr, block_counts);
+        if (const int rc = collect(i, task.state, kAccepted); rc != APD_OK) {
+            return rc;
+        }
+    }
+    return finish();
 }
-
-#define FUS_TRY(expr)                                        \
-    do {                                                     \
-        hipError_t e_ = (expr);                              \
-        if (e_ != hipSuccess) {                              \
-            cleanup();                                       \
-            return fusion_fail(APD_ERR_HIP, #expr, e_);      \
-        }                                                    \
-    } while (0)
 
 }  // namespace
 
@@ -240,11 +364,19 @@ namespace apd_fusion {
 thread_local std::string g_fusion_error;
 thread_local double g_fusion_ms[3] = {0.0, 0.0, 0.0};
 
+namespace {
+
+double ms_since(std::chrono::steady_clock::time_point t)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+// ExportPointCloud (APD.cpp:214-254): header + the views' records in order.  APD_OK, or APD_ERR_IO with g_fusion_error set
 int write_ply(const char *who, const char *ply_path, long long count, const std::vector<std::vector<uint8_t>> &body)
 {
     FILE *f = fopen(ply_path, "wb");
     if (!f) {
-        g_fusion_error = std::string(who) + ": cannot write " + ply_path;
+        g_fusion_error = std::string(who) + ": cannot write " + ply_path;  // no length limit: not through set_error
         return APD_ERR_IO;
     }
     fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
@@ -260,20 +392,133 @@ int write_ply(const char *who, const char *ply_path, long long count, const std:
     return APD_OK;
 }
 
+}  // namespace
+
+int Call::begin(bool eth)
+{
+    g_fusion_error.clear();
+    auto invalid = [this](const char *what) { return apd::set_error(g_fusion_error, APD_ERR_INVALID, "%s: %s", who, what); };
+    if (a.num_views <= 0 || !a.cameras || !a.images || !a.depths || !a.normals || (eth && !a.weaks) || !a.rows || !a.cols || !a.pair_offsets ||
+        !a.pair_indices || !a.ply_path || !a.num_points) {
+        return invalid("null argument");
+    }
+    if (a.image_channels != 1 && a.image_channels != 3) {
+        return invalid("images have 1 (grey) or 3 (blue, green, red) channels");
+    }
+    for (int i = 0; i < a.num_views; ++i) {
+        const int ns = a.pair_offsets[i + 1] - a.pair_offsets[i];
+        if (ns < 0 || ns > APD_MAX_IMAGES) {
+            return invalid("a view has more than APD_MAX_IMAGES sources");
+        }
+        if (a.rows[i] < 0 || a.cols[i] < 0 || (long long)a.rows[i] * a.cols[i] > 0x7fffff00LL) {  // pixel indices are ints
+            return invalid("view size out of range");
+        }
+        for (int k = a.pair_offsets[i]; k < a.pair_offsets[i + 1]; ++k) {
+            if (a.pair_indices[k] < 0 || a.pair_indices[k] >= a.num_views) {
+                return invalid("source index out of range");
+            }
+            // ETH: the consumption of a view's own pixels would be order dependent inside the vote kernel; T&T: the view would read the
+            // masks it writes
+            if (a.pair_indices[k] == i) {
+                return invalid(eth ? "a view lists itself as a source (use the host fusion)" : "a view lists itself as a source");
+            }
+        }
+    }
+    for (int i = 0; i < a.num_views; ++i) {
+        max_px = std::max(max_px, (size_t)pixels(i));
+        max_src = std::max(max_src, sources(i));
+    }
+    body_.resize((size_t)a.num_views);
+    HIP_TRY(hipSetDevice(a.device));
+    return APD_OK;
+}
+
+Call::Call(const char *who_, const Args &args) : who(who_), a(args), t_lap_(std::chrono::steady_clock::now()) {}
+
+void Call::release()
+{
+    for (void *p : owned_) {
+        hipFree(p);
+    }
+    owned_.clear();
+    if (staging_) {
+        hipHostFree(staging_);
+        staging_ = nullptr;
+    }
+}
+
+int Call::hip_failed(const char *expr, hipError_t e, const char *, int) const
+{
+    return apd::set_error(g_fusion_error, APD_ERR_HIP, "%s: %s: %s", who, expr, hipGetErrorString(e));
+}
+
+int Call::alloc_common()
+{
+    HIP_TRY(alloc(max_px * 12, &xyz));
+    HIP_TRY(alloc(max_px * 3, &bgr));
+    HIP_TRY(alloc(max_blocks() * 4, &block_counts));
+    HIP_TRY(alloc(sizeof(int), &total_));
+    HIP_TRY(alloc(max_px * 15, &records_));
+    if (hipHostMalloc(&staging_, max_px * 15 > 0 ? max_px * 15 : 1, hipHostMallocDefault) != hipSuccess) {
+        staging_ = nullptr;  // pageable downloads then
+    }
+    g_fusion_ms[0] = ms_since(t_lap_);
+    t_lap_ = std::chrono::steady_clock::now();
+    return APD_OK;
+}
+
+int Call::collect(int i, const uint8_t *state, uint8_t accepted)
+{
+    const int n = pixels(i);
+    const int blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_fusion_scan, dim3(1), dim3(1024), 0, 0, block_counts, blocks, total_);
+    hipLaunchKernelGGL(k_fusion_compact, dim3(blocks), dim3(256), 0, 0, state, accepted, n, (const float *)xyz, (const uint8_t *)bgr,
+                       (const int *)block_counts, records_);
+    HIP_TRY(hipGetLastError());
+    int npts = 0;
+    HIP_TRY(hipMemcpy(&npts, total_, sizeof(int), hipMemcpyDeviceToHost));
+    if (npts > 0) {
+        std::vector<uint8_t> &part = body_[i];
+        part.resize((size_t)npts * 15);
+        if (staging_) {
+            HIP_TRY(hipMemcpy(staging_, records_, part.size(), hipMemcpyDeviceToHost));
+            memcpy(part.data(), staging_, part.size());
+        } else {
+            HIP_TRY(hipMemcpy(part.data(), records_, part.size(), hipMemcpyDeviceToHost));
+        }
+        count_ += npts;
+    }
+    return APD_OK;
+}
+
+int Call::finish()
+{
+    g_fusion_ms[1] = ms_since(t_lap_);
+    t_lap_ = std::chrono::steady_clock::now();
+    release();
+    const int written = write_ply(who, a.ply_path, count_, body_);
+    if (written != APD_OK) {
+        return written;
+    }
+    *a.num_points = count_;
+    g_fusion_ms[2] = ms_since(t_lap_);
+    return APD_OK;
+}
+
 }  // namespace apd_fusion
 
-extern "C" const char *apd_fusion_last_error(void) { return g_fusion_error.c_str(); }
+extern "C" const char *apd_fusion_last_error(void) { return apd_fusion::g_fusion_error.c_str(); }
 
 extern "C" int apd_fusion_last_timing(double *setup_ms, double *views_ms, double *file_ms)
 {
     if (setup_ms) {
-        *setup_ms = g_fusion_ms[0];
+        *setup_ms = apd_fusion::g_fusion_ms[0];
     }
     if (views_ms) {
-        *views_ms = g_fusion_ms[1];
+        *views_ms = apd_fusion::g_fusion_ms[1];
     }
     if (file_ms) {
-        *file_ms = g_fusion_ms[2];
+        *file_ms = apd_fusion::g_fusion_ms[2];
     }
     return APD_OK;
 }
@@ -283,208 +528,7 @@ extern "C" int apd_fuse_views(int device, int num_views, const apd_camera *camer
                               const uint8_t *const *blocks, const int *rows, const int *cols, const int *pair_offsets, const int *pair_indices, int maps_on_device,
                               const char *ply_path, long long *num_points)
 {
-    g_fusion_error.clear();
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point t) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-    };
-    if (num_views <= 0 || !cameras || !images || !depths || !normals || !weaks || !rows || !cols || !pair_offsets || !pair_indices ||
-        !ply_path || !num_points) {
-        g_fusion_error = "apd_fuse_views: null argument";
-        return APD_ERR_INVALID;
-    }
-    if (image_channels != 1 && image_channels != 3) {
-        g_fusion_error = "apd_fuse_views: images have 1 (grey) or 3 (blue, green, red) channels";
-        return APD_ERR_INVALID;
-    }
-    for (int i = 0; i < num_views; ++i) {
-        const int ns = pair_offsets[i + 1] - pair_offsets[i];
-        if (ns < 0 || ns > kMaxSrc) {
-            g_fusion_error = "apd_fuse_views: a view has more than APD_MAX_IMAGES sources";
-            return APD_ERR_INVALID;
-        }
-        for (int k = pair_offsets[i]; k < pair_offsets[i + 1]; ++k) {
-            if (pair_indices[k] < 0 || pair_indices[k] >= num_views) {
-                g_fusion_error = "apd_fuse_views: source index out of range";
-                return APD_ERR_INVALID;
-            }
-            if (pair_indices[k] == i) {  // the consumption of a view's own pixels would be order dependent inside the vote kernel
-                g_fusion_error = "apd_fuse_views: a view lists itself as a source (use the host fusion)";
-                return APD_ERR_INVALID;
-            }
-        }
-    }
-    std::vector<void *> owned;
-    std::vector<DevView> hv(num_views);
-    DevView *dviews = nullptr;
-    void *staging = nullptr;  // page-locked buffer of the point downloads
-    auto cleanup = [&]() {
-        for (void *p : owned) {
-            hipFree(p);
-        }
-        owned.clear();
-        if (staging) {
-            hipHostFree(staging);
-            staging = nullptr;
-        }
-    };
-    auto dev_alloc = [&](size_t bytes, void **out) -> hipError_t {
-        hipError_t e = hipMalloc(out, bytes > 0 ? bytes : 1);
-        if (e == hipSuccess) {
-            owned.push_back(*out);
-        }
-        return e;
-    };
-    FUS_TRY(hipSetDevice(device));
-    size_t max_px = 0;
-    for (int i = 0; i < num_views; ++i) {
-        const size_t n = (size_t)rows[i] * cols[i];
-        max_px = n > max_px ? n : max_px;
-        DevView &v = hv[i];
-        const apd_camera &c = cameras[i];
-        memcpy(v.geo.K, c.K, sizeof(v.geo.K));
-        memcpy(v.geo.R, c.R, sizeof(v.geo.R));
-        memcpy(v.geo.t, c.t, sizeof(v.geo.t));
-        // -R^T t in float, term order of Get3DPointonWorld (APD.cpp:795-798)
-        v.geo.centre[0] = -(c.R[0] * c.t[0] + c.R[3] * c.t[1] + c.R[6] * c.t[2]);
-        v.geo.centre[1] = -(c.R[1] * c.t[0] + c.R[4] * c.t[1] + c.R[7] * c.t[2]);
-        v.geo.centre[2] = -(c.R[2] * c.t[0] + c.R[5] * c.t[1] + c.R[8] * c.t[2]);
-        v.geo.rows = rows[i];
-        v.geo.cols = cols[i];
-        if (maps_on_device) {
-            v.image = images[i];
-            v.depth = depths[i];
-            v.normal = normals[i];
-            v.weak = weaks[i];
-            v.block = blocks ? blocks[i] : nullptr;
-        } else {
-            void *g, *d, *nm, *w;
-            FUS_TRY(dev_alloc(n * 4 * image_channels, &g));
-            FUS_TRY(dev_alloc(n * 4, &d));
-            FUS_TRY(dev_alloc(n * 12, &nm));
-            FUS_TRY(dev_alloc(n, &w));
-            FUS_TRY(hipMemcpy(g, images[i], n * 4 * image_channels, hipMemcpyHostToDevice));
-            FUS_TRY(hipMemcpy(d, depths[i], n * 4, hipMemcpyHostToDevice));
-            FUS_TRY(hipMemcpy(nm, normals[i], n * 12, hipMemcpyHostToDevice));
-            FUS_TRY(hipMemcpy(w, weaks[i], n, hipMemcpyHostToDevice));
-            v.image = (const float *)g;
-            v.depth = (const float *)d;
-            v.normal = (const float *)nm;
-            v.weak = (const uint8_t *)w;
-            v.block = nullptr;
-            if (blocks && blocks[i]) {
-                void *b;
-                FUS_TRY(dev_alloc(n, &b));
-                FUS_TRY(hipMemcpy(b, blocks[i], n, hipMemcpyHostToDevice));
-                v.block = (const uint8_t *)b;
-            }
-        }
-        void *cons, *claim;
-        FUS_TRY(dev_alloc(n, &cons));
-        FUS_TRY(dev_alloc(n * 8, &claim));
-        FUS_TRY(hipMemset(cons, 0, n));
-        FUS_TRY(hipMemset(claim, 0xFF, n * 8));
-        v.consumed = (uint8_t *)cons;
-        v.claim = (unsigned long long *)claim;
-    }
-    {
-        void *p;
-        FUS_TRY(dev_alloc(sizeof(DevView) * num_views, &p));
-        dviews = (DevView *)p;
-        FUS_TRY(hipMemcpy(dviews, hv.data(), sizeof(DevView) * num_views, hipMemcpyHostToDevice));
-    }
-    int max_src = 1;
-    for (int i = 0; i < num_views; ++i) {
-        max_src = std::max(max_src, pair_offsets[i + 1] - pair_offsets[i]);
-    }
-    const int max_blocks = (int)((max_px + 255) / 256);
-    void *vote_idx, *vote_w, *state, *flags, *xyz_sparse, *grey_sparse, *block_counts, *total, *records;
-    FUS_TRY(dev_alloc(max_px * max_src * 4, &vote_idx));
-    FUS_TRY(dev_alloc(max_px * max_src * 4, &vote_w));
-    FUS_TRY(dev_alloc(max_px, &state));
-    FUS_TRY(dev_alloc(sizeof(int), &flags));
-    FUS_TRY(dev_alloc(max_px * 12, &xyz_sparse));
-    FUS_TRY(dev_alloc(max_px * 3, &grey_sparse));
-    FUS_TRY(dev_alloc((size_t)max_blocks * 4, &block_counts));
-    FUS_TRY(dev_alloc(sizeof(int), &total));
-    FUS_TRY(dev_alloc(max_px * 15, &records));
-
-    // PLY records: x y z float + diffuse_blue/green/red uchar (APD.cpp:214-254), one buffer per view (one growing vector re-allocates and
-    // copies hundreds of megabytes at Tanks&Temples scale), downloaded through one page-locked staging buffer
-    std::vector<std::vector<uint8_t>> body((size_t)num_views);
-    if (hipHostMalloc(&staging, max_px * 15 > 0 ? max_px * 15 : 1, hipHostMallocDefault) != hipSuccess) {
-        staging = nullptr;  // pageable downloads then
-    }
-    g_fusion_ms[0] = ms_since(t_begin);
-    const auto t_views = std::chrono::steady_clock::now();
-    long long count = 0;
-    unsigned epoch = 0;
-    for (int i = 0; i < num_views; ++i) {
-        const int n = rows[i] * cols[i];
-        const int blocks = (n + 255) / 256;
-        RefTask task;
-        task.ref = i;
-        task.num_src = pair_offsets[i + 1] - pair_offsets[i];
-        for (int j = 0; j < task.num_src; ++j) {
-            task.src[j] = pair_indices[pair_offsets[i] + j];
-        }
-        task.vote_idx = (int *)vote_idx;
-        task.vote_w = (float *)vote_w;
-        task.state = (uint8_t *)state;
-        task.flags = (int *)flags;
-        task.channels = image_channels;
-        if (n == 0) {
-            continue;
-        }
-        hipLaunchKernelGGL(k_fusion_votes, dim3(blocks), dim3(256), 0, 0, dviews, task);
-        FUS_TRY(hipGetLastError());
-        int rounds = 0;
-        for (;;) {
-            ++epoch;
-            ++rounds;
-            FUS_TRY(hipMemsetAsync(flags, 0, sizeof(int), 0));
-            hipLaunchKernelGGL(k_fusion_claim, dim3(blocks), dim3(256), 0, 0, dviews, task, epoch);
-            hipLaunchKernelGGL(k_fusion_decide, dim3(blocks), dim3(256), 0, 0, dviews, task, epoch);
-            FUS_TRY(hipGetLastError());
-            int undecided = 0;
-            FUS_TRY(hipMemcpy(&undecided, flags, sizeof(int), hipMemcpyDeviceToHost));
-            if (undecided == 0) {
-                break;
-            }
-            if (rounds > n) {  // cannot happen: the first undecided pixel decides in every round
-                cleanup();
-                g_fusion_error = "apd_fuse_views: consumption rounds did not converge";
-                return APD_ERR_STATE;
-            }
-        }
-        hipLaunchKernelGGL(k_fusion_emit, dim3(blocks), dim3(256), 0, 0, dviews, task, (float *)xyz_sparse, (uint8_t *)grey_sparse,
-                           (int *)block_counts);
-        hipLaunchKernelGGL(k_fusion_scan, dim3(1), dim3(1024), 0, 0, (int *)block_counts, blocks, (int *)total);
-        hipLaunchKernelGGL(k_fusion_compact, dim3(blocks), dim3(256), 0, 0, (const uint8_t *)task.state, (uint8_t)kAccepted, n, (const float *)xyz_sparse,
-                           (const uint8_t *)grey_sparse, (const int *)block_counts, (uint8_t *)records);
-        FUS_TRY(hipGetLastError());
-        int npts = 0;
-        FUS_TRY(hipMemcpy(&npts, total, sizeof(int), hipMemcpyDeviceToHost));
-        (void)rounds;
-        if (npts > 0) {
-            body[i].resize((size_t)npts * 15);
-            if (staging) {
-                FUS_TRY(hipMemcpy(staging, records, (size_t)npts * 15, hipMemcpyDeviceToHost));
-                memcpy(body[i].data(), staging, (size_t)npts * 15);
-            } else {
-                FUS_TRY(hipMemcpy(body[i].data(), records, (size_t)npts * 15, hipMemcpyDeviceToHost));
-            }
-            count += npts;
-        }
-    }
-    g_fusion_ms[1] = ms_since(t_views);
-    const auto t_file = std::chrono::steady_clock::now();
-    cleanup();
-    const int written = apd_fusion::write_ply("apd_fuse_views", ply_path, count, body);
-    if (written != APD_OK) {
-        return written;
-    }
-    *num_points = count;
-    g_fusion_ms[2] = ms_since(t_file);
-    return APD_OK;
+    const apd_fusion::Args a = {device, num_views, cameras, images, image_channels, depths, normals, weaks, blocks, rows, cols, pair_offsets,
+                                pair_indices, maps_on_device, ply_path, num_points};
+    return EthFusion("apd_fuse_views", a).run();
 }

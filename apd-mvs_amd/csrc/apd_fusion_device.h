@@ -1,92 +1,169 @@
-// apd_fusion_device.h -- what the device fusions share (apd_fusion.hip: ETH, apd_fusion_tat.hip: Tanks and Temples): the raster-order
-// compaction of a view's points into the 15-byte PLY records, the PLY writer, and the per-thread error / timing that
-// apd_fusion_last_error and apd_fusion_last_timing report.
+// apd_fusion_device.h -- the host driver the device fusions share (apd_fusion.hip: ETH, apd_fusion_tat.hip: Tanks and Temples).
+// Implemented once, in apd_fusion.hip, together with the two kernels only it launches (k_fusion_scan, k_fusion_compact): argument
+// checks, the device memory of a call, the per-view geometry and maps, the scratch of the point compaction, the download of a
+// view's points, the PLY file, and the per-thread error / timing that apd_fusion_last_error and apd_fusion_last_timing report.
+// A variant derives from Call and adds its own view members, scratch and kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+#include <string.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
+
+#include "../../include/apd_mi355x.h"
+#include "apd_host_error.h"
 
 namespace apd_fusion {
 
 extern thread_local std::string g_fusion_error;
 extern thread_local double g_fusion_ms[3];  // last fusion: set-up (allocations, uploads), views (kernels + point downloads), PLY file
 
-// ExportPointCloud (APD.cpp:214-254): header + the views' records in order.  APD_OK, or APD_ERR_IO with g_fusion_error set
-// (`who` prefixes the message).
-int write_ply(const char *who, const char *ply_path, long long count, const std::vector<std::vector<uint8_t>> &body);
+// The arguments of apd_fuse_views / apd_fuse_views_variant (include/apd_mi355x.h)
+struct Args {
+    int device, num_views;
+    const apd_camera *cameras;
+    const float *const *images;
+    int image_channels;
+    const float *const *depths;
+    const float *const *normals;
+    const uint8_t *const *weaks;
+    const uint8_t *const *blocks;
+    const int *rows, *cols, *pair_offsets, *pair_indices;
+    int maps_on_device;
+    const char *ply_path;
+    long long *num_points;
+};
+
+// One fusion call.  Owns every device allocation and the page-locked staging buffer of the call: whichever way the call returns,
+// they are released, in the order they were made.
+class Call {
+public:
+    Call(const char *who, const Args &args);  // the clock of the set-up starts here
+    ~Call() { release(); }
+    Call(const Call &) = delete;
+    Call &operator=(const Call &) = delete;
+
+protected:
+    const char *const who;  // the entry point, prefix of every message
+    const Args a;
+    size_t max_px = 0;      // pixels of the largest view
+    int max_src = 1;        // sources of the view with the most
+    float *xyz = nullptr;   // [pixel][3] of the view being fused: the points where they are, before the compaction
+    uint8_t *bgr = nullptr; // [pixel][3]
+    int *block_counts = nullptr;  // points per block of 256 pixels
+
+    int hip_failed(const char *expr, hipError_t e, const char *file, int line) const;  // what HIP_TRY returns
+    int pixels(int i) const { return a.rows[i] * a.cols[i]; }  // begin(): fits
+    size_t max_blocks() const { return (max_px + 255) / 256; }  // blocks of 256 pixels of the largest view
+    int sources(int i) const { return a.pair_offsets[i + 1] - a.pair_offsets[i]; }
+
+    template <typename T> hipError_t alloc(size_t bytes, T **out)
+    {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes > 0 ? bytes : 1);
+        if (e == hipSuccess) {
+            owned_.push_back(p);
+            *out = static_cast<T *>(p);
+        }
+        return e;
+    }
+
+    // First step of every variant.  Clears the last error and checks the arguments: APD_ERR_INVALID with "<who>: ..." before any
+    // device is touched.  eth: the weak maps are required, and a view that is its own source is pointed to the host fusion.  Then
+    // selects the device.
+    int begin(bool eth);
+
+    // *out = the caller's map if the maps are on the device, else a device copy of it
+    template <typename T> hipError_t device_map(const T *map, size_t bytes, const T **out)
+    {
+        *out = map;
+        if (a.maps_on_device) {
+            return hipSuccess;
+        }
+        T *copy;
+        hipError_t e = alloc(bytes, &copy);
+        if (e == hipSuccess) {
+            *out = copy;
+            e = hipMemcpy(copy, map, bytes, hipMemcpyHostToDevice);
+        }
+        return e;
+    }
+
+    // What DevView and TatView have in common, but for the block map: the geometry of cameras[i], and the image, depth and normal maps
+    template <typename V> int fill_view(int i, V &v)
+    {
+        const apd_camera &c = a.cameras[i];
+        memcpy(v.geo.K, c.K, sizeof(v.geo.K));
+        memcpy(v.geo.R, c.R, sizeof(v.geo.R));
+        memcpy(v.geo.t, c.t, sizeof(v.geo.t));
+        // -R^T t in float, term order of Get3DPointonWorld (APD.cpp:795-798)
+        v.geo.centre[0] = -(c.R[0] * c.t[0] + c.R[3] * c.t[1] + c.R[6] * c.t[2]);
+        v.geo.centre[1] = -(c.R[1] * c.t[0] + c.R[4] * c.t[1] + c.R[7] * c.t[2]);
+        v.geo.centre[2] = -(c.R[2] * c.t[0] + c.R[5] * c.t[1] + c.R[8] * c.t[2]);
+        v.geo.rows = a.rows[i];
+        v.geo.cols = a.cols[i];
+        v.image = a.images[i];
+        v.depth = a.depths[i];
+        v.normal = a.normals[i];
+        if (!a.maps_on_device) {
+            const size_t n = (size_t)pixels(i);
+            float *g, *d, *nm;
+            HIP_TRY(alloc(n * 4 * a.image_channels, &g));
+            HIP_TRY(alloc(n * 4, &d));
+            HIP_TRY(alloc(n * 12, &nm));
+            HIP_TRY(hipMemcpy(g, a.images[i], n * 4 * a.image_channels, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d, a.depths[i], n * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(nm, a.normals[i], n * 12, hipMemcpyHostToDevice));
+            v.image = g;
+            v.depth = d;
+            v.normal = nm;
+        }
+        return APD_OK;
+    }
+
+    // The optional block map of view i, after the variant's own maps: the last upload of a view, as it always was
+    template <typename V> int fill_block(int i, V &v)
+    {
+        v.block = nullptr;
+        if (a.blocks && a.blocks[i]) {
+            HIP_TRY(device_map(a.blocks[i], (size_t)pixels(i), &v.block));
+        }
+        return APD_OK;
+    }
+
+    // The view table on the device
+    template <typename V> int upload_views(const std::vector<V> &views, V **dviews)
+    {
+        HIP_TRY(alloc(sizeof(V) * views.size(), dviews));
+        HIP_TRY(hipMemcpy(*dviews, views.data(), sizeof(V) * views.size(), hipMemcpyHostToDevice));
+        return APD_OK;
+    }
+
+    // The scratch every variant needs (xyz, bgr, block_counts, and what collect() uses) and the staging buffer, sized for the
+    // largest view.  Ends the set-up: its time is taken here.
+    int alloc_common();
+    // View i has its points in xyz / bgr, block_counts filled, and state[p] == accepted where pixel p is a point: packs them in
+    // raster order as PLY records (k_fusion_scan, k_fusion_compact) and downloads them.
+    int collect(int i, const uint8_t *state, uint8_t accepted);
+    // Takes the time of the views, releases the device memory, writes the file, and then sets *num_points.
+    int finish();
+
+private:
+    void release();
+
+    std::vector<void *> owned_;
+    void *staging_ = nullptr;  // page-locked buffer of the point downloads
+    int *total_ = nullptr;     // points of the view
+    uint8_t *records_ = nullptr;
+    // PLY records: x y z float + diffuse_blue/green/red uchar (APD.cpp:214-254), one buffer per view (one growing vector re-allocates
+    // and copies hundreds of megabytes at Tanks&Temples scale), downloaded through one page-locked staging buffer
+    std::vector<std::vector<uint8_t>> body_;
+    long long count_ = 0;
+    std::chrono::steady_clock::time_point t_lap_;
+};
 
 }  // namespace apd_fusion
-
-// Internal linkage: every fusion source gets its own copy of the two kernels.
-namespace {
-
-// exclusive scan of the block counts (one workgroup; a view has at most a few hundred thousand blocks)
-__global__ __launch_bounds__(1024) void k_fusion_scan(int *__restrict__ counts, int nblocks, int *__restrict__ total)
-{
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int per = (nblocks + 1023) / 1024;
-    const int b0 = t * per, b1 = min(b0 + per, nblocks);
-    int sum = 0;
-    for (int b = b0; b < b1; ++b) {
-        sum += counts[b];
-    }
-    part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - sum;
-    for (int b = b0; b < b1; ++b) {
-        const int c = counts[b];
-        counts[b] = run;
-        run += c;
-    }
-    if (t == 1023) {
-        *total = part[1023];
-    }
-}
-
-// Packs the points of a view (pixels p < n with state[p] == accepted) in raster order as the 15-byte records of the PLY body
-// (x y z float, diffuse_blue / green / red uchar, APD.cpp:214-254): one download per view straight into the file image, no
-// per-point loop on the host.  block_offsets: k_fusion_scan of the per-256-pixel point counts.
-__global__ __launch_bounds__(256) void k_fusion_compact(const uint8_t *__restrict__ state, uint8_t accepted, int n,
-                                                         const float *__restrict__ xyz_sparse, const uint8_t *__restrict__ bgr_sparse,
-                                                         const int *__restrict__ block_offsets, uint8_t *__restrict__ records)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    const bool acc = p < n && state[p] == accepted;
-    const unsigned long long m = __ballot(acc);
-    __shared__ int wave_counts[4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-        wave_counts[wave] = __popcll(m);
-    }
-    __syncthreads();
-    if (acc) {
-        int pos = block_offsets[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) {
-            pos += wave_counts[w];
-        }
-        uint8_t *rec = records + (size_t)pos * 15;
-        for (int k = 0; k < 3; ++k) {
-            const uint32_t bits = __float_as_uint(xyz_sparse[3 * (size_t)p + k]);  // little endian, as the host's memcpy wrote them
-            rec[4 * k + 0] = (uint8_t)(bits & 0xFFu);
-            rec[4 * k + 1] = (uint8_t)((bits >> 8) & 0xFFu);
-            rec[4 * k + 2] = (uint8_t)((bits >> 16) & 0xFFu);
-            rec[4 * k + 3] = (uint8_t)(bits >> 24);
-        }
-        rec[12] = bgr_sparse[3 * (size_t)p + 0];
-        rec[13] = bgr_sparse[3 * (size_t)p + 1];
-        rec[14] = bgr_sparse[3 * (size_t)p + 2];
-    }
-}
-
-}  // namespace

@@ -15,7 +15,8 @@
 //   k_tat_decide  one lane per pixel: the last valid pixel q_j <= p of every source (own wave's ballot, the earlier waves of
 //                 the block, then the block prefix), the costs recomputed at q_j (apd_fusion_math.h: the very arithmetic of the
 //                 scan's pixel, so the same bits the reference stored in diff[j]), the k loop, and the point;
-//   k_fusion_scan + k_fusion_compact (apd_fusion_device.h): the points in raster order as PLY records.
+//   Call::collect (apd_fusion_device.h; k_fusion_scan + k_fusion_compact of apd_fusion.hip): the points in raster order as PLY
+//                 records.
 //
 // Memory per view of n pixels and S sources: 4 n (validity words) + 8 S n / 256 (block values) + 1 n (emitted) + 30 n (the
 // points before and after compaction, as in the ETH fusion) bytes, about 36 bytes per pixel, plus one mask byte per pixel
@@ -24,11 +25,8 @@
 #include <hip/hip_runtime.h>
 
 #include <float.h>
-#include <stdio.h>
 #include <string.h>
 
-#include <algorithm>
-#include <chrono>
 #include <string>
 #include <vector>
 
@@ -39,8 +37,6 @@
 namespace {
 
 using apd_fusion::View;
-using apd_fusion::g_fusion_error;
-using apd_fusion::g_fusion_ms;
 
 constexpr int kMaxSrc = APD_MAX_IMAGES;
 
@@ -281,130 +277,50 @@ __global__ __launch_bounds__(256) void k_tat_decide(const TatView *__restrict__ 
     }
 }
 
-int tat_fail(int code, const char *what, hipError_t e)
-{
-    char buf[256];
-    snprintf(buf, sizeof(buf), "apd_fuse_views_variant: %s: %s", what, hipGetErrorString(e));
-    g_fusion_error = buf;
-    return code;
-}
+struct TatFusion : apd_fusion::Call {
+    using Call::Call;
+    int run(bool intermediate);
+};
 
-#define TAT_TRY(expr)                                        \
-    do {                                                     \
-        hipError_t e_ = (expr);                              \
-        if (e_ != hipSuccess) {                              \
-            cleanup();                                       \
-            return tat_fail(APD_ERR_HIP, #expr, e_);         \
-        }                                                    \
-    } while (0)
-
-int fuse_tat(bool intermediate, int device, int num_views, const apd_camera *cameras, const float *const *images, int image_channels,
-             const float *const *depths, const float *const *normals, const uint8_t *const *blocks, const int *rows, const int *cols,
-             const int *pair_offsets, const int *pair_indices, int maps_on_device, const char *ply_path, long long *num_points)
+int TatFusion::run(bool intermediate)
 {
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point t) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-    };
-    std::vector<void *> owned;
-    std::vector<TatView> hv(num_views);
-    void *staging = nullptr;  // page-locked buffer of the point downloads
-    auto cleanup = [&]() {
-        for (void *p : owned) {
-            hipFree(p);
-        }
-        owned.clear();
-        if (staging) {
-            hipHostFree(staging);
-            staging = nullptr;
-        }
-    };
-    auto dev_alloc = [&](size_t bytes, void **out) -> hipError_t {
-        hipError_t e = hipMalloc(out, bytes > 0 ? bytes : 1);
-        if (e == hipSuccess) {
-            owned.push_back(*out);
-        }
-        return e;
-    };
-    TAT_TRY(hipSetDevice(device));
-    size_t max_px = 0;
-    int max_src = 1;
-    for (int i = 0; i < num_views; ++i) {
-        const size_t n = (size_t)rows[i] * cols[i];
-        max_px = std::max(max_px, n);
-        max_src = std::max(max_src, pair_offsets[i + 1] - pair_offsets[i]);
+    if (const int rc = begin(false); rc != APD_OK) {
+        return rc;
+    }
+    std::vector<TatView> hv(a.num_views);
+    for (int i = 0; i < a.num_views; ++i) {
         TatView &v = hv[i];
-        const apd_camera &c = cameras[i];
-        memcpy(v.geo.K, c.K, sizeof(v.geo.K));
-        memcpy(v.geo.R, c.R, sizeof(v.geo.R));
-        memcpy(v.geo.t, c.t, sizeof(v.geo.t));
-        // -R^T t in float, term order of Get3DPointonWorld (APD.cpp:795-798)
-        v.geo.centre[0] = -(c.R[0] * c.t[0] + c.R[3] * c.t[1] + c.R[6] * c.t[2]);
-        v.geo.centre[1] = -(c.R[1] * c.t[0] + c.R[4] * c.t[1] + c.R[7] * c.t[2]);
-        v.geo.centre[2] = -(c.R[2] * c.t[0] + c.R[5] * c.t[1] + c.R[8] * c.t[2]);
-        v.geo.rows = rows[i];
-        v.geo.cols = cols[i];
-        if (maps_on_device) {
-            v.image = images[i];
-            v.depth = depths[i];
-            v.normal = normals[i];
-            v.block = blocks ? blocks[i] : nullptr;
-        } else {
-            void *g, *d, *nm;
-            TAT_TRY(dev_alloc(n * 4 * image_channels, &g));
-            TAT_TRY(dev_alloc(n * 4, &d));
-            TAT_TRY(dev_alloc(n * 12, &nm));
-            TAT_TRY(hipMemcpy(g, images[i], n * 4 * image_channels, hipMemcpyHostToDevice));
-            TAT_TRY(hipMemcpy(d, depths[i], n * 4, hipMemcpyHostToDevice));
-            TAT_TRY(hipMemcpy(nm, normals[i], n * 12, hipMemcpyHostToDevice));
-            v.image = (const float *)g;
-            v.depth = (const float *)d;
-            v.normal = (const float *)nm;
-            v.block = nullptr;
-            if (blocks && blocks[i]) {
-                void *b;
-                TAT_TRY(dev_alloc(n, &b));
-                TAT_TRY(hipMemcpy(b, blocks[i], n, hipMemcpyHostToDevice));
-                v.block = (const uint8_t *)b;
-            }
+        const size_t n = (size_t)pixels(i);
+        if (const int rc = fill_view(i, v); rc != APD_OK) {
+            return rc;
         }
-        void *mask;
-        TAT_TRY(dev_alloc(n, &mask));
-        TAT_TRY(hipMemset(mask, 0, n));  // APD.cpp:1038, :1205: one zeroed mask per view
-        v.mask = (uint8_t *)mask;
+        if (const int rc = fill_block(i, v); rc != APD_OK) {
+            return rc;
+        }
+        HIP_TRY(alloc(n, &v.mask));
+        HIP_TRY(hipMemset(v.mask, 0, n));  // APD.cpp:1038, :1205: one zeroed mask per view
     }
     TatView *dviews = nullptr;
-    {
-        void *p;
-        TAT_TRY(dev_alloc(sizeof(TatView) * num_views, &p));
-        dviews = (TatView *)p;
-        TAT_TRY(hipMemcpy(dviews, hv.data(), sizeof(TatView) * num_views, hipMemcpyHostToDevice));
+    if (const int rc = upload_views(hv, &dviews); rc != APD_OK) {
+        return rc;
     }
-    const int max_blocks = (int)((max_px + 255) / 256);
-    void *valid, *block_last, *emitted, *xyz, *bgr, *block_counts, *total, *records;
-    TAT_TRY(dev_alloc(max_px * 4, &valid));
-    TAT_TRY(dev_alloc((size_t)max_blocks * max_src * 4, &block_last));
-    TAT_TRY(dev_alloc(max_px, &emitted));
-    TAT_TRY(dev_alloc(max_px * 12, &xyz));
-    TAT_TRY(dev_alloc(max_px * 3, &bgr));
-    TAT_TRY(dev_alloc((size_t)max_blocks * 4, &block_counts));
-    TAT_TRY(dev_alloc(sizeof(int), &total));
-    TAT_TRY(dev_alloc(max_px * 15, &records));
-    std::vector<std::vector<uint8_t>> body((size_t)num_views);
-    if (hipHostMalloc(&staging, max_px * 15 > 0 ? max_px * 15 : 1, hipHostMallocDefault) != hipSuccess) {
-        staging = nullptr;  // pageable downloads then
+    uint32_t *valid;
+    int *block_last;
+    uint8_t *emitted;
+    HIP_TRY(alloc(max_px * 4, &valid));
+    HIP_TRY(alloc(max_blocks() * max_src * 4, &block_last));
+    HIP_TRY(alloc(max_px, &emitted));
+    if (const int rc = alloc_common(); rc != APD_OK) {
+        return rc;
     }
     // APD.cpp:984-989, :1154-1155
     const float dist_base = 0.25f;
     const float depth_base = intermediate ? 1.0f / 3500.0f : 1.0f / 3000.0f;
     const float angle_base = 0.06981317007977318f;  // 4 degrees
     const float angle_grad = 0.05235987755982988f;  // 3 degrees
-    g_fusion_ms[0] = ms_since(t_begin);
-    const auto t_views = std::chrono::steady_clock::now();
-    long long count = 0;
-    for (int i = 0; i < num_views; ++i) {
-        const int n = rows[i] * cols[i];
-        const int S = pair_offsets[i + 1] - pair_offsets[i];
+    for (int i = 0; i < a.num_views; ++i) {
+        const int n = pixels(i);
+        const int S = sources(i);
         if (n == 0 || S < 2) {
             continue;  // the k loop runs from 2 to the number of sources: nothing to emit
         }
@@ -414,52 +330,30 @@ int fuse_tat(bool intermediate, int device, int num_views, const apd_camera *cam
         task.ref = i;
         task.num_src = S;
         task.n = n;
-        task.channels = image_channels;
+        task.channels = a.image_channels;
         task.intermediate = intermediate ? 1 : 0;
         for (int j = 0; j < S; ++j) {
-            task.src[j] = pair_indices[pair_offsets[i] + j];
+            task.src[j] = a.pair_indices[a.pair_offsets[i] + j];
         }
         for (int k = 2; k <= S; ++k) {
             task.max_dist[k] = k * dist_base;
             task.max_depth[k] = k * depth_base;
             task.max_angle[k] = k * angle_grad + angle_base;  // two roundings: the library is built without contraction
         }
-        task.valid = (uint32_t *)valid;
-        task.block_last = (int *)block_last;
-        task.emitted = (uint8_t *)emitted;
-        task.xyz = (float *)xyz;
-        task.bgr = (uint8_t *)bgr;
-        task.block_counts = (int *)block_counts;
+        task.valid = valid;
+        task.block_last = block_last;
+        task.emitted = emitted;
+        task.xyz = xyz;
+        task.bgr = bgr;
+        task.block_counts = block_counts;
         hipLaunchKernelGGL(k_tat_valid, dim3(nblocks), dim3(256), 0, 0, dviews, task);
         hipLaunchKernelGGL(k_tat_scan, dim3(S), dim3(1024), 0, 0, task, nblocks);
         hipLaunchKernelGGL(k_tat_decide, dim3(nblocks), dim3(256), (size_t)S * 256, 0, dviews, task);
-        hipLaunchKernelGGL(k_fusion_scan, dim3(1), dim3(1024), 0, 0, (int *)block_counts, nblocks, (int *)total);
-        hipLaunchKernelGGL(k_fusion_compact, dim3(nblocks), dim3(256), 0, 0, (const uint8_t *)emitted, (uint8_t)1, n, (const float *)xyz,
-                           (const uint8_t *)bgr, (const int *)block_counts, (uint8_t *)records);
-        TAT_TRY(hipGetLastError());
-        int npts = 0;
-        TAT_TRY(hipMemcpy(&npts, total, sizeof(int), hipMemcpyDeviceToHost));
-        if (npts > 0) {
-            body[i].resize((size_t)npts * 15);
-            if (staging) {
-                TAT_TRY(hipMemcpy(staging, records, (size_t)npts * 15, hipMemcpyDeviceToHost));
-                memcpy(body[i].data(), staging, (size_t)npts * 15);
-            } else {
-                TAT_TRY(hipMemcpy(body[i].data(), records, (size_t)npts * 15, hipMemcpyDeviceToHost));
-            }
-            count += npts;
+        if (const int rc = collect(i, emitted, 1); rc != APD_OK) {
+            return rc;
         }
     }
-    g_fusion_ms[1] = ms_since(t_views);
-    const auto t_file = std::chrono::steady_clock::now();
-    cleanup();
-    const int written = apd_fusion::write_ply("apd_fuse_views_variant", ply_path, count, body);
-    if (written != APD_OK) {
-        return written;
-    }
-    *num_points = count;
-    g_fusion_ms[2] = ms_since(t_file);
-    return APD_OK;
+    return finish();
 }
 
 }  // namespace
@@ -474,41 +368,11 @@ extern "C" int apd_fuse_views_variant(int variant, int device, int num_views, co
         return apd_fuse_views(device, num_views, cameras, images, image_channels, depths, normals, weaks, blocks, rows, cols, pair_offsets,
                               pair_indices, maps_on_device, ply_path, num_points);
     }
-    g_fusion_error.clear();
+    const char *who = "apd_fuse_views_variant";
     if (variant != APD_FUSION_TAT_INTERMEDIATE && variant != APD_FUSION_TAT_ADVANCED) {
-        g_fusion_error = "apd_fuse_views_variant: unknown variant " + std::to_string(variant);
-        return APD_ERR_INVALID;
+        return apd::set_error(apd_fusion::g_fusion_error, APD_ERR_INVALID, "%s: unknown variant %d", who, variant);
     }
-    if (num_views <= 0 || !cameras || !images || !depths || !normals || !rows || !cols || !pair_offsets || !pair_indices || !ply_path ||
-        !num_points) {
-        g_fusion_error = "apd_fuse_views_variant: null argument";
-        return APD_ERR_INVALID;
-    }
-    if (image_channels != 1 && image_channels != 3) {
-        g_fusion_error = "apd_fuse_views_variant: images have 1 (grey) or 3 (blue, green, red) channels";
-        return APD_ERR_INVALID;
-    }
-    for (int i = 0; i < num_views; ++i) {
-        const int ns = pair_offsets[i + 1] - pair_offsets[i];
-        if (ns < 0 || ns > kMaxSrc) {
-            g_fusion_error = "apd_fuse_views_variant: a view has more than APD_MAX_IMAGES sources";
-            return APD_ERR_INVALID;
-        }
-        if (rows[i] < 0 || cols[i] < 0 || (long long)rows[i] * cols[i] > 0x7fffff00LL) {
-            g_fusion_error = "apd_fuse_views_variant: view size out of range";
-            return APD_ERR_INVALID;
-        }
-        for (int k = pair_offsets[i]; k < pair_offsets[i + 1]; ++k) {
-            if (pair_indices[k] < 0 || pair_indices[k] >= num_views) {
-                g_fusion_error = "apd_fuse_views_variant: source index out of range";
-                return APD_ERR_INVALID;
-            }
-            if (pair_indices[k] == i) {  // the view would read the masks it writes: order dependent inside a view
-                g_fusion_error = "apd_fuse_views_variant: a view lists itself as a source";
-                return APD_ERR_INVALID;
-            }
-        }
-    }
-    return fuse_tat(variant == APD_FUSION_TAT_INTERMEDIATE, device, num_views, cameras, images, image_channels, depths, normals, blocks, rows,
-                    cols, pair_offsets, pair_indices, maps_on_device, ply_path, num_points);
+    const apd_fusion::Args a = {device, num_views, cameras, images, image_channels, depths, normals, weaks, blocks, rows, cols, pair_offsets,
+                                pair_indices, maps_on_device, ply_path, num_points};
+    return TatFusion(who, a).run(variant == APD_FUSION_TAT_INTERMEDIATE);
 }

@@ -334,7 +334,8 @@ int apd_get_stream(apd_handle h, void **hip_stream);
  * pair.txt order).  maps_on_device != 0: the four map arrays hold DEVICE pointers (e.g. the gathered torch tensors).
  * Views are fused in order, and inside a view the raster-order consumption of source pixels (`masks`) is resolved
  * exactly, so the point list is the one the sequential host loop writes.  A view that lists itself as a source is
- * refused (APD_ERR_INVALID). */
+ * refused (APD_ERR_INVALID), and so is a view whose rows[i] * cols[i] is negative or above 0x7fffff00: a pixel index is
+ * an int on the device. */
 int apd_fuse_views(int device, int num_views, const apd_camera *cameras, const float *const *images, int image_channels,
                    const float *const *depths, const float *const *normals, const uint8_t *const *weaks,
                    const uint8_t *const *blocks, const int *rows, const int *cols, const int *pair_offsets, const int *pair_indices, int maps_on_device, const char *ply_path,

@@ -143,6 +143,76 @@ def test_variant_entry_is_exported_and_refuses_bad_arguments_before_touching_a_d
     del keep
 
 
+def _entry_points(L):
+    """(name, call) of apd_fuse_views and of the three variants of apd_fuse_views_variant: call(device, num_views, *args, path, n)."""
+    L.apd_fusion_last_error.restype = C.c_char_p
+    entries = [(b"apd_fuse_views", L.apd_fuse_views), (b"apd_fuse_views", lambda *a: L.apd_fuse_views_variant(0, *a))]
+    for variant in (1, 2):
+        entries.append((b"apd_fuse_views_variant", lambda *a, v=variant: L.apd_fuse_views_variant(v, *a)))
+    return entries
+
+
+def _refusal_cases(pkg):
+    """name -> the twelve arguments between num_views and ply_path of a two-view call that one shared check refuses."""
+    weak = np.zeros((4, 4), np.uint8)
+    wptr = (C.c_void_p * 2)(weak.ctypes.data, weak.ctypes.data)
+    keep = [weak, wptr]
+
+    def args(pairs=([1], [0]), channels=1, size=(4, 4), **null):
+        k, a = _abi_args(pkg, [list(pairs[0]), list(pairs[1])])
+        keep.append((k, a))
+        a = list(a)
+        a[2], a[5] = channels, wptr
+        a[7], a[8] = (C.c_int * 2)(size[0], 4), (C.c_int * 2)(size[1], 4)
+        for name in null:
+            a[("cameras", "images", "channels", "depths", "normals", "weaks", "blocks", "rows", "cols", "offsets", "indices").index(name)] = None
+        return a
+
+    cases = {"null cameras": args(cameras=None), "null depths": args(depths=None), "null rows": args(rows=None),
+             "null pair indices": args(indices=None), "two channels": args(channels=2), "33 sources": args(pairs=([1] * 33, [])),
+             "source index == num_views": args(pairs=([2], [0])), "negative source index": args(pairs=([1], [-1])),
+             "self-source": args(pairs=([1, 0], [0])), "65536 x 65536": args(size=(65536, 65536)),
+             "negative rows": args(size=(-4, 4))}
+    return keep, cases, args
+
+
+def test_every_fusion_entry_point_refuses_bad_arguments_before_touching_a_device(pkg, tmp_path):
+    """apd_fuse_views and the three variants of apd_fuse_views_variant share one argument check: a null required pointer, two image
+    channels, a view with 33 sources, a source index outside the views, a view that is its own source and a view of 65536 x 65536
+    pixels (rows * cols does not fit the kernels' int pixel index) each give APD_ERR_INVALID, no file, and a message that starts
+    with the entry point's name -- with or without a device.  The ETH loop needs the weak maps, the T&T loops do not."""
+    L = pkg.lib()
+    n = C.c_longlong(-7)
+    out = tmp_path / "x.ply"
+    keep, cases, args = _refusal_cases(pkg)
+    for name, call in _entry_points(L):
+        for what, a in cases.items():
+            assert call(0, 2, *a, str(out).encode(), C.byref(n)) == -1, (name, what)
+            assert L.apd_fusion_last_error().startswith(name + b": "), (name, what, L.apd_fusion_last_error())
+            assert not out.exists() and n.value == -7, (name, what)
+        for bad in ((2, *args(), None, C.byref(n)), (2, *args(), str(out).encode(), None), (0, *args(), str(out).encode(), C.byref(n))):
+            assert call(0, *bad) == -1, (name, bad)
+            assert L.apd_fusion_last_error() == name + b": null argument" and not out.exists() and n.value == -7, (name, bad)
+        written, m = tmp_path / (name.decode() + "_no_weaks.ply"), C.c_longlong(-7)
+        written.unlink(missing_ok=True)
+        st = call(0, 2, *args(weaks=None), str(written).encode(), C.byref(m))
+        if name == b"apd_fuse_views":
+            assert st == -1 and L.apd_fusion_last_error() == b"apd_fuse_views: null argument" and not written.exists() and m.value == -7
+        elif pkg.device_count() > 0:  # past the checks: two views of one source each fuse to a file without points
+            assert st == 0 and written.exists() and m.value == 0 and L.apd_fusion_last_error() == b""
+        else:  # past the checks: the first HIP call fails, APD_ERR_HIP
+            assert st == -2 and not written.exists() and m.value == -7
+            assert L.apd_fusion_last_error().startswith(name + b": hipSetDevice(")
+    # the messages other tests and callers match on
+    assert L.apd_fuse_views(0, 2, *cases["self-source"], str(out).encode(), C.byref(n)) == -1
+    assert L.apd_fusion_last_error() == b"apd_fuse_views: a view lists itself as a source (use the host fusion)"
+    assert L.apd_fuse_views_variant(2, 0, 2, *cases["self-source"], str(out).encode(), C.byref(n)) == -1
+    assert L.apd_fusion_last_error() == b"apd_fuse_views_variant: a view lists itself as a source"
+    assert L.apd_fuse_views_variant(1, 0, 2, *cases["65536 x 65536"], str(out).encode(), C.byref(n)) == -1
+    assert L.apd_fusion_last_error() == b"apd_fuse_views_variant: view size out of range"
+    del keep
+
+
 def test_no_gpu_means_the_tat_fusions_fail_loudly(pkg, tmp_path):
     """No host fallback: without a device the T&T variants return an error and write nothing."""
     if pkg.device_count() > 0:
