@@ -44,49 +44,112 @@ static int hip_failed(const char *expr, hipError_t e, const char *file, int line
     return set_error(g_last_error, APD_ERR_HIP, "%s failed: %s (%s:%d)", expr, hipGetErrorString(e), file, line);
 }
 
-struct apd_context {
-    int device = 0;
-    int W = 0, H = 0;
-    apd_params params{};
-    int num_images = 0;
+// A launcher that fails under a name of its own: "<what> failed: <hip string>".  Everything else goes through HIP_TRY.
+#define LAUNCH_TRY(what, expr)                                                                                     \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess) {                                                                                    \
+            return set_error(g_last_error, APD_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e_));             \
+        }                                                                                                          \
+    } while (0)
+
+// One device allocation, freed with its owner (the allocation's device must be current then) or by release().  Every
+// allocation of this file is one of these, so nothing is freed by name anywhere else.
+struct DevMem {
+    void *p = nullptr;
+    DevMem() = default;
+    DevMem(DevMem &&o) noexcept : p(o.p) { o.p = nullptr; }
+    ~DevMem() { release(); }
+    void release()  // leaves null behind: a re-allocation that fails must not leave a dangling pointer
+    {
+        hipFree(p);  // null is skipped
+        p = nullptr;
+    }
+    hipError_t ensure(size_t bytes) { return p ? hipSuccess : hipMalloc(&p, bytes); }  // allocated once: an owner's buffer has one size
+};
+template <class T>
+struct DevBuf : DevMem {
+    operator T *() const { return static_cast<T *>(p); }
+};
+
+// A W x H image on the device: the float plane and the copies the kernels gather from.  Shared images (apd_image) make each
+// copy once; a handle repacks its own on every upload, because the pixels change.
+struct DeviceImage {
+    enum Copy { PAIRS, TILED, FQUADS };
+    DevBuf<float> img;
+    DevBuf<apd::quad_t> pairs, tiled;  // 2-byte column pairs; the same in 8 x 4 tiles (FIRST_INIT passes: random first iteration)
+    DevBuf<apd::fquad_t> fquads;       // float texel quads: grey values that are not integers 0..255 (e.g. a resampled pyramid level)
+    bool is_u8 = false;
+    DevMem &copy(Copy what) { return what == PAIRS ? pairs : what == TILED ? static_cast<DevMem &>(tiled) : fquads; }
+};
+
+// Allocates the copy if it is missing and packs it from d.img on `s`.  No lock, no synchronise: those are the caller's.
+static hipError_t make_copy(DeviceImage &d, int W, int H, DeviceImage::Copy what, hipStream_t s)
+{
+    const size_t bytes = what == DeviceImage::PAIRS   ? apd::quad_image_bytes(W, H)
+                         : what == DeviceImage::TILED ? apd::quad_tiled_bytes(W, H)
+                                                      : (size_t)(W + 1) * (H + 1) * sizeof(apd::fquad_t);
+    const hipError_t e = d.copy(what).ensure(bytes);
+    if (e != hipSuccess) {
+        return e;
+    }
+    switch (what) {
+    case DeviceImage::PAIRS: return apd::launch_pack_quads(d.img, W, H, d.pairs, s);
+    case DeviceImage::TILED: return apd::launch_pack_quads_tiled(d.img, W, H, d.tiled, s);
+    default: return apd::launch_pack_fquads(d.img, W, H, d.fquads, s);
+    }
+}
+
+// What one upload and one pass leave on a handle: apd_reset assigns a default-constructed value.  Everything declared in
+// apd_context itself survives a reset: the buffers (the mask's too), the options, the stream, the profiling totals.
+struct PassState {
     bool views_uploaded = false;
     bool depths_pending = false;   // apd_upload_views_split on a geometric pass: the depth maps follow with apd_upload_depths
     bool prior_uploaded = false;
     int weak_count = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // device memory
-    std::vector<float *> images;   // the handle's own copies (apd_upload_views); views of shared images (apd_upload_views_shared) are not kept here
-    const float *ref_img = nullptr;  // reference image the kernels read: images[0] or a shared image's
-    std::vector<float *> depths;
-    std::vector<apd::quad_t *> quads;
-    std::vector<apd::quad_t *> quads_tiled;  // second copy in 8 x 4 tiles (FIRST_INIT passes: random first iteration)
-    std::vector<apd::fquad_t *> fquads;
-    int *flag_dev = nullptr;
-    bool use_quads = false;
-    bool have_tiled = false;
-    ViewConst *views_dev = nullptr;
-    float4 *planes = nullptr, *fit_planes = nullptr;
-    float *costs = nullptr;
-    uint32_t *rng = nullptr, *selected_views = nullptr;
-    uint8_t *view_weight = nullptr, *weak_info = nullptr, *weak_reliable = nullptr;
-    short2 *nearest_strong = nullptr, *neighbours = nullptr;
-    int8_t *column_nearest = nullptr;
-    // K9/K10: compacted WEAK pixels per checkerboard colour, rebuilt when weak_info changes (upload, K4, K14)
-    int *weak_list[2] = {nullptr, nullptr};
-    size_t weak_list_cap = 0;  // entries per list
-    int *weak_list_scratch = nullptr;
-    int weak_list_count[2] = {0, 0};
     bool weak_lists_valid = false;
-    bool weak_lists_all_rows = false;  // the valid lists were built for K3 (every row) / for K9, K10 (rows of the HALF launches)
     // weak_info was rewritten (K14, apd_upload_state) after the upload that sized `neighbours`, the index map and the lists: the
     // kernels that walk them (K3, K8, K9, K10) are refused until apd_upload_prior / apd_reset -- the reference builds all three
     // once per object from the map it loads (APD.cpp:526-537) and never runs a second pass on it
     bool weak_map_stale = false;
     bool first_half_done = false;  // apd_run_before_depths ran on this upload (cleared by reset / upload): apd_run_after_depths needs it
-    int options[APD_OPT_COUNT] = {0, 1, 1, 1, 1, 1};  // defaults of include/apd_mi355x.h
-    int *neighbours_map = nullptr;
+    bool have_mask = false;        // per-view pixel mask (apd_upload_mask)
+    int masked_count = 0;
+    bool pass_started = false;     // a kernel of this pass has been launched: the mask can no longer change
+};
+
+struct apd_context : PassState {
+    int device = 0;
+    int W = 0, H = 0;
+    apd_params params{};
+    int num_images = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    // device memory: every member below that is a DevBuf, or holds some, frees itself with the handle
+    std::vector<DeviceImage> images;  // the handle's own copies (apd_upload_views); shared images (apd_upload_views_shared) are not kept here
+    const float *ref_img = nullptr;   // reference image the kernels read: images[0] or a shared image's
+    std::vector<DevBuf<float>> depths;
+    DevBuf<int> flag_dev;
+    bool use_quads = false;
+    bool have_tiled = false;
+    DevBuf<ViewConst> views_dev;
+    // per-pixel state: sizes, initial values and APD_STATE_* ids are in kPixelState below
+    DevBuf<float4> planes, fit_planes;
+    DevBuf<float> costs;
+    DevBuf<uint32_t> rng, selected_views;
+    DevBuf<uint8_t> view_weight, weak_info, weak_reliable;
+    DevBuf<short2> nearest_strong;
+    DevBuf<int8_t> column_nearest;
+    DevBuf<int> neighbours_map;
+    DevBuf<short2> neighbours;  // per WEAK pixel, not per pixel: neighbours_bytes()
     size_t neighbours_cap = 0;
+    // K9/K10: compacted WEAK pixels per checkerboard colour, rebuilt when weak_info changes (upload, K4, K14)
+    DevBuf<int> weak_list[2];
+    size_t weak_list_cap = 0;  // entries per list
+    DevBuf<int> weak_list_scratch;
+    int weak_list_count[2] = {0, 0};
+    bool weak_lists_all_rows = false;  // the valid lists were built for K3 (every row) / for K9, K10 (rows of the HALF launches)
+    int options[APD_OPT_COUNT] = {0, 1, 1, 1, 1, 1};  // defaults of include/apd_mi355x.h
     FrameArgs fa{};
     // profiling
     bool profiling = false;
@@ -99,16 +162,57 @@ struct apd_context {
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
     hipEvent_t export_event = nullptr;   // recorded behind the kernel of the last export (apd_export_event)
-    // per-view pixel mask (apd_upload_mask): the buffer is kept across apd_reset, the mask is not
-    uint8_t *mask = nullptr;
-    bool have_mask = false;
-    int masked_count = 0;
-    bool pass_started = false;        // a kernel of this pass has been launched: the mask can no longer change
-    int *mask_scratch = nullptr;      // masked-pixel count / block sums of the weak index map rebuilt under a mask
-    float4 *dl_planes = nullptr;      // apd_download under a mask: the arrays with the masked pixels cleared
-    uint32_t *dl_views = nullptr;
-    uint8_t *dl_weak = nullptr;
+    DevBuf<uint8_t> mask;                // the buffer is kept across apd_reset, the mask (have_mask) is not
+    DevBuf<int> mask_scratch;            // masked-pixel count / block sums of the weak index map rebuilt under a mask
+    DevBuf<float4> dl_planes;            // apd_download under a mask: the arrays with the masked pixels cleared
+    DevBuf<uint32_t> dl_views;
+    DevBuf<uint8_t> dl_weak;
+
+    ~apd_context()  // with the handle's device current and its stream idle (apd_destroy); the DevBufs follow
+    {
+        if (export_event) {
+            hipEventDestroy(export_event);
+        }
+        for (auto &pe : pending) {
+            hipEventDestroy(pe.start);
+            hipEventDestroy(pe.stop);
+        }
+        for (hipEvent_t e : event_pool) {
+            hipEventDestroy(e);
+        }
+        if (own_stream) {
+            hipStreamDestroy(stream);
+        }
+    }
 };
+
+// The per-pixel state arrays of CudaSpaceInitialization (APD.cpp:636-666), once: create_buffers allocates them, initial_state
+// fills them, state_ptr sizes them.  `neighbours` is the one state array that is not per pixel.
+struct PixelState {
+    DevMem &(*buf)(apd_context *);
+    size_t bytes_per_pixel;
+    int fill;   // byte initial_state sets; < 0: left as allocated
+    int state;  // APD_STATE_* id; < 0: not reachable through apd_download_state / apd_upload_state
+};
+#define BUF(m) [](apd_context *c) -> DevMem & { return c->m; }
+static const PixelState kPixelState[] = {
+    {BUF(costs), sizeof(float), 0, APD_STATE_COSTS},
+    {BUF(rng), 6 * sizeof(uint32_t), 0, APD_STATE_RNG},
+    {BUF(selected_views), sizeof(uint32_t), 0, APD_STATE_SELECTED_VIEWS},
+    {BUF(view_weight), APD_MAX_IMAGES, 0, APD_STATE_VIEW_WEIGHT},  // uninitialised in the reference
+    {BUF(planes), sizeof(float4), 0, APD_STATE_PLANES},
+    {BUF(fit_planes), sizeof(float4), 0, APD_STATE_FIT_PLANES},  // APD.cpp:651
+    {BUF(weak_info), 1, APD_STRONG, APD_STATE_WEAK_INFO},         // APD.cpp:541-547
+    {BUF(weak_reliable), 1, 0, APD_STATE_WEAK_RELIABLE},
+    {BUF(nearest_strong), sizeof(short2), 0, APD_STATE_NEAREST_STRONG},
+    {BUF(column_nearest), 1, -1, -1},  // K2's scratch: its first kernel writes what its second reads
+    {BUF(neighbours_map), sizeof(int), 0, APD_STATE_NEIGHBOURS_MAP},
+};
+#undef BUF
+
+// `neighbours` holds APD_NEIGHBOUR_NUM positions per WEAK pixel of the last apd_upload_prior, + 1: a pixel behind the last
+// WEAK one maps to index weak_count, and K8 forms (never follows) that address.
+static size_t neighbours_bytes(size_t entries) { return entries * APD_NEIGHBOUR_NUM * sizeof(short2); }
 
 static int record_export(apd_context *c)
 {
@@ -236,7 +340,7 @@ static void refresh_frame_args(apd_context *c)
     fa.neighbours_map = c->neighbours_map;
     fa.neighbours = c->neighbours;
     fa.early_out = c->options[APD_OPT_EARLY_OUT];
-    fa.mask = c->have_mask ? c->mask : nullptr;
+    fa.mask = c->have_mask ? (const uint8_t *)c->mask : nullptr;
 }
 
 extern "C" {
@@ -304,21 +408,39 @@ int apd_device_count(void)
 static int initial_state(apd_context *c)
 {
     const size_t n = (size_t)c->W * c->H;
-    HIP_TRY(hipMemsetAsync(c->costs, 0, n * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(c->rng, 0, n * 6 * sizeof(uint32_t), c->stream));
-    HIP_TRY(hipMemsetAsync(c->selected_views, 0, n * sizeof(uint32_t), c->stream));
-    HIP_TRY(hipMemsetAsync(c->view_weight, 0, n * APD_MAX_IMAGES, c->stream));  // uninitialised in the reference
-    HIP_TRY(hipMemsetAsync(c->planes, 0, n * sizeof(float4), c->stream));
-    HIP_TRY(hipMemsetAsync(c->fit_planes, 0, n * sizeof(float4), c->stream));    // APD.cpp:651
-    HIP_TRY(hipMemsetAsync(c->weak_info, APD_STRONG, n, c->stream));             // APD.cpp:541-547
-    HIP_TRY(hipMemsetAsync(c->weak_reliable, 0, n, c->stream));
-    HIP_TRY(hipMemsetAsync(c->nearest_strong, 0, n * sizeof(short2), c->stream));
-    HIP_TRY(hipMemsetAsync(c->neighbours_map, 0, n * sizeof(int), c->stream));
-    HIP_TRY(hipMemsetAsync(c->neighbours, 0, c->neighbours_cap * APD_NEIGHBOUR_NUM * sizeof(short2), c->stream));
+    for (const PixelState &ps : kPixelState) {
+        if (ps.fill >= 0) {
+            HIP_TRY(hipMemsetAsync(ps.buf(c).p, ps.fill, n * ps.bytes_per_pixel, c->stream));
+        }
+    }
+    HIP_TRY(hipMemsetAsync(c->neighbours, 0, neighbours_bytes(c->neighbours_cap), c->stream));
     return APD_OK;
 }
 
-static int create_buffers(apd_context *c, int width, int height, const apd_params *params);
+// Allocations of CudaSpaceInitialization (APD.cpp:636-666).  On failure the caller (apd_create) deletes the context.
+static int create_buffers(apd_context *c, int width, int height, const apd_params *params)
+{
+    HIP_TRY(hipGetDevice(&c->device));
+    c->W = width;
+    c->H = height;
+    c->params = *params;
+    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    c->own_stream = true;
+    const size_t n = (size_t)width * height;
+    for (const PixelState &ps : kPixelState) {
+        HIP_TRY(ps.buf(c).ensure(n * ps.bytes_per_pixel));
+    }
+    HIP_TRY(c->views_dev.ensure(APD_MAX_IMAGES * sizeof(ViewConst)));
+    HIP_TRY(c->neighbours.ensure(neighbours_bytes(1)));
+    c->neighbours_cap = 1;
+    const int st = initial_state(c);
+    if (st != APD_OK) {
+        return st;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    refresh_frame_args(c);
+    return APD_OK;
+}
 
 int apd_create(apd_handle *out, int device, int width, int height, const apd_params *params)
 {
@@ -338,44 +460,10 @@ int apd_create(apd_handle *out, int device, int width, int height, const apd_par
     apd_context *c = new apd_context();
     const int st = create_buffers(c, width, height, params);
     if (st != APD_OK) {
-        apd_destroy(c);  // frees whatever was allocated before the failure (null pointers are skipped), the stream, the context
+        apd_destroy(c);  // frees whatever was allocated before the failure, the stream, the context
         return st;
     }
     *out = c;
-    return APD_OK;
-}
-
-// Allocations of CudaSpaceInitialization (APD.cpp:636-666).  On failure the caller (apd_create) destroys the context.
-static int create_buffers(apd_context *c, int width, int height, const apd_params *params)
-{
-    HIP_TRY(hipGetDevice(&c->device));
-    c->W = width;
-    c->H = height;
-    c->params = *params;
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    c->own_stream = true;
-    const size_t n = (size_t)width * height;
-    // allocations of CudaSpaceInitialization (APD.cpp:636-666)
-    HIP_TRY(hipMalloc(&c->costs, n * sizeof(float)));
-    HIP_TRY(hipMalloc(&c->rng, n * 6 * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->selected_views, n * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->view_weight, n * APD_MAX_IMAGES));
-    HIP_TRY(hipMalloc(&c->planes, n * sizeof(float4)));
-    HIP_TRY(hipMalloc(&c->fit_planes, n * sizeof(float4)));
-    HIP_TRY(hipMalloc(&c->weak_info, n));
-    HIP_TRY(hipMalloc(&c->weak_reliable, n));
-    HIP_TRY(hipMalloc(&c->nearest_strong, n * sizeof(short2)));
-    HIP_TRY(hipMalloc(&c->column_nearest, n));
-    HIP_TRY(hipMalloc(&c->neighbours_map, n * sizeof(int)));
-    HIP_TRY(hipMalloc(&c->views_dev, APD_MAX_IMAGES * sizeof(ViewConst)));
-    HIP_TRY(hipMalloc(&c->neighbours, APD_NEIGHBOUR_NUM * sizeof(short2)));
-    c->neighbours_cap = 1;
-    const int st = initial_state(c);
-    if (st != APD_OK) {
-        return st;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    refresh_frame_args(c);
     return APD_OK;
 }
 
@@ -389,16 +477,7 @@ int apd_reset(apd_handle c, const apd_params *params)
     }
     HIP_TRY(hipSetDevice(c->device));
     c->params = *params;
-    c->views_uploaded = false;
-    c->depths_pending = false;
-    c->prior_uploaded = false;
-    c->weak_count = 0;
-    c->weak_lists_valid = false;
-    c->weak_map_stale = false;
-    c->first_half_done = false;
-    c->have_mask = false;
-    c->masked_count = 0;
-    c->pass_started = false;
+    static_cast<PassState &>(*c) = PassState();
     const int st = initial_state(c);
     if (st != APD_OK) {
         return st;
@@ -414,56 +493,6 @@ int apd_destroy(apd_handle c)
     }
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    for (float *p : c->images) {
-        hipFree(p);
-    }
-    for (float *p : c->depths) {
-        hipFree(p);
-    }
-    for (apd::quad_t *p : c->quads) {
-        hipFree(p);
-    }
-    for (apd::quad_t *p : c->quads_tiled) {
-        hipFree(p);
-    }
-    for (apd::fquad_t *p : c->fquads) {
-        hipFree(p);
-    }
-    hipFree(c->flag_dev);
-    hipFree(c->views_dev);
-    hipFree(c->planes);
-    hipFree(c->fit_planes);
-    hipFree(c->costs);
-    hipFree(c->rng);
-    hipFree(c->selected_views);
-    hipFree(c->view_weight);
-    hipFree(c->weak_info);
-    hipFree(c->weak_reliable);
-    hipFree(c->nearest_strong);
-    hipFree(c->column_nearest);
-    hipFree(c->weak_list[0]);
-    hipFree(c->weak_list[1]);
-    hipFree(c->weak_list_scratch);
-    hipFree(c->neighbours_map);
-    hipFree(c->neighbours);
-    hipFree(c->mask);
-    hipFree(c->mask_scratch);
-    hipFree(c->dl_planes);
-    hipFree(c->dl_views);
-    hipFree(c->dl_weak);
-    if (c->export_event) {
-        hipEventDestroy(c->export_event);
-    }
-    for (auto &pe : c->pending) {
-        hipEventDestroy(pe.start);
-        hipEventDestroy(pe.stop);
-    }
-    for (hipEvent_t e : c->event_pool) {
-        hipEventDestroy(e);
-    }
-    if (c->own_stream) {
-        hipStreamDestroy(c->stream);
-    }
     delete c;
     return APD_OK;
 }
@@ -482,13 +511,24 @@ int apd_set_stream(apd_handle c, void *hip_stream)
     return APD_OK;
 }
 
-// Cameras, per-view constants and the image pointers the kernels read (own copies or shared images): the end of every upload.
-static int finish_upload(apd_context *c, int num_images, const apd_camera *cameras, const float *const *img, const apd::quad_t *const *quad,
-                         const apd::quad_t *const *tiled, const apd::fquad_t *const *fquad, bool want_depths, bool defer_depths)
+// Which derived copies of the source images the kernels of this upload read: texel pairs (and the tiled copy) of 8-bit
+// input, float texel quads of anything else.  The tiled copy serves the gathers of planes that are still random: the first
+// iteration of a FIRST_INIT pass (APD_OPT_TILED_COPY = 2 uses it in every pass; 0 never builds it).
+static void choose_copies(apd_context *c, bool all_u8)
+{
+    const int tiled_mode = c->options[APD_OPT_TILED_COPY];
+    c->use_quads = all_u8 && c->options[APD_OPT_SOURCE_QUADS] != 0;
+    c->have_tiled = c->use_quads && (tiled_mode == 2 || (tiled_mode == 1 && c->params.state == APD_FIRST_INIT));
+}
+
+// Cameras, per-view constants and the image pointers the kernels read (own copies or shared images, with the copies
+// choose_copies decided on): the end of every upload.
+static int finish_upload(apd_context *c, int num_images, const apd_camera *cameras, const std::vector<const DeviceImage *> &img, bool want_depths,
+                         bool defer_depths)
 {
     c->num_images = num_images;
     c->params.num_images = num_images;
-    c->ref_img = img[0];
+    c->ref_img = img[0]->img;
     const apd_camera &ref = cameras[0];
     FrameArgs &fa = c->fa;
     memcpy(fa.K, ref.K, sizeof(fa.K));
@@ -514,11 +554,12 @@ static int finish_upload(apd_context *c, int num_images, const apd_camera *camer
         memcpy(vc.R, src.R, sizeof(vc.R));
         memcpy(vc.t, src.t, sizeof(vc.t));
         memcpy(vc.c, src.c, sizeof(vc.c));
-        vc.img = img[v + 1];
-        vc.depth = want_depths ? c->depths[v + 1] : nullptr;
-        vc.quad = quad[v + 1];
-        vc.quad_tiled = tiled[v + 1];
-        vc.fquad = fquad[v + 1];
+        const DeviceImage &im = *img[v + 1];
+        vc.img = im.img;
+        vc.depth = want_depths ? (float *)c->depths[v + 1] : nullptr;
+        vc.quad = c->use_quads ? (apd::quad_t *)im.pairs : nullptr;
+        vc.quad_tiled = c->have_tiled ? (apd::quad_t *)im.tiled : nullptr;
+        vc.fquad = c->use_quads ? nullptr : (apd::fquad_t *)im.fquads;
     }
     HIP_TRY(hipMemcpyAsync(c->views_dev, vcs.data(), vcs.size() * sizeof(ViewConst), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -541,105 +582,52 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
     // texel-pair / tiled / float-quad copies, all of one size per handle -- and only allocates what it lacks: hipFree
     // synchronises the whole device, i.e. every other handle's stream too, and a scheduler with several views in flight on
     // one device (host/multi_device.cpp) calls this once per (view, pass).  Which copies are valid is decided per upload.
-    auto grow = [](auto &vec, size_t count) {
-        if (vec.size() < count) {
-            vec.resize(count, nullptr);
-        }
-    };
-    grow(c->images, (size_t)num_images);
-    grow(c->depths, (size_t)num_images);
-    grow(c->quads, (size_t)num_images);
-    grow(c->quads_tiled, (size_t)num_images);
-    grow(c->fquads, (size_t)num_images);
+    if (c->images.size() < (size_t)num_images) {
+        c->images.resize((size_t)num_images);
+    }
+    if (c->depths.size() < (size_t)num_images) {
+        c->depths.resize((size_t)num_images);
+    }
     for (int i = 0; i < num_images; ++i) {
         if (cameras[i].width != c->W || cameras[i].height != c->H) {
             return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_views: camera %d is %dx%d, handle is %dx%d", i, cameras[i].width, cameras[i].height,
                              c->W, c->H);
         }
-        if (!c->images[i]) {
-            HIP_TRY(hipMalloc(&c->images[i], n * sizeof(float)));
-        }
-        HIP_TRY(hipMemcpyAsync(c->images[i], images[i], n * sizeof(float), hipMemcpyDefault, c->stream));
+        HIP_TRY(c->images[i].img.ensure(n * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(c->images[i].img, images[i], n * sizeof(float), hipMemcpyDefault, c->stream));
         if (want_depths) {
-            if (!c->depths[i]) {
-                HIP_TRY(hipMalloc(&c->depths[i], n * sizeof(float)));
-            }
+            HIP_TRY(c->depths[i].ensure(n * sizeof(float)));
             if (depths) {
                 HIP_TRY(hipMemcpyAsync(c->depths[i], depths[i], n * sizeof(float), hipMemcpyDefault, c->stream));
             }
         }
     }
     // 8-bit input (integers 0..255 in every view)?  Then also keep the source views as texel quads.
-    if (!c->flag_dev) {
-        HIP_TRY(hipMalloc(&c->flag_dev, sizeof(int)));
-    }
+    HIP_TRY(c->flag_dev.ensure(sizeof(int)));
     const int one = 1;
     HIP_TRY(hipMemcpyAsync(c->flag_dev, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
     for (int i = 0; i < num_images; ++i) {  // the reference view too: K9/K10 keep its sub-patch texels as bytes
-        hipError_t e = apd::launch_check_u8(c->images[i], (int)n, c->flag_dev, c->stream);
-        if (e != hipSuccess) {
-            return set_error(g_last_error, APD_ERR_HIP, "k_check_u8 failed: %s", hipGetErrorString(e));
-        }
+        LAUNCH_TRY("k_check_u8", apd::launch_check_u8(c->images[i].img, (int)n, c->flag_dev, c->stream));
     }
     int all_u8 = 0;
     HIP_TRY(hipMemcpyAsync(&all_u8, c->flag_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->use_quads = all_u8 != 0 && c->options[APD_OPT_SOURCE_QUADS] != 0;
-    if (!c->use_quads) {  // float grey values (e.g. a resampled pyramid level): float texel quads of the source views
-        const size_t fn = (size_t)(c->W + 1) * (c->H + 1);
-        for (int i = 1; i < num_images; ++i) {
-            if (!c->fquads[i]) {
-                HIP_TRY(hipMalloc(&c->fquads[i], fn * sizeof(apd::fquad_t)));
-            }
-            hipError_t e = apd::launch_pack_fquads(c->images[i], c->W, c->H, c->fquads[i], c->stream);
-            if (e != hipSuccess) {
-                return set_error(g_last_error, APD_ERR_HIP, "k_pack_fquads failed: %s", hipGetErrorString(e));
-            }
-        }
-    }
-    if (c->use_quads) {
-        const size_t qbytes = apd::quad_image_bytes(c->W, c->H);
-        for (int i = 1; i < num_images; ++i) {
-            if (!c->quads[i]) {
-                HIP_TRY(hipMalloc(&c->quads[i], qbytes));
-            }
-            hipError_t e = apd::launch_pack_quads(c->images[i], c->W, c->H, c->quads[i], c->stream);
-            if (e != hipSuccess) {
-                return set_error(g_last_error, APD_ERR_HIP, "k_pack_quads failed: %s", hipGetErrorString(e));
-            }
-        }
-        // the tiled copy serves the gathers of planes that are still random: the first iteration of a FIRST_INIT pass
-        // (APD_OPT_TILED_COPY = 2 uses it in every pass; 0 never builds it)
-        const int tiled_mode = c->options[APD_OPT_TILED_COPY];
-        c->have_tiled = tiled_mode == 2 || (tiled_mode == 1 && c->params.state == APD_FIRST_INIT);
-        if (c->have_tiled) {
-            const size_t tbytes = apd::quad_tiled_bytes(c->W, c->H);
-            for (int i = 1; i < num_images; ++i) {
-                if (!c->quads_tiled[i]) {
-                    HIP_TRY(hipMalloc(&c->quads_tiled[i], tbytes));
-                }
-                hipError_t e = apd::launch_pack_quads_tiled(c->images[i], c->W, c->H, c->quads_tiled[i], c->stream);
-                if (e != hipSuccess) {
-                    return set_error(g_last_error, APD_ERR_HIP, "k_pack_quads_tiled failed: %s", hipGetErrorString(e));
-                }
-            }
-        }
-    } else {
-        c->have_tiled = false;
-    }
-    std::vector<const float *> img(num_images);
-    std::vector<const apd::quad_t *> quad(num_images, nullptr), tiled(num_images, nullptr);
-    std::vector<const apd::fquad_t *> fquad(num_images, nullptr);
+    choose_copies(c, all_u8 != 0);
+    std::vector<const DeviceImage *> img(num_images);
     for (int i = 0; i < num_images; ++i) {
-        img[i] = c->images[i];
-        quad[i] = c->use_quads ? c->quads[i] : nullptr;
-        tiled[i] = c->have_tiled ? c->quads_tiled[i] : nullptr;
-        fquad[i] = c->use_quads ? nullptr : c->fquads[i];
+        img[i] = &c->images[i];
     }
-    return finish_upload(c, num_images, cameras, img.data(), quad.data(), tiled.data(), fquad.data(), want_depths, defer_depths);
+    static const char *const pack_kernel[] = {"k_pack_quads", "k_pack_quads_tiled", "k_pack_fquads"};  // by DeviceImage::Copy
+    const DeviceImage::Copy passes[2] = {c->use_quads ? DeviceImage::PAIRS : DeviceImage::FQUADS, DeviceImage::TILED};
+    for (int k = 0; k < (c->have_tiled ? 2 : 1); ++k) {  // every source's first copy, then every source's tiled one
+        for (int i = 1; i < num_images; ++i) {
+            LAUNCH_TRY(pack_kernel[passes[k]], make_copy(c->images[i], c->W, c->H, passes[k], c->stream));
+        }
+    }
+    return finish_upload(c, num_images, cameras, img, want_depths, defer_depths);
 }
 
-static int check_upload_args(apd_context *c, int num_images, const apd_camera *cameras, const float *const *images, const char *who)
+static int check_upload_args(apd_context *c, int num_images, const apd_camera *cameras, const void *images, const char *who)
 {
     if (!c || !cameras || !images || num_images < 2) {
         return set_error(g_last_error, APD_ERR_INVALID, "%s: bad argument", who);
@@ -679,36 +667,21 @@ int apd_upload_views_split(apd_handle c, int num_images, const apd_camera *camer
 // the handles pointers.  Read-only once created; the lazy copies are made under the image's mutex and finished before it is
 // released.
 // ---------------------------------------------------------------------------------------------
-struct apd_image {
+struct apd_image : DeviceImage {
     int device = 0, W = 0, H = 0;
-    float *img = nullptr;
-    apd::quad_t *pairs = nullptr, *tiled = nullptr;
-    apd::fquad_t *fquads = nullptr;
-    bool is_u8 = false;
     std::mutex m;
 };
 
-static int image_ensure(apd_image *im, int what /* 0 pairs, 1 tiled, 2 float quads */, hipStream_t s)
+static int image_ensure(apd_image *im, DeviceImage::Copy what, hipStream_t s)
 {
     std::lock_guard<std::mutex> lock(im->m);
-    hipError_t e = hipSuccess;
-    if (what == 0 && !im->pairs) {
-        HIP_TRY(hipMalloc(&im->pairs, apd::quad_image_bytes(im->W, im->H)));
-        e = apd::launch_pack_quads(im->img, im->W, im->H, im->pairs, s);
-    } else if (what == 1 && !im->tiled) {
-        HIP_TRY(hipMalloc(&im->tiled, apd::quad_tiled_bytes(im->W, im->H)));
-        e = apd::launch_pack_quads_tiled(im->img, im->W, im->H, im->tiled, s);
-    } else if (what == 2 && !im->fquads) {
-        HIP_TRY(hipMalloc(&im->fquads, (size_t)(im->W + 1) * (im->H + 1) * sizeof(apd::fquad_t)));
-        e = apd::launch_pack_fquads(im->img, im->W, im->H, im->fquads, s);
-    } else {
+    if (im->copy(what).p) {
         return APD_OK;
     }
+    hipError_t e = make_copy(*im, im->W, im->H, what, s);
     e = e != hipSuccess ? e : hipStreamSynchronize(s);  // other handles may read the copy as soon as the mutex is free
     if (e != hipSuccess) {  // a copy that was not made must not look ready to the next caller
-        void **made = what == 0 ? (void **)&im->pairs : what == 1 ? (void **)&im->tiled : (void **)&im->fquads;
-        hipFree(*made);
-        *made = nullptr;
+        im->copy(what).release();
         return set_error(g_last_error, APD_ERR_HIP, "packing a shared image failed: %s", hipGetErrorString(e));
     }
     return APD_OK;
@@ -728,21 +701,21 @@ int apd_image_create(apd_image_t *out, int device, int width, int height, const 
     im->W = width;
     im->H = height;
     const size_t n = (size_t)width * height;
-    int *flag = nullptr;
+    DevBuf<int> flag;
     int all_u8 = 1;
-    hipError_t e = hipMalloc(&im->img, n * sizeof(float));
+    hipError_t e = im->img.ensure(n * sizeof(float));
     e = e != hipSuccess ? e : hipMemcpy(im->img, pixels, n * sizeof(float), hipMemcpyDefault);
-    e = e != hipSuccess ? e : hipMalloc(&flag, sizeof(int));
+    e = e != hipSuccess ? e : flag.ensure(sizeof(int));
     e = e != hipSuccess ? e : hipMemcpy(flag, &all_u8, sizeof(int), hipMemcpyHostToDevice);
     e = e != hipSuccess ? e : apd::launch_check_u8(im->img, (int)n, flag, nullptr);
     e = e != hipSuccess ? e : hipMemcpy(&all_u8, flag, sizeof(int), hipMemcpyDeviceToHost);
-    hipFree(flag);
+    flag.release();
     if (e != hipSuccess) {
         apd_image_destroy(im);
         return set_error(g_last_error, APD_ERR_HIP, "apd_image_create: %s", hipGetErrorString(e));
     }
     im->is_u8 = all_u8 != 0;
-    const int rc = image_ensure(im, im->is_u8 ? 0 : 2, nullptr);
+    const int rc = image_ensure(im, im->is_u8 ? DeviceImage::PAIRS : DeviceImage::FQUADS, nullptr);
     if (rc != APD_OK) {
         apd_image_destroy(im);
         return rc;
@@ -751,7 +724,7 @@ int apd_image_create(apd_image_t *out, int device, int width, int height, const 
     return APD_OK;
 }
 
-const float *apd_image_pixels(apd_image_t im) { return im ? im->img : nullptr; }
+const float *apd_image_pixels(apd_image_t im) { return im ? (const float *)im->img : nullptr; }
 
 int apd_image_destroy(apd_image_t im)
 {
@@ -759,21 +732,14 @@ int apd_image_destroy(apd_image_t im)
         return APD_OK;
     }
     hipSetDevice(im->device);
-    hipFree(im->img);
-    hipFree(im->pairs);
-    hipFree(im->tiled);
-    hipFree(im->fquads);
     delete im;
     return APD_OK;
 }
 
 int apd_upload_views_shared(apd_handle c, int num_images, const apd_camera *cameras, const apd_image_t *images)
 {
-    if (!c || !cameras || !images || num_images < 2) {
-        return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_views_shared: bad argument");
-    }
-    if (num_images > APD_MAX_IMAGES) {
-        return set_error(g_last_error, APD_ERR_TOO_MANY, "Can't process so much images: %d", num_images);  // APD.cpp:428-431
+    if (int rc = check_upload_args(c, num_images, cameras, images, "apd_upload_views_shared")) {
+        return rc;
     }
     HIP_TRY(hipSetDevice(c->device));
     bool all_u8 = true;
@@ -786,46 +752,26 @@ int apd_upload_views_shared(apd_handle c, int num_images, const apd_camera *came
         }
         all_u8 = all_u8 && images[i]->is_u8;
     }
-    c->use_quads = all_u8 && c->options[APD_OPT_SOURCE_QUADS] != 0;
-    const int tiled_mode = c->options[APD_OPT_TILED_COPY];
-    c->have_tiled = c->use_quads && (tiled_mode == 2 || (tiled_mode == 1 && c->params.state == APD_FIRST_INIT));
+    choose_copies(c, all_u8);
     const bool geom = c->params.geom_consistency != 0;
-    const size_t n = (size_t)c->W * c->H;
     if (geom) {  // the depth maps follow with apd_upload_depths: their buffers are the handle's own
         if (c->depths.size() < (size_t)num_images) {
-            c->depths.resize((size_t)num_images, nullptr);
+            c->depths.resize((size_t)num_images);
         }
         for (int i = 0; i < num_images; ++i) {
-            if (!c->depths[i]) {
-                HIP_TRY(hipMalloc(&c->depths[i], n * sizeof(float)));
-            }
+            HIP_TRY(c->depths[i].ensure((size_t)c->W * c->H * sizeof(float)));
         }
     }
-    std::vector<const float *> img(num_images);
-    std::vector<const apd::quad_t *> quad(num_images, nullptr), tiled(num_images, nullptr);
-    std::vector<const apd::fquad_t *> fquad(num_images, nullptr);
-    for (int i = 0; i < num_images; ++i) {
-        img[i] = images[i]->img;
-        if (i == 0) {
-            continue;
-        }
-        int rc = APD_OK;
-        if (c->use_quads) {
-            rc = image_ensure(images[i], 0, c->stream);
-            quad[i] = images[i]->pairs;
-            if (rc == APD_OK && c->have_tiled) {
-                rc = image_ensure(images[i], 1, c->stream);
-                tiled[i] = images[i]->tiled;
-            }
-        } else {
-            rc = image_ensure(images[i], 2, c->stream);
-            fquad[i] = images[i]->fquads;
+    for (int i = 1; i < num_images; ++i) {
+        int rc = image_ensure(images[i], c->use_quads ? DeviceImage::PAIRS : DeviceImage::FQUADS, c->stream);
+        if (rc == APD_OK && c->have_tiled) {
+            rc = image_ensure(images[i], DeviceImage::TILED, c->stream);
         }
         if (rc != APD_OK) {
             return rc;
         }
     }
-    return finish_upload(c, num_images, cameras, img.data(), quad.data(), tiled.data(), fquad.data(), geom, geom);
+    return finish_upload(c, num_images, cameras, std::vector<const DeviceImage *>(images, images + num_images), geom, geom);
 }
 
 int apd_upload_depths(apd_handle c, int num_images, const float *const *depths)
@@ -849,7 +795,29 @@ int apd_upload_depths(apd_handle c, int num_images, const float *const *depths)
     return APD_OK;
 }
 
-static int ensure_mask_scratch(apd_context *c);
+// launch_weak_index_map (apd_kernels_weak.hip) scans blocks of kMapChunk = 4096 pixels: block sums in scratch[0 .. blocks),
+// the total behind them.
+static size_t weak_map_blocks(size_t n) { return (n + 4095) / 4096; }
+
+// The weak index map of APD.cpp:526-537 (row-major running count of WEAK pixels) from the handle's weak_info, scanned on the
+// device with `scratch` (weak_map_blocks + 1 ints) for the block sums; *count = number of WEAK pixels.  Synchronises the stream.
+static int rebuild_weak_map(apd_context *c, int *scratch, int *count)
+{
+    const size_t n = (size_t)c->W * c->H;
+    int total = 0;
+    HIP_TRY(apd::launch_weak_index_map(c->weak_info, n, c->neighbours_map, scratch, c->stream));
+    HIP_TRY(hipMemcpyAsync(&total, scratch + weak_map_blocks(n), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *count = total;
+    return APD_OK;
+}
+
+// one int for apd_upload_mask's count of masked pixels, or the scratch of rebuild_weak_map (begin_pass)
+static int ensure_mask_scratch(apd_context *c)
+{
+    HIP_TRY(c->mask_scratch.ensure((weak_map_blocks((size_t)c->W * c->H) + 2) * sizeof(int)));
+    return APD_OK;
+}
 
 int apd_upload_mask(apd_handle c, const uint8_t *mask)
 {
@@ -865,9 +833,7 @@ int apd_upload_mask(apd_handle c, const uint8_t *mask)
     c->masked_count = 0;
     if (mask) {
         const size_t n = (size_t)c->W * c->H;
-        if (!c->mask) {
-            HIP_TRY(hipMalloc(&c->mask, n));
-        }
+        HIP_TRY(c->mask.ensure(n));
         if (int rc = ensure_mask_scratch(c)) {
             return rc;
         }
@@ -892,75 +858,54 @@ int apd_upload_prior(apd_handle c, const float *planes4, const uint32_t *selecte
         return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_prior: null handle");
     }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)c->W * c->H;
     if (planes4) {
-        HIP_TRY(hipMemcpyAsync(c->planes, planes4, n * sizeof(float4), hipMemcpyDefault, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->planes, planes4, apd_state_bytes(c, APD_STATE_PLANES), hipMemcpyDefault, c->stream));
     } else {
-        HIP_TRY(hipMemsetAsync(c->planes, 0, n * sizeof(float4), c->stream));
+        HIP_TRY(hipMemsetAsync(c->planes, 0, apd_state_bytes(c, APD_STATE_PLANES), c->stream));
     }
     if (selected_views) {
-        HIP_TRY(hipMemcpyAsync(c->selected_views, selected_views, n * sizeof(uint32_t), hipMemcpyDefault, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->selected_views, selected_views, apd_state_bytes(c, APD_STATE_SELECTED_VIEWS), hipMemcpyDefault, c->stream));
     } else {
-        HIP_TRY(hipMemsetAsync(c->selected_views, 0, n * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->selected_views, 0, apd_state_bytes(c, APD_STATE_SELECTED_VIEWS), c->stream));
     }
     c->weak_count = 0;
     if (weak_info) {
-        // weak index map of APD.cpp:526-537 (row-major running count of WEAK pixels), scanned on the device; fit_planes
-        // (zeroed below, on the same stream) lends the scratch for the block sums
-        HIP_TRY(hipMemcpyAsync(c->weak_info, weak_info, n, hipMemcpyDefault, c->stream));
-        int *scratch = reinterpret_cast<int *>(c->fit_planes);
-        HIP_TRY(apd::launch_weak_index_map(c->weak_info, n, c->neighbours_map, scratch, c->stream));
-        int count = 0;
-        HIP_TRY(hipMemcpyAsync(&count, scratch + (n + 4095) / 4096, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->weak_count = count;
+        // fit_planes (zeroed below, on the same stream) lends the scratch for the block sums
+        HIP_TRY(hipMemcpyAsync(c->weak_info, weak_info, apd_state_bytes(c, APD_STATE_WEAK_INFO), hipMemcpyDefault, c->stream));
+        if (int rc = rebuild_weak_map(c, static_cast<int *>(c->fit_planes.p), &c->weak_count)) {
+            return rc;
+        }
     } else {
-        HIP_TRY(hipMemsetAsync(c->weak_info, APD_STRONG, n, c->stream));
-        HIP_TRY(hipMemsetAsync(c->neighbours_map, 0, n * sizeof(int), c->stream));
+        HIP_TRY(hipMemsetAsync(c->weak_info, APD_STRONG, apd_state_bytes(c, APD_STATE_WEAK_INFO), c->stream));
+        HIP_TRY(hipMemsetAsync(c->neighbours_map, 0, apd_state_bytes(c, APD_STATE_NEIGHBOURS_MAP), c->stream));
     }
-    // + 1: a pixel behind the last WEAK one maps to index weak_count, and K8 forms (never follows) that address
-    const size_t need = (size_t)c->weak_count + 1;
+    const size_t need = (size_t)c->weak_count + 1;  // see neighbours_bytes
     if (need > c->neighbours_cap) {
-        hipFree(c->neighbours);
-        c->neighbours = nullptr;  // a failing re-allocation must not leave a dangling pointer for apd_destroy
+        c->neighbours.release();
         c->neighbours_cap = 0;
-        HIP_TRY(hipMalloc(&c->neighbours, need * APD_NEIGHBOUR_NUM * sizeof(short2)));
+        HIP_TRY(c->neighbours.ensure(neighbours_bytes(need)));
         c->neighbours_cap = need;
     }
-    HIP_TRY(hipMemsetAsync(c->neighbours, 0, c->neighbours_cap * APD_NEIGHBOUR_NUM * sizeof(short2), c->stream));
+    HIP_TRY(hipMemsetAsync(c->neighbours, 0, neighbours_bytes(c->neighbours_cap), c->stream));
     c->weak_lists_valid = false;
     c->weak_map_stale = false;
     c->first_half_done = false;
     c->pass_started = false;   // a mask (apd_upload_mask, before or after this call) is applied to the new weak map by the first kernel
     if (need > c->weak_list_cap) {  // one colour holds at most every WEAK pixel of the map uploaded above (K4 only removes some)
-        for (int k = 0; k < 2; ++k) {
-            hipFree(c->weak_list[k]);
-            c->weak_list[k] = nullptr;
-        }
+        c->weak_list[0].release();
+        c->weak_list[1].release();
         c->weak_list_cap = 0;
-        HIP_TRY(hipMalloc(&c->weak_list[0], need * sizeof(int)));
-        HIP_TRY(hipMalloc(&c->weak_list[1], need * sizeof(int)));
+        HIP_TRY(c->weak_list[0].ensure(need * sizeof(int)));
+        HIP_TRY(c->weak_list[1].ensure(need * sizeof(int)));
         c->weak_list_cap = need;
     }
-    if (!c->weak_list_scratch) {
-        HIP_TRY(hipMalloc(&c->weak_list_scratch, apd::weak_list_scratch_ints(c->W, c->H) * sizeof(int)));
-    }
-    HIP_TRY(hipMemsetAsync(c->fit_planes, 0, n * sizeof(float4), c->stream));
-    HIP_TRY(hipMemsetAsync(c->view_weight, 0, n * APD_MAX_IMAGES, c->stream));
-    HIP_TRY(hipMemsetAsync(c->weak_reliable, 0, n, c->stream));
+    HIP_TRY(c->weak_list_scratch.ensure(apd::weak_list_scratch_ints(c->W, c->H) * sizeof(int)));
+    HIP_TRY(hipMemsetAsync(c->fit_planes, 0, apd_state_bytes(c, APD_STATE_FIT_PLANES), c->stream));
+    HIP_TRY(hipMemsetAsync(c->view_weight, 0, apd_state_bytes(c, APD_STATE_VIEW_WEIGHT), c->stream));
+    HIP_TRY(hipMemsetAsync(c->weak_reliable, 0, apd_state_bytes(c, APD_STATE_WEAK_RELIABLE), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->prior_uploaded = true;
     refresh_frame_args(c);
-    return APD_OK;
-}
-
-static size_t mask_scratch_ints(size_t n) { return (n + 4095) / 4096 + 2; }
-
-static int ensure_mask_scratch(apd_context *c)
-{
-    if (!c->mask_scratch) {
-        HIP_TRY(hipMalloc(&c->mask_scratch, mask_scratch_ints((size_t)c->W * c->H) * sizeof(int)));
-    }
     return APD_OK;
 }
 
@@ -973,17 +918,12 @@ static int begin_pass(apd_context *c)
         return APD_OK;
     }
     if (c->have_mask) {
-        const size_t n = (size_t)c->W * c->H;
-        HIP_TRY(apd::launch_mask_weak_info(c->mask, c->weak_info, (int)n, c->stream));
+        HIP_TRY(apd::launch_mask_weak_info(c->mask, c->weak_info, c->W * c->H, c->stream));
         if (c->weak_count > 0) {
-            if (int rc = ensure_mask_scratch(c)) {
+            int rc = ensure_mask_scratch(c);
+            if (rc || (rc = rebuild_weak_map(c, c->mask_scratch, &c->weak_count))) {
                 return rc;
             }
-            HIP_TRY(apd::launch_weak_index_map(c->weak_info, n, c->neighbours_map, c->mask_scratch, c->stream));
-            int count = 0;
-            HIP_TRY(hipMemcpyAsync(&count, c->mask_scratch + (n + 4095) / 4096, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->weak_count = count;
         }
         c->weak_lists_valid = false;
     }
@@ -1040,19 +980,18 @@ static int launch_one(apd_context *c, int kernel_id, int iter)
         }
     }
     hipError_t e;
+    int *const weak_list[2] = {c->weak_list[0], c->weak_list[1]};
     switch (kernel_id) {
     case APD_K3_GEN_NEIGHBOURS:
     case APD_K9_BLACK_UPDATE_WEAK:
     case APD_K10_RED_UPDATE_WEAK:
-        if (c->weak_list[0] && (!c->weak_lists_valid || c->weak_lists_all_rows != (kernel_id == APD_K3_GEN_NEIGHBOURS))) {
+        if (weak_list[0] && (!c->weak_lists_valid || c->weak_lists_all_rows != (kernel_id == APD_K3_GEN_NEIGHBOURS))) {
             c->weak_lists_all_rows = kernel_id == APD_K3_GEN_NEIGHBOURS;
-            e = apd::build_weak_lists(c->fa, c->weak_lists_all_rows, c->weak_list, c->weak_list_scratch, c->weak_list_count, c->stream);
-            if (e != hipSuccess) {
-                return set_error(g_last_error, APD_ERR_HIP, "building the WEAK pixel lists failed: %s", hipGetErrorString(e));
-            }
+            LAUNCH_TRY("building the WEAK pixel lists",
+                       apd::build_weak_lists(c->fa, c->weak_lists_all_rows, weak_list, c->weak_list_scratch, c->weak_list_count, c->stream));
             c->weak_lists_valid = true;
         }
-        e = apd::launch_weak_kernel(c->fa, kernel_id, iter, c->stream, c->weak_list, c->weak_list_count);
+        e = apd::launch_weak_kernel(c->fa, kernel_id, iter, c->stream, weak_list, c->weak_list_count);
         break;
     case APD_K4_NEIGHBOUR_UPDATE:  // WEAK -> UNKNOWN: the lists are stale
         c->weak_lists_valid = false;
@@ -1272,41 +1211,36 @@ int apd_download(apd_handle c, float *planes4, uint8_t *weak_info, uint32_t *sel
         return set_error(g_last_error, APD_ERR_INVALID, "apd_download: null handle");
     }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)c->W * c->H;
+    const size_t planes_bytes = apd_state_bytes(c, APD_STATE_PLANES), weak_bytes = apd_state_bytes(c, APD_STATE_WEAK_INFO);
+    const size_t views_bytes = apd_state_bytes(c, APD_STATE_SELECTED_VIEWS);
+    const float4 *src_planes = c->planes;
+    const uint8_t *src_weak = c->weak_info;
+    const uint32_t *src_views = c->selected_views;
     if (c->have_mask) {  // masked pixels leave as plane 0, UNKNOWN, views 0: cleared on the device, then the same three copies
-        if (planes4 && !c->dl_planes) {
-            HIP_TRY(hipMalloc(&c->dl_planes, n * sizeof(float4)));
-        }
-        if (weak_info && !c->dl_weak) {
-            HIP_TRY(hipMalloc(&c->dl_weak, n));
-        }
-        if (selected_views && !c->dl_views) {
-            HIP_TRY(hipMalloc(&c->dl_views, n * sizeof(uint32_t)));
-        }
-        HIP_TRY(apd::launch_masked_download(c->fa, planes4 ? c->dl_planes : nullptr, weak_info ? c->dl_weak : nullptr,
-                                            selected_views ? c->dl_views : nullptr, c->stream));
         if (planes4) {
-            HIP_TRY(hipMemcpyAsync(planes4, c->dl_planes, n * sizeof(float4), hipMemcpyDefault, c->stream));
+            HIP_TRY(c->dl_planes.ensure(planes_bytes));
         }
         if (weak_info) {
-            HIP_TRY(hipMemcpyAsync(weak_info, c->dl_weak, n, hipMemcpyDefault, c->stream));
+            HIP_TRY(c->dl_weak.ensure(weak_bytes));
         }
         if (selected_views) {
-            HIP_TRY(hipMemcpyAsync(selected_views, c->dl_views, n * sizeof(uint32_t), hipMemcpyDefault, c->stream));
+            HIP_TRY(c->dl_views.ensure(views_bytes));
         }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        drain_profile(c);
-        return APD_OK;
+        HIP_TRY(apd::launch_masked_download(c->fa, planes4 ? (float4 *)c->dl_planes : nullptr, weak_info ? (uint8_t *)c->dl_weak : nullptr,
+                                            selected_views ? (uint32_t *)c->dl_views : nullptr, c->stream));
+        src_planes = c->dl_planes;
+        src_weak = c->dl_weak;
+        src_views = c->dl_views;
     }
     // APD.cu:2490-2492
     if (planes4) {
-        HIP_TRY(hipMemcpyAsync(planes4, c->planes, n * sizeof(float4), hipMemcpyDefault, c->stream));
+        HIP_TRY(hipMemcpyAsync(planes4, src_planes, planes_bytes, hipMemcpyDefault, c->stream));
     }
     if (weak_info) {
-        HIP_TRY(hipMemcpyAsync(weak_info, c->weak_info, n, hipMemcpyDefault, c->stream));
+        HIP_TRY(hipMemcpyAsync(weak_info, src_weak, weak_bytes, hipMemcpyDefault, c->stream));
     }
     if (selected_views) {
-        HIP_TRY(hipMemcpyAsync(selected_views, c->selected_views, n * sizeof(uint32_t), hipMemcpyDefault, c->stream));
+        HIP_TRY(hipMemcpyAsync(selected_views, src_views, views_bytes, hipMemcpyDefault, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     drain_profile(c);
@@ -1315,21 +1249,18 @@ int apd_download(apd_handle c, float *planes4, uint8_t *weak_info, uint32_t *sel
 
 static void *state_ptr(apd_context *c, int which, size_t *bytes)
 {
-    const size_t n = (size_t)c->W * c->H;
-    switch (which) {
-    case APD_STATE_PLANES: *bytes = n * 16; return c->planes;
-    case APD_STATE_FIT_PLANES: *bytes = n * 16; return c->fit_planes;
-    case APD_STATE_COSTS: *bytes = n * 4; return c->costs;
-    case APD_STATE_RNG: *bytes = n * 24; return c->rng;
-    case APD_STATE_SELECTED_VIEWS: *bytes = n * 4; return c->selected_views;
-    case APD_STATE_VIEW_WEIGHT: *bytes = n * 32; return c->view_weight;
-    case APD_STATE_WEAK_INFO: *bytes = n; return c->weak_info;
-    case APD_STATE_WEAK_RELIABLE: *bytes = n; return c->weak_reliable;
-    case APD_STATE_NEAREST_STRONG: *bytes = n * 4; return c->nearest_strong;
-    case APD_STATE_NEIGHBOURS_MAP: *bytes = n * 4; return c->neighbours_map;
-    case APD_STATE_NEIGHBOURS: *bytes = (size_t)(c->weak_count > 0 ? c->weak_count : 1) * APD_NEIGHBOUR_NUM * 4; return c->neighbours;
-    default: *bytes = 0; return nullptr;
+    if (which == APD_STATE_NEIGHBOURS) {
+        *bytes = neighbours_bytes(c->weak_count > 0 ? c->weak_count : 1);
+        return c->neighbours.p;
     }
+    for (const PixelState &ps : kPixelState) {
+        if (which >= 0 && ps.state == which) {
+            *bytes = (size_t)c->W * c->H * ps.bytes_per_pixel;
+            return ps.buf(c).p;
+        }
+    }
+    *bytes = 0;
+    return nullptr;
 }
 
 size_t apd_state_bytes(apd_handle c, int which)
@@ -1384,10 +1315,7 @@ int apd_export_depth_normal_device(apd_handle c, float *depth_dev, float *normal
         return set_error(g_last_error, APD_ERR_INVALID, "apd_export_depth_normal_device: bad argument");
     }
     HIP_TRY(hipSetDevice(c->device));
-    hipError_t e = apd::launch_export_depth_normal(c->fa, depth_dev, normal_dev, c->stream);
-    if (e != hipSuccess) {
-        return set_error(g_last_error, APD_ERR_HIP, "export kernel failed: %s", hipGetErrorString(e));
-    }
+    LAUNCH_TRY("export kernel", apd::launch_export_depth_normal(c->fa, depth_dev, normal_dev, c->stream));
     if (int rc = record_export(c)) {
         return rc;
     }
@@ -1401,10 +1329,7 @@ int apd_export_state_device(apd_handle c, float *planes4_dev, uint8_t *weak_dev,
         return set_error(g_last_error, APD_ERR_INVALID, "apd_export_state_device: null handle");
     }
     HIP_TRY(hipSetDevice(c->device));
-    hipError_t e = apd::launch_export_state(c->fa, reinterpret_cast<float4 *>(planes4_dev), weak_dev, views_dev, depth_dev, c->stream);
-    if (e != hipSuccess) {
-        return set_error(g_last_error, APD_ERR_HIP, "export kernel failed: %s", hipGetErrorString(e));
-    }
+    LAUNCH_TRY("export kernel", apd::launch_export_state(c->fa, reinterpret_cast<float4 *>(planes4_dev), weak_dev, views_dev, depth_dev, c->stream));
     if (int rc = record_export(c)) {
         return rc;
     }
