@@ -25,22 +25,16 @@ typedef uint32_t quad_t;
 constexpr int kQuadShift = 2;
 constexpr unsigned kQuadBytes = 1u << kQuadShift;
 
-// Row-major copy of the 8-bit source images ("texel quads").  Default: 2-byte COLUMN PAIRS -- entry (t, u) = (qx + 1, qy + 1)
+// Row-major copy of the 8-bit source images ("texel quads"): 2-byte COLUMN PAIRS -- entry (t, u) = (qx + 1, qy + 1)
 // holds {I(qx, qy), I(qx, qy + 1)} (clamped coordinates) and the dword at byte 2 * (u * (W + 2) + t) is therefore
 // {I(qx,qy), I(qx,qy+1), I(qx+1,qy), I(qx+1,qy+1)}: all four taps of a bilinear fetch in ONE gather, as with 4-byte quads, at
 // half the footprint (twice the pixels per 128-byte line, per L1, per L2).  Half of these gathers are not dword aligned,
-// which costs nothing on gfx950 (tools/unaligned_gather.hip: 18.67 vs 18.85 ms for 1.07e9 lines).  -DAPD_QUAD4 builds the
-// round-1 layout (4-byte entries {I(qx,qy), I(qx+1,qy), I(qx,qy+1), I(qx+1,qy+1)}, pitch W + 1) for A/B runs.
+// which costs nothing on gfx950 (tools/unaligned_gather.hip: 18.67 vs 18.85 ms for 1.07e9 lines).
 // The tiled copy (quad_tiled_offset_tu) is laid out so that its dwords have the byte order of the row-major dword, so there
-// is one decode: kPair2: bytes {t00, t01, t10, t11}, else {t00, t10, t01, t11}.
-#ifndef APD_QUAD4
-constexpr bool kPair2 = true;
-#else
-constexpr bool kPair2 = false;
-#endif
-constexpr int kRowEntryShift = kPair2 ? 1 : 2;
+// is one decode: bytes {t00, t01, t10, t11}.
+constexpr int kRowEntryShift = 1;
 constexpr unsigned kRowEntryBytes = 1u << kRowEntryShift;
-__host__ __device__ __forceinline__ unsigned quad_row_pitch_bytes(int W) { return kPair2 ? 2u * (unsigned)(W + 2) : 4u * (unsigned)(W + 1); }
+__host__ __device__ __forceinline__ unsigned quad_row_pitch_bytes(int W) { return 2u * (unsigned)(W + 2); }
 // + 4: the dword of the last entry reads two bytes past it
 __host__ __device__ __forceinline__ size_t quad_image_bytes(int W, int H) { return (size_t)quad_row_pitch_bytes(W) * (size_t)(H + 1) + 4u; }
 
@@ -522,7 +516,6 @@ __device__ __forceinline__ float sample_bilinear(Ptr img, int W, int H, float sx
 // struct would otherwise be "generic" and cost flat_load + 64-bit address arithmetic per gather).
 typedef const __attribute__((address_space(1))) quad_t *global_quad_ptr;
 typedef const __attribute__((address_space(1))) float *global_f32_ptr;
-typedef const __attribute__((address_space(1))) pair_t *global_pair_ptr;
 typedef const __attribute__((address_space(1))) fquad_t *global_fquad_ptr;
 
 __device__ __forceinline__ fquad_t fquad_fetch(global_fquad_ptr fq, unsigned off)
@@ -538,7 +531,7 @@ __device__ __forceinline__ fquad_t fquad_fetch(global_fquad_ptr fq, unsigned off
 typedef quad_t quad_unaligned_t __attribute__((aligned(2)));
 __device__ __forceinline__ quad_t quad_fetch(global_quad_ptr quad, unsigned off)
 {
-    // one global_load_dword; with 2-byte column pairs the address is only 2-byte aligned
+    // one global_load_dword; the address of a 2-byte column pair is only 2-byte aligned
     return *(const __attribute__((address_space(1))) quad_unaligned_t *)((const __attribute__((address_space(1))) char *)quad + off);
 }
 
@@ -555,13 +548,8 @@ __device__ __forceinline__ float quad_lerp(quad_t t, float a, float b)
     float t00, t10, t01, t11;  // four v_cvt_f32_ubyte<k>; the differences below stay binary32 subtractions (see quad_row_lerp)
     asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t00) : "v"(t));
     asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(t11) : "v"(t));
-    if (kPair2) {
-        asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t01) : "v"(t));
-        asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(t10) : "v"(t));
-    } else {
-        asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t10) : "v"(t));
-        asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(t01) : "v"(t));
-    }
+    asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t01) : "v"(t));
+    asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(t10) : "v"(t));
     const float top = fmaf(a, t10 - t00, t00);
     const float bot = fmaf(a, t11 - t01, t01);
     return fmaf(b, bot - top, top);
@@ -590,17 +578,16 @@ __device__ __forceinline__ int med3_i32(int x, int lo, int hi)
 
 // Second, TILED copy of the 8-bit source images for gathers that land anywhere in the source image (K5 and the first iteration
 // of a FIRST_INIT pass: every lane warps its patch with another random plane).  One tile = one 128-byte line:
-//   kPair2 (default): 7 columns x 8 rows of 2-byte column pairs, each tile row padded with the first pair of the next tile
-//     (8 entries = 16 bytes per row), so that the dword at any entry still holds entries t and t + 1, i.e. the four taps;
-//     an 11 x 11 px warped patch touches ~5.5 tiles (row-major pairs: ~7 lines of 64 x 1 px; round 1's row-major 4-byte quads: ~14);
-//   APD_QUAD4: 8 x 4 four-byte quads (~7.9 tiles per patch; measured against the row-major quads in profiles/r02/tiled_vs_rowmajor.txt:
-//     L1 -> L2 requests per gather 16.5 -> 9.7, first black launch of configs[1] 129 -> 94 ms).
+//   7 columns x 8 rows of 2-byte column pairs, each tile row padded with the first pair of the next tile
+//   (8 entries = 16 bytes per row), so that the dword at any entry still holds entries t and t + 1, i.e. the four taps;
+//   an 11 x 11 px warped patch touches ~5.5 tiles (row-major pairs: ~7 lines of 64 x 1 px; round 1's row-major 4-byte quads: ~14,
+//   and tiles of 8 x 4 of those ~7.9, profiles/r02/tiled_vs_rowmajor.txt).
 // Rows are read better from the row-major copy (window staging, the 3 x 3 stride-5 sub-patches of the weak sweep), which stays.
 // Entry (t, u) = (qx + 1, qy + 1).  Same texels, same arithmetic: same bits.
-constexpr unsigned kTileCols = kPair2 ? 7u : 8u, kTileRows = kPair2 ? 8u : 4u;
+constexpr unsigned kTileCols = 7u, kTileRows = 8u;
 __host__ __device__ __forceinline__ unsigned quad_tiles_x(int W)
 {
-    return kPair2 ? ((unsigned)(W + 2) + kTileCols - 1u) / kTileCols : ((unsigned)(W + 1) + 7u) >> 3;
+    return ((unsigned)(W + 2) + kTileCols - 1u) / kTileCols;
 }
 __host__ __device__ __forceinline__ unsigned quad_tiles_y(int H) { return ((unsigned)(H + 1) + kTileRows - 1u) / kTileRows; }
 __host__ __device__ __forceinline__ size_t quad_tiled_bytes(int W, int H) { return (size_t)quad_tiles_x(W) * quad_tiles_y(H) * 128u + 4u; }
@@ -608,28 +595,25 @@ __host__ __device__ __forceinline__ size_t quad_tiled_bytes(int W, int H) { retu
 // 24-bit multiplier for the 16,384-px widest image apd_create accepts
 __host__ __device__ __forceinline__ unsigned quad_tiled_offset_tu(unsigned t, unsigned u, unsigned tiles_x)
 {
-    if (kPair2) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(APD_TILE_OFFSET_PLAIN)
-        // the same value in nine instructions, five of the 4-cycle class (24-bit multiply-adds, shift-adds; every factor is
-        // below 2^24), where the compiler's choice for the plain expression is twelve with seven of that class
-        unsigned q, t2, r2, uq, ur, tile, off;
-        asm("v_mul_u32_u24 %0, %1, %2" : "=v"(q) : "v"(t), "v"(37450u));
-        asm("v_lshrrev_b32 %0, 18, %1" : "=v"(q) : "v"(q));                            // t / 7
-        asm("v_add_u32 %0, %1, %1" : "=v"(t2) : "v"(t));
-        asm("v_mad_i32_i24 %0, %1, -14, %2" : "=v"(r2) : "v"(q), "v"(t2));              // 2 * (t - 7 q)
-        asm("v_lshrrev_b32 %0, 3, %1" : "=v"(uq) : "v"(u));
-        asm("v_and_b32 %0, 7, %1" : "=v"(ur) : "v"(u));
-        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(tile) : "v"(uq), "v"(tiles_x), "v"(q));
-        asm("v_lshl_add_u32 %0, %1, 7, %2" : "=v"(off) : "v"(tile), "v"(r2));
-        asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"(ur), "v"(off));
-        return off;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the value of the host arm below in nine instructions, five of the 4-cycle class (24-bit multiply-adds, shift-adds; every
+    // factor is below 2^24), where the compiler's choice for the plain expression is twelve with seven of that class
+    unsigned q, t2, r2, uq, ur, tile, off;
+    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(q) : "v"(t), "v"(37450u));
+    asm("v_lshrrev_b32 %0, 18, %1" : "=v"(q) : "v"(q));                            // t / 7
+    asm("v_add_u32 %0, %1, %1" : "=v"(t2) : "v"(t));
+    asm("v_mad_i32_i24 %0, %1, -14, %2" : "=v"(r2) : "v"(q), "v"(t2));              // 2 * (t - 7 q)
+    asm("v_lshrrev_b32 %0, 3, %1" : "=v"(uq) : "v"(u));
+    asm("v_and_b32 %0, 7, %1" : "=v"(ur) : "v"(u));
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(tile) : "v"(uq), "v"(tiles_x), "v"(q));
+    asm("v_lshl_add_u32 %0, %1, 7, %2" : "=v"(off) : "v"(tile), "v"(r2));
+    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"(ur), "v"(off));
+    return off;
 #else
-        const unsigned q = (t * 37450u) >> 18;  // t / 7
-        const unsigned r = t - 7u * q;
-        return (((u >> 3) * tiles_x + q) << 7) | ((u & 7u) << 4) | (r << 1);
+    const unsigned q = (t * 37450u) >> 18;  // t / 7
+    const unsigned r = t - 7u * q;
+    return (((u >> 3) * tiles_x + q) << 7) | ((u & 7u) << 4) | (r << 1);
 #endif
-    }
-    return ((((u >> 2) * tiles_x + (t >> 3)) << 5) | ((u & 3u) << 3) | (t & 7u)) << 2;
 }
 __device__ __forceinline__ unsigned quad_tiled_byte_offset(int qx, int qy, unsigned tiles_x)
 {
@@ -817,13 +801,8 @@ __device__ __forceinline__ void quad_row_lerp(const quad_t (&t)[kPatchN], const 
     for (int j = 0; j < kPatchN; ++j) {
         asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t00[j]) : "v"(t[j]));
         asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(d1[j]) : "v"(t[j]));
-        if (kPair2) {
-            asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t01[j]) : "v"(t[j]));
-            asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(d0[j]) : "v"(t[j]));
-        } else {
-            asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(d0[j]) : "v"(t[j]));
-            asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(t01[j]) : "v"(t[j]));
-        }
+        asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t01[j]) : "v"(t[j]));
+        asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(d0[j]) : "v"(t[j]));
     }
     APD_STAGE();
 #pragma unroll
@@ -1075,7 +1054,7 @@ template <bool kQuad, bool kTiled, typename Ref>
 __device__ __forceinline__ void ncc_fixed_moments_ieee(const FrameArgs &fa, const ViewConst &vc, const Ref &rp, const Homography &H, int px,
                                                        int py, float &sum_s, float &sum_ss, float &sum_rs)
 {
-    if constexpr (APD_IEEE_COMPACT != 0 && Ref::kRuntimeIndex) {
+    if constexpr (Ref::kRuntimeIndex) {
         ncc_fixed_moments_ieee_rolled<kQuad, kTiled, Ref>(fa, vc, rp, H, px, py, sum_s, sum_ss, sum_rs);
     } else {
         ncc_fixed_moments<kQuad, kRecipIeee, kTiled, Ref>(fa, vc, rp, H, px, py, sum_s, sum_ss, sum_rs);
@@ -1227,11 +1206,7 @@ __device__ __forceinline__ void subpatch_issue_quad(const Homography &H, global_
     APD_STAGE();
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-#if APD_K910_SUBPATCH_TILED   // lab build: `srcq` is the tiled copy and `qpitch` its tiles per tile row (profiles/r05/ab_k910_tiled.txt)
-        qx[k] = (int)quad_tiled_byte_offset(qx[k], qy[k], qpitch);
-#else
         qx[k] = (int)quad_byte_offset(qx[k], qy[k], (int)qpitch, (int)(qpitch + kRowEntryBytes));
-#endif
     }
     APD_STAGE();
 #pragma unroll

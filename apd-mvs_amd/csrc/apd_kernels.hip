@@ -229,10 +229,14 @@ __device__ __forceinline__ bool arm_candidate(const FrameArgs &fa, int px, int p
     return true;
 }
 
+// minimum waves per SIMD the register allocator must leave room for (ms per launch at 4096x3072 N=8 -- ref patch in registers:
+// 2: 32.0, 3: 28.3; ref patch in LDS: 3: 28.2, 4: 27.4)
+constexpr int kK67Waves = 4;
+
 // One launch = one colour.  Hypotheses 0..7 are the propagation arms, 8 the current plane,
 // 9..13 the refinement set; a single loop keeps one inlined copy of the 36-sample NCC.
 template <int NMAX, bool kQuad>
-__global__ __launch_bounds__(256, APD_K67_WAVES) void k67_update_strong(FrameArgs fa, int colour, int iter)
+__global__ __launch_bounds__(256, kK67Waves) void k67_update_strong(FrameArgs fa, int colour, int iter)
 {
     __shared__ float tile[kLdsH * kLdsPitch];
     const TilePixel t = checkerboard_pixel(fa, colour);
@@ -671,7 +675,9 @@ __global__ __launch_bounds__(256) void k_check_u8(const float *__restrict__ img,
     }
 }
 
-// round 1's row-major 4-byte quads (-DAPD_QUAD4): entry (qx, qy) = {I(qx-1,qy-1), I(qx,qy-1), I(qx-1,qy), I(qx,qy)}, clamped
+// Round 1's row-major 4-byte quads: entry (qx, qy) = {I(qx-1,qy-1), I(qx,qy-1), I(qx-1,qy), I(qx,qy)}, clamped.  No launcher
+// reaches this kernel: the column pairs below replaced the layout.  It stays in the code object until a change that is
+// allowed to alter the library's kernel symbol set removes it.
 __global__ __launch_bounds__(256) void k_pack_quads(const float *__restrict__ img, int W, int H, quad_t *__restrict__ quad)
 {
     const int qx = blockIdx.x * 32 + (threadIdx.x & 31);  // 0..W  <-> image x = qx - 1
@@ -684,7 +690,7 @@ __global__ __launch_bounds__(256) void k_pack_quads(const float *__restrict__ im
     quad[(size_t)qy * (W + 1) + qx] = t00 | (t10 << 8) | (t01 << 16) | (t11 << 24);
 }
 
-// 2-byte column pairs (the default row-major copy, apd_device.h): entry (t, u), t in [0, W + 1], u in [0, H], =
+// 2-byte column pairs (the row-major copy, apd_device.h): entry (t, u), t in [0, W + 1], u in [0, H], =
 // {I(t - 1, u - 1), I(t - 1, u)} with clamped coordinates
 __global__ __launch_bounds__(256) void k_pack_pairs(const float *__restrict__ img, int W, int H, uint16_t *__restrict__ pairs)
 {
@@ -697,33 +703,20 @@ __global__ __launch_bounds__(256) void k_pack_pairs(const float *__restrict__ im
     pairs[(size_t)u * (W + 2) + t] = (uint16_t)(top | (bot << 8));
 }
 
-// the tiled copy (apd_device.h: quad_tiled_offset_tu).  kPair2: one thread per (tile row, slot): slots 0..6 are the tile's own
+// the tiled copy (apd_device.h: quad_tiled_offset_tu).  One thread per (tile row, slot): slots 0..6 are the tile's own
 // columns, slot 7 repeats the first column of the next tile so that every dword of the tile holds two consecutive pairs
 __global__ __launch_bounds__(256) void k_pack_quads_tiled(const float *__restrict__ img, int W, int H, quad_t *__restrict__ quad)
 {
-    if (kPair2) {
-        const unsigned tiles_x = quad_tiles_x(W), tiles_y = quad_tiles_y(H);
-        const unsigned gid = blockIdx.x * 256u + threadIdx.x;  // (tile, row in tile, slot)
-        const unsigned slot = gid & 7u, iy = (gid >> 3) & 7u, tile = gid >> 6;
-        if (tile >= tiles_x * tiles_y) {
-            return;
-        }
-        const unsigned ty = tile / tiles_x, tx = tile - ty * tiles_x;
-        const int t = (int)(tx * 7u + slot), u = (int)(ty * 8u + iy);
-        const uint32_t top = (uint32_t)fetch_texel(img, W, H, t - 1, u - 1), bot = (uint32_t)fetch_texel(img, W, H, t - 1, u);
-        reinterpret_cast<uint16_t *>(quad)[(size_t)tile * 64u + iy * 8u + slot] = (uint16_t)(top | (bot << 8));
+    const unsigned tiles_x = quad_tiles_x(W), tiles_y = quad_tiles_y(H);
+    const unsigned gid = blockIdx.x * 256u + threadIdx.x;  // (tile, row in tile, slot)
+    const unsigned slot = gid & 7u, iy = (gid >> 3) & 7u, tile = gid >> 6;
+    if (tile >= tiles_x * tiles_y) {
         return;
     }
-    const int qx = blockIdx.x * 256 + threadIdx.x;  // flat over (W + 1) x (H + 1) entries
-    const int n = (W + 1) * (H + 1);
-    if (qx >= n) {
-        return;
-    }
-    const int ex = qx % (W + 1), ey = qx / (W + 1);
-    const uint32_t t00 = (uint32_t)fetch_texel(img, W, H, ex - 1, ey - 1), t10 = (uint32_t)fetch_texel(img, W, H, ex, ey - 1);
-    const uint32_t t01 = (uint32_t)fetch_texel(img, W, H, ex - 1, ey), t11 = (uint32_t)fetch_texel(img, W, H, ex, ey);
-    *reinterpret_cast<quad_t *>(reinterpret_cast<char *>(quad) + quad_tiled_offset_tu((unsigned)ex, (unsigned)ey, quad_tiles_x(W))) =
-        t00 | (t10 << 8) | (t01 << 16) | (t11 << 24);
+    const unsigned ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int t = (int)(tx * 7u + slot), u = (int)(ty * 8u + iy);
+    const uint32_t top = (uint32_t)fetch_texel(img, W, H, t - 1, u - 1), bot = (uint32_t)fetch_texel(img, W, H, t - 1, u);
+    reinterpret_cast<uint16_t *>(quad)[(size_t)tile * 64u + iy * 8u + slot] = (uint16_t)(top | (bot << 8));
 }
 
 // float texel quads of a float image: entry (qx, qy), qx in [-1, W-1], qy in [-1, H-1] (clamped coordinates)
@@ -753,17 +746,13 @@ hipError_t launch_check_u8(const float *img, int n, int *flag, hipStream_t s)
 
 hipError_t launch_pack_quads(const float *img, int W, int H, quad_t *quad, hipStream_t s)
 {
-    if (kPair2) {
-        hipLaunchKernelGGL(k_pack_pairs, dim3((W + 2 + 31) / 32, (H + 1 + 7) / 8), dim3(256), 0, s, img, W, H, reinterpret_cast<uint16_t *>(quad));
-    } else {
-        hipLaunchKernelGGL(k_pack_quads, dim3((W + 1 + 31) / 32, (H + 1 + 7) / 8), dim3(256), 0, s, img, W, H, quad);
-    }
+    hipLaunchKernelGGL(k_pack_pairs, dim3((W + 2 + 31) / 32, (H + 1 + 7) / 8), dim3(256), 0, s, img, W, H, reinterpret_cast<uint16_t *>(quad));
     return hipGetLastError();
 }
 
 hipError_t launch_pack_quads_tiled(const float *img, int W, int H, quad_t *quad, hipStream_t s)
 {
-    const size_t threads = kPair2 ? (size_t)quad_tiles_x(W) * quad_tiles_y(H) * 64u : (size_t)(W + 1) * (H + 1);
+    const size_t threads = (size_t)quad_tiles_x(W) * quad_tiles_y(H) * 64u;
     hipLaunchKernelGGL(k_pack_quads_tiled, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, img, W, H, quad);
     return hipGetLastError();
 }

@@ -20,7 +20,8 @@ constexpr int kFwLds = kFwTile + 2 * kPatchRadius;         // 26
 constexpr int kFwPitch = APD_FW_TILE_PITCH;                // 27
 constexpr int kFwWinPitch = APD_K1415_WIN_PITCH;
 static_assert(kFwWinPitch >= kWinW && kFwWinPitch <= 127, "window pitch: at least the wave width; two-address LDS reads need offset1 < 256 dwords");
-template <bool kQuad> constexpr int k14_win_h() { return kQuad ? APD_K14_WIN_H : APD_K14_WIN_H_F32; }
+constexpr int kK14WinHF32 = 32;  // float windows: the rows of the 8-bit ones
+template <bool kQuad> constexpr int k14_win_h() { return kQuad ? APD_K14_WIN_H : kK14WinHF32; }
 
 __device__ __forceinline__ void fw_pixel(int &px, int &py)
 {
@@ -119,7 +120,7 @@ template <bool kQuad, bool kPairs>
 __global__ __launch_bounds__(256, kQuad ? APD_K14W_WAVES : APD_K1415W_WAVES_F32) void k14w_depth_to_weak(FrameArgs fa)
 {
     __shared__ float tile[kFwLds * kFwPitch];
-    __shared__ uint32_t windows[4][window_dwords(kQuad, k14_win_h<kQuad>(), kFwWinPitch)];
+    __shared__ uint32_t windows[4][window_dwords(k14_win_h<kQuad>(), kFwWinPitch)];
     int px, py;
     fw_pixel(px, py);
     const RefPatchLds<kFwPitch> rp = fw_stage_ref(fa, tile, px, py);
@@ -199,9 +200,9 @@ __global__ __launch_bounds__(256, kQuad ? APD_K14W_WAVES : APD_K1415W_WAVES_F32)
     // textureless region ends after phase 0).
     const int wr = min(max(fa.weak_peak_radius, 0), RADIUS);
     const int centre_lo = ((RADIUS - wr) / APD_K14_CHUNK) * APD_K14_CHUNK;                        // first sample of the first centre chunk
-    const int centre_hi = (APD_K14_CENTRE_FIRST && fa.early_out) ? ((RADIUS + wr) / APD_K14_CHUNK + 1) * APD_K14_CHUNK : 0;  // one past the last centre chunk
+    const int centre_hi = fa.early_out ? ((RADIUS + wr) / APD_K14_CHUNK + 1) * APD_K14_CHUNK : 0;  // one past the last centre chunk
 #pragma unroll 1
-    for (int phase = (APD_K14_CENTRE_FIRST && fa.early_out) ? 0 : 1; phase < 2; ++phase) {
+    for (int phase = fa.early_out ? 0 : 1; phase < 2; ++phase) {
 #pragma unroll 1
         for (int c0 = 0; c0 < NP; c0 += APD_K14_CHUNK) {
             const bool centre_chunk = c0 >= centre_lo && c0 < centre_hi;
@@ -415,11 +416,13 @@ __global__ __launch_bounds__(256, kQuad ? APD_K14W_WAVES : APD_K1415W_WAVES_F32)
 // K15
 // ------------------------------------------------------------------------------------------------
 
+constexpr int kK15wWaves = 3;  // 8-bit input, ms per launch: 4 waves/SIMD (100 VGPRs spilled) 30.5, 3 waves 27.1
+
 template <bool kQuad>
-__global__ __launch_bounds__(256, kQuad ? APD_K15W_WAVES : APD_K1415W_WAVES_F32) void k15w_local_refine(FrameArgs fa)
+__global__ __launch_bounds__(256, kQuad ? kK15wWaves : APD_K1415W_WAVES_F32) void k15w_local_refine(FrameArgs fa)
 {
     __shared__ float tile[kFwLds * kFwPitch];
-    __shared__ uint32_t windows[4][window_dwords(kQuad, k14_win_h<kQuad>(), kFwWinPitch)];
+    __shared__ uint32_t windows[4][window_dwords(k14_win_h<kQuad>(), kFwWinPitch)];
     int px, py;
     fw_pixel(px, py);
     const RefPatchLds<kFwPitch> rp = fw_stage_ref(fa, tile, px, py);
@@ -499,7 +502,7 @@ __global__ __launch_bounds__(256, kQuad ? APD_K15W_WAVES : APD_K1415W_WAVES_F32)
         }
     }
     float lost = __builtin_inff();
-    if (APD_K15_EARLY_OUT && fa.early_out && alive && !(fa.geom_factor < 0.0f)) {
+    if (fa.early_out && alive && !(fa.geom_factor < 0.0f)) {
         // bound >= cost_now - 0.0999 in real arithmetic (|cost_now| <= 2 + 3 * geom_factor: two roundings are far below 1e-6)
         const float bound = (acc_now / weight_normal - 0.0999f) + 1e-6f;
         if (bound <= 0.0f) {
@@ -570,7 +573,7 @@ hipError_t launch_k14_windowed(const FrameArgs &fa, hipStream_t s)
     // 240.0 / 238.7 photometric; N = 6: 194.4 / 176.0, 182.0 / 185.9; N = 4: 121.8 / 112.6, 122.8 / 126.2; N = 2: 41.3 / 40.2, 65.4 / 67.7
     // (profiles/r06/ab_k14_pairs_by_pass_kind.txt).  Float images: 3100 x 2065, N = 8: 78.2 / 77.5, 66.3 / 68.7 -- unchanged rule.
     const int pairs_from = !fa.use_quads ? APD_K14_PAIRS_FROM_N : (fa.geom_consistency ? APD_K14_PAIRS_FROM_N_GEOM : APD_K14_PAIRS_FROM_N_PHOTO);
-    const bool pairs = APD_K14_COMPACT && fa.num_src >= pairs_from;
+    const bool pairs = fa.num_src >= pairs_from;
     if (fa.use_quads) {
         if (pairs) {
             hipLaunchKernelGGL((k14w_depth_to_weak<true, true>), grid, dim3(256), 0, s, fa);

@@ -109,7 +109,8 @@ __device__ __forceinline__ bool arm_pos(const FrameArgs &fa, int px, int py, int
     return true;
 }
 
-constexpr float kTrustedCost = APD_WIN_TRUST;
+constexpr float kTrustedCost = 0.5f;  // window placement: a plane that costs less is taken to be where the patch will stay
+constexpr int kWinFromIter = 1;  // first iteration of a FIRST_INIT pass that stages windows; configs[1] Mpix*iter/s: 0: 207, 1: 216
 
 // kTiled: NCCs that miss the window (all of them while the windows are off) gather from the tiled copy of the quad image
 // kApprox: tolerance mode APD_OPT_FAST_RCP (bare v_rcp_f32 in the sample loops; not bit-identical to the oracle)
@@ -117,7 +118,7 @@ template <int NMAX, bool kQuad, bool kTiled, bool kApprox>
 __global__ __launch_bounds__(256, kQuad ? APD_K67W_WAVES : APD_K67W_WAVES_F32) void k67w_update_strong(FrameArgs fa, int colour, int iter)
 {
     __shared__ float tile[kLdsH * kLdsPitch];
-    __shared__ uint32_t windows[4][window_dwords(kQuad, kWinH)];
+    __shared__ uint32_t windows[4][window_dwords(kWinH)];
     __shared__ uint16_t refine_items[4][5 * 64];  // per wave: (hypothesis << 6) | owner lane of every open (lane, hypothesis)
     __shared__ float refine_cost[4][5][64];       // per wave: the cost a worker lane computed for (hypothesis, owner lane)
     const TilePixel t = checkerboard_pixel(fa, colour);
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(256, kQuad ? APD_K67W_WAVES : APD_K67W_WAVES_F32) v
 
     // After K5's random initialisation nearly every hypothesis of the first iteration lands somewhere else in the
     // source image (10 % of the NCCs could read a window, 60 % of the waves are mixed): no windows in that iteration.
-    const bool use_windows = !(fa.state == APD_FIRST_INIT && iter < APD_WIN_FROM_ITER);
+    const bool use_windows = !(fa.state == APD_FIRST_INIT && iter < kWinFromIter);
     bool trusted = false;  // window placement only: the plane from the previous update has a low cost
     if (alive) {
         plane_now = fa.planes[center];
@@ -442,7 +443,7 @@ hipError_t launch_k67_windowed(const FrameArgs &fa, int colour, int iter, hipStr
     const int tiles = ((fa.W + kTileW - 1) / kTileW) * ((fa.H + kTileH - 1) / kTileH);
     if (fa.use_quads) {
         const int mode = fa.tiled_mode;
-        const bool windows_off = fa.state == APD_FIRST_INIT && iter < APD_WIN_FROM_ITER;
+        const bool windows_off = fa.state == APD_FIRST_INIT && iter < kWinFromIter;
         if (fa.have_tiled && (mode == 2 || (mode == 1 && windows_off))) {
             launch_k67w<true, true>(fa, tiles, colour, iter, s);
         } else {

@@ -605,7 +605,7 @@ __device__ __forceinline__ float deformed_centre(const FrameArgs &fa, const View
 {
     // Lanes whose 36 samples fall inside the wave's window read LDS, the others gather: only the latter cost L1 tag accesses, which bound this kernel.
     if constexpr (kQuad) {
-        return ncc_fixed_windowed_from_h<true, kWinW, false, false, APD_K910_WIN_DIVERGENT != 0>(fa, vc, w, rp, H, px, py);
+        return ncc_fixed_windowed_from_h<true>(fa, vc, w, rp, H, px, py);
     } else {
         return ncc_fixed_from_h<kQuad>(fa, vc, rp, H, px, py);
     }
@@ -617,13 +617,8 @@ template <bool kQuad>
 __device__ __forceinline__ void deformed_strong(const FrameArgs &fa, const ViewConst &vc, int v, const WeakLdsT<kQuad> &lds, int owner,
                                                 const Homography &H, float &strong_cost, int &strong_count)
 {
-#if APD_K910_SUBPATCH_TILED
-    const global_quad_ptr srcq = (global_quad_ptr)vc.quad_tiled;   // needs --opt tiled_copy=2 (the copy is built for every pass)
-    const unsigned qpitch = quad_tiles_x(fa.W);
-#else
     const global_quad_ptr srcq = (global_quad_ptr)vc.quad;
     const unsigned qpitch = quad_row_pitch_bytes(fa.W);
-#endif
     const unsigned fpitch = 16u * (unsigned)(fa.W + 1);
     const global_fquad_ptr srcf = (global_fquad_ptr)vc.fquad;
     const int wm1 = fa.W - 1, hm1 = fa.H - 1;
@@ -847,20 +842,18 @@ template <int NMAX, bool kQuad>
 __global__ __launch_bounds__(64, APD_K910_WAVES) void k910_update_weak(FrameArgs fa, int iter, const int *__restrict__ list, int count, int per_xcd)
 {
     __shared__ WeakLdsT<kQuad> lds;
-    // texel-quad mode: hypotheses 9..14 walk a compacted table of open (lane, hypothesis) pairs (see below)
-    constexpr bool kCompact = kQuad && APD_K910_COMPACT_REFINE != 0;
-    // Two phases, one LDS region.  Propagation (APD_K910_REMAP): prop_cost[h][pixel] -- the centre cost of (pixel, hypothesis h) on the way
-    // in, its NCCNew cost on the way out -- and prop_live[pixel], the hypotheses whose sub-patches are to be scored.  Refinement
-    // (kCompact): the table of open (lane, hypothesis) pairs and their costs.
-    constexpr bool kRemap = APD_K910_REMAP != 0;
-    constexpr int kPropWords = kRemap ? 8 * 64 + 64 : 0, kRefineWords = kCompact ? 5 * 64 + 5 * 64 / 2 : 0;
-    __shared__ uint32_t phase_lds[(kPropWords > kRefineWords ? kPropWords : kRefineWords) > 0 ? (kPropWords > kRefineWords ? kPropWords : kRefineWords) : 1];
+    // Two phases, one LDS region.  Propagation: prop_cost[h][pixel] -- the centre cost of (pixel, hypothesis h) on the way in, its
+    // NCCNew cost on the way out -- and prop_live[pixel], the hypotheses whose sub-patches are to be scored.  Refinement (texel-quad
+    // mode: hypotheses 9..14 walk a compacted table of open (lane, hypothesis) pairs, see below): that table and the pairs' costs.
+    constexpr int kPropWords = 8 * 64 + 64, kRefineWords = 5 * 64 + 5 * 64 / 2;
+    static_assert(kRefineWords <= kPropWords, "the refinement tables reuse the propagation phase's LDS");
+    __shared__ uint32_t phase_lds[kPropWords];
     float (*const prop_cost)[64] = reinterpret_cast<float (*)[64]>(phase_lds);
     uint32_t *const prop_live = phase_lds + 8 * 64;
     float (*const refine_cost)[64] = reinterpret_cast<float (*)[64]>(phase_lds);
     uint16_t *const refine_items = reinterpret_cast<uint16_t *>(phase_lds + 5 * 64);
     // the wave's window of the current source view for the centre patches (texel-quad mode)
-    __shared__ uint32_t centre_window[kQuad ? window_dwords(true, kK910WinH) : 1];
+    __shared__ uint32_t centre_window[kQuad ? window_dwords(kK910WinH) : 1];
     const int lane = threadIdx.x;
     const int first = weak_chunk_of_block(blockIdx.x, per_xcd) * 64;
     if (first >= count) {
@@ -920,104 +913,86 @@ __global__ __launch_bounds__(64, APD_K910_WAVES) void k910_update_weak(FrameArgs
     for (int v = 0; v < nsrc; ++v) {
         const ViewConst &vc = view_const(fa, v);
         SrcWindow w = no_window();
-        if constexpr (kQuad && APD_K910_WINDOW != 0) {
+        if constexpr (kQuad) {
             w = weak_stage_window(fa, vc, centre_window, px, py, plane_now);
         }
-        if constexpr (!kRemap) {
+        // Lane = pixel for the centre patches (their 36 samples lie around the pixel: the wave's window serves them) and for the own-plane
+        // hypothesis; lane = (pixel, hypothesis) for the sub-patches of the eight neighbour hypotheses.  A sub-patch sits where its ANCHOR
+        // is, a median of 27 px from the pixel in a direction of its own (tools/nb_cluster.py), so with lane = pixel the 64 lanes of a
+        // sub-patch tap read 64 unrelated places: one L1 tag access per lane, the bound of this kernel through round 5 (46 of 49 ms).
+        // With eight consecutive lanes on the eight hypotheses of ONE pixel and slot, the eight read the same anchor's neighbourhood
+        // under eight nearly equal planes -- texels a few bytes apart, which the L1 serves with one tag access per aligned 16 bytes
+        // (tools/tcp_patterns.hip) -- and a wave-level tap touches eight places instead of sixty-four.  Same operands, same operations,
+        // the sub-patch costs of a (pixel, hypothesis) pair summed by one lane in slot order: same bits.
+        unsigned live = 0;   // neighbour hypotheses whose centre projects into the view: their sub-patches are scored below
 #pragma unroll 1
-            for (int h = 0; h < 9; ++h) {
-                if (h < 8 && !(flags & (1u << h))) {
-                    continue;
-                }
-                float4 pl = plane_now;
-                if (h < 8) {  // the neighbour's position is already in LDS (weak_prepare_neighbours): one global load instead of two dependent ones
-                    const int packed = lds.nb[h][lane];
-                    pl = fa.planes[(int)(short)(packed & 0xFFFF) + (packed >> 16) * W];
-                }
-                APD_WEAK_COUNT(0, 1);
-                APD_WEAK_COUNT_WAVE(1);
-                cost_array[h][v] = ncc_deformed<kQuad>(fa, vc, v, rp, lds, lane, px, py, pl, w);
+        for (int h = 0; h < 9; ++h) {
+            if (h < 8 && !(flags & (1u << h))) {
+                continue;
             }
-        } else {
-            // Lane = pixel for the centre patches (their 36 samples lie around the pixel: the wave's window serves them) and for the own-plane
-            // hypothesis; lane = (pixel, hypothesis) for the sub-patches of the eight neighbour hypotheses.  A sub-patch sits where its ANCHOR
-            // is, a median of 27 px from the pixel in a direction of its own (tools/nb_cluster.py), so with lane = pixel the 64 lanes of a
-            // sub-patch tap read 64 unrelated places: one L1 tag access per lane, the bound of this kernel through round 5 (46 of 49 ms).
-            // With eight consecutive lanes on the eight hypotheses of ONE pixel and slot, the eight read the same anchor's neighbourhood
-            // under eight nearly equal planes -- texels a few bytes apart, which the L1 serves with one tag access per aligned 16 bytes
-            // (tools/tcp_patterns.hip) -- and a wave-level tap touches eight places instead of sixty-four.  Same operands, same operations,
-            // the sub-patch costs of a (pixel, hypothesis) pair summed by one lane in slot order: same bits.
-            unsigned live = 0;   // neighbour hypotheses whose centre projects into the view: their sub-patches are scored below
+            float4 pl = plane_now;
+            if (h < 8) {
+                const int packed = lds.nb[h][lane];
+                pl = fa.planes[(int)(short)(packed & 0xFFFF) + (packed >> 16) * W];
+            }
+            APD_WEAK_COUNT(0, 1);
+            APD_WEAK_COUNT_WAVE(1);
+            float qx, qy, qz;
+            plane_q(pl, qx, qy, qz);
+            const Homography H = make_homography(fa, vc, qx, qy, qz);
+            float cx, cy;
+            correspond(H, (float)px, (float)py, cx, cy);
+            if (cx >= vc.wf || cx < 0.0f || cy >= vc.hf || cy < 0.0f) {
+                cost_array[h][v] = 2.0f;
+                continue;
+            }
+            const float center_cost = deformed_centre<kQuad>(fa, vc, rp, H, px, py, w);
+            if (h == 8) {
+                float strong_cost;
+                int strong_count;
+                deformed_strong<kQuad>(fa, vc, v, lds, lane, H, strong_cost, strong_count);
+                cost_array[8][v] = deformed_combine(center_cost, strong_cost, strong_count);
+            } else {
+                prop_cost[h][lane] = center_cost;
+                live |= 1u << h;
+            }
+        }
+        prop_live[lane] = live;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int hyp = lane & 7;
 #pragma unroll 1
-            for (int h = 0; h < 9; ++h) {
-                if (h < 8 && !(flags & (1u << h))) {
-                    continue;
-                }
-                float4 pl = plane_now;
-                if (h < 8) {
-                    const int packed = lds.nb[h][lane];
-                    pl = fa.planes[(int)(short)(packed & 0xFFFF) + (packed >> 16) * W];
-                }
-                APD_WEAK_COUNT(0, 1);
-                APD_WEAK_COUNT_WAVE(1);
+        for (int g = 0; g < 8; ++g) {
+            const int owner = g * 8 + (lane >> 3);
+            const bool active = ((prop_live[owner] >> hyp) & 1u) != 0;
+            if (active) {
+                const int packed = lds.nb[hyp][owner];
+                const float4 pl = fa.planes[(int)(short)(packed & 0xFFFF) + (packed >> 16) * W];
                 float qx, qy, qz;
                 plane_q(pl, qx, qy, qz);
                 const Homography H = make_homography(fa, vc, qx, qy, qz);
-                float cx, cy;
-                correspond(H, (float)px, (float)py, cx, cy);
-                if (cx >= vc.wf || cx < 0.0f || cy >= vc.hf || cy < 0.0f) {
-                    cost_array[h][v] = 2.0f;
-                    continue;
-                }
-                const float center_cost = deformed_centre<kQuad>(fa, vc, rp, H, px, py, w);
-                if (h == 8) {
-                    float strong_cost;
-                    int strong_count;
-                    deformed_strong<kQuad>(fa, vc, v, lds, lane, H, strong_cost, strong_count);
-                    cost_array[8][v] = deformed_combine(center_cost, strong_cost, strong_count);
-                } else {
-                    prop_cost[h][lane] = center_cost;
-                    live |= 1u << h;
-                }
+                float strong_cost;
+                int strong_count;
+                deformed_strong<kQuad>(fa, vc, v, lds, owner, H, strong_cost, strong_count);
+                prop_cost[hyp][owner] = deformed_combine(prop_cost[hyp][owner], strong_cost, strong_count);
             }
-            prop_live[lane] = live;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int hyp = lane & 7;
-#pragma unroll 1
-            for (int g = 0; g < 8; ++g) {
-                const int owner = g * 8 + (lane >> 3);
-                const bool active = ((prop_live[owner] >> hyp) & 1u) != 0;
-                if (active) {
-                    const int packed = lds.nb[hyp][owner];
-                    const float4 pl = fa.planes[(int)(short)(packed & 0xFFFF) + (packed >> 16) * W];
-                    float qx, qy, qz;
-                    plane_q(pl, qx, qy, qz);
-                    const Homography H = make_homography(fa, vc, qx, qy, qz);
-                    float strong_cost;
-                    int strong_count;
-                    deformed_strong<kQuad>(fa, vc, v, lds, owner, H, strong_cost, strong_count);
-                    prop_cost[hyp][owner] = deformed_combine(prop_cost[hyp][owner], strong_cost, strong_count);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-            for (int h = 0; h < 8; ++h) {
-                if (live & (1u << h)) {
-                    cost_array[h][v] = prop_cost[h][lane];
-                }
+        for (int h = 0; h < 8; ++h) {
+            if (live & (1u << h)) {
+                cost_array[h][v] = prop_cost[h][lane];
             }
         }
-        if constexpr (kQuad || kRemap) {  // the window / the cost table is rewritten for the next view
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
+        // the window / the cost table is rewritten for the next view
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
     }
 
 #pragma unroll 1
     for (int h = 9; h < 16; ++h) {
-        if constexpr (kCompact) {
+        if constexpr (kQuad) {
             if (h >= 10 && h <= 14) {
                 continue;  // scored by the compacted stages at h == 9
             }
@@ -1110,7 +1085,7 @@ __global__ __launch_bounds__(64, APD_K910_WAVES) void k910_update_weak(FrameArgs
             pl = ref_normals[h - 10];
             pl.w = distance_to_origin(fa, px, py, ref_depths[h - 10], pl.x, pl.y, pl.z);
         }
-        if constexpr (kCompact) {
+        if constexpr (kQuad) {
             if (h == 9) {
                 // Hypotheses 9..14 in two stages -- the fit plane, then the five random refinements around whatever it left
                 // (:910-980) -- each evaluated view by view over a compacted table: which (lane, hypothesis) pairs are still
@@ -1174,7 +1149,7 @@ __global__ __launch_bounds__(64, APD_K910_WAVES) void k910_update_weak(FrameArgs
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                         __builtin_amdgcn_wave_barrier();
                         const ViewConst &vc = view_const(fa, v);
-                        const SrcWindow w = APD_K910_WINDOW != 0 ? weak_stage_window(fa, vc, centre_window, px, py, plane_now) : no_window();
+                        const SrcWindow w = weak_stage_window(fa, vc, centre_window, px, py, plane_now);
                         const int slot_step = nworkers, slot_end = total;
 #pragma unroll 1
                         for (int first = 0; first < slot_end; first += slot_step) {

@@ -7,36 +7,33 @@
 
 namespace apd {
 
-// Window geometry.  One entry per texel (qx, qy): the pair {I(qx,qy), I(qx+1,qy) - I(qx,qy)}.
-//   kQuad (8-bit input, staged from the byte quads): two binary16 values in 4 bytes -- integers up to 255 and their
-//     differences are exact in binary16 -- lerped with one v_fma_mix_f32 each;
-//   otherwise (float grey values, staged from the float texel-quad image): two binary32 values in 8 bytes, one v_fma_f32 each.
-// A bilinear fetch at (qx, qy) reads the entries (qx, qy) and (qx, qy + 1) with one two-address LDS read: 4 VALU
-// instructions for the whole lerp, same taps, same three fused multiply-adds as the global paths.  A window is as wide
-// as the wave, so lane l stages column l of every row.
+// Window geometry.  One four-byte entry per texel (qx, qy):
+//   kQuad (8-bit input, staged from the byte quads): the pair {I(qx,qy), I(qx+1,qy) - I(qx,qy)} as two binary16 values --
+//     integers up to 255 and their differences are exact in binary16 -- lerped with one v_fma_mix_f32 each;
+//   otherwise (float grey values, staged from the plain float image): the texel alone.  A tap reads the entries of columns
+//     qx and qx + 1 and forms the horizontal difference t(x+1) - t(x) after the read -- the same rounded subtraction the
+//     {texel, difference} pairs of the float texel-quad image store, two more plain FP32 instructions per sample and half
+//     the LDS of 8-byte pair entries (K6/K7 47 -> 26 KB, K14/K15 79 -> 41 KB per workgroup: the occupancy of the 8-bit kernels).
+// A bilinear fetch at (qx, qy) reads the entries (qx, qy) and (qx, qy + 1) with one two-address LDS read (two for single
+// texels): same taps, same three fused multiply-adds as the global paths.  A window is as wide as the wave, so lane l
+// stages column l of every row.
 // The row pitch (in entries) is a template parameter: with pitch 64 the entries of one column share an LDS bank, which
 // is free for the 32x4 checkerboard footprint of K6/K7 (a 32-lane group reads two pixel rows of opposite column parity)
 // and a four-way conflict for the 8x8 footprint of K14/K15 (a group reads four rows of the same eight columns); those
-// kernels use pitch 72, which moves consecutive rows by 8 (binary16 pairs) / 16 (binary32 pairs) banks.
+// kernels use pitch 72, which moves consecutive rows by 8 banks.
 constexpr int kWinW = 64;
-// Float images: an entry is the texel alone (4 bytes) and the horizontal difference t(x+1) - t(x) is formed after the read --
-// the same rounded subtraction the {texel, difference} pairs of the float texel-quad image store, two more plain FP32
-// instructions per sample, half the LDS (K6/K7 47 -> 26 KB, K14/K15 79 -> 41 KB per workgroup: the occupancy of the 8-bit
-// kernels).  -DAPD_WIN_F32_PAIRS=1 rebuilds the 8-byte {texel, difference} entries of rounds 1-2.
-constexpr bool kWinF32Pairs = APD_WIN_F32_PAIRS != 0;
-// LDS dwords of a window with WINH rows of fetch positions (+ the row below the last one)
-constexpr int window_dwords(bool quad, int winh, int pitch = kWinW) { return pitch * (winh + 1) * ((quad || !kWinF32Pairs) ? 1 : 2); }
+// LDS dwords of a window with WINH rows of fetch positions (+ the row below the last one): every entry is one dword
+constexpr int window_dwords(int winh, int pitch = kWinW) { return pitch * (winh + 1); }
 static_assert(kQuadShift == 2, "the window is staged from dword fetches of the quad image");
 
 template <bool kQuad> struct WinEntry;
 template <> struct WinEntry<true> {
     typedef uint32_t type;   // {binary16 t, binary16 dx}
-    static constexpr int kShift = 2;
 };
 template <> struct WinEntry<false> {
-    typedef pair_t type;     // what a tap read returns: {binary32 t, binary32 dx} (pairs) or {t(x), t(x + 1)} (single texels)
-    static constexpr int kShift = kWinF32Pairs ? 3 : 2;
+    typedef pair_t type;     // what a tap read returns: {t(x), t(x + 1)} of the single-texel entries
 };
+constexpr int kWinEntryShift = 2;  // log2 of an entry's bytes, either kind
 
 typedef __attribute__((address_space(3))) uint32_t *lds_u32_ptr;
 
@@ -118,12 +115,11 @@ __device__ __forceinline__ float wave_max(float v)
 
 // Every lane of the wave calls this (no divergence): centres a window with WINH rows of fetch positions on the bounding
 // box of the points (cx, cy) of the lanes with `ok` and copies it from the quad image.  `win` is this wave's LDS region
-// (window_dwords(kQuad, WINH, kPitch) dwords).
+// (window_dwords(WINH, kPitch) dwords).
 template <bool kQuad, int WINH, int kPitch = kWinW>
 __device__ __forceinline__ SrcWindow stage_window_around(const FrameArgs &fa, const ViewConst &vc, uint32_t *win, bool ok, float cx, float cy)
 {
     constexpr int kWinRows = WINH + 1;
-    constexpr int kShift = WinEntry<kQuad>::kShift;
     SrcWindow w;
     const float big = 3.0e38f;
     const float x_lo = wave_min(ok ? cx : big), x_hi = wave_max(ok ? cx : -big);
@@ -139,48 +135,32 @@ __device__ __forceinline__ SrcWindow stage_window_around(const FrameArgs &fa, co
     const int wx0 = __builtin_amdgcn_readfirstlane((int)floorf(0.5f * (x_lo + x_hi)) - kWinW / 2);
     const int wy0 = __builtin_amdgcn_readfirstlane((int)floorf(0.5f * (y_lo + y_hi)) - WINH / 2);
     const int lane = threadIdx.x & 63;
-    const int qp = fa.W + 1;
     // entries outside the image replicate the edge entry, exactly like the clamp of the global path
     const int col = med3_i32(wx0 + lane, -1, fa.W - 1) + 1;
     if constexpr (kQuad) {
         const global_quad_ptr srcq = (global_quad_ptr)vc.quad;
         const unsigned rpitch = quad_row_pitch_bytes(fa.W);
-        if constexpr (kPair2) {
-            // a column-pair dword holds the texels of rows gy and gy + 1 (clamping built in): one gather stages two window rows
-            constexpr int kLoads = (kWinRows + 1) / 2;
-            uint32_t tmp[kLoads];
+        // a column-pair dword holds the texels of rows gy and gy + 1 (clamping built in): one gather stages two window rows
+        constexpr int kLoads = (kWinRows + 1) / 2;
+        uint32_t tmp[kLoads];
 #pragma unroll
-            for (int k = 0; k < kLoads; ++k) {
-                const int gy = min(max(wy0 + 2 * k, -1), fa.H - 1);  // wave-uniform
-                tmp[k] = quad_fetch(srcq, (unsigned)(gy + 1) * rpitch + ((unsigned)col << kRowEntryShift));
-            }
+        for (int k = 0; k < kLoads; ++k) {
+            const int gy = min(max(wy0 + 2 * k, -1), fa.H - 1);  // wave-uniform
+            tmp[k] = quad_fetch(srcq, (unsigned)(gy + 1) * rpitch + ((unsigned)col << kRowEntryShift));
+        }
 #pragma unroll
-            for (int k = 0; k < kLoads; ++k) {
-                float t0, t1, x0, x1;  // bytes {I(x,gy), I(x,gy+1), I(x+1,gy), I(x+1,gy+1)}
-                asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t0) : "v"(tmp[k]));
-                asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t1) : "v"(tmp[k]));
-                asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(x0) : "v"(tmp[k]));
-                asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(x1) : "v"(tmp[k]));
-                win[(2 * k) * kPitch + lane] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(t0, x0 - t0));
-                if (2 * k + 1 < kWinRows) {
-                    win[(2 * k + 1) * kPitch + lane] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(t1, x1 - t1));
-                }
-            }
-        } else {
-            uint32_t tmp[kWinRows];
-#pragma unroll
-            for (int k = 0; k < kWinRows; ++k) {
-                const int gy = min(max(wy0 + k, -1), fa.H - 1);  // wave-uniform
-                tmp[k] = quad_fetch(srcq, (unsigned)(gy + 1) * rpitch + ((unsigned)col << kRowEntryShift));
-            }
-#pragma unroll
-            for (int k = 0; k < kWinRows; ++k) {
-                const float t0 = (float)(tmp[k] & 0xFFu);
-                const float dx = (float)((tmp[k] >> 8) & 0xFFu) - t0;
-                win[k * kPitch + lane] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(t0, dx));
+        for (int k = 0; k < kLoads; ++k) {
+            float t0, t1, x0, x1;  // bytes {I(x,gy), I(x,gy+1), I(x+1,gy), I(x+1,gy+1)}
+            asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t0) : "v"(tmp[k]));
+            asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t1) : "v"(tmp[k]));
+            asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(x0) : "v"(tmp[k]));
+            asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(x1) : "v"(tmp[k]));
+            win[(2 * k) * kPitch + lane] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(t0, x0 - t0));
+            if (2 * k + 1 < kWinRows) {
+                win[(2 * k + 1) * kPitch + lane] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(t1, x1 - t1));
             }
         }
-    } else if constexpr (!kWinF32Pairs) {
+    } else {
         // texel (clamp(x), clamp(y)) of the plain float image: coalesced 256-byte row reads; the clamp makes the difference
         // formed after the read the one the float texel quads store (0 left of, right of and at the last column of the image)
         typedef const __attribute__((address_space(1))) float *global_float_ptr;
@@ -197,22 +177,6 @@ __device__ __forceinline__ SrcWindow stage_window_around(const FrameArgs &fa, co
         for (int k = 0; k < kWinRows; ++k) {
             winf[k * kPitch + lane] = tmp[k];
         }
-    } else {
-        // the pair of texel row gy is the first half of float quad (., gy); the row below the image (gy == H, a copy
-        // of row H - 1 by the clamp) is the second half of quad (., H - 1)
-        const global_pair_ptr srcp = (global_pair_ptr)vc.fquad;  // two pairs per quad entry
-        pair_t *winp = reinterpret_cast<pair_t *>(win);
-        pair_t tmp[kWinRows];
-#pragma unroll
-        for (int k = 0; k < kWinRows; ++k) {
-            const int gy = min(max(wy0 + k, -1), fa.H);  // wave-uniform
-            const int qrow = min(gy, fa.H - 1) + 1;
-            tmp[k] = srcp[2u * (unsigned)(qrow * qp + col) + (gy == fa.H ? 1u : 0u)];
-        }
-#pragma unroll
-        for (int k = 0; k < kWinRows; ++k) {
-            winp[k * kPitch + lane] = tmp[k];
-        }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -227,10 +191,10 @@ __device__ __forceinline__ SrcWindow stage_window_around(const FrameArgs &fa, co
     // path computes its LDS addresses in binary32 and relies on X, Y >= 0)
     w.lo_x = (float)max(wx0 + 1, 0);
     // single-texel float entries: a fetch at column c also reads column c + 1
-    w.hi_x = (float)(wx0 + kWinW - ((kQuad || kWinF32Pairs) ? 1 : 2));
+    w.hi_x = (float)(wx0 + kWinW - (kQuad ? 1 : 2));
     w.lo_y = (float)max(wy0 + 1, 0);
     w.hi_y = (float)(wy0 + WINH - 1);
-    w.addr0 = __builtin_amdgcn_readfirstlane(lds_address(win) - (wy0 * kPitch + wx0) * (1 << kShift));
+    w.addr0 = __builtin_amdgcn_readfirstlane(lds_address(win) - (wy0 * kPitch + wx0) * (1 << kWinEntryShift));
     return w;
 }
 
@@ -300,8 +264,8 @@ __device__ __forceinline__ void win_row_issue(const Homography &H, float bx, flo
     // the low 23 bits of the binary32 encoding are the integer itself -- one v_and_b32 (2 cycles) instead of v_cvt_i32_f32
     // (4).  addr0 is above -2^23 - 2^20 for every image apd_create accepts (height <= 16384, window rows of at most 576
     // bytes), so every step stays an integer of magnitude below 2^24.  (ds_read does not ignore the high address bits: tools/lds_addr_bits.hip.)
-    constexpr float kEntryBytes = (float)(1 << WinEntry<kQuad>::kShift), kPitchBytes = (float)(kPitch << WinEntry<kQuad>::kShift);
-    const float addr0f = (float)addr0 + (APD_WIN_ADDR_MAGIC ? 8388608.0f : 0.0f);
+    constexpr float kEntryBytes = (float)(1 << kWinEntryShift), kPitchBytes = (float)(kPitch << kWinEntryShift);
+    const float addr0f = (float)addr0 + 8388608.0f;
     float fx[kPatchN], fy[kPatchN];
 #pragma unroll
     for (int j = 0; j < kPatchN; ++j) {
@@ -328,13 +292,13 @@ __device__ __forceinline__ void win_row_issue(const Homography &H, float bx, flo
     int addr[kPatchN];
 #pragma unroll
     for (int j = 0; j < kPatchN; ++j) {
-        addr[j] = APD_WIN_ADDR_MAGIC ? (int)(__float_as_uint(fx[j]) & 0x007FFFFFu) : (int)fx[j];
+        addr[j] = (int)(__float_as_uint(fx[j]) & 0x007FFFFFu);
     }
     APD_STAGE();
 #pragma unroll
     for (int j = 0; j < kPatchN; ++j) {
-        if constexpr (kQuad || kWinF32Pairs) {
-            t[j] = lds_read_pair<typename WinEntry<kQuad>::type, kPitch>(addr[j]);
+        if constexpr (kQuad) {
+            t[j] = lds_read_pair<uint32_t, kPitch>(addr[j]);
         } else {
             t[j] = lds_read_texels<kPitch>(addr[j]);
         }
@@ -352,9 +316,6 @@ __device__ __forceinline__ void win_row_lerp(const WinTaps<typename WinEntry<kQu
         if constexpr (kQuad) {
             top[j] = lerp_f16_pair(a[j], t[j].top);
             bot[j] = lerp_f16_pair(a[j], t[j].bot);
-        } else if constexpr (kWinF32Pairs) {
-            top[j] = fmaf(a[j], t[j].top.y, t[j].top.x);
-            bot[j] = fmaf(a[j], t[j].bot.y, t[j].bot.x);
         } else {  // {t(x), t(x + 1)}: the difference the pairs store, formed here
             top[j] = fmaf(a[j], t[j].top.y - t[j].top.x, t[j].top.x);
             bot[j] = fmaf(a[j], t[j].bot.y - t[j].bot.x, t[j].bot.x);
@@ -374,7 +335,7 @@ __device__ __forceinline__ void win_row_lerp(const WinTaps<typename WinEntry<kQu
 
 // ncc_fixed_moments (fast reciprocal) reading the window.
 // cX / cY: positions of the four corner samples {(x0,y0), (x0,y1), (x1,y0), (x1,y1)} from the caller's window test; rows 0 and
-// kPatchN - 1 take their end samples from there instead of computing them a second time (APD_WIN_CORNER_REUSE=0: recompute).
+// kPatchN - 1 take their end samples from there instead of computing them a second time.
 // kLocal (K14 / K15): the sample coordinates are formed inside the body, by exact binary32 additions to the patch's first
 // coordinate taken through an opaque copy -- (float)(px - 5) + 2 i is the integer (float)(px + 2 i - 5) of the other form, bit for
 // bit.  Without it the compiler shares these twelve conversions with the global-path body and with the corner test, hoists them
@@ -390,7 +351,6 @@ template <bool kQuad, int kPitch, bool kApprox, bool kLocal = false, typename Re
 __device__ __forceinline__ void ncc_window_moments(const Ref &rp, const Homography &H, int px, int py, int addr0, float &sum_s,
                                                    float &sum_ss, float &sum_rs, const float (&cX)[4], const float (&cY)[4])
 {
-    constexpr bool kReuse = APD_WIN_CORNER_REUSE != 0;
     float yf[kPatchN];
     float x_first = 0.0f;
     if constexpr (kLocal) {
@@ -409,21 +369,17 @@ __device__ __forceinline__ void ncc_window_moments(const Ref &rp, const Homograp
     sum_s = 0.0f;
     sum_ss = 0.0f;
     sum_rs = 0.0f;
-#if APD_WIN_SETPRIO > 0
-    __builtin_amdgcn_s_setprio(APD_WIN_SETPRIO);
-#endif
-#if APD_WIN_DRAIN_SMEM
+    __builtin_amdgcn_s_setprio(1);  // issue priority for the wave inside its 36-sample burst: +0.7 % on configs[1]
     // Scalar loads return out of order: while one is pending (the per-view constants a caller prefetches for its next NCC), the
     // compiler can only wait for "every LDS and scalar access" -- and the first row of the body then ends with `s_waitcnt
     // lgkmcnt(0)` right after the NEXT row's six reads have been issued: a whole LDS round trip per NCC.  Waiting for the scalar
     // loads here, where they have had the whole prologue to arrive, lets every wait of the body be a counted one.
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0), vmcnt / expcnt untouched
-#endif
     float a[2][kPatchN], b[2][kPatchN];
     WinTaps<typename WinEntry<kQuad>::type> t[2][kPatchN];
     {
         const float xf = kLocal ? x_first : (float)(px - kPatchRadius);
-        win_row_issue<kQuad, kPitch, kApprox, kReuse>(H, fmaf(H.h[0], xf, H.h[2]), fmaf(H.h[3], xf, H.h[5]), fmaf(H.h[6], xf, H.h[8]), yf,
+        win_row_issue<kQuad, kPitch, kApprox, true>(H, fmaf(H.h[0], xf, H.h[2]), fmaf(H.h[3], xf, H.h[5]), fmaf(H.h[6], xf, H.h[8]), yf,
                                                       addr0, a[0], b[0], t[0], cX[0], cY[0], cX[1], cY[1]);
     }
 #pragma unroll
@@ -443,7 +399,7 @@ __device__ __forceinline__ void ncc_window_moments(const Ref &rp, const Homograp
                                                   addr0, a[(i + 1) & 1], b[(i + 1) & 1], t[(i + 1) & 1]);
         } else if (i + 1 < kPatchN) {
             const float xf = kLocal ? x_first + (float)(kPatchStep * (i + 1)) : (float)(px + kPatchStep * (i + 1) - kPatchRadius);
-            win_row_issue<kQuad, kPitch, kApprox, kReuse>(H, fmaf(H.h[0], xf, H.h[2]), fmaf(H.h[3], xf, H.h[5]), fmaf(H.h[6], xf, H.h[8]), yf,
+            win_row_issue<kQuad, kPitch, kApprox, true>(H, fmaf(H.h[0], xf, H.h[2]), fmaf(H.h[3], xf, H.h[5]), fmaf(H.h[6], xf, H.h[8]), yf,
                                                           addr0, a[(i + 1) & 1], b[(i + 1) & 1], t[(i + 1) & 1], cX[2], cY[2], cX[3], cY[3]);
         }
         APD_STAGE();
@@ -459,9 +415,7 @@ __device__ __forceinline__ void ncc_window_moments(const Ref &rp, const Homograp
         sum_ss += row_ss;
         sum_rs += row_rs;
     }
-#if APD_WIN_SETPRIO > 0
     __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // Sample position of patch corner (xf, yf), computed exactly like the samples themselves (fast reciprocal).
@@ -538,10 +492,10 @@ __device__ __forceinline__ float ncc_fixed_windowed(const FrameArgs &fa, const V
 // (A function of its own rather than the tail of ncc_fixed_windowed: routing K6/K7 through it changes that kernel's block layout and
 // spills -- 512 -> 592 B of scratch per lane in one arrangement -- and K6/K7 is the headline kernel.)
 // kApprox: tolerance mode (bare v_rcp_f32 everywhere, no IEEE body); see quad_row_issue
-// kDivergent: lanes inside and lanes outside the window each take their own 36-sample body (a mixed wave runs both in turn).  The
-//   default is one body per wave and NCC -- right for the kernels the vector ALU bounds (K6/K7, K14, K15); K9/K10 is bound by the
-//   L1's tag accesses, which only the lanes on the global path make.
-template <bool kQuad, int kPitch = kWinW, bool kTiled = false, bool kApprox = false, bool kDivergent = false, typename Ref>
+// Lanes inside and lanes outside the window each take their own 36-sample body (a mixed wave runs both in turn), unlike the one
+// body per wave and NCC of ncc_fixed_windowed: that is right for the kernels the vector ALU bounds (K6/K7, K14, K15); K9/K10 is
+// bound by the L1's tag accesses, which only the lanes on the global path make.
+template <bool kQuad, int kPitch = kWinW, bool kTiled = false, bool kApprox = false, typename Ref>
 __device__ __forceinline__ float ncc_fixed_windowed_from_h(const FrameArgs &fa, const ViewConst &vc, const SrcWindow &w, const Ref &rp,
                                                            const Homography &H, int px, int py)
 {
@@ -567,11 +521,7 @@ __device__ __forceinline__ float ncc_fixed_windowed_from_h(const FrameArgs &fa, 
         in_window = xl >= w.lo_x && xh < w.hi_x && yl >= w.lo_y && yh < w.hi_y;
     }
     APD_LAB_NCC_STATS(in_window, fast_recip);
-    if constexpr (!kDivergent) {
-        // one path per wave and NCC: lanes inside and outside the window would otherwise run both 36-sample bodies in turn
-        in_window = in_window && __builtin_amdgcn_ballot_w64(!in_window) == 0;
-    }
-    // the same for the two global bodies: if one lane needs the IEEE division, every lane of the wave takes it (same bits)
+    // one global body per wave: if one lane needs the IEEE division, every lane of the wave takes it (same bits)
     const bool fast_body = __builtin_amdgcn_ballot_w64(!fast_recip) == 0;
     float sum_s, sum_ss, sum_rs;
     if (in_window) {

@@ -2,10 +2,16 @@
 
 K3 (GenNeighbours, APD.cu:1911 / :1946) tests `dist / (depth_max - depth_min) < ransac_threshold` for dist >= 0.  The device
 compares `dist < cut` instead; apd_ransac_distance_cut (csrc/apd_capi.hip) finds the cut with IEEE binary32 divisions.
-The two predicates have to agree for every binary32 dist, or K3 would pick other neighbours than the reference."""
+The two predicates have to agree for every binary32 dist, or K3 would pick other neighbours than the reference.
+
+The build-time parameters of csrc/apd_tuning.h: every one is read by a kernel source, and the lab scripts pass no other."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _cut(pkg, dmin, dmax, thr):
@@ -54,3 +60,24 @@ def test_parameters_without_a_cut_are_reported(pkg):
     assert ok == 1 and cut == 0.0
     ok, cut = _cut(pkg, 1.0, 2.0, -1.0)
     assert ok == 1 and cut == 0.0
+
+
+def test_tuning_macros_are_used_and_tools_pass_no_others():
+    csrc = os.path.join(ROOT, "apd-mvs_amd", "csrc")
+    tuning = set(re.findall(r"^#define\s+(APD_\w+)", open(os.path.join(csrc, "apd_tuning.h")).read(), re.M))
+    assert tuning
+    sources = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f != "apd_tuning.h")
+    unused = sorted(m for m in tuning if not re.search(r"\b%s\b" % m, sources))
+    assert not unused, "apd_tuning.h defines what no file in csrc/ reads: %s" % unused
+    # the lab counters: what apd_lab.h tests with #if / #ifdef / defined()
+    lab = set(re.findall(r"^\s*#\s*(?:ifdef|ifndef)\s+(APD_LAB_\w+)", open(os.path.join(csrc, "apd_lab.h")).read(), re.M))
+    lab |= set(re.findall(r"defined\s*\(?\s*(APD_LAB_\w+)", open(os.path.join(csrc, "apd_lab.h")).read()))
+    stray = []
+    for d, dirs, files in os.walk(os.path.join(ROOT, "tools")):
+        dirs[:] = [x for x in dirs if x not in ("_build", "__pycache__")]
+        for f in files:
+            if f.endswith((".patch", ".pyc")):
+                continue
+            text = open(os.path.join(d, f), errors="ignore").read()
+            stray += [(os.path.relpath(os.path.join(d, f), ROOT), m) for m in re.findall(r"-D(APD_\w+)", text) if m not in tuning and m not in lab]
+    assert not stray, "tools/ pass -D flags that neither apd_tuning.h defines nor apd_lab.h tests: %s" % stray

@@ -48,7 +48,7 @@ __device__ __forceinline__ ByteWindow no_byte_window()
 // stages columns 2 l and 2 l + 1, two window rows per load.
 __device__ __forceinline__ ByteWindow stage_byte_window(const FrameArgs &fa, const ViewConst &vc, uint32_t *win, bool ok, float cx, float cy)
 {
-    static_assert(kPair2 && kQuadShift == 2, "the byte window is staged from the 2-byte column pairs");
+    static_assert(kRowEntryShift == 1 && kQuadShift == 2, "the byte window is staged from the 2-byte column pairs");
     ByteWindow w = no_byte_window();
     const float big = 3.0e38f;
     const float x_lo = wave_min(ok ? cx : big), x_hi = wave_max(ok ? cx : -big);

@@ -137,7 +137,7 @@ def main():
                 allin = (inside | ~v).reshape(g * nwg, 512).all(-1).mean()
                 line += " %dx%d (%.0f KB): %.3f of the anchors, %.3f of the waves complete |" % (cw, ch, cw * ch / 1024.0, inside.sum() / v.sum(), allin)
             print(line)
-        # The lane = (pixel, hypothesis) mapping of round 6 (k910_update_weak, APD_K910_REMAP): a wave-level sub-patch tap is issued for the eight
+        # The lane = (pixel, hypothesis) mapping of round 6 (the propagation phase of k910_update_weak): a wave-level sub-patch tap is issued for the eight
         # pixels of a group x their eight hypotheses at ONE slot index.  Lanes with the same (anchor of the slot, anchor of the hypothesis) pair
         # read the same addresses (one L1 tag access for all of them).  How many distinct pairs per 64 lanes -- in K3's slot order (sorted by
         # plane-fit weight per pixel) and with every pixel walking its anchors in the order of their angle around it?
