@@ -28,7 +28,7 @@ hipError_t launch_mask_weak_info(const uint8_t *mask, uint8_t *weak, int n, hipS
 hipError_t launch_mask_count(const uint8_t *mask, int n, int *count, hipStream_t s);
 hipError_t launch_check_u8(const float *img, int n, int *flag, hipStream_t s);
 hipError_t launch_weak_index_map(const uint8_t *weak, size_t n, int *map, int *scratch, hipStream_t s);
-hipError_t launch_pack_quads(const float *img, int W, int H, quad_t *quad, hipStream_t s);
+hipError_t launch_pack_pairs(const float *img, int W, int H, quad_t *quad, hipStream_t s);
 hipError_t launch_pack_quads_tiled(const float *img, int W, int H, quad_t *quad, hipStream_t s);
 hipError_t launch_pack_fquads(const float *img, int W, int H, fquad_t *fq, hipStream_t s);
 }  // namespace apd
@@ -94,7 +94,7 @@ static hipError_t make_copy(DeviceImage &d, int W, int H, DeviceImage::Copy what
         return e;
     }
     switch (what) {
-    case DeviceImage::PAIRS: return apd::launch_pack_quads(d.img, W, H, d.pairs, s);
+    case DeviceImage::PAIRS: return apd::launch_pack_pairs(d.img, W, H, d.pairs, s);
     case DeviceImage::TILED: return apd::launch_pack_quads_tiled(d.img, W, H, d.tiled, s);
     default: return apd::launch_pack_fquads(d.img, W, H, d.fquads, s);
     }
@@ -617,7 +617,7 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
     for (int i = 0; i < num_images; ++i) {
         img[i] = &c->images[i];
     }
-    static const char *const pack_kernel[] = {"k_pack_quads", "k_pack_quads_tiled", "k_pack_fquads"};  // by DeviceImage::Copy
+    static const char *const pack_kernel[] = {"k_pack_pairs", "k_pack_quads_tiled", "k_pack_fquads"};  // by DeviceImage::Copy
     const DeviceImage::Copy passes[2] = {c->use_quads ? DeviceImage::PAIRS : DeviceImage::FQUADS, DeviceImage::TILED};
     for (int k = 0; k < (c->have_tiled ? 2 : 1); ++k) {  // every source's first copy, then every source's tiled one
         for (int i = 1; i < num_images; ++i) {

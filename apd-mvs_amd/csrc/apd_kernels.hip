@@ -52,46 +52,9 @@ __global__ __launch_bounds__(64) void k1_init_random_states(FrameArgs fa)
 // K5  RandomInitialization (APD.cu:806-835) with the initial costs of :616-693
 // ------------------------------------------------------------------------------------------------
 
-// Full-frame kernels (K5, K14, K15): a wave64 covers a (64 / APD_FF_ROWS) x APD_FF_ROWS block of pixels, four waves a
-// workgroup tile (same trade-off as APD_CB_ROWS in apd_sweep.h).
-constexpr int kFfWaveH = APD_FF_ROWS, kFfWaveW = 64 / kFfWaveH;
-constexpr int kFfWavesX = (kFfWaveH == 8) ? 2 : 1, kFfWavesY = 4 / kFfWavesX;
-constexpr int kFullTileW = kFfWaveW * kFfWavesX, kFullTileH = kFfWaveH * kFfWavesY;  // 16x16 (rows 8, 4) or 32x8 (rows 2)
-constexpr int kFullLdsW = kFullTileW + 2 * kPatchRadius, kFullLdsH = kFullTileH + 2 * kPatchRadius;
+// The full-frame tiling (full_frame_pixel, stage_full_frame_ref) is in apd_sweep.h; the window-less kernels pad the tile
+// rows to an odd pitch.
 constexpr int kFullPitch = kFullLdsW | 1;
-
-__device__ __forceinline__ void full_frame_pixel(int &px, int &py)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    px = blockIdx.x * kFullTileW + (wave % kFfWavesX) * kFfWaveW + lane % kFfWaveW;
-    py = blockIdx.y * kFullTileH + (wave / kFfWavesX) * kFfWaveH + lane / kFfWaveW;
-}
-
-// Stages the workgroup's reference tile + 5 px halo (clamp-to-edge) and returns this lane's patch accessor; the 36
-// texels stay in LDS, only their two moments live in registers.  Every thread of the block must call it.
-__device__ __forceinline__ RefPatchLds<kFullPitch> stage_full_frame_ref(const FrameArgs &fa, float *tile, int px, int py)
-{
-    const int x0 = blockIdx.x * kFullTileW - kPatchRadius, y0 = blockIdx.y * kFullTileH - kPatchRadius;
-    for (int idx = threadIdx.x; idx < kFullLdsW * kFullLdsH; idx += 256) {
-        const int r = idx / kFullLdsW, c = idx - r * kFullLdsW;
-        tile[r * kFullPitch + c] = fetch_texel(fa.ref_img, fa.W, fa.H, x0 + c, y0 + r);
-    }
-    __syncthreads();
-    RefPatchLds<kFullPitch> rp;
-    rp.base = &tile[(py - y0 - kPatchRadius) * kFullPitch + (px - x0 - kPatchRadius)];
-    RefPatch tmp;
-#pragma unroll
-    for (int i = 0; i < kPatchN; ++i) {
-#pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            tmp.v[i * kPatchN + j] = rp.at(i, j);
-        }
-    }
-    ref_patch_finish(tmp);
-    rp.mean = tmp.mean;
-    rp.var = tmp.var;
-    return rp;
-}
 
 // kTiled: the NCCs of the random planes (FIRST_INIT) gather from the tiled copy of the quad image
 template <bool kQuad, bool kTiled>
@@ -100,7 +63,7 @@ __global__ __launch_bounds__(256) void k5_random_initialization(FrameArgs fa)
     __shared__ float tile[kFullLdsH * kFullPitch];
     int px, py;
     full_frame_pixel(px, py);
-    const RefPatchLds<kFullPitch> rp = stage_full_frame_ref(fa, tile, px, py);
+    const RefPatchLds<kFullPitch> rp = stage_full_frame_ref<kFullPitch>(fa, tile, px, py);
     if (px >= fa.W || py >= fa.H) {
         return;
     }
@@ -176,59 +139,6 @@ __global__ __launch_bounds__(256) void k5_random_initialization(FrameArgs fa)
 // K6/K7  Black/RedPixelUpdateStrong -> CheckerboardPropagationStrong (APD.cu:982-1321, 837-890)
 // ------------------------------------------------------------------------------------------------
 
-// Cheapest candidate of propagation arm `arm` (order of APD.cu:1020: near/far x up,down,left,right).
-__device__ __forceinline__ bool arm_candidate(const FrameArgs &fa, int px, int py, int arm, int &pos)
-{
-    const int d = arm >> 1;
-    const int dx = (d == 2) ? -1 : (d == 3 ? 1 : 0);
-    const int dy = (d == 0) ? -1 : (d == 1 ? 1 : 0);
-    const float *__restrict__ costs = fa.costs;
-    const int W = fa.W;
-    if (arm & 1) {  // far: +-3, then ten more at stride 2 (:1021-1095)
-        if (!inside(fa, px + 3 * dx, py + 3 * dy)) {
-            return false;
-        }
-        int best = (px + 3 * dx) + (py + 3 * dy) * W;
-        float cmin = costs[best];
-        for (int i = 1; i < 11; ++i) {
-            const int qx = px + (3 + 2 * i) * dx, qy = py + (3 + 2 * i) * dy;
-            if (inside(fa, qx, qy)) {
-                const int q = qx + qy * W;
-                const float c = costs[q];
-                if (c < cmin) {
-                    cmin = c;
-                    best = q;
-                }
-            }
-        }
-        pos = best;
-        return true;
-    }
-    // near: +-1, then three V-shaped pairs, negative side first (:1097-1199)
-    if (!inside(fa, px + dx, py + dy)) {
-        return false;
-    }
-    const int ex = dy != 0 ? 1 : 0, ey = dx != 0 ? 1 : 0;
-    int best = (px + dx) + (py + dy) * W;
-    float cmin = costs[best];
-    for (int i = 0; i < 3; ++i) {
-        for (int sgn = -1; sgn <= 1; sgn += 2) {
-            const int qx = px + (2 + i) * dx + sgn * (1 + i) * ex;
-            const int qy = py + (2 + i) * dy + sgn * (1 + i) * ey;
-            if (inside(fa, qx, qy)) {
-                const int q = qx + qy * W;
-                const float c = costs[q];
-                if (c < cmin) {
-                    cmin = c;
-                    best = q;
-                }
-            }
-        }
-    }
-    pos = best;
-    return true;
-}
-
 // minimum waves per SIMD the register allocator must leave room for (ms per launch at 4096x3072 N=8 -- ref patch in registers:
 // 2: 32.0, 3: 28.3; ref patch in LDS: 3: 28.2, 4: 27.4)
 constexpr int kK67Waves = 4;
@@ -254,7 +164,7 @@ __global__ __launch_bounds__(256, kK67Waves) void k67_update_strong(FrameArgs fa
     if (fa.weak_info[center] == APD_WEAK || masked_out(fa, center)) {
         return;
     }
-    // the 36 reference texels stay in the LDS tile (one ds_read per sample); only their moments live in registers
+    // ref_patch_from_lds (apd_sweep.h), written out: through the helper this kernel's generated code changes
     RefPatchLds<kLdsPitch> rp;
     rp.base = &tile[t.ly * kLdsPitch + t.lx];
     {
@@ -497,35 +407,13 @@ __device__ __forceinline__ float disparity_sample_cost(const FrameArgs &fa, cons
     return acc;
 }
 
-// baseline + weight sum over the selected views (:2036-2044); no image access
-__device__ __forceinline__ int baseline_and_weight(const FrameArgs &fa, uint32_t sel, const ViewWeights<32> &vw, float &base_line, float &weight_normal)
-{
-    float bl = 0, wn = 0.0f;
-    int valid = 0;
-    for (int v = 0; v < fa.num_src; ++v) {
-        if (bit_test(sel, (unsigned)v)) {
-            const ViewConst &vc = view_const(fa, v);
-            wn += (float)vw.get(v);
-            const float d0 = fa.c[0] - vc.c[0];
-            const float d1 = fa.c[1] - vc.c[1];
-            const float d2 = fa.c[2] - vc.c[2];
-            const double tv = (double)(d0 * d0 + d1 * d1 + d2 * d2);
-            bl += sqrtf((float)tv);
-            valid++;
-        }
-    }
-    base_line = bl;
-    weight_normal = wn;
-    return valid;
-}
-
 template <bool kQuad>
 __global__ __launch_bounds__(256) void k14_depth_to_weak(FrameArgs fa)
 {
     __shared__ float tile[kFullLdsH * kFullPitch];
     int px, py;
     full_frame_pixel(px, py);
-    const RefPatchLds<kFullPitch> rp = stage_full_frame_ref(fa, tile, px, py);
+    const RefPatchLds<kFullPitch> rp = stage_full_frame_ref<kFullPitch>(fa, tile, px, py);
     if (px >= fa.W || py >= fa.H) {
         return;
     }
@@ -609,7 +497,7 @@ __global__ __launch_bounds__(256) void k15_local_refine(FrameArgs fa)
     __shared__ float tile[kFullLdsH * kFullPitch];
     int px, py;
     full_frame_pixel(px, py);
-    const RefPatchLds<kFullPitch> rp = stage_full_frame_ref(fa, tile, px, py);
+    const RefPatchLds<kFullPitch> rp = stage_full_frame_ref<kFullPitch>(fa, tile, px, py);
     if (px >= fa.W || py >= fa.H) {
         return;
     }
@@ -675,21 +563,6 @@ __global__ __launch_bounds__(256) void k_check_u8(const float *__restrict__ img,
     }
 }
 
-// Round 1's row-major 4-byte quads: entry (qx, qy) = {I(qx-1,qy-1), I(qx,qy-1), I(qx-1,qy), I(qx,qy)}, clamped.  No launcher
-// reaches this kernel: the column pairs below replaced the layout.  It stays in the code object until a change that is
-// allowed to alter the library's kernel symbol set removes it.
-__global__ __launch_bounds__(256) void k_pack_quads(const float *__restrict__ img, int W, int H, quad_t *__restrict__ quad)
-{
-    const int qx = blockIdx.x * 32 + (threadIdx.x & 31);  // 0..W  <-> image x = qx - 1
-    const int qy = blockIdx.y * 8 + (threadIdx.x >> 5);   // 0..H
-    if (qx > W || qy > H) {
-        return;
-    }
-    const uint32_t t00 = (uint32_t)fetch_texel(img, W, H, qx - 1, qy - 1), t10 = (uint32_t)fetch_texel(img, W, H, qx, qy - 1);
-    const uint32_t t01 = (uint32_t)fetch_texel(img, W, H, qx - 1, qy), t11 = (uint32_t)fetch_texel(img, W, H, qx, qy);
-    quad[(size_t)qy * (W + 1) + qx] = t00 | (t10 << 8) | (t01 << 16) | (t11 << 24);
-}
-
 // 2-byte column pairs (the row-major copy, apd_device.h): entry (t, u), t in [0, W + 1], u in [0, H], =
 // {I(t - 1, u - 1), I(t - 1, u)} with clamped coordinates
 __global__ __launch_bounds__(256) void k_pack_pairs(const float *__restrict__ img, int W, int H, uint16_t *__restrict__ pairs)
@@ -744,7 +617,7 @@ hipError_t launch_check_u8(const float *img, int n, int *flag, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_pack_quads(const float *img, int W, int H, quad_t *quad, hipStream_t s)
+hipError_t launch_pack_pairs(const float *img, int W, int H, quad_t *quad, hipStream_t s)
 {
     hipLaunchKernelGGL(k_pack_pairs, dim3((W + 2 + 31) / 32, (H + 1 + 7) / 8), dim3(256), 0, s, img, W, H, reinterpret_cast<uint16_t *>(quad));
     return hipGetLastError();
@@ -809,15 +682,7 @@ hipError_t launch_kernel(const FrameArgs &fa, int kernel_id, int iter, hipStream
         if (fa.k67_windows) {
             return launch_k67_windowed(fa, colour, iter, s);
         }
-        if (fa.num_src <= 8) {
-            launch_k67<8>(fa, colour, iter, s);
-        } else if (fa.num_src <= 12) {
-            launch_k67<12>(fa, colour, iter, s);
-        } else if (fa.num_src <= 16) {
-            launch_k67<16>(fa, colour, iter, s);
-        } else {
-            launch_k67<32>(fa, colour, iter, s);
-        }
+        with_view_capacity(fa.num_src, [&](auto nmax) { launch_k67<decltype(nmax)::value>(fa, colour, iter, s); });
         break;
     }
     case APD_K11_GET_DEPTH_NORMAL:

@@ -15,68 +15,15 @@
 
 namespace apd {
 
-constexpr int kFwTile = 16;                                // workgroup tile: 16x16 pixels, wave64 = 8x8
-constexpr int kFwLds = kFwTile + 2 * kPatchRadius;         // 26
+// The full-frame tiling of apd_sweep.h at its default: the lanes of a wave exchange work below as an 8x8 block of pixels.
+static_assert(kFullTileW == 16 && kFullTileH == 16 && kFfWaveW == 8, "the windowed K14/K15 need APD_FF_ROWS = 8");
+constexpr int kFwTile = kFullTileW;                        // workgroup tile: 16x16 pixels, wave64 = 8x8
+constexpr int kFwLds = kFullLdsW;                          // 26
 constexpr int kFwPitch = APD_FW_TILE_PITCH;                // 27
 constexpr int kFwWinPitch = APD_K1415_WIN_PITCH;
 static_assert(kFwWinPitch >= kWinW && kFwWinPitch <= 127, "window pitch: at least the wave width; two-address LDS reads need offset1 < 256 dwords");
 constexpr int kK14WinHF32 = 32;  // float windows: the rows of the 8-bit ones
 template <bool kQuad> constexpr int k14_win_h() { return kQuad ? APD_K14_WIN_H : kK14WinHF32; }
-
-__device__ __forceinline__ void fw_pixel(int &px, int &py)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    px = blockIdx.x * kFwTile + (wave & 1) * 8 + (lane & 7);
-    py = blockIdx.y * kFwTile + (wave >> 1) * 8 + (lane >> 3);
-}
-
-// Stages the workgroup's reference tile + 5 px halo (clamp-to-edge); the 36 texels of a lane's patch stay in LDS.
-__device__ __forceinline__ RefPatchLds<kFwPitch> fw_stage_ref(const FrameArgs &fa, float *tile, int px, int py)
-{
-    const int x0 = blockIdx.x * kFwTile - kPatchRadius, y0 = blockIdx.y * kFwTile - kPatchRadius;
-    for (int idx = threadIdx.x; idx < kFwLds * kFwLds; idx += 256) {
-        const int r = idx / kFwLds, c = idx - r * kFwLds;
-        tile[r * kFwPitch + c] = fetch_texel(fa.ref_img, fa.W, fa.H, x0 + c, y0 + r);
-    }
-    __syncthreads();
-    RefPatchLds<kFwPitch> rp;
-    rp.base = &tile[(py - y0 - kPatchRadius) * kFwPitch + (px - x0 - kPatchRadius)];
-    RefPatch tmp;
-#pragma unroll
-    for (int i = 0; i < kPatchN; ++i) {
-#pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            tmp.v[i * kPatchN + j] = rp.at(i, j);
-        }
-    }
-    ref_patch_finish(tmp);
-    rp.mean = tmp.mean;
-    rp.var = tmp.var;
-    return rp;
-}
-
-// baseline + weight sum over the selected views (:2036-2044); no image access
-__device__ __forceinline__ int fw_baseline_and_weight(const FrameArgs &fa, uint32_t sel, const ViewWeights<32> &vw, float &base_line,
-                                                      float &weight_normal)
-{
-    float bl = 0, wn = 0.0f;
-    int valid = 0;
-    for (int v = 0; v < fa.num_src; ++v) {
-        if (bit_test(sel, (unsigned)v)) {
-            const ViewConst &vc = view_const(fa, v);
-            wn += (float)vw.get(v);
-            const float d0 = fa.c[0] - vc.c[0];
-            const float d1 = fa.c[1] - vc.c[1];
-            const float d2 = fa.c[2] - vc.c[2];
-            const double tv = (double)(d0 * d0 + d1 * d1 + d2 * d2);
-            bl += sqrtf((float)tv);
-            valid++;
-        }
-    }
-    base_line = bl;
-    weight_normal = wn;
-    return valid;
-}
 
 // Window of view vc around where the pixels of the wave land when their planes are (origin normal, distance w).
 template <bool kQuad>
@@ -122,8 +69,8 @@ __global__ __launch_bounds__(256, kQuad ? APD_K14W_WAVES : APD_K1415W_WAVES_F32)
     __shared__ float tile[kFwLds * kFwPitch];
     __shared__ uint32_t windows[4][window_dwords(k14_win_h<kQuad>(), kFwWinPitch)];
     int px, py;
-    fw_pixel(px, py);
-    const RefPatchLds<kFwPitch> rp = fw_stage_ref(fa, tile, px, py);
+    full_frame_pixel(px, py);
+    const RefPatchLds<kFwPitch> rp = stage_full_frame_ref<kFwPitch>(fa, tile, px, py);
     uint32_t *win = windows[threadIdx.x >> 6];
     const int wave_id = threadIdx.x >> 6;
     const int W = fa.W, H = fa.H;
@@ -159,7 +106,7 @@ __global__ __launch_bounds__(256, kQuad ? APD_K14W_WAVES : APD_K1415W_WAVES_F32)
     if (alive) {
         sel = fa.selected_views[center];
         vw.load(fa, center);
-        const int valid = fw_baseline_and_weight(fa, sel, vw, base_line, weight_normal);
+        const int valid = baseline_and_weight(fa, sel, vw, base_line, weight_normal);
         if (valid == 0) {
             fa.weak_info[center] = APD_UNKNOWN;
             alive = false;
@@ -424,8 +371,8 @@ __global__ __launch_bounds__(256, kQuad ? kK15wWaves : APD_K1415W_WAVES_F32) voi
     __shared__ float tile[kFwLds * kFwPitch];
     __shared__ uint32_t windows[4][window_dwords(k14_win_h<kQuad>(), kFwWinPitch)];
     int px, py;
-    fw_pixel(px, py);
-    const RefPatchLds<kFwPitch> rp = fw_stage_ref(fa, tile, px, py);
+    full_frame_pixel(px, py);
+    const RefPatchLds<kFwPitch> rp = stage_full_frame_ref<kFwPitch>(fa, tile, px, py);
     uint32_t *win = windows[threadIdx.x >> 6];
     const int W = fa.W, H = fa.H;
     const int center = px + py * W;
@@ -450,7 +397,7 @@ __global__ __launch_bounds__(256, kQuad ? kK15wWaves : APD_K1415W_WAVES_F32) voi
         sel = fa.selected_views[center];
         vw.load(fa, center);
         float base_line;
-        const int valid = fw_baseline_and_weight(fa, sel, vw, base_line, weight_normal);
+        const int valid = baseline_and_weight(fa, sel, vw, base_line, weight_normal);
         if (weight_normal == 0 || valid == 0) {
             alive = false;
         } else {

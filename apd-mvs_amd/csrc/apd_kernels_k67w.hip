@@ -56,59 +56,6 @@ __device__ __forceinline__ SrcWindow stage_window(const FrameArgs &fa, const Vie
     return stage_window_around<kQuad, kWinH>(fa, vc, win, ok, cx, cy);
 }
 
-// Cheapest candidate of propagation arm `arm` (order of APD.cu:1020: near/far x up,down,left,right).
-__device__ __forceinline__ bool arm_pos(const FrameArgs &fa, int px, int py, int arm, int &pos)
-{
-    const int d = arm >> 1;
-    const int dx = (d == 2) ? -1 : (d == 3 ? 1 : 0);
-    const int dy = (d == 0) ? -1 : (d == 1 ? 1 : 0);
-    const float *__restrict__ costs = fa.costs;
-    const int W = fa.W;
-    if (arm & 1) {  // far: +-3, then ten more at stride 2 (:1021-1095)
-        if (!inside(fa, px + 3 * dx, py + 3 * dy)) {
-            return false;
-        }
-        int best = (px + 3 * dx) + (py + 3 * dy) * W;
-        float cmin = costs[best];
-        for (int i = 1; i < 11; ++i) {
-            const int qx = px + (3 + 2 * i) * dx, qy = py + (3 + 2 * i) * dy;
-            if (inside(fa, qx, qy)) {
-                const int q = qx + qy * W;
-                const float c = costs[q];
-                if (c < cmin) {
-                    cmin = c;
-                    best = q;
-                }
-            }
-        }
-        pos = best;
-        return true;
-    }
-    // near: +-1, then three V-shaped pairs, negative side first (:1097-1199)
-    if (!inside(fa, px + dx, py + dy)) {
-        return false;
-    }
-    const int ex = dy != 0 ? 1 : 0, ey = dx != 0 ? 1 : 0;
-    int best = (px + dx) + (py + dy) * W;
-    float cmin = costs[best];
-    for (int i = 0; i < 3; ++i) {
-        for (int sgn = -1; sgn <= 1; sgn += 2) {
-            const int qx = px + (2 + i) * dx + sgn * (1 + i) * ex;
-            const int qy = py + (2 + i) * dy + sgn * (1 + i) * ey;
-            if (inside(fa, qx, qy)) {
-                const int q = qx + qy * W;
-                const float c = costs[q];
-                if (c < cmin) {
-                    cmin = c;
-                    best = q;
-                }
-            }
-        }
-    }
-    pos = best;
-    return true;
-}
-
 constexpr float kTrustedCost = 0.5f;  // window placement: a plane that costs less is taken to be where the patch will stay
 constexpr int kWinFromIter = 1;  // first iteration of a FIRST_INIT pass that stages windows; configs[1] Mpix*iter/s: 0: 207, 1: 216
 
@@ -136,22 +83,7 @@ __global__ __launch_bounds__(256, kQuad ? APD_K67W_WAVES : APD_K67W_WAVES_F32) v
     if (__builtin_amdgcn_ballot_w64(alive) == 0) {
         return;
     }
-    // the 36 reference texels stay in the LDS tile (one ds_read per sample); only their moments live in registers
-    RefPatchLds<kLdsPitch> rp;
-    rp.base = &tile[t.ly * kLdsPitch + t.lx];
-    {
-        RefPatch tmp;
-#pragma unroll
-        for (int i = 0; i < kPatchN; ++i) {
-#pragma unroll
-            for (int j = 0; j < kPatchN; ++j) {
-                tmp.v[i * kPatchN + j] = rp.at(i, j);
-            }
-        }
-        ref_patch_finish(tmp);
-        rp.mean = tmp.mean;
-        rp.var = tmp.var;
-    }
+    const RefPatchLds<kLdsPitch> rp = ref_patch_from_lds<kLdsPitch>(&tile[t.ly * kLdsPitch + t.lx]);
 
     const int nsrc = fa.num_src;
     Rng rng = Rng{0, 0, 0, 0, 0, 0};
@@ -182,7 +114,7 @@ __global__ __launch_bounds__(256, kQuad ? APD_K67W_WAVES : APD_K67W_WAVES_F32) v
 #pragma unroll 1
         for (int h = 0; h < 8; ++h) {
             int pos = 0;
-            if (arm_pos(fa, px, py, h, pos)) {
+            if (arm_candidate(fa, px, py, h, pos)) {
                 flags |= 1u << h;
             }
             positions[h] = pos;
@@ -413,15 +345,9 @@ __global__ __launch_bounds__(256, kQuad ? APD_K67W_WAVES : APD_K67W_WAVES_F32) v
 template <bool kQuad, bool kTiled, bool kApprox>
 static void launch_k67w_n(const FrameArgs &fa, int tiles, int colour, int iter, hipStream_t s)
 {
-    if (fa.num_src <= 8) {
-        hipLaunchKernelGGL((k67w_update_strong<8, kQuad, kTiled, kApprox>), dim3(tiles), dim3(256), 0, s, fa, colour, iter);
-    } else if (fa.num_src <= 12) {  // ten sources is the common MVS count: do not pay scratch for sixteen columns
-        hipLaunchKernelGGL((k67w_update_strong<12, kQuad, kTiled, kApprox>), dim3(tiles), dim3(256), 0, s, fa, colour, iter);
-    } else if (fa.num_src <= 16) {
-        hipLaunchKernelGGL((k67w_update_strong<16, kQuad, kTiled, kApprox>), dim3(tiles), dim3(256), 0, s, fa, colour, iter);
-    } else {
-        hipLaunchKernelGGL((k67w_update_strong<32, kQuad, kTiled, kApprox>), dim3(tiles), dim3(256), 0, s, fa, colour, iter);
-    }
+    with_view_capacity(fa.num_src, [&](auto nmax) {
+        hipLaunchKernelGGL((k67w_update_strong<decltype(nmax)::value, kQuad, kTiled, kApprox>), dim3(tiles), dim3(256), 0, s, fa, colour, iter);
+    });
 }
 
 template <bool kQuad, bool kTiled>

@@ -1497,15 +1497,7 @@ hipError_t launch_weak_kernel(const FrameArgs &fa, int kernel_id, int iter, hipS
         if (!weak_list || !weak_list[colour]) {
             break;  // no prior state was uploaded: every pixel is STRONG (APD.cpp:541-547)
         }
-        if (fa.num_src <= 8) {
-            launch_k910<8>(fa, weak_list[colour], weak_count[colour], iter, s);
-        } else if (fa.num_src <= 12) {
-            launch_k910<12>(fa, weak_list[colour], weak_count[colour], iter, s);
-        } else if (fa.num_src <= 16) {
-            launch_k910<16>(fa, weak_list[colour], weak_count[colour], iter, s);
-        } else {
-            launch_k910<32>(fa, weak_list[colour], weak_count[colour], iter, s);
-        }
+        with_view_capacity(fa.num_src, [&](auto nmax) { launch_k910<decltype(nmax)::value>(fa, weak_list[colour], weak_count[colour], iter, s); });
         break;
     }
     default:

@@ -1,7 +1,10 @@
-// apd_sweep.h -- pieces shared by the strong and weak checkerboard kernels.
+// apd_sweep.h -- pieces shared by the strong and weak checkerboard kernels, by the two forms of K6/K7 (with LDS source
+// windows, apd_kernels_k67w.hip; without, apd_kernels.hip) and by the full-frame kernels K5, K14, K15 in both forms.
 #pragma once
 
 #include <float.h>
+
+#include <type_traits>
 
 #include "apd_device.h"
 
@@ -62,6 +65,27 @@ __device__ __forceinline__ bool checkerboard_active(const FrameArgs &fa, const T
 {
     // rows beyond half_rows are never visited by the reference's HALF launch (APD.cu:2402)
     return t.px < fa.W && t.py < fa.H && t.py < fa.half_rows;
+}
+
+// The 36 reference texels stay in the LDS tile (one ds_read per sample); only their moments live in registers.
+// `base` is the texel at offset (-radius, -radius) of the lane's pixel.
+template <int kPitch>
+__device__ __forceinline__ RefPatchLds<kPitch> ref_patch_from_lds(const float *base)
+{
+    RefPatchLds<kPitch> rp;
+    rp.base = base;
+    RefPatch tmp;
+#pragma unroll
+    for (int i = 0; i < kPatchN; ++i) {
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            tmp.v[i * kPatchN + j] = rp.at(i, j);
+        }
+    }
+    ref_patch_finish(tmp);
+    rp.mean = tmp.mean;
+    rp.var = tmp.var;
+    return rp;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -234,6 +258,136 @@ __device__ __forceinline__ void make_refinement_set(const FrameArgs &fa, int px,
     normals[2] = n_rand;
     normals[3] = n_pert;
     normals[4] = plane;
+}
+
+// ------------------------------------------------------------------------------------------------
+// K6/K7  Black/RedPixelUpdateStrong (APD.cu:982-1321): shared by the kernel with LDS source windows and the one without.
+// Their tile staging, decision block and commit are written out in each kernel: as a shared inlined function every form
+// tried changed the generated code of one of the two (profiles/shared_sweep/isa_identity.txt).
+// ------------------------------------------------------------------------------------------------
+
+// Cheapest candidate of propagation arm `arm` (order of APD.cu:1020: near/far x up,down,left,right).
+__device__ __forceinline__ bool arm_candidate(const FrameArgs &fa, int px, int py, int arm, int &pos)
+{
+    const int d = arm >> 1;
+    const int dx = (d == 2) ? -1 : (d == 3 ? 1 : 0);
+    const int dy = (d == 0) ? -1 : (d == 1 ? 1 : 0);
+    const float *__restrict__ costs = fa.costs;
+    const int W = fa.W;
+    if (arm & 1) {  // far: +-3, then ten more at stride 2 (:1021-1095)
+        if (!inside(fa, px + 3 * dx, py + 3 * dy)) {
+            return false;
+        }
+        int best = (px + 3 * dx) + (py + 3 * dy) * W;
+        float cmin = costs[best];
+        for (int i = 1; i < 11; ++i) {
+            const int qx = px + (3 + 2 * i) * dx, qy = py + (3 + 2 * i) * dy;
+            if (inside(fa, qx, qy)) {
+                const int q = qx + qy * W;
+                const float c = costs[q];
+                if (c < cmin) {
+                    cmin = c;
+                    best = q;
+                }
+            }
+        }
+        pos = best;
+        return true;
+    }
+    // near: +-1, then three V-shaped pairs, negative side first (:1097-1199)
+    if (!inside(fa, px + dx, py + dy)) {
+        return false;
+    }
+    const int ex = dy != 0 ? 1 : 0, ey = dx != 0 ? 1 : 0;
+    int best = (px + dx) + (py + dy) * W;
+    float cmin = costs[best];
+    for (int i = 0; i < 3; ++i) {
+        for (int sgn = -1; sgn <= 1; sgn += 2) {
+            const int qx = px + (2 + i) * dx + sgn * (1 + i) * ex;
+            const int qy = py + (2 + i) * dy + sgn * (1 + i) * ey;
+            if (inside(fa, qx, qy)) {
+                const int q = qx + qy * W;
+                const float c = costs[q];
+                if (c < cmin) {
+                    cmin = c;
+                    best = q;
+                }
+            }
+        }
+    }
+    pos = best;
+    return true;
+}
+
+// The kernels that keep a per-pixel table over the views are compiled for NMAX = 8, 12, 16 and 32 columns: calls
+// f(std::integral_constant<int, NMAX>) with the smallest that holds num_src.  Ten sources is the common MVS count: it
+// does not pay scratch for sixteen columns.
+template <typename F>
+static inline void with_view_capacity(int num_src, F &&f)
+{
+    if (num_src <= 8) {
+        f(std::integral_constant<int, 8>());
+    } else if (num_src <= 12) {
+        f(std::integral_constant<int, 12>());
+    } else if (num_src <= 16) {
+        f(std::integral_constant<int, 16>());
+    } else {
+        f(std::integral_constant<int, 32>());
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// full-frame kernels (K5, K14, K15; K14 and K15 with and without LDS source windows)
+// ------------------------------------------------------------------------------------------------
+
+// A wave64 covers a (64 / APD_FF_ROWS) x APD_FF_ROWS block of pixels, four waves a workgroup tile (same trade-off as
+// APD_CB_ROWS above).
+constexpr int kFfWaveH = APD_FF_ROWS, kFfWaveW = 64 / kFfWaveH;
+constexpr int kFfWavesX = (kFfWaveH == 8) ? 2 : 1, kFfWavesY = 4 / kFfWavesX;
+constexpr int kFullTileW = kFfWaveW * kFfWavesX, kFullTileH = kFfWaveH * kFfWavesY;  // 16x16 (rows 8, 4) or 32x8 (rows 2)
+constexpr int kFullLdsW = kFullTileW + 2 * kPatchRadius, kFullLdsH = kFullTileH + 2 * kPatchRadius;
+
+__device__ __forceinline__ void full_frame_pixel(int &px, int &py)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    px = blockIdx.x * kFullTileW + (wave % kFfWavesX) * kFfWaveW + lane % kFfWaveW;
+    py = blockIdx.y * kFullTileH + (wave / kFfWavesX) * kFfWaveH + lane / kFfWaveW;
+}
+
+// Stages the workgroup's reference tile + 5 px halo (clamp-to-edge) at kPitch floats per row and returns this lane's patch
+// accessor.  Every thread of the block must call it.
+template <int kPitch>
+__device__ __forceinline__ RefPatchLds<kPitch> stage_full_frame_ref(const FrameArgs &fa, float *tile, int px, int py)
+{
+    const int x0 = blockIdx.x * kFullTileW - kPatchRadius, y0 = blockIdx.y * kFullTileH - kPatchRadius;
+    for (int idx = threadIdx.x; idx < kFullLdsW * kFullLdsH; idx += 256) {
+        const int r = idx / kFullLdsW, c = idx - r * kFullLdsW;
+        tile[r * kPitch + c] = fetch_texel(fa.ref_img, fa.W, fa.H, x0 + c, y0 + r);
+    }
+    __syncthreads();
+    return ref_patch_from_lds<kPitch>(&tile[(py - y0 - kPatchRadius) * kPitch + (px - x0 - kPatchRadius)]);
+}
+
+// baseline + weight sum over the selected views (:2036-2044); no image access
+__device__ __forceinline__ int baseline_and_weight(const FrameArgs &fa, uint32_t sel, const ViewWeights<32> &vw, float &base_line, float &weight_normal)
+{
+    float bl = 0, wn = 0.0f;
+    int valid = 0;
+    for (int v = 0; v < fa.num_src; ++v) {
+        if (bit_test(sel, (unsigned)v)) {
+            const ViewConst &vc = view_const(fa, v);
+            wn += (float)vw.get(v);
+            const float d0 = fa.c[0] - vc.c[0];
+            const float d1 = fa.c[1] - vc.c[1];
+            const float d2 = fa.c[2] - vc.c[2];
+            const double tv = (double)(d0 * d0 + d1 * d1 + d2 * d2);
+            bl += sqrtf((float)tv);
+            valid++;
+        }
+    }
+    base_line = bl;
+    weight_normal = wn;
+    return valid;
 }
 
 }  // namespace apd

@@ -17,10 +17,8 @@
 #ifndef APD_CB_ROWS
 #define APD_CB_ROWS 4  // pixel rows of a wave's checkerboard footprint (profiles/r01/tuning/tune_rows.txt)
 #endif
-
-// ---- apd_kernels.hip ----
 #ifndef APD_FF_ROWS
-#define APD_FF_ROWS 8  // pixel rows of a wave's block in the full-frame kernels (profiles/r01/tuning/tune_rows.txt)
+#define APD_FF_ROWS 8  // pixel rows of a wave's block in the full-frame kernels (profiles/r01/tuning/tune_rows.txt); the windowed K14/K15 need 8
 #endif
 
 // ---- apd_kernels_k67w.hip ----

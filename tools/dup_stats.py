@@ -4,7 +4,7 @@ regions share planes exactly and K6/K7 scores the same (plane, view) several tim
 
 Measured from the state the kernel itself sees: before the black launch of iteration i for black pixels, between the black and
 the red launch for red pixels.  The arm search is restated with torch on the GPU (strict `<`, first minimum wins, exactly
-arm_pos() of csrc/apd_kernels_k67w.hip); nothing in the library is instrumented.
+arm_candidate() of csrc/apd_sweep.h); nothing in the library is instrumented.
 
 Prints per (iteration, colour): the mean number of DISTINCT hypotheses per pixel, the histogram, and the mean over wave
 footprints (32 x 4 px, the 64 same-colour pixels one wave64 owns) of the per-wave MAXIMUM -- the trip count a wave would
