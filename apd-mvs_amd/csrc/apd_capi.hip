@@ -442,6 +442,13 @@ static int create_buffers(apd_context *c, int width, int height, const apd_param
     return APD_OK;
 }
 
+// The derived float-quad copy of a source has (W + 1) x (H + 1) entries of 16 bytes and the kernels form its byte offsets in 32
+// bits (fquad_byte_offset): the whole image must stay below 2^32 bytes.  Every other per-image copy is smaller.
+static bool frame_area_supported(int width, int height)
+{
+    return ((uint64_t)width + 1u) * ((uint64_t)height + 1u) * 16u < (1ull << 32);
+}
+
 int apd_create(apd_handle *out, int device, int width, int height, const apd_params *params)
 {
     if (!out || !params || width <= 0 || height <= 0) {
@@ -449,6 +456,9 @@ int apd_create(apd_handle *out, int device, int width, int height, const apd_par
     }
     if (width > 16384 || height > 16384) {  // pixel coordinates travel as short2 and through 24-bit multiply-adds
         return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_create: image larger than 16384 x 16384 px");
+    }
+    if (!frame_area_supported(width, height)) {
+        return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_create: a float-quad image of %d x %d px passes 2^32 bytes (32-bit byte offsets)", width, height);
     }
     if (params->strong_radius != 5 || params->strong_increment != 2 || params->weak_radius != 5 || params->weak_increment != 5) {
         // the reference never changes these (main.h:84-87); the kernels are specialised for them
@@ -689,7 +699,7 @@ static int image_ensure(apd_image *im, DeviceImage::Copy what, hipStream_t s)
 
 int apd_image_create(apd_image_t *out, int device, int width, int height, const float *pixels)
 {
-    if (!out || !pixels || width <= 0 || height <= 0 || width > 16384 || height > 16384) {
+    if (!out || !pixels || width <= 0 || height <= 0 || width > 16384 || height > 16384 || !frame_area_supported(width, height)) {
         return set_error(g_last_error, APD_ERR_INVALID, "apd_image_create: bad argument");
     }
     if (device >= 0) {

@@ -120,7 +120,9 @@ void apd_default_params(apd_params *p);
 /* APD::APD(const Problem&) (APD.cpp:356-359) + the allocations of CudaSpaceInitialization
  * (APD.cpp:636-666).  `device` < 0 keeps the current device (reference: cudaSetDevice, main.cpp:153).
  * Limits (APD_ERR_UNSUPPORTED otherwise): width, height <= 16384 (16-bit neighbour coordinates, 24-bit index
- * arithmetic); patch geometry strong 5/2, weak 5/5. */
+ * arithmetic) and (width + 1) * (height + 1) * 16 < 2^32 (32-bit byte offsets into the float texel-quad copy of a source:
+ * 16384 x 16382 is the largest frame with a 16384-px axis); patch geometry strong 5/2, weak 5/5.  Non-positive sizes are
+ * APD_ERR_INVALID.  No handle is returned on failure. */
 int apd_create(apd_handle *out, int device, int width, int height, const apd_params *params);
 
 /* ~APD (APD.cpp:361-397). */
@@ -162,6 +164,7 @@ int apd_run_after_depths(apd_handle h);
  * apd_upload_views_shared == apd_upload_views_split without the copies (images[0] the reference view; every image of the handle's
  * size and on its device; in a geometric pass the depth maps follow with apd_upload_depths).  An image may serve any number of
  * handles on any threads at once and must outlive the passes that use it.  Same bits as the copying uploads. */
+/* apd_image_create returns APD_ERR_INVALID for every size no handle can have (non-positive, or outside apd_create's limits). */
 typedef struct apd_image *apd_image_t;
 int apd_image_create(apd_image_t *out, int device, int width, int height, const float *pixels);
 int apd_image_destroy(apd_image_t image);

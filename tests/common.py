@@ -103,9 +103,21 @@ def load_into_oracle(o, snap):
             getattr(o, oa)[...] = snap[name]
 
 
-def assert_windows_equal(o, snap, windows, where, weak_before=None):
+def canon_nan(a):
+    """Raw words with every NaN mapped to one pattern: a float word that is NaN on BOTH sides compares equal whatever its sign and
+    payload (x86 and gfx950 differ in those of generated NaNs); a NaN on one side only still differs."""
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.float32:
+        w = a.view(np.uint32).copy()
+        w[np.isnan(a)] = 0x7FC00000
+        return w.view(np.uint8)
+    return a.view(np.uint8)
+
+
+def assert_windows_equal(o, snap, windows, where, weak_before=None, bits=bits):
     """HIP snapshot vs oracle, bit for bit, on every window (x0, y0, x1, y1).  The neighbour table is indexed by WEAK pixel:
-    its rows are compared for the pixels of the window that were WEAK when the table was allocated (`weak_before`)."""
+    its rows are compared for the pixels of the window that were WEAK when the table was allocated (`weak_before`).
+    `bits`: the byte view compared (default: the raw bytes; canon_nan: NaN on both sides equal)."""
     nmap = o.neighbours_map
     for (x0, y0, x1, y1) in windows:
         for name, _, oa in ORACLE_STATES:
@@ -124,7 +136,7 @@ def assert_windows_equal(o, snap, windows, where, weak_before=None):
                 raise AssertionError("%s: HIP and oracle differ in `%s` on window %s (%d bytes)" % (where, name, (x0, y0, x1, y1), int(diff)))
 
 
-def fullsize_lockstep(pkg, h, o, schedule, windows, label, log=None):
+def fullsize_lockstep(pkg, h, o, schedule, windows, label, log=None, bits=bits):
     """The HIP path runs every kernel of `schedule` over the whole image; the oracle runs the same kernel on the windows
     only, from the HIP path's own pre-kernel state (copied in once per kernel), and the windows are compared bit for bit
     after every kernel.  Launches never read what they write (red/black colouring), so a window's result does not depend on
@@ -153,7 +165,7 @@ def fullsize_lockstep(pkg, h, o, schedule, windows, label, log=None):
         o.set_roi()
         t2 = time.perf_counter()
         snap = download_all(pkg, h)
-        assert_windows_equal(o, snap, windows, "%s after K%d(iter %d)" % (label, kid, it), weak_alloc)
+        assert_windows_equal(o, snap, windows, "%s after K%d(iter %d)" % (label, kid, it), weak_alloc, bits)
         load_into_oracle(o, snap)
         compared += 1
         if log is not None:

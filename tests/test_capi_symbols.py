@@ -111,3 +111,15 @@ def test_library_carries_the_digest_of_the_trees_sources(pkg, tmp_path):
 
     with pytest.raises(pkg.ApdError, match="stale HIP library"):
         pkg.check_build_id(Stale())
+
+
+@pytest.mark.parametrize("W,H,status", [(16385, 1, -5), (1, 16385, -5), (0, 8, -1), (8, -1, -1), (16384, 16384, -5), (16383, 16383, -5)])
+def test_frame_sizes_are_refused_before_any_device_call(pkg, W, H, status):
+    """apd_create's size limits (include/apd_mi355x.h) are argument checks: they answer without a device, return no handle and
+    leave a message.  (W + 1) * (H + 1) * 16 must stay below 2^32: 16385^2 * 16 and 16384^2 * 16 do not."""
+    L = pkg.lib()
+    out = C.c_void_p()
+    params = pkg.default_params()
+    assert L.apd_create(C.byref(out), 0, W, H, C.byref(params)) == status
+    assert out.value is None and b"apd_create" in L.apd_last_error()
+    assert ((W + 1) * (H + 1) * 16 >= 2 ** 32) == (W <= 16384 and H <= 16384 and status == -5)
