@@ -443,7 +443,7 @@ static int create_buffers(apd_context *c, int width, int height, const apd_param
 }
 
 // The derived float-quad copy of a source has (W + 1) x (H + 1) entries of 16 bytes and the kernels form its byte offsets in 32
-// bits (fquad_byte_offset): the whole image must stay below 2^32 bytes.  Every other per-image copy is smaller.
+// bits (entry_byte_offset): the whole image must stay below 2^32 bytes.  Every other per-image copy is smaller.
 static bool frame_area_supported(int width, int height)
 {
     return ((uint64_t)width + 1u) * ((uint64_t)height + 1u) * 16u < (1ull << 32);

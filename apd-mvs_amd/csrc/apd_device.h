@@ -241,6 +241,24 @@ __device__ __forceinline__ float ncc_cost_from_moments(float var_r, float var_s,
     return fmaxf(0.0f, fminf(2.0f, 1.0f - div_rn_mid(covar, denom)));
 }
 
+// The whole tail from the three source-side sums of an N-sample patch (inv_w = 1 / N): scale them, form the source variance,
+// return 2 for a flat patch, else the cost.  kRefTested: the caller has returned 2 for var_r < kMinVar before it sampled (the
+// fixed patch); the reference tests both variances here, which gives the same result.
+constexpr float kMinVar = 1e-5f;
+template <bool kRefTested>
+__device__ __forceinline__ float ncc_cost_from_sums(float mean_r, float var_r, float sum_s, float sum_ss, float sum_rs, float inv_w)
+{
+    sum_s *= inv_w;
+    sum_ss *= inv_w;
+    sum_rs *= inv_w;
+    const float var_s = fmaf(-sum_s, sum_s, sum_ss);
+    if ((!kRefTested && var_r < kMinVar) || var_s < kMinVar) {
+        return 2.0f;
+    }
+    const float covar = fmaf(-mean_r, sum_s, sum_rs);
+    return ncc_cost_from_moments(var_r, var_s, covar);
+}
+
 // ------------------------------------------------------------------------------------------------
 // XORWOW (contract C8): state kept in six registers; AoS of 6 words per pixel in HBM
 // ------------------------------------------------------------------------------------------------
@@ -527,7 +545,7 @@ __device__ __forceinline__ fquad_t fquad_fetch(global_fquad_ptr fq, unsigned off
 // sample_bilinear on 8-bit data (the taps are the same floats, the lerp is the same three fmaf).
 // A NaN/Inf coordinate gives a NaN weight, so the sample is NaN whatever texel is read and the index clamp only
 // has to keep the address in range.  Fetch and interpolation are separate so a caller can put several gathers
-// in flight before consuming the first one (quad_row_issue / quad_row_lerp, subpatch_cost_quad).
+// in flight before consuming the first one (row_issue / row_lerp, subpatch_issue / subpatch_finish).
 typedef quad_t quad_unaligned_t __attribute__((aligned(2)));
 __device__ __forceinline__ quad_t quad_fetch(global_quad_ptr quad, unsigned off)
 {
@@ -545,7 +563,7 @@ __device__ __forceinline__ float lerp_f16_pair(float a, uint32_t p)
 
 __device__ __forceinline__ float quad_lerp(quad_t t, float a, float b)
 {
-    float t00, t10, t01, t11;  // four v_cvt_f32_ubyte<k>; the differences below stay binary32 subtractions (see quad_row_lerp)
+    float t00, t10, t01, t11;  // four v_cvt_f32_ubyte<k>; the differences below stay binary32 subtractions (see TexelFormat::row_lerp)
     asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t00) : "v"(t));
     asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(t11) : "v"(t));
     asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t01) : "v"(t));
@@ -620,13 +638,14 @@ __device__ __forceinline__ unsigned quad_tiled_byte_offset(int qx, int qy, unsig
     return quad_tiled_offset_tu((unsigned)(qx + 1), (unsigned)(qy + 1), tiles_x);
 }
 
-// byte offset of quad entry (qx, qy), qx in [-1, W-1], qy in [-1, H-1]: qy*pitch + (pitch + entry) + entry*qx with
-// pitch = (W+1)*entry bytes, two instructions
-__device__ __forceinline__ unsigned quad_byte_offset(int qx, int qy, int pitch, int origin)
+// byte offset of entry (qx, qy), qx in [-1, W-1], qy in [-1, H-1], of a row-major image with (1 << kShift)-byte entries:
+// qy*pitch + origin + (qx << kShift) with origin = pitch + one entry (entry (-1, -1) is at byte 0), two instructions
+template <int kShift>
+__device__ __forceinline__ unsigned entry_byte_offset(int qx, int qy, int pitch, int origin)
 {
     int row, off;
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(row) : "v"(qy), "v"(pitch), "v"(origin));
-    asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(off) : "v"(qx), "v"(row), "n"(kRowEntryShift));
+    asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(off) : "v"(qx), "v"(row), "n"(kShift));
     return (unsigned)off;
 }
 
@@ -697,233 +716,211 @@ __device__ __forceinline__ void ref_patch_from_global(RefPatch &rp, const float 
 // allowed to re-serialise the chains to save registers.
 #define APD_STAGE() __builtin_amdgcn_sched_barrier(0)
 
-// byte offset of a 16-byte float quad entry (qx, qy): qy*pitch + (pitch + 16) + 16*qx with pitch = (W+1)*16 bytes
-__device__ __forceinline__ unsigned fquad_byte_offset(int qx, int qy, int pitch, int origin)
-{
-    int row, off;
-    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(row) : "v"(qy), "v"(pitch), "v"(origin));
-    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"(qx), "v"(row));
-    return (unsigned)off;
-}
-
-// Sample positions of one patch row (fixed x, six y) -> bilinear weights + texel-quad gathers in flight.
 // Reciprocal of the sample loops: kRecipIeee -- IEEE division (any denominator); kRecipExact -- v_rcp_f32 + one Newton step,
 // the correctly rounded reciprocal on the range denominators_fast() checks (the default path); kRecipApprox -- the bare
 // v_rcp_f32 (<= 1 ulp), what the reference's own --use_fast_math build does (CMakeLists.txt:20): the optional tolerance
 // mode APD_OPT_FAST_RCP, NOT bit-identical to the oracle (tests/test_gpu_fast_rcp.py states what it keeps).
 enum { kRecipIeee = 0, kRecipExact = 1, kRecipApprox = 2 };
 
-template <int kRecip, bool kTiled = false>
-__device__ __forceinline__ void quad_row_issue(const Homography &H, float bx, float by, float bz, const float (&yf)[kPatchN],
-                                               global_quad_ptr srcq, unsigned pitch, int wm1, int hm1,
-                                               float (&a)[kPatchN], float (&b)[kPatchN], quad_t (&t)[kPatchN])
+// Bilinear tap positions of N samples in lock step (contract C2 / C3 / C7), whatever the image format: the caller has filled
+// the denominators z and the numerators X, Y (six samples of a patch row, nine of a 3 x 3 sub-patch); out come the weights
+// a, b and the clamped integer coordinates (qx, qy) of the entry that holds the four taps.  Ends with the clamp: the barrier
+// behind it opens taps_fetch.
+template <int N, int kRecip>
+__device__ __forceinline__ void tap_positions(float (&z)[N], float (&X)[N], float (&Y)[N], int wm1, int hm1, float (&a)[N],
+                                              float (&b)[N], int (&qx)[N], int (&qy)[N])
 {
-    float z[kPatchN], X[kPatchN], Y[kPatchN], r[kPatchN];
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        z[j] = fmaf(H.h[7], yf[j], bz);
-        X[j] = fmaf(H.h[1], yf[j], bx);
-        Y[j] = fmaf(H.h[4], yf[j], by);
-    }
+    float r[N];
     APD_STAGE();
-    if (kRecip == kRecipApprox) {
+    if constexpr (kRecip == kRecipApprox) {
 #pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            r[j] = __builtin_amdgcn_rcpf(z[j]);
+        for (int k = 0; k < N; ++k) {
+            r[k] = __builtin_amdgcn_rcpf(z[k]);
         }
-    } else if (kRecip == kRecipExact) {
+    } else if constexpr (kRecip == kRecipExact) {
 #pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            r[j] = __builtin_amdgcn_rcpf(z[j]);
-        }
-        APD_STAGE();
-#pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            z[j] = fmaf(-z[j], r[j], 1.0f);
+        for (int k = 0; k < N; ++k) {
+            r[k] = __builtin_amdgcn_rcpf(z[k]);
         }
         APD_STAGE();
 #pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            r[j] = fmaf(z[j], r[j], r[j]);
+        for (int k = 0; k < N; ++k) {
+            z[k] = fmaf(-z[k], r[k], 1.0f);
+        }
+        APD_STAGE();
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            r[k] = fmaf(z[k], r[k], r[k]);
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            r[j] = 1.0f / z[j];
+        for (int k = 0; k < N; ++k) {
+            r[k] = 1.0f / z[k];
         }
     }
     APD_STAGE();
 #pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        X[j] *= r[j];
-        Y[j] *= r[j];
-    }
-    APD_STAGE();
-    int qx[kPatchN], qy[kPatchN];
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        a[j] = __builtin_amdgcn_fractf(X[j]);
-        b[j] = __builtin_amdgcn_fractf(Y[j]);
-        qx[j] = cvt_floor_i32(X[j]);
-        qy[j] = cvt_floor_i32(Y[j]);
+    for (int k = 0; k < N; ++k) {
+        X[k] *= r[k];
+        Y[k] *= r[k];
     }
     APD_STAGE();
 #pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        qx[j] = med3_i32(qx[j], -1, wm1);
-        qy[j] = med3_i32(qy[j], -1, hm1);
+    for (int k = 0; k < N; ++k) {
+        a[k] = __builtin_amdgcn_fractf(X[k]);
+        b[k] = __builtin_amdgcn_fractf(Y[k]);
+        qx[k] = cvt_floor_i32(X[k]);
+        qy[k] = cvt_floor_i32(Y[k]);
     }
     APD_STAGE();
 #pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
+    for (int k = 0; k < N; ++k) {
+        qx[k] = med3_i32(qx[k], -1, wm1);
+        qy[k] = med3_i32(qy[k], -1, hm1);
+    }
+}
+
+// The two source image formats of the global-memory path, as the sample loops see them.  kQuad: the 8-bit column-pair image
+// (row-major, or tiled with kTiled), one dword per bilinear fetch; otherwise the float texel-quad image, 16 bytes per fetch.
+template <bool kQuad, bool kTiled = false>
+struct TexelFormat;
+
+template <bool kTiled>
+struct TexelFormat<true, kTiled> {
+    typedef global_quad_ptr ptr_t;
+    typedef quad_t tap_t;
+    static __device__ __forceinline__ ptr_t image(const ViewConst &vc) { return (ptr_t)(kTiled ? vc.quad_tiled : vc.quad); }
+    // bytes per row, or tiles per tile row of the tiled copy
+    static __device__ __forceinline__ unsigned pitch(int W) { return kTiled ? quad_tiles_x(W) : quad_row_pitch_bytes(W); }
+    static __device__ __forceinline__ unsigned byte_offset(int qx, int qy, unsigned pitch)
+    {
         if constexpr (kTiled) {
-            qx[j] = (int)quad_tiled_byte_offset(qx[j], qy[j], pitch);  // `pitch` = tiles per tile row here
+            return quad_tiled_byte_offset(qx, qy, pitch);
         } else {
-            qx[j] = (int)quad_byte_offset(qx[j], qy[j], (int)pitch, (int)(pitch + kRowEntryBytes));
+            return entry_byte_offset<kRowEntryShift>(qx, qy, (int)pitch, (int)(pitch + kRowEntryBytes));
         }
     }
+    static __device__ __forceinline__ tap_t fetch(ptr_t img, unsigned off) { return quad_fetch(img, off); }
+    static __device__ __forceinline__ float lerp(tap_t t, float a, float b) { return quad_lerp(t, a, b); }
+    // six taps in lock step (same three fmaf per sample as lerp)
+    static __device__ __forceinline__ void row_lerp(const tap_t (&t)[kPatchN], const float (&a)[kPatchN], const float (&b)[kPatchN],
+                                                    float (&v)[kPatchN])
+    {
+        float t00[kPatchN], t01[kPatchN];
+        // byte k -> float with v_cvt_f32_ubyte<k> (4 cycles), the two differences as binary32 subtractions (2 cycles): left to
+        // itself the compiler subtracts the bytes as integers (SDWA) and converts the difference, two 4-cycle instructions each
+        float d0[kPatchN], d1[kPatchN];
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t00[j]) : "v"(t[j]));
+            asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(d1[j]) : "v"(t[j]));
+            asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t01[j]) : "v"(t[j]));
+            asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(d0[j]) : "v"(t[j]));
+        }
+        APD_STAGE();
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            d0[j] -= t00[j];
+            d1[j] -= t01[j];
+        }
+        APD_STAGE();
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            t00[j] = fmaf(a[j], d0[j], t00[j]);
+            t01[j] = fmaf(a[j], d1[j], t01[j]);
+        }
+        APD_STAGE();
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            t01[j] -= t00[j];
+        }
+        APD_STAGE();
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            v[j] = fmaf(b[j], t01[j], t00[j]);
+        }
+    }
+};
+
+template <bool kTiled>
+struct TexelFormat<false, kTiled> {  // there is no tiled copy of the float image
+    typedef global_fquad_ptr ptr_t;
+    typedef fquad_t tap_t;
+    static constexpr int kEntryShift = 4;
+    static __device__ __forceinline__ ptr_t image(const ViewConst &vc) { return (ptr_t)vc.fquad; }
+    static __device__ __forceinline__ unsigned pitch(int W) { return (unsigned)(W + 1) << kEntryShift; }
+    static __device__ __forceinline__ unsigned byte_offset(int qx, int qy, unsigned pitch)
+    {
+        return entry_byte_offset<kEntryShift>(qx, qy, (int)pitch, (int)(pitch + (1u << kEntryShift)));
+    }
+    static __device__ __forceinline__ tap_t fetch(ptr_t img, unsigned off) { return fquad_fetch(img, off); }
+    static __device__ __forceinline__ float lerp(tap_t t, float a, float b)
+    {
+        const float top = fmaf(a, t.y, t.x);
+        const float bot = fmaf(a, t.w, t.z);
+        return fmaf(b, bot - top, top);
+    }
+    static __device__ __forceinline__ void row_lerp(const tap_t (&t)[kPatchN], const float (&a)[kPatchN], const float (&b)[kPatchN],
+                                                    float (&v)[kPatchN])
+    {
+        float top[kPatchN], bot[kPatchN];
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            top[j] = fmaf(a[j], t[j].y, t[j].x);
+            bot[j] = fmaf(a[j], t[j].w, t[j].z);
+        }
+        APD_STAGE();
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            bot[j] -= top[j];
+        }
+        APD_STAGE();
+#pragma unroll
+        for (int j = 0; j < kPatchN; ++j) {
+            v[j] = fmaf(b[j], bot[j], top[j]);
+        }
+    }
+};
+
+// Last two stages of an issue: byte offsets of the N entries, then the N gathers in flight.
+template <typename Fmt, int N>
+__device__ __forceinline__ void taps_fetch(typename Fmt::ptr_t img, unsigned pitch, int (&qx)[N], const int (&qy)[N],
+                                           typename Fmt::tap_t (&t)[N])
+{
     APD_STAGE();
 #pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        t[j] = quad_fetch(srcq, (unsigned)qx[j]);
+    for (int k = 0; k < N; ++k) {
+        qx[k] = (int)Fmt::byte_offset(qx[k], qy[k], pitch);
+    }
+    APD_STAGE();
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        t[k] = Fmt::fetch(img, (unsigned)qx[k]);
     }
 }
 
-// Gathered quads + weights of one row -> six bilinear values (same three fmaf per sample as quad_lerp).
-__device__ __forceinline__ void quad_row_lerp(const quad_t (&t)[kPatchN], const float (&a)[kPatchN], const float (&b)[kPatchN],
-                                              float (&v)[kPatchN])
+// Sample positions of one patch row (fixed x, six y) -> bilinear weights + gathers in flight.  Fetch and interpolation are
+// separate so that a caller can put the gathers of the next rows in flight before it consumes this one.
+template <bool kQuad, int kRecip, bool kTiled = false>
+__device__ __forceinline__ void row_issue(const Homography &H, float bx, float by, float bz, const float (&yf)[kPatchN],
+                                          typename TexelFormat<kQuad, kTiled>::ptr_t img, unsigned pitch, int wm1, int hm1,
+                                          float (&a)[kPatchN], float (&b)[kPatchN],
+                                          typename TexelFormat<kQuad, kTiled>::tap_t (&t)[kPatchN])
 {
-    float t00[kPatchN], t01[kPatchN];
-    // byte k -> float with v_cvt_f32_ubyte<k> (4 cycles), the two differences as binary32 subtractions (2 cycles): left to
-    // itself the compiler subtracts the bytes as integers (SDWA) and converts the difference, two 4-cycle instructions each
-    float d0[kPatchN], d1[kPatchN];
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t00[j]) : "v"(t[j]));
-        asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(d1[j]) : "v"(t[j]));
-        asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t01[j]) : "v"(t[j]));
-        asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(d0[j]) : "v"(t[j]));
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        d0[j] -= t00[j];
-        d1[j] -= t01[j];
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        t00[j] = fmaf(a[j], d0[j], t00[j]);
-        t01[j] = fmaf(a[j], d1[j], t01[j]);
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        t01[j] -= t00[j];
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        v[j] = fmaf(b[j], t01[j], t00[j]);
-    }
-}
-
-// The same two stages for float texel-quad images (float grey values).
-template <int kRecip>
-__device__ __forceinline__ void fquad_row_issue(const Homography &H, float bx, float by, float bz, const float (&yf)[kPatchN],
-                                                global_fquad_ptr fq, unsigned pitch, int wm1, int hm1, float (&a)[kPatchN],
-                                                float (&b)[kPatchN], fquad_t (&t)[kPatchN])
-{
-    float z[kPatchN], X[kPatchN], Y[kPatchN], r[kPatchN];
+    float z[kPatchN], X[kPatchN], Y[kPatchN];
 #pragma unroll
     for (int j = 0; j < kPatchN; ++j) {
         z[j] = fmaf(H.h[7], yf[j], bz);
         X[j] = fmaf(H.h[1], yf[j], bx);
         Y[j] = fmaf(H.h[4], yf[j], by);
     }
-    APD_STAGE();
-    if (kRecip == kRecipApprox) {
-#pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            r[j] = __builtin_amdgcn_rcpf(z[j]);
-        }
-    } else if (kRecip == kRecipExact) {
-#pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            r[j] = __builtin_amdgcn_rcpf(z[j]);
-        }
-        APD_STAGE();
-#pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            z[j] = fmaf(-z[j], r[j], 1.0f);
-        }
-        APD_STAGE();
-#pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            r[j] = fmaf(z[j], r[j], r[j]);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kPatchN; ++j) {
-            r[j] = 1.0f / z[j];
-        }
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        X[j] *= r[j];
-        Y[j] *= r[j];
-    }
-    APD_STAGE();
     int qx[kPatchN], qy[kPatchN];
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        a[j] = __builtin_amdgcn_fractf(X[j]);
-        b[j] = __builtin_amdgcn_fractf(Y[j]);
-        qx[j] = cvt_floor_i32(X[j]);
-        qy[j] = cvt_floor_i32(Y[j]);
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        qx[j] = med3_i32(qx[j], -1, wm1);
-        qy[j] = med3_i32(qy[j], -1, hm1);
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        qx[j] = (int)fquad_byte_offset(qx[j], qy[j], (int)pitch, (int)(pitch + 16u));
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        t[j] = fquad_fetch(fq, (unsigned)qx[j]);
-    }
-}
-
-__device__ __forceinline__ void fquad_row_lerp(const fquad_t (&t)[kPatchN], const float (&a)[kPatchN], const float (&b)[kPatchN],
-                                               float (&v)[kPatchN])
-{
-    float top[kPatchN], bot[kPatchN];
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        top[j] = fmaf(a[j], t[j].y, t[j].x);
-        bot[j] = fmaf(a[j], t[j].w, t[j].z);
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        bot[j] -= top[j];
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int j = 0; j < kPatchN; ++j) {
-        v[j] = fmaf(b[j], bot[j], top[j]);
-    }
+    tap_positions<kPatchN, kRecip>(z, X, Y, wm1, hm1, a, b, qx, qy);
+    taps_fetch<TexelFormat<kQuad, kTiled>>(img, pitch, qx, qy, t);
 }
 
 // The 36 warped source samples of one fixed patch and their three moments (APD.cu:561-583), summed in the
-// reference's order (row partial sums, then total).  kRecip (see quad_row_issue); kRecipExact: every denominator is known to be in the
+// reference's order (row partial sums, then total).  kRecip (see tap_positions); kRecipExact: every denominator is known to be in the
 // range where recip_fast is the correctly rounded reciprocal.
 template <bool kQuad, int kRecip, bool kTiled, typename Ref>
 __device__ __forceinline__ void ncc_fixed_moments(const FrameArgs &fa, const ViewConst &vc, const Ref &rp, const Homography &H_in,
@@ -931,11 +928,10 @@ __device__ __forceinline__ void ncc_fixed_moments(const FrameArgs &fa, const Vie
 {
     const Homography &H = H_in;
     const int px = px_in, py = py_in;
-    const global_quad_ptr srcq = (global_quad_ptr)(kTiled ? vc.quad_tiled : vc.quad);
+    typedef TexelFormat<kQuad, kTiled> Fmt;
+    const typename Fmt::ptr_t src = Fmt::image(vc);
     const int W = fa.W, Hh = fa.H;
-    const unsigned qpitch = kTiled ? quad_tiles_x(W) : quad_row_pitch_bytes(W);
-    const unsigned fpitch = 16u * (unsigned)(W + 1);
-    const global_fquad_ptr srcf = (global_fquad_ptr)vc.fquad;
+    const unsigned pitch = Fmt::pitch(W);
     const int wm1 = W - 1, hm1 = Hh - 1;
     float yf[kPatchN];
 #pragma unroll
@@ -949,17 +945,12 @@ __device__ __forceinline__ void ncc_fixed_moments(const FrameArgs &fa, const Vie
     // is reduced
     constexpr int kDepth = APD_ROW_PREFETCH, kBuf = kDepth + 1;
     float a[kBuf][kPatchN], b[kBuf][kPatchN];
-    quad_t t[kQuad ? kBuf : 1][kPatchN];
-    fquad_t tf[kQuad ? 1 : kBuf][kPatchN];
+    typename Fmt::tap_t t[kBuf][kPatchN];
 #pragma unroll
     for (int r = 0; r < kDepth; ++r) {
         const float xf = (float)(px + kPatchStep * r - kPatchRadius);
         const float bx = fmaf(H.h[0], xf, H.h[2]), by = fmaf(H.h[3], xf, H.h[5]), bz = fmaf(H.h[6], xf, H.h[8]);
-        if constexpr (kQuad) {
-            quad_row_issue<kRecip, kTiled>(H, bx, by, bz, yf, srcq, qpitch, wm1, hm1, a[r], b[r], t[r]);
-        } else {
-            fquad_row_issue<kRecip>(H, bx, by, bz, yf, srcf, fpitch, wm1, hm1, a[r], b[r], tf[r]);
-        }
+        row_issue<kQuad, kRecip, kTiled>(H, bx, by, bz, yf, src, pitch, wm1, hm1, a[r], b[r], t[r]);
     }
 #pragma unroll
     for (int i = 0; i < kPatchN; ++i) {
@@ -968,18 +959,10 @@ __device__ __forceinline__ void ncc_fixed_moments(const FrameArgs &fa, const Vie
             const int n = (i + kDepth) % kBuf;
             const float xf = (float)(px + kPatchStep * (i + kDepth) - kPatchRadius);
             const float bx = fmaf(H.h[0], xf, H.h[2]), by = fmaf(H.h[3], xf, H.h[5]), bz = fmaf(H.h[6], xf, H.h[8]);
-            if constexpr (kQuad) {
-                quad_row_issue<kRecip, kTiled>(H, bx, by, bz, yf, srcq, qpitch, wm1, hm1, a[n], b[n], t[n]);
-            } else {
-                fquad_row_issue<kRecip>(H, bx, by, bz, yf, srcf, fpitch, wm1, hm1, a[n], b[n], tf[n]);
-            }
+            row_issue<kQuad, kRecip, kTiled>(H, bx, by, bz, yf, src, pitch, wm1, hm1, a[n], b[n], t[n]);
         }
         APD_STAGE();
-        if constexpr (kQuad) {
-            quad_row_lerp(t[i % kBuf], a[i % kBuf], b[i % kBuf], v);
-        } else {
-            fquad_row_lerp(tf[i % kBuf], a[i % kBuf], b[i % kBuf], v);
-        }
+        Fmt::row_lerp(t[i % kBuf], a[i % kBuf], b[i % kBuf], v);
         float ref[kPatchN];
 #pragma unroll
         for (int j = 0; j < kPatchN; ++j) {
@@ -1007,11 +990,10 @@ template <bool kQuad, bool kTiled, typename Ref>
 __device__ __forceinline__ void ncc_fixed_moments_ieee_rolled(const FrameArgs &fa, const ViewConst &vc, const Ref &rp, const Homography &H,
                                                               int px, int py, float &sum_s, float &sum_ss, float &sum_rs)
 {
-    const global_quad_ptr srcq = (global_quad_ptr)(kTiled ? vc.quad_tiled : vc.quad);
+    typedef TexelFormat<kQuad, kTiled> Fmt;
+    const typename Fmt::ptr_t src = Fmt::image(vc);
     const int W = fa.W, Hh = fa.H;
-    const unsigned qpitch = kTiled ? quad_tiles_x(W) : quad_row_pitch_bytes(W);
-    const unsigned fpitch = 16u * (unsigned)(W + 1);
-    const global_fquad_ptr srcf = (global_fquad_ptr)vc.fquad;
+    const unsigned pitch = Fmt::pitch(W);
     const int wm1 = W - 1, hm1 = Hh - 1;
     sum_s = 0.0f;
     sum_ss = 0.0f;
@@ -1029,15 +1011,7 @@ __device__ __forceinline__ void ncc_fixed_moments_ieee_rolled(const FrameArgs &f
             const float X = fmaf(H.h[1], yf, bx) * r, Y = fmaf(H.h[4], yf, by) * r;
             const float a = __builtin_amdgcn_fractf(X), b = __builtin_amdgcn_fractf(Y);
             const int qx = med3_i32(cvt_floor_i32(X), -1, wm1), qy = med3_i32(cvt_floor_i32(Y), -1, hm1);
-            float v;
-            if constexpr (kQuad) {
-                const unsigned off = kTiled ? quad_tiled_byte_offset(qx, qy, qpitch) : quad_byte_offset(qx, qy, (int)qpitch, (int)(qpitch + kRowEntryBytes));
-                v = quad_lerp(quad_fetch(srcq, off), a, b);
-            } else {
-                const fquad_t t = fquad_fetch(srcf, fquad_byte_offset(qx, qy, (int)fpitch, (int)(fpitch + 16u)));
-                const float top = fmaf(a, t.y, t.x), bot = fmaf(a, t.w, t.z);
-                v = fmaf(b, bot - top, top);
-            }
+            const float v = Fmt::lerp(Fmt::fetch(src, Fmt::byte_offset(qx, qy, pitch)), a, b);
             const float ref = rp.at(i, j);
             row_s += v;
             row_ss = fmaf(v, v, row_ss);
@@ -1079,7 +1053,6 @@ template <bool kQuad, typename Ref, bool kTiled = false>
 __device__ __forceinline__ float ncc_fixed_from_h(const FrameArgs &fa, const ViewConst &vc, const Ref &rp, const Homography &H,
                                                   int px, int py)
 {
-    const float kMinVar = 1e-5f;
     if (rp.var < kMinVar) {
         return 2.0f;  // the reference tests this after sampling; the result is the same
     }
@@ -1095,16 +1068,7 @@ __device__ __forceinline__ float ncc_fixed_from_h(const FrameArgs &fa, const Vie
     } else {
         ncc_fixed_moments_ieee<kQuad, kTiled, Ref>(fa, vc, rp, H, px, py, sum_s, sum_ss, sum_rs);
     }
-    const float inv_w = 1.0f / 36.0f;
-    sum_s *= inv_w;
-    sum_ss *= inv_w;
-    sum_rs *= inv_w;
-    const float var_s = fmaf(-sum_s, sum_s, sum_ss);
-    if (var_s < kMinVar) {
-        return 2.0f;
-    }
-    const float covar = fmaf(-rp.mean, sum_s, sum_rs);
-    return ncc_cost_from_moments(rp.var, var_s, covar);
+    return ncc_cost_from_sums<true>(rp.mean, rp.var, sum_s, sum_ss, sum_rs, 1.0f / 36.0f);
 }
 
 // ComputeBilateralNCCOld for plane q = n/d against source view vc.  kQuad selects the texel-quad image.
@@ -1123,25 +1087,24 @@ __device__ __forceinline__ float ncc_fixed(const FrameArgs &fa, const ViewConst 
 
 // ------------------------------------------------------------------------------------------------
 // 3x3 sub-patch (weak_radius 5, weak_increment 5) around a reliable neighbour: the k >= 1 terms of
-// ComputeBilateralNCCNew (APD.cu:461-505) on texel-quad images.  The reference side (nine texels and
+// ComputeBilateralNCCNew (APD.cu:461-505), on either image format.  The reference side (nine texels and
 // their moments) depends on the neighbour only and is prepared once per pixel by the caller.
 // ------------------------------------------------------------------------------------------------
 
 constexpr int kSubN = 3;       // offsets -5, 0, 5
 constexpr int kSubStep = 5;
 
-// Nine warped samples in lock step (same stages as quad_row_issue), reduced in the reference's order.
-// ref_rows[i] packs the three reference texels of x offset i (y offset j in byte j).
+// Nine warped samples in lock step (tap_positions, the stages of row_issue), reduced in the reference's order.
 // kRecip: kRecipExact (every denominator in the fast range) or kRecipIeee (any denominator; same bits where both are valid).
 // Two halves, so that a caller can have the nine gathers of the next sub-patch in flight while it reduces this one
 // (K9/K10, two waves per SIMD: latency is what is left once the traffic is halved).
-template <int kRecip = kRecipExact>
-__device__ __forceinline__ void subpatch_issue_quad(const Homography &H, global_quad_ptr srcq, unsigned qpitch, int wm1, int hm1, int cx,
-                                                    int cy, float (&a)[kSubN * kSubN], float (&b)[kSubN * kSubN],
-                                                    quad_t (&t)[kSubN * kSubN])
+template <bool kQuad, int kRecip = kRecipExact>
+__device__ __forceinline__ void subpatch_issue(const Homography &H, typename TexelFormat<kQuad>::ptr_t img, unsigned pitch, int wm1,
+                                               int hm1, int cx, int cy, float (&a)[kSubN * kSubN], float (&b)[kSubN * kSubN],
+                                               typename TexelFormat<kQuad>::tap_t (&t)[kSubN * kSubN])
 {
     constexpr int N = kSubN * kSubN;
-    float z[N], X[N], Y[N], r[N];
+    float z[N], X[N], Y[N];
 #pragma unroll
     for (int i = 0; i < kSubN; ++i) {
         const float xf = (float)(cx + kSubStep * (i - 1));
@@ -1156,74 +1119,41 @@ __device__ __forceinline__ void subpatch_issue_quad(const Homography &H, global_
             Y[i * kSubN + j] = fmaf(H.h[4], yf, by);
         }
     }
-    APD_STAGE();
-    if constexpr (kRecip == kRecipExact) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            r[k] = __builtin_amdgcn_rcpf(z[k]);
-        }
-        APD_STAGE();
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            z[k] = fmaf(-z[k], r[k], 1.0f);
-        }
-        APD_STAGE();
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            r[k] = fmaf(z[k], r[k], r[k]);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            r[k] = 1.0f / z[k];
-        }
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        X[k] *= r[k];
-        Y[k] *= r[k];
-    }
-    APD_STAGE();
     int qx[N], qy[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        a[k] = __builtin_amdgcn_fractf(X[k]);
-        b[k] = __builtin_amdgcn_fractf(Y[k]);
-        qx[k] = cvt_floor_i32(X[k]);
-        qy[k] = cvt_floor_i32(Y[k]);
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        qx[k] = med3_i32(qx[k], -1, wm1);
-        qy[k] = med3_i32(qy[k], -1, hm1);
-    }
+    tap_positions<N, kRecip>(z, X, Y, wm1, hm1, a, b, qx, qy);
     APD_LAB_SUBPATCH_ROWS(qx, qy);
     // (Round 4 measured taking taps 0 and 1 of a row with ONE 16-byte load where they share a row segment -- 98.9 % of the rows do:
     // L1 tag accesses per launch -24 %, launch time 49.2 -> 56.7 ms; the tag count was a proxy, a 16-byte gather keeps the address /
     // data path of the L1 busy four times as long as a dword.  profiles/r04/ab_k910_row_segments.txt.  Nine dword gathers it is.)
-    APD_STAGE();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        qx[k] = (int)quad_byte_offset(qx[k], qy[k], (int)qpitch, (int)(qpitch + kRowEntryBytes));
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        t[k] = quad_fetch(srcq, (unsigned)qx[k]);
-    }
+    taps_fetch<TexelFormat<kQuad>>(img, pitch, qx, qy, t);
 }
 
-__device__ __forceinline__ float subpatch_finish_quad(const quad_t (&t)[kSubN * kSubN], const float (&a)[kSubN * kSubN],
-                                                      const float (&b)[kSubN * kSubN], const uint32_t (&ref_rows)[kSubN], float mean_r,
-                                                      float var_r)
+// The nine reference texels of a sub-patch, x offset i, y offset j: packed bytes in registers (8-bit images; rows[i] holds
+// the three texels of x offset i, y offset j in byte j), or floats read with a stride (float images: the kernel's LDS table).
+template <bool kQuad>
+struct SubRef;
+template <>
+struct SubRef<true> {
+    const uint32_t (&rows)[kSubN];
+    __device__ __forceinline__ float at(int i, int j) const { return (float)((rows[i] >> (8 * j)) & 0xFFu); }
+};
+template <>
+struct SubRef<false> {
+    const float *base;
+    int stride;
+    __device__ __forceinline__ float at(int i, int j) const { return base[(i * kSubN + j) * stride]; }
+};
+
+template <bool kQuad>
+__device__ __forceinline__ float subpatch_finish(const typename TexelFormat<kQuad>::tap_t (&t)[kSubN * kSubN],
+                                                 const float (&a)[kSubN * kSubN], const float (&b)[kSubN * kSubN],
+                                                 const SubRef<kQuad> &ref, float mean_r, float var_r)
 {
     constexpr int N = kSubN * kSubN;
     float v[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-        v[k] = quad_lerp(t[k], a[k], b[k]);
+        v[k] = TexelFormat<kQuad>::lerp(t[k], a[k], b[k]);
     }
     float sum_s = 0.0f, sum_ss = 0.0f, sum_rs = 0.0f;
 #pragma unroll
@@ -1232,131 +1162,7 @@ __device__ __forceinline__ float subpatch_finish_quad(const quad_t (&t)[kSubN * 
 #pragma unroll
         for (int j = 0; j < kSubN; ++j) {
             const float val = v[i * kSubN + j];
-            const float ref = (float)((ref_rows[i] >> (8 * j)) & 0xFFu);
-            row_s += val;
-            row_ss = fmaf(val, val, row_ss);
-            row_rs = fmaf(ref, val, row_rs);
-        }
-        sum_s += row_s;
-        sum_ss += row_ss;
-        sum_rs += row_rs;
-    }
-    const float inv_w = 1.0f / 9.0f;
-    sum_s *= inv_w;
-    sum_ss *= inv_w;
-    sum_rs *= inv_w;
-    const float var_s = fmaf(-sum_s, sum_s, sum_ss);
-    const float kMinVar = 1e-5f;
-    if (var_r < kMinVar || var_s < kMinVar) {
-        return 2.0f;
-    }
-    const float covar = fmaf(-mean_r, sum_s, sum_rs);
-    return ncc_cost_from_moments(var_r, var_s, covar);
-}
-
-template <int kRecip = kRecipExact>
-__device__ __forceinline__ float subpatch_cost_quad(const Homography &H, global_quad_ptr srcq, unsigned qpitch, int wm1, int hm1,
-                                                    int cx, int cy, const uint32_t (&ref_rows)[kSubN], float mean_r, float var_r)
-{
-    float a[kSubN * kSubN], b[kSubN * kSubN];
-    quad_t t[kSubN * kSubN];
-    subpatch_issue_quad<kRecip>(H, srcq, qpitch, wm1, hm1, cx, cy, a, b, t);
-    APD_STAGE();
-    return subpatch_finish_quad(t, a, b, ref_rows, mean_r, var_r);
-}
-
-// The same sub-patch on a float texel-quad image (float grey values); ref[i * 3 + j] is read with stride `ref_stride` floats.
-template <int kRecip = kRecipExact>
-__device__ __forceinline__ float subpatch_cost_fquad(const Homography &H, global_fquad_ptr fq, unsigned fpitch, int wm1, int hm1,
-                                                     int cx, int cy, const float *ref, int ref_stride, float mean_r, float var_r)
-{
-    constexpr int N = kSubN * kSubN;
-    float z[N], X[N], Y[N], r[N];
-#pragma unroll
-    for (int i = 0; i < kSubN; ++i) {
-        const float xf = (float)(cx + kSubStep * (i - 1));
-        const float bx = fmaf(H.h[0], xf, H.h[2]);
-        const float by = fmaf(H.h[3], xf, H.h[5]);
-        const float bz = fmaf(H.h[6], xf, H.h[8]);
-#pragma unroll
-        for (int j = 0; j < kSubN; ++j) {
-            const float yf = (float)(cy + kSubStep * (j - 1));
-            z[i * kSubN + j] = fmaf(H.h[7], yf, bz);
-            X[i * kSubN + j] = fmaf(H.h[1], yf, bx);
-            Y[i * kSubN + j] = fmaf(H.h[4], yf, by);
-        }
-    }
-    APD_STAGE();
-    if constexpr (kRecip == kRecipExact) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            r[k] = __builtin_amdgcn_rcpf(z[k]);
-        }
-        APD_STAGE();
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            z[k] = fmaf(-z[k], r[k], 1.0f);
-        }
-        APD_STAGE();
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            r[k] = fmaf(z[k], r[k], r[k]);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            r[k] = 1.0f / z[k];
-        }
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        X[k] *= r[k];
-        Y[k] *= r[k];
-    }
-    APD_STAGE();
-    float a[N], b[N];
-    int qx[N], qy[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        a[k] = __builtin_amdgcn_fractf(X[k]);
-        b[k] = __builtin_amdgcn_fractf(Y[k]);
-        qx[k] = cvt_floor_i32(X[k]);
-        qy[k] = cvt_floor_i32(Y[k]);
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        qx[k] = med3_i32(qx[k], -1, wm1);
-        qy[k] = med3_i32(qy[k], -1, hm1);
-    }
-    APD_STAGE();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        qx[k] = (int)fquad_byte_offset(qx[k], qy[k], (int)fpitch, (int)(fpitch + 16u));
-    }
-    APD_STAGE();
-    fquad_t t[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        t[k] = fquad_fetch(fq, (unsigned)qx[k]);
-    }
-    APD_STAGE();
-    float v[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const float top = fmaf(a[k], t[k].y, t[k].x);
-        const float bot = fmaf(a[k], t[k].w, t[k].z);
-        v[k] = fmaf(b[k], bot - top, top);
-    }
-    float sum_s = 0.0f, sum_ss = 0.0f, sum_rs = 0.0f;
-#pragma unroll
-    for (int i = 0; i < kSubN; ++i) {
-        float row_s = 0.0f, row_ss = 0.0f, row_rs = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kSubN; ++j) {
-            const float val = v[i * kSubN + j];
-            const float rf = ref[(i * kSubN + j) * ref_stride];
+            const float rf = ref.at(i, j);
             row_s += val;
             row_ss = fmaf(val, val, row_ss);
             row_rs = fmaf(rf, val, row_rs);
@@ -1365,17 +1171,18 @@ __device__ __forceinline__ float subpatch_cost_fquad(const Homography &H, global
         sum_ss += row_ss;
         sum_rs += row_rs;
     }
-    const float inv_w = 1.0f / 9.0f;
-    sum_s *= inv_w;
-    sum_ss *= inv_w;
-    sum_rs *= inv_w;
-    const float var_s = fmaf(-sum_s, sum_s, sum_ss);
-    const float kMinVar = 1e-5f;
-    if (var_r < kMinVar || var_s < kMinVar) {
-        return 2.0f;
-    }
-    const float covar = fmaf(-mean_r, sum_s, sum_rs);
-    return ncc_cost_from_moments(var_r, var_s, covar);
+    return ncc_cost_from_sums<false>(mean_r, var_r, sum_s, sum_ss, sum_rs, 1.0f / 9.0f);
+}
+
+template <bool kQuad, int kRecip = kRecipExact>
+__device__ __forceinline__ float subpatch_cost(const Homography &H, typename TexelFormat<kQuad>::ptr_t img, unsigned pitch, int wm1,
+                                               int hm1, int cx, int cy, const SubRef<kQuad> &ref, float mean_r, float var_r)
+{
+    float a[kSubN * kSubN], b[kSubN * kSubN];
+    typename TexelFormat<kQuad>::tap_t t[kSubN * kSubN];
+    subpatch_issue<kQuad, kRecip>(H, img, pitch, wm1, hm1, cx, cy, a, b, t);
+    APD_STAGE();
+    return subpatch_finish<kQuad>(t, a, b, ref, mean_r, var_r);
 }
 
 // Generic patch (any centre / radius / increment): sub-patches of ComputeBilateralNCCNew
@@ -1417,17 +1224,8 @@ __device__ __forceinline__ float patch_cost_generic(const FrameArgs &fa, const V
     const float inv_w = 1.0f / wsum;
     sum_r *= inv_w;
     sum_rr *= inv_w;
-    sum_s *= inv_w;
-    sum_ss *= inv_w;
-    sum_rs *= inv_w;
     const float var_r = fmaf(-sum_r, sum_r, sum_rr);
-    const float var_s = fmaf(-sum_s, sum_s, sum_ss);
-    const float kMinVar = 1e-5f;
-    if (var_r < kMinVar || var_s < kMinVar) {
-        return 2.0f;
-    }
-    const float covar = fmaf(-sum_r, sum_s, sum_rs);
-    return ncc_cost_from_moments(var_r, var_s, covar);
+    return ncc_cost_from_sums<false>(sum_r, var_r, sum_s, sum_ss, sum_rs, inv_w);
 }
 
 // ------------------------------------------------------------------------------------------------

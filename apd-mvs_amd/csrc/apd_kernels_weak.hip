@@ -529,6 +529,17 @@ struct WeakLdsT {
             var_r = var[k][lane];
         }
     }
+    // how subpatch_finish reads the nine texels of sub-patch k: the row dwords load_sub returned, or column `lane` of the table.
+    // Called inside each arm's subpatch_cost call: formed once ahead of the exact / IEEE branch, the table address changes the
+    // float kernels' code (profiles/texel_formats/isa_identity.txt).
+    __device__ __forceinline__ SubRef<kQuad> sub_ref(int k, int lane, const uint32_t (&rows)[kSubN]) const
+    {
+        if constexpr (kQuad) {
+            return SubRef<true>{rows};
+        } else {
+            return SubRef<false>{&ref[k][0][lane], 64};
+        }
+    }
 };
 typedef WeakLdsT<true> WeakLds;
 
@@ -617,10 +628,9 @@ template <bool kQuad>
 __device__ __forceinline__ void deformed_strong(const FrameArgs &fa, const ViewConst &vc, int v, const WeakLdsT<kQuad> &lds, int owner,
                                                 const Homography &H, float &strong_cost, int &strong_count)
 {
-    const global_quad_ptr srcq = (global_quad_ptr)vc.quad;
-    const unsigned qpitch = quad_row_pitch_bytes(fa.W);
-    const unsigned fpitch = 16u * (unsigned)(fa.W + 1);
-    const global_fquad_ptr srcf = (global_fquad_ptr)vc.fquad;
+    typedef TexelFormat<kQuad> Fmt;
+    const typename Fmt::ptr_t src = Fmt::image(vc);
+    const unsigned pitch = Fmt::pitch(fa.W);
     const int wm1 = fa.W - 1, hm1 = fa.H - 1;
     strong_cost = 0.0f;
     strong_count = 0;
@@ -651,17 +661,9 @@ __device__ __forceinline__ void deformed_strong(const FrameArgs &fa, const ViewC
         float mean_r, var_r;
         lds.load_sub(k, owner, ref_rows, mean_r, var_r);
         if (__builtin_amdgcn_ballot_w64(!fast) == 0) {
-            if constexpr (kQuad) {
-                c = subpatch_cost_quad<kRecipExact>(H, srcq, qpitch, wm1, hm1, nbx, nby, ref_rows, mean_r, var_r);
-            } else {
-                c = subpatch_cost_fquad<kRecipExact>(H, srcf, fpitch, wm1, hm1, nbx, nby, &lds.ref[k][0][owner], 64, mean_r, var_r);
-            }
+            c = subpatch_cost<kQuad, kRecipExact>(H, src, pitch, wm1, hm1, nbx, nby, lds.sub_ref(k, owner, ref_rows), mean_r, var_r);
         } else {
-            if constexpr (kQuad) {
-                c = subpatch_cost_quad<kRecipIeee>(H, srcq, qpitch, wm1, hm1, nbx, nby, ref_rows, mean_r, var_r);
-            } else {
-                c = subpatch_cost_fquad<kRecipIeee>(H, srcf, fpitch, wm1, hm1, nbx, nby, &lds.ref[k][0][owner], 64, mean_r, var_r);
-            }
+            c = subpatch_cost<kQuad, kRecipIeee>(H, src, pitch, wm1, hm1, nbx, nby, lds.sub_ref(k, owner, ref_rows), mean_r, var_r);
         }
         strong_cost += c;
         strong_count++;

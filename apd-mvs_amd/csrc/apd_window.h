@@ -208,7 +208,7 @@ __device__ __forceinline__ int win_byte_address(int qx, int qy, int addr0)
     return off;
 }
 
-// quad_row_issue / fquad_row_issue for samples known to lie inside the window: no clamps, LDS addresses.
+// row_issue for samples known to lie inside the window: no clamps, LDS addresses.
 // kEnds: the positions of samples 0 and kPatchN - 1 of this row are patch corners the caller has already computed with
 // corner_position (the same instructions on the same operands, hence the same bits): (Xa, Ya) and (Xb, Yb).
 template <bool kQuad, int kPitch, bool kApprox = false, bool kEnds = false>
@@ -429,7 +429,7 @@ __device__ __forceinline__ void corner_position(const Homography &H, float xf, f
 }
 
 // ComputeBilateralNCCOld (APD.cu:530-614) for plane q = n/d against source view vc, window first.
-// kApprox: tolerance mode (bare v_rcp_f32 everywhere, no IEEE body); see quad_row_issue
+// kApprox: tolerance mode (bare v_rcp_f32 everywhere, no IEEE body); see tap_positions
 template <bool kQuad, int kPitch = kWinW, bool kTiled = false, bool kApprox = false, bool kLocal = false, typename Ref>
 __device__ __forceinline__ float ncc_fixed_windowed(const FrameArgs &fa, const ViewConst &vc, const SrcWindow &w, const Ref &rp, int px,
                                                     int py, float qx, float qy, float qz)
@@ -440,7 +440,6 @@ __device__ __forceinline__ float ncc_fixed_windowed(const FrameArgs &fa, const V
     if (cx >= vc.wf || cx < 0.0f || cy >= vc.hf || cy < 0.0f) {
         return 2.0f;
     }
-    const float kMinVar = 1e-5f;
     if (rp.var < kMinVar) {
         return 2.0f;
     }
@@ -476,22 +475,13 @@ __device__ __forceinline__ float ncc_fixed_windowed(const FrameArgs &fa, const V
     } else {
         ncc_fixed_moments_ieee<kQuad, kTiled, Ref>(fa, vc, rp, H, px, py, sum_s, sum_ss, sum_rs);
     }
-    const float inv_w = 1.0f / 36.0f;
-    sum_s *= inv_w;
-    sum_ss *= inv_w;
-    sum_rs *= inv_w;
-    const float var_s = fmaf(-sum_s, sum_s, sum_ss);
-    if (var_s < kMinVar) {
-        return 2.0f;
-    }
-    const float covar = fmaf(-rp.mean, sum_s, sum_rs);
-    return ncc_cost_from_moments(rp.var, var_s, covar);
+    return ncc_cost_from_sums<true>(rp.mean, rp.var, sum_s, sum_ss, sum_rs, 1.0f / 36.0f);
 }
 
 // The same cost for an already projected centre (the caller has done the bounds test of APD.cu:546): K9/K10's centre patch.
 // (A function of its own rather than the tail of ncc_fixed_windowed: routing K6/K7 through it changes that kernel's block layout and
 // spills -- 512 -> 592 B of scratch per lane in one arrangement -- and K6/K7 is the headline kernel.)
-// kApprox: tolerance mode (bare v_rcp_f32 everywhere, no IEEE body); see quad_row_issue
+// kApprox: tolerance mode (bare v_rcp_f32 everywhere, no IEEE body); see tap_positions
 // Lanes inside and lanes outside the window each take their own 36-sample body (a mixed wave runs both in turn), unlike the one
 // body per wave and NCC of ncc_fixed_windowed: that is right for the kernels the vector ALU bounds (K6/K7, K14, K15); K9/K10 is
 // bound by the L1's tag accesses, which only the lanes on the global path make.
@@ -499,7 +489,6 @@ template <bool kQuad, int kPitch = kWinW, bool kTiled = false, bool kApprox = fa
 __device__ __forceinline__ float ncc_fixed_windowed_from_h(const FrameArgs &fa, const ViewConst &vc, const SrcWindow &w, const Ref &rp,
                                                            const Homography &H, int px, int py)
 {
-    const float kMinVar = 1e-5f;
     if (rp.var < kMinVar) {
         return 2.0f;
     }
@@ -533,16 +522,7 @@ __device__ __forceinline__ float ncc_fixed_windowed_from_h(const FrameArgs &fa, 
     } else {
         ncc_fixed_moments_ieee<kQuad, kTiled, Ref>(fa, vc, rp, H, px, py, sum_s, sum_ss, sum_rs);
     }
-    const float inv_w = 1.0f / 36.0f;
-    sum_s *= inv_w;
-    sum_ss *= inv_w;
-    sum_rs *= inv_w;
-    const float var_s = fmaf(-sum_s, sum_s, sum_ss);
-    if (var_s < kMinVar) {
-        return 2.0f;
-    }
-    const float covar = fmaf(-rp.mean, sum_s, sum_rs);
-    return ncc_cost_from_moments(rp.var, var_s, covar);
+    return ncc_cost_from_sums<true>(rp.mean, rp.var, sum_s, sum_ss, sum_rs, 1.0f / 36.0f);
 }
 
 }  // namespace apd
