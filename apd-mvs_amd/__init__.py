@@ -57,6 +57,16 @@ class Params(C.Structure):
     ]
 
 
+class FusionOptions(C.Structure):
+    """apd_fusion_options (include/apd_mi355x.h): the ETH fusion's acceptance rule as values, and the form of the result."""
+
+    _fields_ = [
+        ("struct_size", C.c_size_t), ("variant", C.c_int), ("max_reproj_error", C.c_float), ("max_relative_depth", C.c_float),
+        ("max_angle", C.c_float), ("depth_weight", C.c_float), ("angle_weight", C.c_float), ("min_consistent", C.c_int),
+        ("factor_strong", C.c_float), ("factor_weak", C.c_float), ("ply_normals", C.c_int), ("result_on_device", C.c_int),
+    ]
+
+
 class ApdError(RuntimeError):
     pass
 
@@ -154,6 +164,20 @@ def lib():
     L.apd_get_option.argtypes = [H, C.c_int, C.POINTER(C.c_int)]
     L.apd_last_error.restype = C.c_char_p
     L.apd_device_count.restype = C.c_int
+    L.apd_exchange_last_error.restype = C.c_char_p
+    L.apd_fusion_default_options.argtypes = [C.POINTER(FusionOptions)]
+    L.apd_fusion_default_options.restype = None
+    ipp = C.POINTER(C.c_int)
+    L.apd_fuse_views_opt.argtypes = [C.POINTER(FusionOptions), C.c_int, C.c_int, C.c_void_p, fpp, C.c_int, fpp, fpp, fpp, fpp, ipp, ipp, ipp, ipp,
+                                     C.c_int, C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_void_p)]
+    L.apd_points_count.argtypes = [C.c_void_p]
+    L.apd_points_count.restype = C.c_longlong
+    L.apd_points_on_device.argtypes = [C.c_void_p]
+    for n in ("xyz", "normal", "bgr", "support", "view", "pixel"):
+        getattr(L, "apd_points_" + n).argtypes = [C.c_void_p]
+        getattr(L, "apd_points_" + n).restype = C.c_void_p
+    L.apd_points_destroy.argtypes = [C.c_void_p]
+    L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     _lib = L
     return L
 
@@ -169,6 +193,75 @@ def default_params(**kw):
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_fusion_options(**kw):
+    """apd_fusion_default_options (the reference's literals, 15-byte PLY records, host results) with the given fields replaced."""
+    o = FusionOptions()
+    lib().apd_fusion_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k not in dict(FusionOptions._fields_):
+            raise TypeError("apd_fusion_options has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class _Borrowed:
+    """Memory of a Points object as an array interface; keeps its owner alive."""
+
+    def __init__(self, owner, address, shape, typestr):
+        self.owner = owner
+        self.__array_interface__ = {"data": (address, True), "shape": shape, "typestr": typestr, "version": 3}
+
+
+class Points:
+    """One fusion's points (apd_points_t) in PLY order as arrays: xyz float32 [N, 3] (the reference pixel's lifted point),
+    normal float32 [N, 3] (its normal as given, not renormalised), bgr uint8 [N, 3], support uint8 [N] (the votes the point was
+    accepted with), view and pixel int32 [N] (reference view and raster index in it).  A host result gives read-only numpy views
+    of the library's memory, valid while an array or this object lives; a device result gives torch tensors on its device,
+    filled by device-to-device copies (no host round trip) and independent of this object."""
+
+    _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
+               ("pixel", 1, "<i4", 4))
+
+    def __init__(self, handle, device=0):
+        L = lib()
+        self._p = handle
+        self.device = int(device)
+        self.count = int(L.apd_points_count(handle))
+        self.on_device = bool(L.apd_points_on_device(handle))
+        for name, width, typestr, size in self._FIELDS:
+            address = getattr(L, "apd_points_" + name)(handle)
+            shape = (self.count, width) if width > 1 else (self.count,)
+            if self.on_device:
+                import torch
+                t = torch.empty(shape, dtype={"<f4": torch.float32, "|u1": torch.uint8, "<i4": torch.int32}[typestr],
+                                device=torch.device("cuda", self.device))
+                if self.count:
+                    rc = L.apd_device_memcpy(self.device, t.data_ptr(), address, self.count * width * size)
+                    if rc != 0:
+                        raise ApdError("apd error %d copying the points: %s" % (rc, L.apd_exchange_last_error()))
+                setattr(self, name, t)
+            elif self.count:
+                setattr(self, name, np.asarray(_Borrowed(self, address, shape, typestr)))
+            else:
+                setattr(self, name, np.empty(shape, np.dtype(typestr)))
+        if self.on_device:
+            self.close()   # the tensors own their memory
+
+    def __len__(self):
+        return self.count
+
+    def close(self):
+        if self._p:
+            lib().apd_points_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def make_camera(K, R, t, width, height, depth_min, depth_max):

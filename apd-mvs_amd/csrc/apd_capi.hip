@@ -373,7 +373,7 @@ void apd_default_params(apd_params *p)
 }
 
 const char *apd_last_error(void) { return g_last_error.c_str(); }
-int apd_version(void) { return 106; }
+int apd_version(void) { return 107; }
 
 // Digest of the HIP sources, headers and compiler flags this library was built from (apd-mvs_amd/build.py writes it next to the
 // objects before compiling this file): what apd_mvs_amd.build.expected_build_id() returns for the same tree.

@@ -16,7 +16,14 @@
 // pixel's decision only ever depends on decisions of earlier pixels: same result as the raster-order loop, bit for bit.
 // Accepted pixels then consume their supports, and a block scan compacts the points in raster order.
 //
-// The second half of the file is the host driver of every device fusion (apd_fusion_device.h), the T&T ones included.
+// The acceptance rule's eight values (apd_fusion_options) reach the kernels in RefTask, as kernel arguments.  A pixel is decided
+// when no vote is waiting, whatever min_consistent is; no pixel is rejected early because its possible votes fell below
+// min_consistent (the only early rejection is the one there always was: a pixel without any vote has nothing to claim).
+//
+// The second half of the file is the host driver of every device fusion (apd_fusion_device.h), the T&T ones included.  Points in
+// memory (apd_points_t): the total is not known before the last view, so the seven arrays grow geometrically on the device
+// (reserve_points: twice the capacity, one device-to-device copy of what is there) and k_fusion_compact_soa appends each view's
+// points at the running count; a host result is one download at the end.  Nothing is sized by pixels x views.
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
@@ -64,11 +71,15 @@ __global__ __launch_bounds__(1024) void k_fusion_scan(int *__restrict__ counts, 
 
 // Packs the points of a view (pixels p < n with state[p] == accepted) in raster order as the 15-byte records of the PLY body
 // (x y z float, diffuse_blue / green / red uchar, APD.cpp:214-254): one download per view straight into the file image, no
-// per-point loop on the host.  block_offsets: k_fusion_scan of the per-256-pixel point counts.
+// per-point loop on the host.  block_offsets: k_fusion_scan of the per-256-pixel point counts.  kNormals: the 27-byte records
+// x y z nx ny nz + colour, the normal read from the view's normal map at the pixel.
+template <bool kNormals>
 __global__ __launch_bounds__(256) void k_fusion_compact(const uint8_t *__restrict__ state, uint8_t accepted, int n,
                                                          const float *__restrict__ xyz_sparse, const uint8_t *__restrict__ bgr_sparse,
-                                                         const int *__restrict__ block_offsets, uint8_t *__restrict__ records)
+                                                         const float *__restrict__ normal_map, const int *__restrict__ block_offsets,
+                                                         uint8_t *__restrict__ records)
 {
+    constexpr int kFloats = kNormals ? 6 : 3, kRecord = 4 * kFloats + 3;
     const int p = blockIdx.x * 256 + threadIdx.x;
     const bool acc = p < n && state[p] == accepted;
     const unsigned long long m = __ballot(acc);
@@ -83,17 +94,53 @@ __global__ __launch_bounds__(256) void k_fusion_compact(const uint8_t *__restric
         for (int w = 0; w < wave; ++w) {
             pos += wave_counts[w];
         }
-        uint8_t *rec = records + (size_t)pos * 15;
-        for (int k = 0; k < 3; ++k) {
-            const uint32_t bits = __float_as_uint(xyz_sparse[3 * (size_t)p + k]);  // little endian, as the host's memcpy wrote them
+        uint8_t *rec = records + (size_t)pos * kRecord;
+        for (int k = 0; k < kFloats; ++k) {
+            // little endian, as the host's memcpy wrote them
+            const uint32_t bits = __float_as_uint(k < 3 ? xyz_sparse[3 * (size_t)p + k] : normal_map[3 * (size_t)p + (k - 3)]);
             rec[4 * k + 0] = (uint8_t)(bits & 0xFFu);
             rec[4 * k + 1] = (uint8_t)((bits >> 8) & 0xFFu);
             rec[4 * k + 2] = (uint8_t)((bits >> 16) & 0xFFu);
             rec[4 * k + 3] = (uint8_t)(bits >> 24);
         }
-        rec[12] = bgr_sparse[3 * (size_t)p + 0];
-        rec[13] = bgr_sparse[3 * (size_t)p + 1];
-        rec[14] = bgr_sparse[3 * (size_t)p + 2];
+        rec[4 * kFloats + 0] = bgr_sparse[3 * (size_t)p + 0];
+        rec[4 * kFloats + 1] = bgr_sparse[3 * (size_t)p + 1];
+        rec[4 * kFloats + 2] = bgr_sparse[3 * (size_t)p + 2];
+    }
+}
+
+// The same points as a structure of arrays, appended at `base`: point base + block offset + rank in the block gets xyz, the
+// normal of the view's normal map at the pixel, colour, support, the view and the raster index.  One lane per pixel; the rank
+// inside a wave from the ballot and mbcnt, across the four waves of the block through LDS.  Every offset is a size_t.
+__global__ __launch_bounds__(256) void k_fusion_compact_soa(const uint8_t *__restrict__ state, uint8_t accepted, int n, int view,
+                                                             const float *__restrict__ xyz_sparse, const uint8_t *__restrict__ bgr_sparse,
+                                                             const uint8_t *__restrict__ support_sparse,
+                                                             const float *__restrict__ normal_map, const int *__restrict__ block_offsets,
+                                                             size_t base, apd_fusion::PointArrays out)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const bool acc = p < n && state[p] == accepted;
+    const unsigned long long m = __ballot(acc);
+    __shared__ int wave_counts[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+        wave_counts[wave] = __popcll(m);
+    }
+    __syncthreads();
+    if (acc) {
+        int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        for (int w = 0; w < wave; ++w) {
+            rank += wave_counts[w];
+        }
+        const size_t pos = base + (size_t)block_offsets[blockIdx.x] + (size_t)rank;
+        for (int k = 0; k < 3; ++k) {
+            out.xyz[3 * pos + k] = xyz_sparse[3 * (size_t)p + k];
+            out.normal[3 * pos + k] = normal_map[3 * (size_t)p + k];
+            out.bgr[3 * pos + k] = bgr_sparse[3 * (size_t)p + k];
+        }
+        out.support[pos] = support_sparse[p];
+        out.view[pos] = view;
+        out.pixel[pos] = p;
     }
 }
 
@@ -121,6 +168,11 @@ struct RefTask {
     uint8_t *state;          // 0 inactive, 1 undecided, 2 accepted, 3 rejected
     int *flags;              // [0] undecided pixels left after this round
     int channels;            // of the images
+    uint8_t *support;        // [pixel]: num_consistent of an accepted pixel
+    // the acceptance rule (apd_fusion_options; apd_fusion_math.h)
+    float max_reproj_error, max_relative_depth, max_angle, depth_weight, angle_weight;
+    int min_consistent;
+    float factor_strong, factor_weak;
 };
 
 enum : uint8_t { kInactive = 0, kUndecided = 1, kAccepted = 2, kRejected = 3 };
@@ -154,7 +206,8 @@ __global__ __launch_bounds__(256) void k_fusion_votes(const DevView *__restrict_
                 const float src_depth = sv.depth[s];
                 if (sv.consumed[s] != 1 && !(src_depth <= 0.0f)) {
                     const float src_n[3] = {sv.normal[3 * (size_t)s], sv.normal[3 * (size_t)s + 1], sv.normal[3 * (size_t)s + 2]};
-                    if (apd_fusion::vote_check(rv.geo, sv.geo, c, r, ref_depth, ref_n, sc, sr, src_depth, src_n, w)) {
+                    if (apd_fusion::vote_check(rv.geo, sv.geo, c, r, ref_depth, ref_n, sc, sr, src_depth, src_n, task.max_reproj_error,
+                                                   task.max_relative_depth, task.max_angle, task.depth_weight, task.angle_weight, w)) {
                         idx = s;
                         votes++;
                     }
@@ -226,7 +279,7 @@ __global__ __launch_bounds__(256) void k_fusion_decide(const DevView *__restrict
             agreeing++;
         }
     }
-    const bool ok = apd_fusion::accept_point(agreeing, consistency, (int)rv.weak[p]);
+    const bool ok = apd_fusion::accept_point(agreeing, consistency, (int)rv.weak[p], task.min_consistent, task.factor_strong, task.factor_weak);
     __threadfence();
     reinterpret_cast<volatile uint8_t *>(task.state)[p] = ok ? kAccepted : kRejected;
 }
@@ -266,6 +319,7 @@ __global__ __launch_bounds__(256) void k_fusion_emit(const DevView *__restrict__
         for (int k = 0; k < 3; ++k) {
             bgr_sparse[3 * (size_t)p + k] = static_cast<uint8_t>(colour[k] / (agreeing + 1));
         }
+        task.support[p] = (uint8_t)agreeing;
     }
     const unsigned long long m = __ballot(acc);
     __shared__ int wave_counts[4];
@@ -318,6 +372,15 @@ int EthFusion::run()
     if (const int rc = alloc_common(); rc != APD_OK) {
         return rc;
     }
+    task.support = support;
+    task.max_reproj_error = a.opt.max_reproj_error;
+    task.max_relative_depth = a.opt.max_relative_depth;
+    task.max_angle = a.opt.max_angle;
+    task.depth_weight = a.opt.depth_weight;
+    task.angle_weight = a.opt.angle_weight;
+    task.min_consistent = a.opt.min_consistent;
+    task.factor_strong = a.opt.factor_strong;
+    task.factor_weak = a.opt.factor_weak;
     unsigned epoch = 0;
     for (int i = 0; i < a.num_views; ++i) {
         const int n = pixels(i);
@@ -350,7 +413,7 @@ int EthFusion::run()
             }
         }
         hipLaunchKernelGGL(k_fusion_emit, dim3(blocks), dim3(256), 0, 0, dviews, task, xyz, bgr, block_counts);
-        if (const int rc = collect(i, task.state, kAccepted); rc != APD_OK) {
+        if (const int rc = collect(i, task.state, kAccepted, hv[i].normal); rc != APD_OK) {
             return rc;
         }
     }
@@ -359,7 +422,16 @@ int EthFusion::run()
 
 }  // namespace
 
+// One fusion's points (apd_points_t): the arrays are host memory (malloc) or device memory on `device`
+struct apd_points {
+    int device, on_device;
+    long long count;
+    apd_fusion::PointArrays arrays;
+};
+
 namespace apd_fusion {
+
+int run_eth(const char *who, const Args &args) { return EthFusion(who, args).run(); }
 
 thread_local std::string g_fusion_error;
 thread_local double g_fusion_ms[3] = {0.0, 0.0, 0.0};
@@ -372,15 +444,16 @@ double ms_since(std::chrono::steady_clock::time_point t)
 }
 
 // ExportPointCloud (APD.cpp:214-254): header + the views' records in order.  APD_OK, or APD_ERR_IO with g_fusion_error set
-int write_ply(const char *who, const char *ply_path, long long count, const std::vector<std::vector<uint8_t>> &body)
+int write_ply(const char *who, const char *ply_path, long long count, const std::vector<std::vector<uint8_t>> &body, bool normals)
 {
     FILE *f = fopen(ply_path, "wb");
     if (!f) {
         g_fusion_error = std::string(who) + ": cannot write " + ply_path;  // no length limit: not through set_error
         return APD_ERR_IO;
     }
-    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-               "property uchar diffuse_blue\nproperty uchar diffuse_green\nproperty uchar diffuse_red\nend_header\n", (int)count);
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+               "property uchar diffuse_blue\nproperty uchar diffuse_green\nproperty uchar diffuse_red\nend_header\n", (int)count,
+            normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "");
     bool ok = true;
     for (const std::vector<uint8_t> &part : body) {
         ok = ok && (part.empty() || fwrite(part.data(), 1, part.size(), f) == part.size());
@@ -392,6 +465,28 @@ int write_ply(const char *who, const char *ply_path, long long count, const std:
     return APD_OK;
 }
 
+void free_device_arrays(PointArrays &p)
+{
+    hipFree(p.xyz);
+    hipFree(p.normal);
+    hipFree(p.bgr);
+    hipFree(p.support);
+    hipFree(p.view);
+    hipFree(p.pixel);
+    p = PointArrays();
+}
+
+void free_host_arrays(PointArrays &p)
+{
+    free(p.xyz);
+    free(p.normal);
+    free(p.bgr);
+    free(p.support);
+    free(p.view);
+    free(p.pixel);
+    p = PointArrays();
+}
+
 }  // namespace
 
 int Call::begin(bool eth)
@@ -399,7 +494,7 @@ int Call::begin(bool eth)
     g_fusion_error.clear();
     auto invalid = [this](const char *what) { return apd::set_error(g_fusion_error, APD_ERR_INVALID, "%s: %s", who, what); };
     if (a.num_views <= 0 || !a.cameras || !a.images || !a.depths || !a.normals || (eth && !a.weaks) || !a.rows || !a.cols || !a.pair_offsets ||
-        !a.pair_indices || !a.ply_path || !a.num_points) {
+        !a.pair_indices || (!a.ply_path && !a.points) || !a.num_points) {
         return invalid("null argument");
     }
     if (a.image_channels != 1 && a.image_channels != 3) {
@@ -456,51 +551,144 @@ int Call::alloc_common()
 {
     HIP_TRY(alloc(max_px * 12, &xyz));
     HIP_TRY(alloc(max_px * 3, &bgr));
+    HIP_TRY(alloc(max_px, &support));
     HIP_TRY(alloc(max_blocks() * 4, &block_counts));
     HIP_TRY(alloc(sizeof(int), &total_));
-    HIP_TRY(alloc(max_px * 15, &records_));
-    if (hipHostMalloc(&staging_, max_px * 15 > 0 ? max_px * 15 : 1, hipHostMallocDefault) != hipSuccess) {
-        staging_ = nullptr;  // pageable downloads then
+    if (a.ply_path) {  // without a file no record is packed or downloaded
+        const size_t bytes = max_px * (size_t)record_bytes();
+        HIP_TRY(alloc(bytes, &records_));
+        if (hipHostMalloc(&staging_, bytes > 0 ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
+            staging_ = nullptr;  // pageable downloads then
+        }
     }
     g_fusion_ms[0] = ms_since(t_lap_);
     t_lap_ = std::chrono::steady_clock::now();
     return APD_OK;
 }
 
-int Call::collect(int i, const uint8_t *state, uint8_t accepted)
+int Call::collect(int i, const uint8_t *state, uint8_t accepted, const float *normal)
 {
     const int n = pixels(i);
     const int blocks = (n + 255) / 256;
     hipLaunchKernelGGL(k_fusion_scan, dim3(1), dim3(1024), 0, 0, block_counts, blocks, total_);
-    hipLaunchKernelGGL(k_fusion_compact, dim3(blocks), dim3(256), 0, 0, state, accepted, n, (const float *)xyz, (const uint8_t *)bgr,
-                       (const int *)block_counts, records_);
+    if (a.ply_path && a.opt.ply_normals) {
+        hipLaunchKernelGGL(k_fusion_compact<true>, dim3(blocks), dim3(256), 0, 0, state, accepted, n, (const float *)xyz, (const uint8_t *)bgr,
+                           normal, (const int *)block_counts, records_);
+    } else if (a.ply_path) {
+        hipLaunchKernelGGL(k_fusion_compact<false>, dim3(blocks), dim3(256), 0, 0, state, accepted, n, (const float *)xyz, (const uint8_t *)bgr,
+                           normal, (const int *)block_counts, records_);
+    }
     HIP_TRY(hipGetLastError());
     int npts = 0;
     HIP_TRY(hipMemcpy(&npts, total_, sizeof(int), hipMemcpyDeviceToHost));
-    if (npts > 0) {
+    if (npts <= 0) {
+        return APD_OK;
+    }
+    if (a.ply_path) {
         std::vector<uint8_t> &part = body_[i];
-        part.resize((size_t)npts * 15);
+        part.resize((size_t)npts * record_bytes());
         if (staging_) {
             HIP_TRY(hipMemcpy(staging_, records_, part.size(), hipMemcpyDeviceToHost));
             memcpy(part.data(), staging_, part.size());
         } else {
             HIP_TRY(hipMemcpy(part.data(), records_, part.size(), hipMemcpyDeviceToHost));
         }
-        count_ += npts;
     }
+    if (a.points) {
+        if (const int rc = reserve_points(count_ + npts); rc != APD_OK) {
+            return rc;
+        }
+        hipLaunchKernelGGL(k_fusion_compact_soa, dim3(blocks), dim3(256), 0, 0, state, accepted, n, i, (const float *)xyz, (const uint8_t *)bgr,
+                           (const uint8_t *)support, normal, (const int *)block_counts, (size_t)count_, soa_);
+        HIP_TRY(hipGetLastError());
+    }
+    count_ += npts;
     return APD_OK;
+}
+
+int Call::reserve_points(long long need)
+{
+    if (need <= soa_capacity_) {
+        return APD_OK;
+    }
+    const long long capacity = std::max({need, 2 * soa_capacity_, 4096LL});
+    const size_t c = (size_t)capacity, have = (size_t)count_;
+    PointArrays grown;
+    struct Guard {
+        PointArrays &p;
+        ~Guard() { free_device_arrays(p); }  // whatever `grown` still holds when this function returns
+    } guard{grown};
+    HIP_TRY(hipMalloc((void **)&grown.xyz, c * 12));
+    HIP_TRY(hipMalloc((void **)&grown.normal, c * 12));
+    HIP_TRY(hipMalloc((void **)&grown.bgr, c * 3));
+    HIP_TRY(hipMalloc((void **)&grown.support, c));
+    HIP_TRY(hipMalloc((void **)&grown.view, c * 4));
+    HIP_TRY(hipMalloc((void **)&grown.pixel, c * 4));
+    if (have > 0) {
+        HIP_TRY(hipMemcpy(grown.xyz, soa_.xyz, have * 12, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(grown.normal, soa_.normal, have * 12, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(grown.bgr, soa_.bgr, have * 3, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(grown.support, soa_.support, have, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(grown.view, soa_.view, have * 4, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(grown.pixel, soa_.pixel, have * 4, hipMemcpyDeviceToDevice));
+    }
+    std::swap(soa_, grown);  // the guard frees the old arrays
+    soa_capacity_ = capacity;
+    return APD_OK;
+}
+
+void Call::release_points()
+{
+    free_device_arrays(soa_);
+    soa_capacity_ = 0;
 }
 
 int Call::finish()
 {
     g_fusion_ms[1] = ms_since(t_lap_);
     t_lap_ = std::chrono::steady_clock::now();
+    apd_points *pts = nullptr;
+    if (a.points) {
+        HIP_TRY(hipDeviceSynchronize());  // the last view's compaction
+        pts = new apd_points{a.device, a.opt.result_on_device ? 1 : 0, count_, PointArrays()};
+        if (pts->on_device) {
+            std::swap(pts->arrays, soa_);
+            soa_capacity_ = 0;
+        } else if (count_ > 0) {
+            const size_t c = (size_t)count_;
+            PointArrays &h = pts->arrays;
+            h.xyz = (float *)malloc(c * 12);
+            h.normal = (float *)malloc(c * 12);
+            h.bgr = (uint8_t *)malloc(c * 3);
+            h.support = (uint8_t *)malloc(c);
+            h.view = (int32_t *)malloc(c * 4);
+            h.pixel = (int32_t *)malloc(c * 4);
+            hipError_t e = (h.xyz && h.normal && h.bgr && h.support && h.view && h.pixel) ? hipSuccess : hipErrorOutOfMemory;
+            e = e != hipSuccess ? e : hipMemcpy(h.xyz, soa_.xyz, c * 12, hipMemcpyDeviceToHost);
+            e = e != hipSuccess ? e : hipMemcpy(h.normal, soa_.normal, c * 12, hipMemcpyDeviceToHost);
+            e = e != hipSuccess ? e : hipMemcpy(h.bgr, soa_.bgr, c * 3, hipMemcpyDeviceToHost);
+            e = e != hipSuccess ? e : hipMemcpy(h.support, soa_.support, c, hipMemcpyDeviceToHost);
+            e = e != hipSuccess ? e : hipMemcpy(h.view, soa_.view, c * 4, hipMemcpyDeviceToHost);
+            e = e != hipSuccess ? e : hipMemcpy(h.pixel, soa_.pixel, c * 4, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                apd_points_destroy(pts);
+                return hip_failed("download of the points", e, __FILE__, __LINE__);
+            }
+        }
+        release_points();
+    }
     release();
-    const int written = write_ply(who, a.ply_path, count_, body_);
-    if (written != APD_OK) {
-        return written;
+    if (a.ply_path) {
+        const int written = write_ply(who, a.ply_path, count_, body_, a.opt.ply_normals != 0);
+        if (written != APD_OK) {
+            apd_points_destroy(pts);
+            return written;
+        }
     }
     *a.num_points = count_;
+    if (a.points) {
+        *a.points = pts;
+    }
     g_fusion_ms[2] = ms_since(t_lap_);
     return APD_OK;
 }
@@ -530,5 +718,41 @@ extern "C" int apd_fuse_views(int device, int num_views, const apd_camera *camer
 {
     const apd_fusion::Args a = {device, num_views, cameras, images, image_channels, depths, normals, weaks, blocks, rows, cols, pair_offsets,
                                 pair_indices, maps_on_device, ply_path, num_points};
-    return EthFusion("apd_fuse_views", a).run();
+    return apd_fusion::run_eth("apd_fuse_views", a);
+}
+
+extern "C" void apd_fusion_default_options(apd_fusion_options *o)
+{
+    if (o) {
+        *o = apd_fusion::default_options();
+    }
+}
+
+extern "C" long long apd_points_count(apd_points_t p) { return p ? p->count : 0; }
+extern "C" int apd_points_on_device(apd_points_t p) { return p ? p->on_device : 0; }
+extern "C" const float *apd_points_xyz(apd_points_t p) { return p ? p->arrays.xyz : nullptr; }
+extern "C" const float *apd_points_normal(apd_points_t p) { return p ? p->arrays.normal : nullptr; }
+extern "C" const uint8_t *apd_points_bgr(apd_points_t p) { return p ? p->arrays.bgr : nullptr; }
+extern "C" const uint8_t *apd_points_support(apd_points_t p) { return p ? p->arrays.support : nullptr; }
+extern "C" const int32_t *apd_points_view(apd_points_t p) { return p ? p->arrays.view : nullptr; }
+extern "C" const int32_t *apd_points_pixel(apd_points_t p) { return p ? p->arrays.pixel : nullptr; }
+
+extern "C" int apd_points_destroy(apd_points_t p)
+{
+    if (!p) {
+        return APD_OK;
+    }
+    if (p->on_device) {
+        int current = 0;
+        const bool known = hipGetDevice(&current) == hipSuccess;
+        hipSetDevice(p->device);
+        apd_fusion::free_device_arrays(p->arrays);
+        if (known) {
+            hipSetDevice(current);
+        }
+    } else {
+        apd_fusion::free_host_arrays(p->arrays);
+    }
+    delete p;
+    return APD_OK;
 }

@@ -1,7 +1,8 @@
 // apd_fusion_device.h -- the host driver the device fusions share (apd_fusion.hip: ETH, apd_fusion_tat.hip: Tanks and Temples).
 // Implemented once, in apd_fusion.hip, together with the two kernels only it launches (k_fusion_scan, k_fusion_compact): argument
 // checks, the device memory of a call, the per-view geometry and maps, the scratch of the point compaction, the download of a
-// view's points, the PLY file, and the per-thread error / timing that apd_fusion_last_error and apd_fusion_last_timing report.
+// view's points, the PLY file, the points in memory (apd_points_t), and the per-thread error / timing that apd_fusion_last_error
+// and apd_fusion_last_timing report.
 // A variant derives from Call and adds its own view members, scratch and kernels.
 #pragma once
 
@@ -22,7 +23,32 @@ namespace apd_fusion {
 extern thread_local std::string g_fusion_error;
 extern thread_local double g_fusion_ms[3];  // last fusion: set-up (allocations, uploads), views (kernels + point downloads), PLY file
 
-// The arguments of apd_fuse_views / apd_fuse_views_variant (include/apd_mi355x.h)
+// apd_fusion_default_options: the reference's literals, a PLY of 15-byte records, host results
+inline apd_fusion_options default_options()
+{
+    apd_fusion_options o;
+    memset(&o, 0, sizeof(o));
+    o.struct_size = sizeof(o);
+    o.variant = APD_FUSION_ETH;
+    o.max_reproj_error = 2.0f;
+    o.max_relative_depth = 0.01f;
+    o.max_angle = 0.174533f;
+    o.depth_weight = 200.0f;
+    o.angle_weight = 10.0f;
+    o.min_consistent = 1;
+    o.factor_strong = 0.3f;
+    o.factor_weak = 0.45f;
+    return o;
+}
+
+// The seven arrays of an apd_points_t, on the device while the views are fused
+struct PointArrays {
+    float *xyz = nullptr, *normal = nullptr;
+    uint8_t *bgr = nullptr, *support = nullptr;
+    int32_t *view = nullptr, *pixel = nullptr;
+};
+
+// The arguments of apd_fuse_views / apd_fuse_views_variant / apd_fuse_views_opt (include/apd_mi355x.h)
 struct Args {
     int device, num_views;
     const apd_camera *cameras;
@@ -36,14 +62,23 @@ struct Args {
     int maps_on_device;
     const char *ply_path;
     long long *num_points;
+    apd_fusion_options opt = default_options();
+    apd_points_t *points = nullptr;  // apd_fuse_views_opt: where the points in memory go; then ply_path may be null
 };
+
+// The ETH fusion (apd_fusion.hip) for apd_fuse_views_opt, which lives beside the T&T fusions (apd_fusion_tat.hip)
+int run_eth(const char *who, const Args &args);
 
 // One fusion call.  Owns every device allocation and the page-locked staging buffer of the call: whichever way the call returns,
 // they are released, in the order they were made.
 class Call {
 public:
     Call(const char *who, const Args &args);  // the clock of the set-up starts here
-    ~Call() { release(); }
+    ~Call()
+    {
+        release();
+        release_points();
+    }
     Call(const Call &) = delete;
     Call &operator=(const Call &) = delete;
 
@@ -54,6 +89,7 @@ protected:
     int max_src = 1;        // sources of the view with the most
     float *xyz = nullptr;   // [pixel][3] of the view being fused: the points where they are, before the compaction
     uint8_t *bgr = nullptr; // [pixel][3]
+    uint8_t *support = nullptr;  // [pixel]: votes the point was accepted with
     int *block_counts = nullptr;  // points per block of 256 pixels
 
     int hip_failed(const char *expr, hipError_t e, const char *file, int line) const;  // what HIP_TRY returns
@@ -143,17 +179,23 @@ protected:
         return APD_OK;
     }
 
-    // The scratch every variant needs (xyz, bgr, block_counts, and what collect() uses) and the staging buffer, sized for the
+    // The scratch every variant needs (xyz, bgr, support, block_counts, and what collect() uses) and the staging buffer, sized for the
     // largest view.  Ends the set-up: its time is taken here.
     int alloc_common();
     // View i has its points in xyz / bgr, block_counts filled, and state[p] == accepted where pixel p is a point: packs them in
-    // raster order as PLY records (k_fusion_scan, k_fusion_compact) and downloads them.
-    int collect(int i, const uint8_t *state, uint8_t accepted);
-    // Takes the time of the views, releases the device memory, writes the file, and then sets *num_points.
+    // raster order as PLY records (k_fusion_scan, k_fusion_compact; 27-byte records with the normals of the view's map `normal`
+    // when the options ask for them) and downloads them, if a file is wanted; appends them to the arrays of the points in memory
+    // (k_fusion_compact_soa), if those are wanted.
+    int collect(int i, const uint8_t *state, uint8_t accepted, const float *normal);
+    // Takes the time of the views, brings a host result down, releases the device memory, writes the file, and then sets
+    // *num_points and *points.
     int finish();
 
 private:
     void release();
+    int record_bytes() const { return a.opt.ply_normals ? 27 : 15; }
+    int reserve_points(long long need);  // room for `need` points in soa_, kept across a growth
+    void release_points();
 
     std::vector<void *> owned_;
     void *staging_ = nullptr;  // page-locked buffer of the point downloads
@@ -163,6 +205,8 @@ private:
     // and copies hundreds of megabytes at Tanks&Temples scale), downloaded through one page-locked staging buffer
     std::vector<std::vector<uint8_t>> body_;
     long long count_ = 0;
+    PointArrays soa_;            // the points in memory so far, device memory outside owned_: handed to the apd_points_t or freed
+    long long soa_capacity_ = 0;
     std::chrono::steady_clock::time_point t_lap_;
 };
 

@@ -169,26 +169,45 @@ APD_HD void measure(const View &ref, const View &src, int c, int r, float ref_de
     }
 }
 
-// Backward check of reference pixel (c, r) against source pixel (sc, sr) with depth src_depth and normal src_n:
-// thresholds 2 px, 1 % depth, 10 degrees (APD.cpp:905-925).  `weight` is exp(-score), the term added to the consistency.
+// The acceptance rule of the ETH loop with its eight values as arguments (apd_fusion_options, include/apd_mi355x.h).  The
+// reference's literals are the defaults: 2.0f, 0.01f, 0.174533f, 200 (an int the reference converts to 200.0f), 10, 1, 0.3f,
+// 0.45f.  The values are floats used in the operation order of the literals -- `200 * x` and `depth_weight * x` with
+// depth_weight == 200.0f are the same IEEE multiply under -ffp-contract=off -- so default options cannot change a bit; the
+// literal forms below forward here, and the host build and both device paths keep one copy of the arithmetic.
+//
+// Backward check of reference pixel (c, r) against source pixel (sc, sr) with depth src_depth and normal src_n (APD.cpp:905-925).
+// `weight` is exp(-score), the term added to the consistency.
 APD_HD bool vote_check(const View &ref, const View &src, int c, int r, float ref_depth, const float ref_n[3], int sc, int sr,
-                       float src_depth, const float src_n[3], float &weight)
+                       float src_depth, const float src_n[3], float max_reproj_error, float max_relative_depth, float max_angle,
+                       float depth_weight, float angle_weight, float &weight)
 {
     float reproj_error, relative_depth_diff, angle;
     measure(ref, src, c, r, ref_depth, ref_n, sc, sr, src_depth, src_n, reproj_error, relative_depth_diff, angle);
-    if (!(reproj_error < 2.0f && relative_depth_diff < 0.01f && angle < 0.174533f)) {
+    if (!(reproj_error < max_reproj_error && relative_depth_diff < max_relative_depth && angle < max_angle)) {
         return false;
     }
-    const float score = reproj_error + 200 * relative_depth_diff + angle * 10;
+    const float score = reproj_error + depth_weight * relative_depth_diff + angle * angle_weight;
     weight = exp_c9(-score);
     return true;
 }
 
+// thresholds 2 px, 1 % depth, 10 degrees
+APD_HD bool vote_check(const View &ref, const View &src, int c, int r, float ref_depth, const float ref_n[3], int sc, int sr,
+                       float src_depth, const float src_n[3], float &weight)
+{
+    return vote_check(ref, src, c, r, ref_depth, ref_n, sc, sr, src_depth, src_n, 2.0f, 0.01f, 0.174533f, 200.0f, 10.0f, weight);
+}
+
 // WEAK pixels need stronger agreement (APD.cpp:937-938); weak_state 0 == WEAK (main.h:69-73)
+APD_HD bool accept_point(int agreeing, float consistency, int weak_state, int min_consistent, float factor_strong, float factor_weak)
+{
+    const float factor = (weak_state == 0 ? factor_weak : factor_strong);
+    return agreeing >= min_consistent && (consistency > factor * agreeing);
+}
+
 APD_HD bool accept_point(int agreeing, float consistency, int weak_state)
 {
-    const float factor = (weak_state == 0 ? 0.45f : 0.3f);
-    return agreeing >= 1 && (consistency > factor * agreeing);
+    return accept_point(agreeing, consistency, weak_state, 1, 0.3f, 0.45f);
 }
 
 }  // namespace apd_fusion

@@ -64,6 +64,7 @@ struct TatTask {
     uint8_t *emitted;        // [pixel]: 1 = the pixel is a point
     float *xyz;              // [pixel][3]
     uint8_t *bgr;            // [pixel][3]
+    uint8_t *support;        // [pixel]: `count` of the round that emitted the point
     int *block_counts;       // points per block
 };
 
@@ -260,6 +261,7 @@ __global__ __launch_bounds__(256) void k_tat_decide(const TatView *__restrict__ 
             for (int k = 0; k < 3; ++k) {
                 task.bgr[3 * (size_t)p + k] = static_cast<uint8_t>(colour[k]);
             }
+            task.support[p] = (uint8_t)count;
             rv.mask[p] = 1;
         }
     }
@@ -345,11 +347,12 @@ int TatFusion::run(bool intermediate)
         task.emitted = emitted;
         task.xyz = xyz;
         task.bgr = bgr;
+        task.support = support;
         task.block_counts = block_counts;
         hipLaunchKernelGGL(k_tat_valid, dim3(nblocks), dim3(256), 0, 0, dviews, task);
         hipLaunchKernelGGL(k_tat_scan, dim3(S), dim3(1024), 0, 0, task, nblocks);
         hipLaunchKernelGGL(k_tat_decide, dim3(nblocks), dim3(256), (size_t)S * 256, 0, dviews, task);
-        if (const int rc = collect(i, emitted, 1); rc != APD_OK) {
+        if (const int rc = collect(i, emitted, 1, hv[i].normal); rc != APD_OK) {
             return rc;
         }
     }
@@ -375,4 +378,56 @@ extern "C" int apd_fuse_views_variant(int variant, int device, int num_views, co
     const apd_fusion::Args a = {device, num_views, cameras, images, image_channels, depths, normals, weaks, blocks, rows, cols, pair_offsets,
                                 pair_indices, maps_on_device, ply_path, num_points};
     return TatFusion(who, a).run(variant == APD_FUSION_TAT_INTERMEDIATE);
+}
+
+extern "C" int apd_fuse_views_opt(const apd_fusion_options *options, int device, int num_views, const apd_camera *cameras,
+                                  const float *const *images, int image_channels, const float *const *depths, const float *const *normals,
+                                  const uint8_t *const *weaks, const uint8_t *const *blocks, const int *rows, const int *cols,
+                                  const int *pair_offsets, const int *pair_indices, int maps_on_device, const char *ply_path,
+                                  long long *num_points, apd_points_t *points)
+{
+    const char *who = "apd_fuse_views_opt";
+    std::string &err = apd_fusion::g_fusion_error;
+    if (!options) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: null options", who);
+    }
+    if (options->struct_size != sizeof(apd_fusion_options)) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: struct_size %zu is not sizeof(apd_fusion_options) = %zu", who, options->struct_size,
+                              sizeof(apd_fusion_options));
+    }
+    const apd_fusion_options o = *options, d = apd_fusion::default_options();
+    if (o.variant != APD_FUSION_ETH && o.variant != APD_FUSION_TAT_INTERMEDIATE && o.variant != APD_FUSION_TAT_ADVANCED) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: unknown variant %d", who, o.variant);
+    }
+    const struct {
+        const char *name;
+        float value, preset;
+    } values[] = {{"max_reproj_error", o.max_reproj_error, d.max_reproj_error}, {"max_relative_depth", o.max_relative_depth, d.max_relative_depth},
+                  {"max_angle", o.max_angle, d.max_angle},                      {"depth_weight", o.depth_weight, d.depth_weight},
+                  {"angle_weight", o.angle_weight, d.angle_weight},             {"factor_strong", o.factor_strong, d.factor_strong},
+                  {"factor_weak", o.factor_weak, d.factor_weak}};
+    bool preset = o.min_consistent == d.min_consistent;
+    for (const auto &v : values) {
+        if (!(v.value >= 0.0f) || v.value > FLT_MAX) {
+            return apd::set_error(err, APD_ERR_INVALID, "%s: %s is negative or not finite", who, v.name);
+        }
+        preset = preset && v.value == v.preset;
+    }
+    if (o.min_consistent < 1 || o.min_consistent > APD_MAX_IMAGES) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: min_consistent %d is outside 1 .. %d", who, o.min_consistent, APD_MAX_IMAGES);
+    }
+    if (!ply_path && !points) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: ply_path and points are both NULL", who);
+    }
+    if (o.variant != APD_FUSION_ETH && !preset) {
+        return apd::set_error(err, APD_ERR_UNSUPPORTED, "%s: the thresholds apply to APD_FUSION_ETH only; the T&T loops keep their own", who);
+    }
+    apd_fusion::Args a = {device, num_views, cameras, images, image_channels, depths, normals, weaks, blocks, rows, cols, pair_offsets,
+                          pair_indices, maps_on_device, ply_path, num_points};
+    a.opt = o;
+    a.points = points;
+    if (o.variant == APD_FUSION_ETH) {
+        return apd_fusion::run_eth(who, a);
+    }
+    return TatFusion(who, a).run(o.variant == APD_FUSION_TAT_INTERMEDIATE);
 }

@@ -158,6 +158,9 @@ void SetFusionDevice(int device);  // additive: HIP device of the fusion (defaul
 // additive: which of the reference's fusion loops RunFusion and the in-memory paths run: APD_FUSION_ETH (RunFusion, the default),
 // APD_FUSION_TAT_INTERMEDIATE or APD_FUSION_TAT_ADVANCED (APD.cpp:979-1296; the reference switches by editing main.cpp:219)
 void SetFusionVariant(int variant);
+// additive: the options of the fusion (apd_fusion_options, include/apd_mi355x.h: the ETH loop's acceptance rule as values, normals
+// in the PLY file) that RunFusion, the in-memory paths and apdhost_fuse hand to apd_fuse_views_opt; its `variant` included
+void SetFusionOptions(const apd_fusion_options &options);
 
 class APD {
 public:

@@ -2,7 +2,7 @@
 // SetFusionVariant, RunFusion_TAT_Intermediate / RunFusion_TAT_advanced (APD.cpp:979-1296), and ExportPointCloud
 // (APD.cpp:214-254) produce, i.e. <dense>/APD/APD.ply.
 //
-// The fusion itself runs on the GPU (apd_fuse_views_variant, csrc/apd_fusion.hip and csrc/apd_fusion_tat.hip); this file is the drop-in entry point
+// The fusion itself runs on the GPU (apd_fuse_views_opt, csrc/apd_fusion.hip and csrc/apd_fusion_tat.hip); this file is the drop-in entry point
 // RunFusion, which reads the maps the way the reference does and hands them over.  There is no host fallback: a failing
 // device fusion ends the program like any other device error.  (The reference's sequential loop lives in
 // oracle/fusion_oracle.cpp as the checker of the device fusion.)
@@ -29,6 +29,24 @@ namespace {
 int g_fusion_device = 0;
 int g_fusion_variant = APD_FUSION_ETH;  // which of the reference's loops (APD_FUSION_*, include/apd_mi355x.h)
 
+// SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
+apd_fusion_options &fusion_options()
+{
+    static apd_fusion_options o = [] {
+        apd_fusion_options d;
+        apd_fusion_default_options(&d);
+        return d;
+    }();
+    return o;
+}
+
+apd_fusion_options call_options()
+{
+    apd_fusion_options o = fusion_options();
+    o.variant = g_fusion_variant;
+    return o;
+}
+
 struct FusionView {
     Camera cam;
     Mat image;     // float 0..255: 3 channels (blue, green, red, cv::imread(IMREAD_COLOR), APD.cpp:859) or 1 (grey)
@@ -38,8 +56,10 @@ struct FusionView {
     Mat block;     // optional uint8 mask of <dense>/blocks (APD.cpp:849-853); empty = none
 };
 
-// Device fusion through the C ABI (host pointers).
-long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const path &ply_path)
+// Device fusion through the C ABI (host pointers).  options: nullptr = those of SetFusionOptions; ply_path may be null when
+// points is not.
+long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const char *ply_path,
+                        const apd_fusion_options *options = nullptr, apd_points_t *points = nullptr)
 {
     const int V = (int)views.size();
     std::vector<apd_camera> cams(V);
@@ -67,9 +87,10 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
     }
     long long n = 0;
     const int channels = (V > 0 && views[0].image.type == MAT_32FC3) ? 3 : 1;
-    const int st = apd_fuse_views_variant(g_fusion_variant, g_fusion_device, V, cams.data(), imgs.data(), channels, deps.data(), nors.data(),
-                                          weaks.data(), any_block ? blocks.data() : nullptr, rows.data(), cols.data(), offs.data(), idx.data(), 0,
-                                          ply_path.string().c_str(), &n);
+    const apd_fusion_options opt = options ? *options : call_options();
+    const int st = apd_fuse_views_opt(&opt, g_fusion_device, V, cams.data(), imgs.data(), channels, deps.data(), nors.data(), weaks.data(),
+                                      any_block ? blocks.data() : nullptr, rows.data(), cols.data(), offs.data(), idx.data(), 0, ply_path, &n,
+                                      points);
     if (st != APD_OK) {
         std::cerr << apd_fusion_last_error() << std::endl;
         return -1;
@@ -82,6 +103,12 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
 void SetFusionDevice(int device) { g_fusion_device = device; }
 
 void SetFusionVariant(int variant) { g_fusion_variant = variant; }
+
+void SetFusionOptions(const apd_fusion_options &options)
+{
+    fusion_options() = options;
+    g_fusion_variant = options.variant;
+}
 
 // Reads every view's final maps from <dense>/APD/<id>/ and fuses them into APD/APD.ply (APD.cpp:826-977).
 void RunFusion(const path &dense_folder, const std::vector<Problem> &problems) { RunFusionWithMaps(dense_folder, problems, nullptr); }
@@ -210,7 +237,7 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     const path ply_path = dense_folder / path("APD") / path("APD.ply");
     const auto t_fuse = std::chrono::steady_clock::now();
     std::cout << "Fusion inputs ready: " << std::chrono::duration_cast<std::chrono::milliseconds>(t_fuse - t_inputs).count() << " ms" << std::endl;
-    const long long n = fuse_dispatch(views, sources, ply_path);
+    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str());
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms" << std::endl;
     if (n < 0) {
         exit(EXIT_FAILURE);  // like every other device error of the reference (CudaSafeCall, APD.cpp:315-323)
@@ -392,9 +419,10 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
     std::cout << "Fusion inputs ready: prepared in " << f->prepare_ms << " ms behind the passes, waited "
               << std::chrono::duration_cast<std::chrono::milliseconds>(t_fuse - t_wait).count() << " ms" << std::endl;
     long long count = 0;
-    const int st = apd_fuse_views_variant(g_fusion_variant, f->device, V, cams.data(), f->imgs.data(), f->channels, depths.data(), normals.data(),
-                                          weaks.data(), f->any_block ? f->blocks.data() : nullptr, rws.data(), cls.data(), offs.data(), idx.data(), 1,
-                                          ply_path.string().c_str(), &count);
+    const apd_fusion_options fusion = call_options();
+    const int st = apd_fuse_views_opt(&fusion, f->device, V, cams.data(), f->imgs.data(), f->channels, depths.data(), normals.data(), weaks.data(),
+                                      f->any_block ? f->blocks.data() : nullptr, rws.data(), cls.data(), offs.data(), idx.data(), 1,
+                                      ply_path.string().c_str(), &count, nullptr);
     double ms_setup = 0, ms_views = 0, ms_file = 0;
     apd_fusion_last_timing(&ms_setup, &ms_views, &ms_file);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms (set-up "
@@ -412,11 +440,12 @@ extern "C" {
 
 // Flat entry for the Python pipeline (maps already in memory after the all-gather): per-view pointers, all maps of view
 // i are rows[i] x cols[i]; sources of view i are pair_indices[pair_offsets[i] .. pair_offsets[i+1]).  Returns the
-// number of points written to `ply_path`.
-long long apdhost_fuse(int num_views, const apd_camera *cameras, const float *const *images, int image_channels,
-                       const float *const *depths, const float *const *normals, const uint8_t *const *weaks,
-                       const uint8_t *const *blocks, const int *rows, const int *cols, const int *pair_offsets,
-                       const int *pair_indices, const char *ply_path)
+// number of points written to `ply_path`.  apdhost_fuse_opt: with the options of this call (nullptr: those of
+// apdhost_set_fusion_options), a file, the points in memory (*points, apd_points_destroy) or both, as apd_fuse_views_opt.
+long long apdhost_fuse_opt(const apd_fusion_options *options, int num_views, const apd_camera *cameras, const float *const *images,
+                           int image_channels, const float *const *depths, const float *const *normals, const uint8_t *const *weaks,
+                           const uint8_t *const *blocks, const int *rows, const int *cols, const int *pair_offsets, const int *pair_indices,
+                           const char *ply_path, apd_points_t *points)
 {
     std::vector<FusionView> views(num_views);
     std::vector<std::vector<int>> sources(num_views);
@@ -440,7 +469,16 @@ long long apdhost_fuse(int num_views, const apd_camera *cameras, const float *co
         }
         sources[i].assign(pair_indices + pair_offsets[i], pair_indices + pair_offsets[i + 1]);
     }
-    return fuse_dispatch(views, sources, path(ply_path));  // -1: the device fusion failed (message on stderr)
+    return fuse_dispatch(views, sources, ply_path, options, points);  // -1: the device fusion failed (message on stderr)
+}
+
+long long apdhost_fuse(int num_views, const apd_camera *cameras, const float *const *images, int image_channels,
+                       const float *const *depths, const float *const *normals, const uint8_t *const *weaks,
+                       const uint8_t *const *blocks, const int *rows, const int *cols, const int *pair_offsets,
+                       const int *pair_indices, const char *ply_path)
+{
+    return apdhost_fuse_opt(nullptr, num_views, cameras, images, image_channels, depths, normals, weaks, blocks, rows, cols, pair_offsets,
+                            pair_indices, ply_path, nullptr);
 }
 
 }  // extern "C"

@@ -165,4 +165,12 @@ void apdhost_set_fusion_device(int device) { SetFusionDevice(device); }
 // Fusion loop of apdhost_fuse / RunFusion: APD_FUSION_ETH (default), APD_FUSION_TAT_INTERMEDIATE, APD_FUSION_TAT_ADVANCED
 void apdhost_set_fusion_variant(int variant) { SetFusionVariant(variant); }
 
+// Options of apdhost_fuse / RunFusion (apd_fusion_options, `variant` included); nullptr: the defaults
+void apdhost_set_fusion_options(const apd_fusion_options *options)
+{
+    apd_fusion_options o;
+    apd_fusion_default_options(&o);
+    SetFusionOptions(options ? *options : o);
+}
+
 }  // extern "C"

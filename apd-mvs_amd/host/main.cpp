@@ -2,6 +2,13 @@
 //
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
+//       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
+//       [--ply-normals]
+//
+// --fusion-*: the acceptance rule of the ETH fusion (apd_fusion_options, include/apd_mi355x.h: votes a point needs, the three
+// thresholds, the STRONG / WEAK factors); refused with another --fusion, whose loops keep their own thresholds.  --ply-normals:
+// APD.ply with nx ny nz, the reference pixel's normal, for every loop.  A bad value is refused with the usage line before
+// anything is read or written.  Without these flags APD.ply keeps its bytes.
 //
 // --masks [DIR] (default DIR: masks): <dense_folder>/DIR/<%08d>.jpg|pgm are per-view pixel masks, grey < 128 = masked out of
 // PatchMatch (apd_upload_mask: the pixels cost no NCC and leave as depth 0 / UNKNOWN); a view without a file is unmasked, a file
@@ -54,8 +61,54 @@ bool ParseOptions(int argc, char **argv, Options &o)
             dst = strtoull(argv[++i], nullptr, 10);
             return true;
         };
+        // a non-negative finite number that fills the whole token
+        auto real = [](const char *text, float &dst) {
+            char *end = nullptr;
+            const float f = strtof(text, &end);
+            if (end == text || *end != '\0' || !(f >= 0.0f) || f > 3.402823466e+38f) {
+                return false;
+            }
+            dst = f;
+            return true;
+        };
+        auto threshold = [&](float &dst) {
+            const char *text = i + 1 < argc ? argv[++i] : "";
+            if (!real(text, dst)) {
+                fprintf(stderr, "bad value '%s' of %s: a non-negative number\n", text, a.c_str());
+                return false;
+            }
+            o.fusion_thresholds_set = true;
+            return true;
+        };
         uint64_t v = 0;
-        if (a == "--seed") {
+        if (a == "--fusion-min-consistent") {
+            const char *text = i + 1 < argc ? argv[++i] : "";
+            char *end = nullptr;
+            const long n = strtol(text, &end, 10);
+            if (end == text || *end != '\0' || n < 1 || n > APD_MAX_IMAGES) {
+                fprintf(stderr, "bad value '%s' of %s: 1 .. %d\n", text, a.c_str(), APD_MAX_IMAGES);
+                return false;
+            }
+            o.fusion.min_consistent = (int)n;
+            o.fusion_thresholds_set = true;
+        } else if (a == "--fusion-reproj") {
+            if (!threshold(o.fusion.max_reproj_error)) return false;
+        } else if (a == "--fusion-depth") {
+            if (!threshold(o.fusion.max_relative_depth)) return false;
+        } else if (a == "--fusion-angle") {
+            if (!threshold(o.fusion.max_angle)) return false;
+        } else if (a == "--fusion-factors") {
+            const std::string both = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = both.find(',');
+            if (comma == std::string::npos || !real(both.substr(0, comma).c_str(), o.fusion.factor_strong) ||
+                !real(both.substr(comma + 1).c_str(), o.fusion.factor_weak)) {
+                fprintf(stderr, "bad value '%s' of %s: STRONG,WEAK, two non-negative numbers\n", both.c_str(), a.c_str());
+                return false;
+            }
+            o.fusion_thresholds_set = true;
+        } else if (a == "--ply-normals") {
+            o.fusion.ply_normals = 1;
+        } else if (a == "--seed") {
             if (!value(o.seed)) return false;
         } else if (a == "--iters") {
             if (!value(v)) return false;
@@ -134,6 +187,11 @@ bool ParseOptions(int argc, char **argv, Options &o)
             return false;
         }
     }
+    if (o.fusion_thresholds_set && o.fusion_variant != APD_FUSION_ETH) {
+        fprintf(stderr, "--fusion-min-consistent, --fusion-reproj, --fusion-depth, --fusion-angle and --fusion-factors apply to --fusion eth only\n");
+        return false;
+    }
+    o.fusion.variant = o.fusion_variant;
     return true;
 }
 
@@ -259,7 +317,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -273,7 +331,7 @@ int main(int argc, char **argv)
     }
     APD::SetDevice(opt.gpu_index);
     SetFusionDevice(opt.gpu_index);
-    SetFusionVariant(opt.fusion_variant);
+    SetFusionOptions(opt.fusion);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

@@ -29,6 +29,13 @@ struct Options {
     int max_src = 0;        // > 0: keep only the first N sources of each pair.txt entry (they are sorted by score)
     bool single_level = false, keep_maps = false, no_fusion = false;
     int fusion_variant = APD_FUSION_ETH;  // --fusion eth | tat-intermediate | tat-advanced
+    // --fusion-min-consistent N, --fusion-reproj PX, --fusion-depth REL, --fusion-angle RAD, --fusion-factors STRONG,WEAK, --ply-normals
+    apd_fusion_options fusion = [] {
+        apd_fusion_options o;
+        apd_fusion_default_options(&o);
+        return o;
+    }();
+    bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)
     bool clean_exit = false;          // --clean-exit: return from main() instead of _Exit (exit handlers run: profilers)
     double scheduler_free_gb = 0;     // --scheduler-free-gb X: RunMultiDevice's own fit test counts at most X GB of free device memory (main()'s

@@ -493,7 +493,7 @@ def load_colour_images(folder, ids):
 FUSION_VARIANTS = {"eth": 0, "tat_intermediate": 1, "tat_advanced": 2}  # APD_FUSION_* of include/apd_mi355x.h
 
 
-def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth"):
+def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -501,13 +501,25 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     resampled to the depth-map size if it differs (RescaleImageAndCamera, APD.cpp:729-750).  colour_images: optional
     float32 [H, W, 3] arrays (blue, green, red, as load_colour_images returns them) for the point colours; the grey
     images of the scene otherwise (blue = green = red).  block_masks: optional uint8 [H, W] arrays (or None per view), the
-    `blocks/mask_<id>.jpg` of APD.cpp:849-853: reference pixels below 128 are not fused.  Returns the number of points."""
+    `blocks/mask_<id>.jpg` of APD.cpp:849-853: reference pixels below 128 are not fused.  Returns the number of points.
+    options: a FusionOptions (default_fusion_options(min_consistent=2, ...): the ETH loop's acceptance rule, ply_normals,
+    result_on_device; its `variant` is set from `variant`), None for the reference's behaviour.  return_points: also return the
+    points as a Points object (numpy views, or torch tensors on `device` with result_on_device): (count, Points); ply_path may
+    then be None and no file is written."""
     import ctypes as C
+    from . import Points, default_fusion_options
     if variant not in FUSION_VARIANTS:
         raise ValueError("unknown fusion variant %r: one of %s" % (variant, ", ".join(sorted(FUSION_VARIANTS))))
+    if ply_path is None and not return_points:
+        raise ValueError("fuse: neither a PLY file nor the points are asked for")
     L = host_lib()
     L.apdhost_set_fusion_device(int(device))
     L.apdhost_set_fusion_variant(FUSION_VARIANTS[variant])
+    L.apdhost_fuse_opt.restype = C.c_longlong
+    opt = default_fusion_options()
+    if options is not None:
+        C.memmove(C.byref(opt), C.byref(options), C.sizeof(opt))
+    opt.variant = FUSION_VARIANTS[variant]
     V = scene.num_views
     cam_t = type(scene.cameras[0])
     cams = (cam_t * V)()
@@ -551,8 +563,9 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     if block_masks is not None:
         keep = [None if b is None else np.ascontiguousarray(b, np.uint8) for b in block_masks]
         blocks = (C.c_void_p * V)(*[None if b is None else b.ctypes.data for b in keep])
-    n = L.apdhost_fuse(V, C.byref(cams), ptrs(imgs), channels, ptrs(deps), ptrs(nors), ptrs(weaks), blocks, rows, cols, offs, idx,
-                       str(ply_path).encode())
+    handle = C.c_void_p()
+    n = L.apdhost_fuse_opt(C.byref(opt), V, C.byref(cams), ptrs(imgs), channels, ptrs(deps), ptrs(nors), ptrs(weaks), blocks, rows, cols, offs,
+                           idx, None if ply_path is None else str(ply_path).encode(), C.byref(handle) if return_points else None)
     if n < 0:
-        raise RuntimeError("device fusion failed (apd_fuse_views_variant, %s): see stderr" % variant)
-    return int(n)
+        raise RuntimeError("device fusion failed (apd_fuse_views_opt, %s): see stderr" % variant)
+    return (int(n), Points(handle, device)) if return_points else int(n)

@@ -362,6 +362,64 @@ int apd_fuse_views_variant(int variant, int device, int num_views, const apd_cam
                            const uint8_t *const *blocks, const int *rows, const int *cols, const int *pair_offsets,
                            const int *pair_indices, int maps_on_device, const char *ply_path, long long *num_points);
 
+/* Options of one fusion call.  The acceptance rule of the ETH loop (APD.cpp:941-951) as values instead of literals, and the
+ * form of the result.  apd_fusion_default_options sets struct_size and today's behaviour: with it, apd_fuse_views_opt writes
+ * the bytes apd_fuse_views_variant writes.  A vote needs reprojection error < max_reproj_error (pixels), relative depth
+ * difference < max_relative_depth and normal angle < max_angle (radians); it adds exp(-(reproj + depth_weight * depth +
+ * angle_weight * angle)) to the consistency; a pixel becomes a point with at least min_consistent votes and consistency >
+ * factor * votes, factor_strong for a STRONG / UNKNOWN pixel and factor_weak for a WEAK one.  The eight values apply to
+ * APD_FUSION_ETH only: the Tanks and Temples loops keep their own ladder of thresholds that grow with the round k, and a T&T
+ * variant with any of the eight off its default is refused (APD_ERR_UNSUPPORTED).  The output options apply to all three. */
+typedef struct apd_fusion_options {
+    size_t struct_size;           /* sizeof(apd_fusion_options) of the caller's header: first, so that the struct can grow */
+    int    variant;               /* APD_FUSION_ETH | _TAT_INTERMEDIATE | _TAT_ADVANCED */
+    float  max_reproj_error;      /* 2.0      */
+    float  max_relative_depth;    /* 0.01     */
+    float  max_angle;             /* 0.174533 */
+    float  depth_weight;          /* 200      */
+    float  angle_weight;          /* 10       */
+    int    min_consistent;        /* 1; 1 .. APD_MAX_IMAGES */
+    float  factor_strong;         /* 0.3      */
+    float  factor_weak;           /* 0.45     */
+    int    ply_normals;           /* 0: 15-byte records x y z + colour; 1: x y z nx ny nz + colour, 27 bytes */
+    int    result_on_device;      /* where the arrays of an apd_points_t live: 0 host memory, 1 device memory on `device` */
+} apd_fusion_options;
+void apd_fusion_default_options(apd_fusion_options *o);
+
+/* The points of one fusion as a structure of arrays, in the order of the PLY file: views in order, pixels of a view in raster
+ * order.  Point k has
+ *   xyz      3 floats: the reference pixel's lifted point (the reference averages only colour);
+ *   normal   3 floats: the reference pixel's normal as given in normals[view], copied, not renormalised;
+ *   bgr      3 bytes: the colour of the PLY record;
+ *   support  1 byte: the votes the point was accepted with (ETH: num_consistent >= min_consistent; T&T: `count` of the round
+ *            that emitted it);
+ *   view, pixel   int32 each: the index of the reference view and the raster index row * cols + col in it.
+ * The arrays are host memory, or device memory on the call's device when options.result_on_device was set (then nothing is
+ * downloaded unless a PLY file is asked for as well).  They belong to the object and live until apd_points_destroy; an accessor
+ * of an object without points may return NULL. */
+typedef struct apd_points *apd_points_t;
+long long apd_points_count(apd_points_t p);
+int apd_points_on_device(apd_points_t p);
+const float *apd_points_xyz(apd_points_t p);
+const float *apd_points_normal(apd_points_t p);
+const uint8_t *apd_points_bgr(apd_points_t p);
+const uint8_t *apd_points_support(apd_points_t p);
+const int32_t *apd_points_view(apd_points_t p);
+const int32_t *apd_points_pixel(apd_points_t p);
+int apd_points_destroy(apd_points_t p);
+
+/* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
+ * points in memory (*points, released with apd_points_destroy; untouched when the call fails), or both from one fusion.  With
+ * ply_normals the file has the properties x y z nx ny nz (float) before the three colour bytes.  Refused with APD_ERR_INVALID
+ * before any device is touched, message "apd_fuse_views_opt: ...": struct_size other than sizeof(apd_fusion_options), an
+ * unknown variant, a threshold, weight or factor that is negative or not finite, min_consistent outside 1 .. APD_MAX_IMAGES,
+ * ply_path and points both NULL, and everything apd_fuse_views refuses. */
+int apd_fuse_views_opt(const apd_fusion_options *options, int device, int num_views, const apd_camera *cameras,
+                       const float *const *images, int image_channels, const float *const *depths, const float *const *normals,
+                       const uint8_t *const *weaks, const uint8_t *const *blocks, const int *rows, const int *cols,
+                       const int *pair_offsets, const int *pair_indices, int maps_on_device, const char *ply_path,
+                       long long *num_points, apd_points_t *points);
+
 /* Host-side constant of K3 (GenNeighbours, APD.cu:1911 / :1946): its inlier test `dist / (depth_max - depth_min) <
  * ransac_threshold` (dist >= 0) is evaluated on the device as `dist < cut`, the same predicate for every binary32 dist because
  * x -> RN(x / d) is monotone.  Returns 1 and the cut, or 0 when the parameters admit none (the kernel then divides).  Needs
