@@ -165,11 +165,14 @@ def lib():
     L.apd_last_error.restype = C.c_char_p
     L.apd_device_count.restype = C.c_int
     L.apd_exchange_last_error.restype = C.c_char_p
+    L.apd_fusion_last_error.restype = C.c_char_p
     L.apd_fusion_default_options.argtypes = [C.POINTER(FusionOptions)]
     L.apd_fusion_default_options.restype = None
     ipp = C.POINTER(C.c_int)
     L.apd_fuse_views_opt.argtypes = [C.POINTER(FusionOptions), C.c_int, C.c_int, C.c_void_p, fpp, C.c_int, fpp, fpp, fpp, fpp, ipp, ipp, ipp, ipp,
                                      C.c_int, C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_void_p)]
+    L.apd_filter_views.argtypes = [C.POINTER(FusionOptions), C.c_int, C.c_int, C.c_void_p, fpp, fpp, fpp, fpp, ipp, ipp, ipp, ipp, C.c_int,
+                                   fpp, fpp, fpp, C.c_int]
     L.apd_points_count.argtypes = [C.c_void_p]
     L.apd_points_count.restype = C.c_longlong
     L.apd_points_on_device.argtypes = [C.c_void_p]

@@ -26,6 +26,7 @@
 // points at the running count; a host result is one download at the end.  Nothing is sized by pixels x views.
 #include <hip/hip_runtime.h>
 
+#include <float.h>
 #include <stdio.h>
 
 #include <algorithm>
@@ -489,15 +490,50 @@ void free_host_arrays(PointArrays &p)
 
 }  // namespace
 
-int Call::begin(bool eth)
+int check_options(const char *who, const apd_fusion_options *options, bool *preset_out)
+{
+    std::string &err = g_fusion_error;
+    if (!options) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: null options", who);
+    }
+    if (options->struct_size != sizeof(apd_fusion_options)) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: struct_size %zu is not sizeof(apd_fusion_options) = %zu", who, options->struct_size,
+                              sizeof(apd_fusion_options));
+    }
+    const apd_fusion_options o = *options, d = default_options();
+    if (o.variant != APD_FUSION_ETH && o.variant != APD_FUSION_TAT_INTERMEDIATE && o.variant != APD_FUSION_TAT_ADVANCED) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: unknown variant %d", who, o.variant);
+    }
+    const struct {
+        const char *name;
+        float value, preset;
+    } values[] = {{"max_reproj_error", o.max_reproj_error, d.max_reproj_error}, {"max_relative_depth", o.max_relative_depth, d.max_relative_depth},
+                  {"max_angle", o.max_angle, d.max_angle},                      {"depth_weight", o.depth_weight, d.depth_weight},
+                  {"angle_weight", o.angle_weight, d.angle_weight},             {"factor_strong", o.factor_strong, d.factor_strong},
+                  {"factor_weak", o.factor_weak, d.factor_weak}};
+    bool preset = o.min_consistent == d.min_consistent;
+    for (const auto &v : values) {
+        if (!(v.value >= 0.0f) || v.value > FLT_MAX) {
+            return apd::set_error(err, APD_ERR_INVALID, "%s: %s is negative or not finite", who, v.name);
+        }
+        preset = preset && v.value == v.preset;
+    }
+    if (o.min_consistent < 1 || o.min_consistent > APD_MAX_IMAGES) {
+        return apd::set_error(err, APD_ERR_INVALID, "%s: min_consistent %d is outside 1 .. %d", who, o.min_consistent, APD_MAX_IMAGES);
+    }
+    *preset_out = preset;
+    return APD_OK;
+}
+
+int Call::begin(bool eth, bool points)
 {
     g_fusion_error.clear();
     auto invalid = [this](const char *what) { return apd::set_error(g_fusion_error, APD_ERR_INVALID, "%s: %s", who, what); };
-    if (a.num_views <= 0 || !a.cameras || !a.images || !a.depths || !a.normals || (eth && !a.weaks) || !a.rows || !a.cols || !a.pair_offsets ||
-        !a.pair_indices || (!a.ply_path && !a.points) || !a.num_points) {
+    if (a.num_views <= 0 || !a.cameras || (points && !a.images) || !a.depths || !a.normals || (eth && !a.weaks) || !a.rows || !a.cols ||
+        !a.pair_offsets || !a.pair_indices || (points && ((!a.ply_path && !a.points) || !a.num_points))) {
         return invalid("null argument");
     }
-    if (a.image_channels != 1 && a.image_channels != 3) {
+    if (points && a.image_channels != 1 && a.image_channels != 3) {
         return invalid("images have 1 (grey) or 3 (blue, green, red) channels");
     }
     for (int i = 0; i < a.num_views; ++i) {
@@ -561,9 +597,15 @@ int Call::alloc_common()
             staging_ = nullptr;  // pageable downloads then
         }
     }
-    g_fusion_ms[0] = ms_since(t_lap_);
-    t_lap_ = std::chrono::steady_clock::now();
+    g_fusion_ms[0] = lap();
     return APD_OK;
+}
+
+double Call::lap()
+{
+    const double ms = ms_since(t_lap_);
+    t_lap_ = std::chrono::steady_clock::now();
+    return ms;
 }
 
 int Call::collect(int i, const uint8_t *state, uint8_t accepted, const float *normal)
@@ -645,8 +687,7 @@ void Call::release_points()
 
 int Call::finish()
 {
-    g_fusion_ms[1] = ms_since(t_lap_);
-    t_lap_ = std::chrono::steady_clock::now();
+    g_fusion_ms[1] = lap();
     apd_points *pts = nullptr;
     if (a.points) {
         HIP_TRY(hipDeviceSynchronize());  // the last view's compaction

@@ -3,7 +3,9 @@
 // checks, the device memory of a call, the per-view geometry and maps, the scratch of the point compaction, the download of a
 // view's points, the PLY file, the points in memory (apd_points_t), and the per-thread error / timing that apd_fusion_last_error
 // and apd_fusion_last_timing report.
-// A variant derives from Call and adds its own view members, scratch and kernels.
+// A variant derives from Call and adds its own view members, scratch and kernels.  The geometric filter (apd_filter.hip,
+// apd_filter_views) derives from it too: it shares the argument checks, the memory and the geometry-and-maps half of a view, and
+// takes no images and makes no points.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -66,6 +68,11 @@ struct Args {
     apd_points_t *points = nullptr;  // apd_fuse_views_opt: where the points in memory go; then ply_path may be null
 };
 
+// What apd_fuse_views_opt and apd_filter_views refuse in their options, APD_ERR_INVALID with "<who>: ...": null, a struct_size of
+// another header, an unknown variant, one of the seven float values negative or not finite, min_consistent outside
+// 1 .. APD_MAX_IMAGES.  *preset: the eight values are the defaults.
+int check_options(const char *who, const apd_fusion_options *options, bool *preset);
+
 // The ETH fusion (apd_fusion.hip) for apd_fuse_views_opt, which lives beside the T&T fusions (apd_fusion_tat.hip)
 int run_eth(const char *who, const Args &args);
 
@@ -110,8 +117,8 @@ protected:
 
     // First step of every variant.  Clears the last error and checks the arguments: APD_ERR_INVALID with "<who>: ..." before any
     // device is touched.  eth: the weak maps are required, and a view that is its own source is pointed to the host fusion.  Then
-    // selects the device.
-    int begin(bool eth);
+    // selects the device.  points = false (the filter): no images, no PLY file and no points are asked for or looked at.
+    int begin(bool eth, bool points = true);
 
     // *out = the caller's map if the maps are on the device, else a device copy of it
     template <typename T> hipError_t device_map(const T *map, size_t bytes, const T **out)
@@ -129,8 +136,8 @@ protected:
         return e;
     }
 
-    // What DevView and TatView have in common, but for the block map: the geometry of cameras[i], and the image, depth and normal maps
-    template <typename V> int fill_view(int i, V &v)
+    // The geometry of cameras[i] and the depth and normal maps: what every view of every variant and of the filter has
+    template <typename V> int fill_maps(int i, V &v)
     {
         const apd_camera &c = a.cameras[i];
         memcpy(v.geo.K, c.K, sizeof(v.geo.K));
@@ -142,23 +149,16 @@ protected:
         v.geo.centre[2] = -(c.R[2] * c.t[0] + c.R[5] * c.t[1] + c.R[8] * c.t[2]);
         v.geo.rows = a.rows[i];
         v.geo.cols = a.cols[i];
-        v.image = a.images[i];
-        v.depth = a.depths[i];
-        v.normal = a.normals[i];
-        if (!a.maps_on_device) {
-            const size_t n = (size_t)pixels(i);
-            float *g, *d, *nm;
-            HIP_TRY(alloc(n * 4 * a.image_channels, &g));
-            HIP_TRY(alloc(n * 4, &d));
-            HIP_TRY(alloc(n * 12, &nm));
-            HIP_TRY(hipMemcpy(g, a.images[i], n * 4 * a.image_channels, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d, a.depths[i], n * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(nm, a.normals[i], n * 12, hipMemcpyHostToDevice));
-            v.image = g;
-            v.depth = d;
-            v.normal = nm;
-        }
+        HIP_TRY(device_map(a.depths[i], (size_t)pixels(i) * 4, &v.depth));
+        HIP_TRY(device_map(a.normals[i], (size_t)pixels(i) * 12, &v.normal));
         return APD_OK;
+    }
+
+    // What DevView and TatView have in common, but for the block map: fill_maps and the image
+    template <typename V> int fill_view(int i, V &v)
+    {
+        HIP_TRY(device_map(a.images[i], (size_t)pixels(i) * 4 * a.image_channels, &v.image));
+        return fill_maps(i, v);
     }
 
     // The optional block map of view i, after the variant's own maps: the last upload of a view, as it always was
@@ -190,6 +190,8 @@ protected:
     // Takes the time of the views, brings a host result down, releases the device memory, writes the file, and then sets
     // *num_points and *points.
     int finish();
+    // ms since the constructor or the last lap(): the set-up ends and the views end where a variant says so
+    double lap();
 
 private:
     void release();

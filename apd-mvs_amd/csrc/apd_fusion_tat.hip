@@ -388,34 +388,11 @@ extern "C" int apd_fuse_views_opt(const apd_fusion_options *options, int device,
 {
     const char *who = "apd_fuse_views_opt";
     std::string &err = apd_fusion::g_fusion_error;
-    if (!options) {
-        return apd::set_error(err, APD_ERR_INVALID, "%s: null options", who);
+    bool preset = false;
+    if (const int rc = apd_fusion::check_options(who, options, &preset); rc != APD_OK) {
+        return rc;
     }
-    if (options->struct_size != sizeof(apd_fusion_options)) {
-        return apd::set_error(err, APD_ERR_INVALID, "%s: struct_size %zu is not sizeof(apd_fusion_options) = %zu", who, options->struct_size,
-                              sizeof(apd_fusion_options));
-    }
-    const apd_fusion_options o = *options, d = apd_fusion::default_options();
-    if (o.variant != APD_FUSION_ETH && o.variant != APD_FUSION_TAT_INTERMEDIATE && o.variant != APD_FUSION_TAT_ADVANCED) {
-        return apd::set_error(err, APD_ERR_INVALID, "%s: unknown variant %d", who, o.variant);
-    }
-    const struct {
-        const char *name;
-        float value, preset;
-    } values[] = {{"max_reproj_error", o.max_reproj_error, d.max_reproj_error}, {"max_relative_depth", o.max_relative_depth, d.max_relative_depth},
-                  {"max_angle", o.max_angle, d.max_angle},                      {"depth_weight", o.depth_weight, d.depth_weight},
-                  {"angle_weight", o.angle_weight, d.angle_weight},             {"factor_strong", o.factor_strong, d.factor_strong},
-                  {"factor_weak", o.factor_weak, d.factor_weak}};
-    bool preset = o.min_consistent == d.min_consistent;
-    for (const auto &v : values) {
-        if (!(v.value >= 0.0f) || v.value > FLT_MAX) {
-            return apd::set_error(err, APD_ERR_INVALID, "%s: %s is negative or not finite", who, v.name);
-        }
-        preset = preset && v.value == v.preset;
-    }
-    if (o.min_consistent < 1 || o.min_consistent > APD_MAX_IMAGES) {
-        return apd::set_error(err, APD_ERR_INVALID, "%s: min_consistent %d is outside 1 .. %d", who, o.min_consistent, APD_MAX_IMAGES);
-    }
+    const apd_fusion_options o = *options;
     if (!ply_path && !points) {
         return apd::set_error(err, APD_ERR_INVALID, "%s: ply_path and points are both NULL", who);
     }

@@ -116,16 +116,19 @@ void RunFusion(const path &dense_folder, const std::vector<Problem> &problems) {
 // Inputs of the fusion besides the maps: colour image, camera, optional block mask of every view, resampled to the size of
 // the maps when that differs from the image's (RescaleImageAndCamera, APD.cpp:729-750), and the sources of every view as view
 // indices.  maps: host maps (RunFusionWithMaps) or nullptr with map_cols x map_rows > 0 (the maps are on the device) or
-// nullptr with 0 x 0 (read the files).
+// nullptr with 0 x 0 (read the files).  for_filter: the inputs of the geometric filter (--filtered-maps) -- no colour image (its
+// size is the grey image's, which the passes have decoded), the weak maps whatever the fusion variant, and no progress lines.
 namespace {
 
 // log: where the reference's progress lines go ("Reading image ...", "Fusing image ...", APD.cpp:855, :899); the prefetch worker
 // collects them and RunFusionOnDevice prints them where the reference would, after the passes' own lines.
 bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> &problems, const std::vector<FinalMaps> *maps, int map_cols,
                            int map_rows, std::vector<FusionView> &views, std::vector<std::vector<int>> &sources, unsigned threads = 0,
-                           std::ostream *log = nullptr)
+                           std::ostream *log = nullptr, bool for_filter = false)
 {
-    std::ostream &out = log ? *log : std::cout;
+    std::ostringstream unheard;
+    std::ostream &out = for_filter ? unheard : log ? *log : std::cout;
+    const bool need_weak = for_filter || g_fusion_variant == APD_FUSION_ETH;
     const bool on_device = !maps && map_cols > 0 && map_rows > 0;
     views.assign(problems.size(), FusionView());
     std::unordered_map<int, int> index_of_id;
@@ -140,7 +143,8 @@ bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> 
     ParallelFor(problems.size(), [&](size_t i) {
         const Problem &problem = problems[i];
         FusionView &v = views[i];
-        if (!ReadColorImage(dense_folder / path("images") / path(ToFormatIndex(problem.ref_image_id)), v.image)) {
+        const path image_stem = dense_folder / path("images") / path(ToFormatIndex(problem.ref_image_id));
+        if (!(for_filter ? ReadGrayImageShared(image_stem, v.image) : ReadColorImage(image_stem, v.image))) {
             failed[i] = 1;
             return;
         }
@@ -155,11 +159,11 @@ bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> 
             } else {
                 ReadBinMat(problem.result_folder / path("depths.dmb"), v.depth);
                 ReadBinMat(problem.result_folder / path("normals.dmb"), v.normal);
-                if (g_fusion_variant == APD_FUSION_ETH) {  // the T&T loops read depths and normals only (APD.cpp:1023-1024, :1190-1191)
+                if (need_weak) {  // the T&T loops read depths and normals only (APD.cpp:1023-1024, :1190-1191)
                     ReadBinMat(problem.result_folder / path("weak.bin"), v.weak);
                 }
             }
-            if (v.depth.empty() || v.normal.empty() || (v.weak.empty() && g_fusion_variant == APD_FUSION_ETH)) {
+            if (v.depth.empty() || v.normal.empty() || (v.weak.empty() && need_weak)) {
                 std::cerr << "Missing maps of view " << problem.ref_image_id << " in " << problem.result_folder << std::endl;
                 failed[i] = 1;
                 return;
@@ -170,6 +174,14 @@ bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> 
         if (cols != v.image.cols || rows != v.image.rows) {  // RescaleImageAndCamera, APD.cpp:729-750
             const float scale_x = cols / static_cast<float>(v.image.cols);
             const float scale_y = rows / static_cast<float>(v.image.rows);
+            v.cam.K[0] *= scale_x;
+            v.cam.K[2] *= scale_x;
+            v.cam.K[4] *= scale_y;
+            v.cam.K[5] *= scale_y;
+        }
+        if (for_filter) {
+            v.image = Mat();  // the cache's matrix: looked at for its size only
+        } else if (cols != v.image.cols || rows != v.image.rows) {
             // the reference resizes the 8-bit colour image: each channel resampled, then rounded back to 8 bit
             const size_t n_in = (size_t)v.image.rows * v.image.cols, n_out = (size_t)rows * cols;
             Mat out(rows, cols, MAT_32FC3), plane(v.image.rows, v.image.cols, MAT_32FC1), scaled;
@@ -183,10 +195,6 @@ bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> 
                 }
             }
             v.image = out;
-            v.cam.K[0] *= scale_x;
-            v.cam.K[2] *= scale_x;
-            v.cam.K[4] *= scale_y;
-            v.cam.K[5] *= scale_y;
         }
         v.cam.width = cols;
         v.cam.height = rows;
@@ -434,6 +442,125 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
         exit(EXIT_FAILURE);
     }
     std::cout << "Fused " << count << " points into " << ply_path << std::endl;
+}
+
+// ---- --filtered-maps: the geometric filter (apd_filter_views, csrc/apd_filter.hip) ----
+
+namespace {
+
+// Filters the views whose maps are given (host pointers, or device pointers on the fusion device with maps_on_device; blocks may be
+// null) and writes depths_filtered.dmb, consistency.dmb and votes.bin into every view's result folder.  The rule is the fusion's
+// (--fusion-*); a Tanks and Temples variant has refused those flags, so the filter then runs the defaults.
+void filter_and_write(const std::vector<Problem> &problems, const std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources,
+                      const float *const *depths, const float *const *normals, const uint8_t *const *weaks, const uint8_t *const *blocks,
+                      int cols, int rows, int maps_on_device)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const int V = (int)views.size();
+    std::vector<apd_camera> cams(V);
+    std::vector<int> rws(V), cls(V), offs(V + 1, 0), idx;
+    std::vector<Mat> depth(V), votes(V), consistency(V);
+    std::vector<float *> depth_out(V), consistency_out(V);
+    std::vector<uint8_t *> votes_out(V);
+    for (int i = 0; i < V; ++i) {
+        cams[i] = views[i].cam;
+        rws[i] = rows > 0 ? rows : views[i].depth.rows;
+        cls[i] = cols > 0 ? cols : views[i].depth.cols;
+        idx.insert(idx.end(), sources[i].begin(), sources[i].end());
+        offs[i + 1] = (int)idx.size();
+        depth[i].create(rws[i], cls[i], MAT_32FC1);
+        votes[i].create(rws[i], cls[i], MAT_8UC1);
+        consistency[i].create(rws[i], cls[i], MAT_32FC1);
+        depth_out[i] = depth[i].ptr<float>();
+        votes_out[i] = votes[i].ptr<uint8_t>();
+        consistency_out[i] = consistency[i].ptr<float>();
+    }
+    if (idx.empty()) {
+        idx.push_back(0);
+    }
+    apd_fusion_options rule = fusion_options();
+    rule.variant = APD_FUSION_ETH;
+    const int st = apd_filter_views(&rule, g_fusion_device, V, cams.data(), depths, normals, weaks, blocks, rws.data(), cls.data(), offs.data(),
+                                    idx.data(), maps_on_device, depth_out.data(), votes_out.data(), consistency_out.data(), 0);
+    if (st != APD_OK) {
+        std::cerr << apd_fusion_last_error() << std::endl;
+        exit(EXIT_FAILURE);
+    }
+    double ms_setup = 0, ms_views = 0;
+    apd_fusion_last_timing(&ms_setup, &ms_views, nullptr);
+    for (int i = 0; i < V; ++i) {
+        const path &folder = problems[i].result_folder;
+        std::filesystem::create_directories(folder);
+        const std::pair<const char *, const Mat *> files[3] = {{"depths_filtered.dmb", &depth[i]}, {"consistency.dmb", &consistency[i]}, {"votes.bin", &votes[i]}};
+        for (const auto &f : files) {
+            if (!WriteBinMat(folder / f.first, *f.second)) {
+                std::cerr << "cannot write " << (folder / f.first).string() << std::endl;
+                exit(EXIT_FAILURE);
+            }
+        }
+    }
+    std::cout << "Filtered maps of " << V << " views: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count()
+              << " ms (set-up " << (long long)ms_setup << ", views " << (long long)ms_views << ")" << std::endl;
+}
+
+}  // namespace
+
+// From the four state files of every view, as RunFusion reads them
+void RunFilter(const path &dense_folder, const std::vector<Problem> &problems)
+{
+    std::vector<FusionView> views;
+    std::vector<std::vector<int>> sources;
+    if (!prepare_fusion_inputs(dense_folder, problems, nullptr, 0, 0, views, sources, 0, nullptr, true)) {
+        exit(EXIT_FAILURE);
+    }
+    const int V = (int)views.size();
+    std::vector<const float *> deps(V), nors(V);
+    std::vector<const uint8_t *> weaks(V), blocks(V, nullptr);
+    bool any_block = false;
+    for (int i = 0; i < V; ++i) {
+        deps[i] = views[i].depth.ptr<float>();
+        nors[i] = views[i].normal.ptr<float>();
+        weaks[i] = views[i].weak.ptr<uint8_t>();
+        if (!views[i].block.empty()) {
+            blocks[i] = views[i].block.ptr<uint8_t>();
+            any_block = true;
+        }
+    }
+    filter_and_write(problems, views, sources, deps.data(), nors.data(), weaks.data(), any_block ? blocks.data() : nullptr, 0, 0, 0);
+}
+
+// The final maps are on `device` (cols x rows each): cameras and block masks are read here, the masks go up, only the outputs come
+// down
+void RunFilterOnDevice(const path &dense_folder, const std::vector<Problem> &problems, int device, int cols, int rows,
+                       const std::vector<const float *> &depths, const std::vector<const float *> &normals, const std::vector<const uint8_t *> &weaks)
+{
+    std::vector<FusionView> views;
+    std::vector<std::vector<int>> sources;
+    if (!prepare_fusion_inputs(dense_folder, problems, nullptr, cols, rows, views, sources, 0, nullptr, true)) {
+        exit(EXIT_FAILURE);
+    }
+    const int V = (int)views.size();
+    std::vector<const uint8_t *> blocks(V, nullptr);
+    std::vector<void *> owned;
+    for (int i = 0; i < V; ++i) {
+        if (views[i].block.empty()) {
+            continue;
+        }
+        void *p = nullptr;
+        if (apd_device_malloc(device, (size_t)rows * cols, &p) != APD_OK || apd_device_memcpy(device, p, views[i].block.data(), (size_t)rows * cols) != APD_OK) {
+            std::cerr << "filter: upload of a block mask failed: " << apd_exchange_last_error() << std::endl;
+            exit(EXIT_FAILURE);
+        }
+        owned.push_back(p);
+        blocks[i] = (const uint8_t *)p;
+    }
+    const int fusion_device = g_fusion_device;
+    g_fusion_device = device;
+    filter_and_write(problems, views, sources, depths.data(), normals.data(), weaks.data(), owned.empty() ? nullptr : blocks.data(), cols, rows, 1);
+    g_fusion_device = fusion_device;
+    for (void *p : owned) {
+        apd_device_free(device, p);
+    }
 }
 
 extern "C" {

@@ -3,7 +3,12 @@
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
-//       [--ply-normals]
+//       [--ply-normals] [--filtered-maps]
+//
+// --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
+// (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
+// (the defaults with a Tanks and Temples --fusion) and <dense>/blocks like the fusion.  Every driver takes it, with or without
+// --no-fusion, and the files stay when the state files are removed.
 //
 // --fusion-*: the acceptance rule of the ETH fusion (apd_fusion_options, include/apd_mi355x.h: votes a point needs, the three
 // thresholds, the STRONG / WEAK factors); refused with another --fusion, whose loops keep their own thresholds.  --ply-normals:
@@ -108,6 +113,8 @@ bool ParseOptions(int argc, char **argv, Options &o)
             o.fusion_thresholds_set = true;
         } else if (a == "--ply-normals") {
             o.fusion.ply_normals = 1;
+        } else if (a == "--filtered-maps") {
+            o.filtered_maps = true;
         } else if (a == "--seed") {
             if (!value(o.seed)) return false;
         } else if (a == "--iters") {
@@ -317,7 +324,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -449,6 +456,9 @@ int main(int argc, char **argv)
         if (pass.iteration % 4 == 3) {
             printf("Round: %d done\n", pass.level);
         }
+    }
+    if (opt.filtered_maps) {
+        RunFilter(opt.dense_folder, problems);
     }
     if (!opt.no_fusion) {
         RunFusion(opt.dense_folder, problems);  // main.cpp:219

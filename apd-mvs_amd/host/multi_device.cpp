@@ -324,6 +324,7 @@ struct Scheduler {
     void ExportAndPublish(int r, Lane &lane, const Pass &pass, int v, ViewIo &io);
     void ReleasePassBuffers();
     void GatherFinalMaps();
+    void Filter();
     void WriteKeptMaps();
     void PrintExchangeSummary();
     void Fuse();
@@ -1013,6 +1014,20 @@ void Scheduler::PrintExchangeSummary()
            apd_exchange_backend(exchange));
 }
 
+// --filtered-maps: on the gathered maps, where they are
+void Scheduler::Filter()
+{
+    std::vector<const float *> d(V), n(V);
+    for (int v = 0; v < V; ++v) {
+        d[v] = fuse_depth[v].as<float>();
+        n[v] = fuse_normal[v].as<float>();
+    }
+    if (LW != W0 || LH != H0) {
+        throw std::runtime_error("the last pass did not run at the full resolution");  // BuildSchedule ends at scale 1
+    }
+    RunFilterOnDevice(opt.dense_folder, problems, ranks[0].device, W0, H0, d, n, fuse_weak);
+}
+
 void Scheduler::Fuse()
 {
     std::filesystem::create_directories(opt.dense_folder / "APD");
@@ -1073,6 +1088,9 @@ int RunMultiDevice(const Options &opt, std::vector<Problem> &problems)
         const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_all).count();
         printf("All passes done: %lld ms\n", (long long)ms);
         ms_gather = stage.lap();
+        if (opt.filtered_maps) {
+            s.Filter();
+        }
         if (!opt.no_fusion) {
             s.Fuse();
         }

@@ -35,6 +35,7 @@ struct Options {
         apd_fusion_default_options(&o);
         return o;
     }();
+    bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)
     bool clean_exit = false;          // --clean-exit: return from main() instead of _Exit (exit handlers run: profilers)
@@ -169,5 +170,13 @@ void RunFusionOnDevice(FusionPrefetch *inputs, const std::vector<const float *> 
                        const std::vector<const uint8_t *> &weaks);
 void CancelFusionInputs(FusionPrefetch *inputs);
 bool FusionInputsFailed(const FusionPrefetch *inputs, std::string *why);
+
+// --filtered-maps: the geometric filter (apd_filter_views) with the rule of SetFusionOptions on every view's final maps, read from
+// the result folders (RunFilter) or resident on `device` (RunFilterOnDevice: only the outputs come down); writes
+// depths_filtered.dmb and consistency.dmb (as depths.dmb) and votes.bin (as weak.bin) into every result folder.  Honours
+// <dense>/blocks like the fusion.
+void RunFilter(const path &dense_folder, const std::vector<Problem> &problems);
+void RunFilterOnDevice(const path &dense_folder, const std::vector<Problem> &problems, int device, int cols, int rows,
+                       const std::vector<const float *> &depths, const std::vector<const float *> &normals, const std::vector<const uint8_t *> &weaks);
 
 #endif  // APD_MI355X_HOST_SCHEDULE_H_

@@ -569,3 +569,85 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     if n < 0:
         raise RuntimeError("device fusion failed (apd_fuse_views_opt, %s): see stderr" % variant)
     return (int(n), Points(handle, device)) if return_points else int(n)
+
+
+class FilteredMaps:
+    """One view of filter_maps: depth float32 [H, W] (0 where the pixel is rejected), votes uint8 [H, W] (agreeing sources),
+    consistency float32 [H, W] (sum of exp(-score) over the agreeing sources)."""
+
+    def __init__(self, depth, votes, consistency):
+        self.depth, self.votes, self.consistency = depth, votes, consistency
+
+    def __iter__(self):
+        return iter((self.depth, self.votes, self.consistency))
+
+
+def filter_maps(scene, results, device=0, block_masks=None, options=None, on_device=False):
+    """The geometric filter (apd_filter_views, csrc/apd_filter.hip) on the gathered maps: per view what the vote test of RunFusion
+    (APD.cpp:896-951) says about its own pixels, every view judged against the unfiltered maps of its sources (nothing is
+    consumed, so the result of a view depends on no other view's).  Takes the maps of `results` like fuse() (weak maps resampled
+    to the depth-map size, K scaled when the maps are not at the camera's size) and no images.  block_masks as in fuse().
+    options: a FusionOptions (the ETH loop's acceptance rule; default_fusion_options(min_consistent=2, ...)), None for the
+    reference's literals.  Returns a list of FilteredMaps, one per view: numpy arrays, or with on_device=True torch tensors on
+    `device` (the maps go up as tensors, the filter writes into the returned ones, nothing comes down)."""
+    import ctypes as C
+    from . import ApdError, default_fusion_options, lib
+    L = lib()
+    opt = default_fusion_options()
+    if options is not None:
+        C.memmove(C.byref(opt), C.byref(options), C.sizeof(opt))
+    V = scene.num_views
+    cam_t = type(scene.cameras[0])
+    cams = (cam_t * V)()
+    rows, cols = (C.c_int * V)(), (C.c_int * V)()
+    if on_device:
+        import torch
+        dev = torch.device("cuda", int(device))
+        place = lambda a: torch.from_numpy(a).to(dev)
+        empty = lambda shape, dt: torch.empty(shape, dtype={np.float32: torch.float32, np.uint8: torch.uint8}[dt], device=dev)
+        addr = lambda a: a.data_ptr()
+    else:
+        place = lambda a: a
+        empty = lambda shape, dt: np.empty(shape, dt)
+        addr = lambda a: a.ctypes.data
+    deps, nors, weaks, outs = [], [], [], []
+    for v in range(V):
+        st = results[v]
+        h, w = st.depth.shape
+        cam = cam_t.from_buffer_copy(scene.cameras[v])
+        if cam.width > 0 and cam.height > 0 and (cam.height, cam.width) != (h, w):  # RescaleImageAndCamera, APD.cpp:729-750
+            sx = np.float32(w) / np.float32(cam.width)
+            sy = np.float32(h) / np.float32(cam.height)
+            cam.K[0] = float(np.float32(cam.K[0]) * sx)
+            cam.K[2] = float(np.float32(cam.K[2]) * sx)
+            cam.K[4] = float(np.float32(cam.K[4]) * sy)
+            cam.K[5] = float(np.float32(cam.K[5]) * sy)
+        cams[v] = cam
+        rows[v], cols[v] = h, w
+        deps.append(place(np.ascontiguousarray(st.depth, np.float32)))
+        nors.append(place(np.ascontiguousarray(st.normal, np.float32)))
+        weaks.append(place(np.ascontiguousarray(rescale_nearest(st.weak, w, h), np.uint8)))
+        outs.append(FilteredMaps(empty((h, w), np.float32), empty((h, w), np.uint8), empty((h, w), np.float32)))
+    offs = (C.c_int * (V + 1))()
+    flat = []
+    for v in range(V):
+        offs[v] = len(flat)
+        flat += [s for s in scene.pairs[v] if s < V]  # source-only views have no maps to check against
+    offs[V] = len(flat)
+    idx = (C.c_int * max(len(flat), 1))(*flat)
+
+    def ptrs(arrs):
+        return (C.c_void_p * V)(*[None if a is None else addr(a) for a in arrs])
+
+    blocks = None
+    if block_masks is not None:
+        keep = [None if b is None else place(np.ascontiguousarray(b, np.uint8)) for b in block_masks]
+        blocks = ptrs(keep)
+    if on_device:
+        torch.cuda.synchronize(dev)  # the uploads, before the library's own stream reads them
+    rc = L.apd_filter_views(C.byref(opt), int(device), V, C.byref(cams), ptrs(deps), ptrs(nors), ptrs(weaks), blocks, rows, cols, offs, idx,
+                            int(on_device), ptrs([o.depth for o in outs]), ptrs([o.votes for o in outs]),
+                            ptrs([o.consistency for o in outs]), int(on_device))
+    if rc != 0:
+        raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+    return outs

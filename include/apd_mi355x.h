@@ -420,6 +420,28 @@ int apd_fuse_views_opt(const apd_fusion_options *options, int device, int num_vi
                        const int *pair_offsets, const int *pair_indices, int maps_on_device, const char *ply_path,
                        long long *num_points, apd_points_t *points);
 
+/* The geometric filter: per view what the vote test of RunFusion (APD.cpp:896-951) says about its own pixels -- a filtered depth
+ * map, the number of agreeing sources and the consistency score -- without the loop's consumption of source pixels (`masks`,
+ * APD.cpp:928, :959), which makes a view's result depend on the views fused before it.  Inputs as apd_fuse_views_opt, minus the
+ * images; of `options` only struct_size, variant (APD_FUSION_ETH) and the eight values of the rule are read.  Pixel p of view i:
+ * where blocks[i][p] < 128 or depths[i][p] <= 0, votes = 0, consistency = 0 and depth_out = 0.  Otherwise the pixel is lifted
+ * (Get3DPointonWorld) and, for each source in pair.txt order, projected into it (APD.cpp:896-899); a source pixel with depth > 0
+ * that passes the three thresholds (APD.cpp:941) adds 1 to votes and exp(-(reproj + depth_weight * depth + angle_weight * angle))
+ * to consistency (a float sum in source order from 0, APD.cpp:944-947); depth_out = depths[i][p] if votes >= min_consistent and
+ * consistency > factor * votes (APD.cpp:950-951), else 0.  votes and consistency are written for every pixel, accepted or not.
+ * Every view is judged against the unfiltered maps of its sources: the result of a view depends on no other view's.
+ * depth_out, votes_out, consistency_out: per-view caller-owned buffers of rows[i] * cols[i] elements, device pointers on
+ * `device` with outputs_on_device != 0, host pointers otherwise; a table or any entry may be NULL and is then not written.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_filter_views: ...": what apd_fuse_views_opt refuses in
+ * its options, a variant other than APD_FUSION_ETH, no output pointer at all, an output pointer equal to an input map, and
+ * everything apd_fuse_views refuses of its views.  apd_fusion_last_error / apd_fusion_last_timing report on it (set-up, views; the
+ * file time is 0). */
+int apd_filter_views(const apd_fusion_options *options, int device, int num_views, const apd_camera *cameras,
+                     const float *const *depths, const float *const *normals, const uint8_t *const *weaks,
+                     const uint8_t *const *blocks, const int *rows, const int *cols, const int *pair_offsets,
+                     const int *pair_indices, int maps_on_device, float *const *depth_out, uint8_t *const *votes_out,
+                     float *const *consistency_out, int outputs_on_device);
+
 /* Host-side constant of K3 (GenNeighbours, APD.cu:1911 / :1946): its inlier test `dist / (depth_max - depth_min) <
  * ransac_threshold` (dist >= 0) is evaluated on the device as `dist < cut`, the same predicate for every binary32 dist because
  * x -> RN(x / d) is monotone.  Returns 1 and the cut, or 0 when the parameters admit none (the kernel then divides).  Needs
