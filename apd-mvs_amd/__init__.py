@@ -176,9 +176,11 @@ def lib():
     L.apd_points_count.argtypes = [C.c_void_p]
     L.apd_points_count.restype = C.c_longlong
     L.apd_points_on_device.argtypes = [C.c_void_p]
-    for n in ("xyz", "normal", "bgr", "support", "view", "pixel"):
+    for n in ("xyz", "normal", "bgr", "support", "view", "pixel", "sources"):
         getattr(L, "apd_points_" + n).argtypes = [C.c_void_p]
         getattr(L, "apd_points_" + n).restype = C.c_void_p
+    L.apd_points_visibility.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.apd_points_write_vis.argtypes = [C.c_void_p, C.c_char_p]
     L.apd_points_destroy.argtypes = [C.c_void_p]
     L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     _lib = L
@@ -220,12 +222,16 @@ class _Borrowed:
 class Points:
     """One fusion's points (apd_points_t) in PLY order as arrays: xyz float32 [N, 3] (the reference pixel's lifted point),
     normal float32 [N, 3] (its normal as given, not renormalised), bgr uint8 [N, 3], support uint8 [N] (the votes the point was
-    accepted with), view and pixel int32 [N] (reference view and raster index in it).  A host result gives read-only numpy views
-    of the library's memory, valid while an array or this object lives; a device result gives torch tensors on its device,
-    filled by device-to-device copies (no host round trip) and independent of this object."""
+    accepted with), view and pixel int32 [N] (reference view and raster index in it), sources uint32 [N] (bit j: the j-th source
+    of the point's view is one of those votes; a device result holds the same bit patterns as int32).  A host result gives
+    read-only numpy views of the library's memory, valid while an array or this object lives; a device result gives torch tensors
+    on its device, filled by device-to-device copies (no host round trip) and independent of this object.  visibility() and
+    write_vis() are the library's (apd_points_visibility, apd_points_write_vis); the object keeps the library's points for them
+    until close()."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
-               ("pixel", 1, "<i4", 4))
+               ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
+    _TORCH = {"<f4": "float32", "|u1": "uint8", "<i4": "int32", "<u4": "int32", "<i8": "int64"}
 
     def __init__(self, handle, device=0):
         L = lib()
@@ -233,27 +239,53 @@ class Points:
         self.device = int(device)
         self.count = int(L.apd_points_count(handle))
         self.on_device = bool(L.apd_points_on_device(handle))
+        self._lists = None
         for name, width, typestr, size in self._FIELDS:
             address = getattr(L, "apd_points_" + name)(handle)
-            shape = (self.count, width) if width > 1 else (self.count,)
-            if self.on_device:
-                import torch
-                t = torch.empty(shape, dtype={"<f4": torch.float32, "|u1": torch.uint8, "<i4": torch.int32}[typestr],
-                                device=torch.device("cuda", self.device))
-                if self.count:
-                    rc = L.apd_device_memcpy(self.device, t.data_ptr(), address, self.count * width * size)
-                    if rc != 0:
-                        raise ApdError("apd error %d copying the points: %s" % (rc, L.apd_exchange_last_error()))
-                setattr(self, name, t)
-            elif self.count:
-                setattr(self, name, np.asarray(_Borrowed(self, address, shape, typestr)))
-            else:
-                setattr(self, name, np.empty(shape, np.dtype(typestr)))
+            setattr(self, name, self._array(address, (self.count, width) if width > 1 else (self.count,), typestr, size))
+
+    def _array(self, address, shape, typestr, size):
+        """`shape` elements at `address` of the library's memory: a torch tensor (a device-to-device copy) or a numpy view."""
+        count = int(np.prod(shape))
         if self.on_device:
-            self.close()   # the tensors own their memory
+            import torch
+            t = torch.empty(shape, dtype=getattr(torch, self._TORCH[typestr]), device=torch.device("cuda", self.device))
+            if count:
+                rc = lib().apd_device_memcpy(self.device, t.data_ptr(), address, count * size)
+                if rc != 0:
+                    raise ApdError("apd error %d copying the points: %s" % (rc, lib().apd_exchange_last_error()))
+            return t
+        if count:
+            return np.asarray(_Borrowed(self, address, shape, typestr))
+        return np.empty(shape, np.dtype(typestr))
 
     def __len__(self):
         return self.count
+
+    def visibility(self):
+        """(offsets int64 [N + 1], views int32 [offsets[N]]): point k is seen by views[offsets[k]:offsets[k + 1]], its own view first,
+        then its agreeing sources as indices of views of the fusion call in ascending bit order of sources[k].  Built by the library
+        on the first call, on the device for a device result."""
+        if self._lists is None:
+            if not self._p:
+                raise ApdError("Points.visibility: the points are closed")
+            L = lib()
+            offsets, views = C.c_void_p(), C.c_void_p()
+            rc = L.apd_points_visibility(self._p, C.byref(offsets), C.byref(views))
+            if rc != 0:
+                raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+            off = self._array(offsets.value, (self.count + 1,), "<i8", 8)
+            self._lists = (off, self._array(views.value, (int(off[-1]),), "<i4", 4))
+        return self._lists
+
+    def write_vis(self, path):
+        """COLMAP's fused.ply.vis of these points (apd_points_write_vis): the lists of visibility()."""
+        if not self._p:
+            raise ApdError("Points.write_vis: the points are closed")
+        L = lib()
+        rc = L.apd_points_write_vis(self._p, str(path).encode())
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
 
     def close(self):
         if self._p:

@@ -21,9 +21,12 @@
 // min_consistent (the only early rejection is the one there always was: a pixel without any vote has nothing to claim).
 //
 // The second half of the file is the host driver of every device fusion (apd_fusion_device.h), the T&T ones included.  Points in
-// memory (apd_points_t): the total is not known before the last view, so the seven arrays grow geometrically on the device
+// memory (apd_points_t): the total is not known before the last view, so the arrays grow geometrically on the device
 // (reserve_points: twice the capacity, one device-to-device copy of what is there) and k_fusion_compact_soa appends each view's
-// points at the running count; a host result is one download at the end.  Nothing is sized by pixels x views.
+// points at the running count; a host result is one download at the end.  Nothing is sized by pixels x views.  Among the arrays
+// is `sources`, per point the sources whose votes it was accepted with as a bit mask (k_fusion_emit / k_tat_decide write it per
+// pixel, only when the points are asked for); apd_points_visibility turns the masks into lists of views, on the device for
+// device-resident points (k_vis_count, k_vis_scan, k_vis_scatter below).
 #include <hip/hip_runtime.h>
 
 #include <float.h>
@@ -111,11 +114,12 @@ __global__ __launch_bounds__(256) void k_fusion_compact(const uint8_t *__restric
 }
 
 // The same points as a structure of arrays, appended at `base`: point base + block offset + rank in the block gets xyz, the
-// normal of the view's normal map at the pixel, colour, support, the view and the raster index.  One lane per pixel; the rank
-// inside a wave from the ballot and mbcnt, across the four waves of the block through LDS.  Every offset is a size_t.
+// normal of the view's normal map at the pixel, colour, support, the agreeing sources, the view and the raster index.  One lane per
+// pixel; the rank inside a wave from the ballot and mbcnt, across the four waves of the block through LDS.  Every offset is a size_t.
 __global__ __launch_bounds__(256) void k_fusion_compact_soa(const uint8_t *__restrict__ state, uint8_t accepted, int n, int view,
                                                              const float *__restrict__ xyz_sparse, const uint8_t *__restrict__ bgr_sparse,
                                                              const uint8_t *__restrict__ support_sparse,
+                                                             const uint32_t *__restrict__ agreeing_sparse,
                                                              const float *__restrict__ normal_map, const int *__restrict__ block_offsets,
                                                              size_t base, apd_fusion::PointArrays out)
 {
@@ -140,8 +144,119 @@ __global__ __launch_bounds__(256) void k_fusion_compact_soa(const uint8_t *__res
             out.bgr[3 * pos + k] = bgr_sparse[3 * (size_t)p + k];
         }
         out.support[pos] = support_sparse[p];
+        out.sources[pos] = agreeing_sparse[p];
         out.view[pos] = view;
         out.pixel[pos] = p;
+    }
+}
+
+// ---- visibility lists of device-resident points (apd_points_visibility) ----
+// Point k has 1 + popcount(sources[k]) entries: its own view, then the views behind the set bits in ascending bit order.  Three
+// kernels: per block of 256 points the number of entries (k_vis_count), an exclusive 64-bit scan of those block sums by one
+// workgroup (k_vis_scan: a full ETH3D or 152-view run has more than 10^8 points, so the entries can pass 2^31 and every offset
+// is 64-bit; 1024 lanes, each over a run of consecutive blocks, so up to kVisScanSpan points every lane has one block), and the
+// scatter, which repeats the block's own scan in LDS (k_vis_scatter).
+
+constexpr long long kVisScanSpan = 1024LL * 256;  // points up to which every lane of k_vis_scan scans at most one block sum
+
+// the bits of sources[k] that name a source of the point's view: all of them, by construction of the mask
+__device__ __forceinline__ uint32_t vis_mask(const uint32_t *__restrict__ sources, const int32_t *__restrict__ view,
+                                             const int *__restrict__ pair_offsets, size_t k, int &first)
+{
+    const int v = view[k];
+    first = pair_offsets[v];
+    const int ns = pair_offsets[v + 1] - first;
+    return sources[k] & (ns >= 32 ? 0xFFFFFFFFu : ((1u << ns) - 1u));
+}
+
+// exclusive scan of one value per lane over the 256 lanes of the block; *block_total: the sum
+__device__ __forceinline__ int vis_block_scan(int value, int *block_total)
+{
+    __shared__ int part[256];
+    const int t = threadIdx.x;
+    part[t] = value;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int v = (t >= off) ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    *block_total = part[255];
+    return part[t] - value;
+}
+
+__global__ __launch_bounds__(256) void k_vis_count(const uint32_t *__restrict__ sources, const int32_t *__restrict__ view,
+                                                    const int *__restrict__ pair_offsets, size_t n, long long *__restrict__ block_sums)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    int first;
+    const int entries = k < n ? 1 + __popc(vis_mask(sources, view, pair_offsets, k, first)) : 0;
+    int total;
+    vis_block_scan(entries, &total);
+    if (threadIdx.x == 0) {
+        block_sums[blockIdx.x] = total;
+    }
+}
+
+// block_sums[b] becomes the number of entries before block b; *total: all entries
+__global__ __launch_bounds__(1024) void k_vis_scan(long long *__restrict__ block_sums, size_t nblocks, long long *__restrict__ total)
+{
+    __shared__ long long part[1024];
+    const size_t t = threadIdx.x;
+    const size_t per = (nblocks + 1023) / 1024;
+    const size_t b0 = t * per < nblocks ? t * per : nblocks, b1 = b0 + per < nblocks ? b0 + per : nblocks;
+    long long sum = 0;
+    for (size_t b = b0; b < b1; ++b) {
+        sum += block_sums[b];
+    }
+    part[t] = sum;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const long long v = ((int)t >= off) ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    long long run = part[t] - sum;
+    for (size_t b = b0; b < b1; ++b) {
+        const long long c = block_sums[b];
+        block_sums[b] = run;
+        run += c;
+    }
+    if (t == 1023) {
+        *total = part[1023];
+    }
+}
+
+// offsets[k] = entries before point k (offsets[n] = all of them); views[offsets[k] ..]: the point's view, then its agreeing sources
+__global__ __launch_bounds__(256) void k_vis_scatter(const uint32_t *__restrict__ sources, const int32_t *__restrict__ view,
+                                                      const int *__restrict__ pair_offsets, const int *__restrict__ pair_indices, size_t n,
+                                                      const long long *__restrict__ block_prefix, const long long *__restrict__ total,
+                                                      long long *__restrict__ offsets, int32_t *__restrict__ views)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    int first = 0;
+    uint32_t m = 0;
+    int entries = 0;
+    if (k < n) {
+        m = vis_mask(sources, view, pair_offsets, k, first);
+        entries = 1 + __popc(m);
+    }
+    int block_total;
+    const long long at = block_prefix[blockIdx.x] + vis_block_scan(entries, &block_total);
+    if (k < n) {
+        offsets[k] = at;
+        int32_t *list = views + at;
+        *list++ = view[k];
+        while (m) {
+            const int j = __ffs(m) - 1;
+            m &= m - 1;
+            *list++ = pair_indices[first + j];
+        }
+    }
+    if (k == 0) {
+        offsets[n] = *total;
     }
 }
 
@@ -170,6 +285,7 @@ struct RefTask {
     int *flags;              // [0] undecided pixels left after this round
     int channels;            // of the images
     uint8_t *support;        // [pixel]: num_consistent of an accepted pixel
+    uint32_t *agreeing;      // [pixel]: bit j = source j is one of them; null: not asked for
     // the acceptance rule (apd_fusion_options; apd_fusion_math.h)
     float max_reproj_error, max_relative_depth, max_angle, depth_weight, angle_weight;
     int min_consistent;
@@ -303,11 +419,13 @@ __global__ __launch_bounds__(256) void k_fusion_emit(const DevView *__restrict__
             colour[k] = rv.image[(size_t)p * nc + (nc == 3 ? k : 0)];
         }
         int agreeing = 0;
+        uint32_t used = 0;
         for (int j = 0; j < task.num_src; ++j) {
             const int s = task.vote_idx[(size_t)p * task.num_src + j];
             if (s >= 0) {
                 const DevView &sv = views[task.src[j]];
                 sv.consumed[s] = 1;
+                used |= 1u << j;
                 for (int k = 0; k < 3; ++k) {
                     colour[k] += sv.image[(size_t)s * nc + (nc == 3 ? k : 0)];
                 }
@@ -321,6 +439,9 @@ __global__ __launch_bounds__(256) void k_fusion_emit(const DevView *__restrict__
             bgr_sparse[3 * (size_t)p + k] = static_cast<uint8_t>(colour[k] / (agreeing + 1));
         }
         task.support[p] = (uint8_t)agreeing;
+        if (task.agreeing) {
+            task.agreeing[p] = used;
+        }
     }
     const unsigned long long m = __ballot(acc);
     __shared__ int wave_counts[4];
@@ -374,6 +495,7 @@ int EthFusion::run()
         return rc;
     }
     task.support = support;
+    task.agreeing = agreeing;
     task.max_reproj_error = a.opt.max_reproj_error;
     task.max_relative_depth = a.opt.max_relative_depth;
     task.max_angle = a.opt.max_angle;
@@ -425,9 +547,13 @@ int EthFusion::run()
 
 // One fusion's points (apd_points_t): the arrays are host memory (malloc) or device memory on `device`
 struct apd_points {
-    int device, on_device;
-    long long count;
+    int device = 0, on_device = 0;
+    long long count = 0;
     apd_fusion::PointArrays arrays;
+    std::vector<int> pair_offsets, pair_indices;  // the call's source lists: what bit j of sources[k] means
+    // apd_points_visibility: built on the first call, where the arrays live (host: malloc; device: hipMalloc)
+    long long *vis_offsets = nullptr;
+    int32_t *vis_views = nullptr;
 };
 
 namespace apd_fusion {
@@ -474,6 +600,7 @@ void free_device_arrays(PointArrays &p)
     hipFree(p.support);
     hipFree(p.view);
     hipFree(p.pixel);
+    hipFree(p.sources);
     p = PointArrays();
 }
 
@@ -485,6 +612,7 @@ void free_host_arrays(PointArrays &p)
     free(p.support);
     free(p.view);
     free(p.pixel);
+    free(p.sources);
     p = PointArrays();
 }
 
@@ -588,6 +716,9 @@ int Call::alloc_common()
     HIP_TRY(alloc(max_px * 12, &xyz));
     HIP_TRY(alloc(max_px * 3, &bgr));
     HIP_TRY(alloc(max_px, &support));
+    if (a.points) {  // the PLY-only call has no such buffer and its emit kernels no such store
+        HIP_TRY(alloc(max_px * 4, &agreeing));
+    }
     HIP_TRY(alloc(max_blocks() * 4, &block_counts));
     HIP_TRY(alloc(sizeof(int), &total_));
     if (a.ply_path) {  // without a file no record is packed or downloaded
@@ -641,7 +772,7 @@ int Call::collect(int i, const uint8_t *state, uint8_t accepted, const float *no
             return rc;
         }
         hipLaunchKernelGGL(k_fusion_compact_soa, dim3(blocks), dim3(256), 0, 0, state, accepted, n, i, (const float *)xyz, (const uint8_t *)bgr,
-                           (const uint8_t *)support, normal, (const int *)block_counts, (size_t)count_, soa_);
+                           (const uint8_t *)support, (const uint32_t *)agreeing, normal, (const int *)block_counts, (size_t)count_, soa_);
         HIP_TRY(hipGetLastError());
     }
     count_ += npts;
@@ -666,6 +797,7 @@ int Call::reserve_points(long long need)
     HIP_TRY(hipMalloc((void **)&grown.support, c));
     HIP_TRY(hipMalloc((void **)&grown.view, c * 4));
     HIP_TRY(hipMalloc((void **)&grown.pixel, c * 4));
+    HIP_TRY(hipMalloc((void **)&grown.sources, c * 4));
     if (have > 0) {
         HIP_TRY(hipMemcpy(grown.xyz, soa_.xyz, have * 12, hipMemcpyDeviceToDevice));
         HIP_TRY(hipMemcpy(grown.normal, soa_.normal, have * 12, hipMemcpyDeviceToDevice));
@@ -673,6 +805,7 @@ int Call::reserve_points(long long need)
         HIP_TRY(hipMemcpy(grown.support, soa_.support, have, hipMemcpyDeviceToDevice));
         HIP_TRY(hipMemcpy(grown.view, soa_.view, have * 4, hipMemcpyDeviceToDevice));
         HIP_TRY(hipMemcpy(grown.pixel, soa_.pixel, have * 4, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(grown.sources, soa_.sources, have * 4, hipMemcpyDeviceToDevice));
     }
     std::swap(soa_, grown);  // the guard frees the old arrays
     soa_capacity_ = capacity;
@@ -691,7 +824,12 @@ int Call::finish()
     apd_points *pts = nullptr;
     if (a.points) {
         HIP_TRY(hipDeviceSynchronize());  // the last view's compaction
-        pts = new apd_points{a.device, a.opt.result_on_device ? 1 : 0, count_, PointArrays()};
+        pts = new apd_points();
+        pts->device = a.device;
+        pts->on_device = a.opt.result_on_device ? 1 : 0;
+        pts->count = count_;
+        pts->pair_offsets.assign(a.pair_offsets, a.pair_offsets + a.num_views + 1);
+        pts->pair_indices.assign(a.pair_indices, a.pair_indices + a.pair_offsets[a.num_views]);
         if (pts->on_device) {
             std::swap(pts->arrays, soa_);
             soa_capacity_ = 0;
@@ -704,13 +842,15 @@ int Call::finish()
             h.support = (uint8_t *)malloc(c);
             h.view = (int32_t *)malloc(c * 4);
             h.pixel = (int32_t *)malloc(c * 4);
-            hipError_t e = (h.xyz && h.normal && h.bgr && h.support && h.view && h.pixel) ? hipSuccess : hipErrorOutOfMemory;
+            h.sources = (uint32_t *)malloc(c * 4);
+            hipError_t e = (h.xyz && h.normal && h.bgr && h.support && h.view && h.pixel && h.sources) ? hipSuccess : hipErrorOutOfMemory;
             e = e != hipSuccess ? e : hipMemcpy(h.xyz, soa_.xyz, c * 12, hipMemcpyDeviceToHost);
             e = e != hipSuccess ? e : hipMemcpy(h.normal, soa_.normal, c * 12, hipMemcpyDeviceToHost);
             e = e != hipSuccess ? e : hipMemcpy(h.bgr, soa_.bgr, c * 3, hipMemcpyDeviceToHost);
             e = e != hipSuccess ? e : hipMemcpy(h.support, soa_.support, c, hipMemcpyDeviceToHost);
             e = e != hipSuccess ? e : hipMemcpy(h.view, soa_.view, c * 4, hipMemcpyDeviceToHost);
             e = e != hipSuccess ? e : hipMemcpy(h.pixel, soa_.pixel, c * 4, hipMemcpyDeviceToHost);
+            e = e != hipSuccess ? e : hipMemcpy(h.sources, soa_.sources, c * 4, hipMemcpyDeviceToHost);
             if (e != hipSuccess) {
                 apd_points_destroy(pts);
                 return hip_failed("download of the points", e, __FILE__, __LINE__);
@@ -777,6 +917,207 @@ extern "C" const uint8_t *apd_points_bgr(apd_points_t p) { return p ? p->arrays.
 extern "C" const uint8_t *apd_points_support(apd_points_t p) { return p ? p->arrays.support : nullptr; }
 extern "C" const int32_t *apd_points_view(apd_points_t p) { return p ? p->arrays.view : nullptr; }
 extern "C" const int32_t *apd_points_pixel(apd_points_t p) { return p ? p->arrays.pixel : nullptr; }
+extern "C" const uint32_t *apd_points_sources(apd_points_t p) { return p ? p->arrays.sources : nullptr; }
+
+namespace {
+
+// Selects the device of device-resident points for one call and puts the caller's back
+struct PointsDevice {
+    int previous = -1;
+    explicit PointsDevice(const apd_points *p)
+    {
+        if (p->on_device && hipGetDevice(&previous) != hipSuccess) {
+            previous = -1;
+        }
+    }
+    ~PointsDevice()
+    {
+        if (previous >= 0) {
+            hipSetDevice(previous);
+        }
+    }
+};
+
+int vis_hip_failed(const char *expr, hipError_t e, const char *, int)
+{
+    return apd::set_error(apd_fusion::g_fusion_error, APD_ERR_HIP, "apd_points_visibility: %s: %s", expr, hipGetErrorString(e));
+}
+
+// The lists of host-resident points: the plain loop
+int build_visibility_host(apd_points *p)
+{
+    const size_t n = (size_t)p->count;
+    long long *offsets = (long long *)malloc((n + 1) * sizeof(long long));
+    if (!offsets) {
+        return apd::set_error(apd_fusion::g_fusion_error, APD_ERR_HIP, "apd_points_visibility: out of host memory");
+    }
+    const apd_fusion::PointArrays &a = p->arrays;
+    long long total = 0;
+    for (size_t k = 0; k < n; ++k) {
+        offsets[k] = total;
+        total += 1 + __builtin_popcount(a.sources[k]);
+    }
+    offsets[n] = total;
+    int32_t *views = (int32_t *)malloc(total > 0 ? (size_t)total * sizeof(int32_t) : sizeof(int32_t));
+    if (!views) {
+        free(offsets);
+        return apd::set_error(apd_fusion::g_fusion_error, APD_ERR_HIP, "apd_points_visibility: out of host memory");
+    }
+    for (size_t k = 0; k < n; ++k) {
+        int32_t *list = views + offsets[k];
+        *list++ = a.view[k];
+        const int first = p->pair_offsets[(size_t)a.view[k]];
+        for (int j = 0; j < 32; ++j) {
+            if ((a.sources[k] >> j) & 1u) {
+                *list++ = p->pair_indices[(size_t)(first + j)];
+            }
+        }
+    }
+    p->vis_offsets = offsets;
+    p->vis_views = views;
+    return APD_OK;
+}
+
+// The lists of device-resident points, on their device: k_vis_count, k_vis_scan, k_vis_scatter
+int build_visibility_device(apd_points *p)
+{
+    const auto hip_failed = vis_hip_failed;  // what HIP_TRY returns here
+    const size_t n = (size_t)p->count;
+    const size_t nblocks = (n + 255) / 256;
+    struct Scratch {
+        std::vector<void *> owned;
+        ~Scratch()
+        {
+            for (void *q : owned) {
+                hipFree(q);
+            }
+        }
+        hipError_t alloc(size_t bytes, void **out)
+        {
+            const hipError_t e = hipMalloc(out, bytes > 0 ? bytes : 1);
+            if (e == hipSuccess) {
+                owned.push_back(*out);
+            }
+            return e;
+        }
+        void keep(void *q) { owned.erase(std::find(owned.begin(), owned.end(), q)); }
+    } scratch;
+    long long *offsets = nullptr, *block_sums = nullptr, *dtotal = nullptr;
+    int32_t *views = nullptr;
+    int *pair_offsets = nullptr, *pair_indices = nullptr;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(scratch.alloc((n + 1) * sizeof(long long), (void **)&offsets));
+    long long total = 0;
+    if (n == 0) {
+        HIP_TRY(hipMemset(offsets, 0, sizeof(long long)));
+    } else {
+        HIP_TRY(scratch.alloc(nblocks * sizeof(long long), (void **)&block_sums));
+        HIP_TRY(scratch.alloc(sizeof(long long), (void **)&dtotal));
+        HIP_TRY(scratch.alloc(p->pair_offsets.size() * sizeof(int), (void **)&pair_offsets));
+        HIP_TRY(scratch.alloc(p->pair_indices.size() * sizeof(int), (void **)&pair_indices));
+        HIP_TRY(hipMemcpy(pair_offsets, p->pair_offsets.data(), p->pair_offsets.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (!p->pair_indices.empty()) {
+            HIP_TRY(hipMemcpy(pair_indices, p->pair_indices.data(), p->pair_indices.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
+        const apd_fusion::PointArrays &a = p->arrays;
+        hipLaunchKernelGGL(k_vis_count, dim3((unsigned)nblocks), dim3(256), 0, 0, (const uint32_t *)a.sources, (const int32_t *)a.view,
+                           (const int *)pair_offsets, n, block_sums);
+        hipLaunchKernelGGL(k_vis_scan, dim3(1), dim3(1024), 0, 0, block_sums, nblocks, dtotal);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(&total, dtotal, sizeof(long long), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(scratch.alloc(total > 0 ? (size_t)total * sizeof(int32_t) : sizeof(int32_t), (void **)&views));
+    if (n > 0) {
+        const apd_fusion::PointArrays &a = p->arrays;
+        hipLaunchKernelGGL(k_vis_scatter, dim3((unsigned)nblocks), dim3(256), 0, 0, (const uint32_t *)a.sources, (const int32_t *)a.view,
+                           (const int *)pair_offsets, (const int *)pair_indices, n, (const long long *)block_sums, (const long long *)dtotal,
+                           offsets, views);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    scratch.keep(offsets);
+    scratch.keep(views);
+    p->vis_offsets = offsets;
+    p->vis_views = views;
+    return APD_OK;
+}
+
+}  // namespace
+
+extern "C" int apd_points_visibility(apd_points_t p, const long long **offsets, const int32_t **views)
+{
+    apd_fusion::g_fusion_error.clear();
+    if (!p || !offsets || !views) {
+        return apd::set_error(apd_fusion::g_fusion_error, APD_ERR_INVALID, "apd_points_visibility: null argument");
+    }
+    if (!p->vis_offsets) {
+        PointsDevice device(p);
+        if (const int rc = p->on_device ? build_visibility_device(p) : build_visibility_host(p); rc != APD_OK) {
+            return rc;
+        }
+    }
+    *offsets = p->vis_offsets;
+    *views = p->vis_views;
+    return APD_OK;
+}
+
+extern "C" int apd_points_write_vis(apd_points_t p, const char *path)
+{
+    std::string &err = apd_fusion::g_fusion_error;
+    err.clear();
+    if (!p || !path) {
+        return apd::set_error(err, APD_ERR_INVALID, "apd_points_write_vis: null argument");
+    }
+    const long long *offsets = nullptr;
+    const int32_t *views = nullptr;
+    if (const int rc = apd_points_visibility(p, &offsets, &views); rc != APD_OK) {
+        return rc;
+    }
+    const size_t n = (size_t)p->count;
+    std::vector<long long> host_offsets;
+    std::vector<int32_t> host_views;
+    if (p->on_device) {  // one download of each array
+        PointsDevice device(p);
+        host_offsets.resize(n + 1);
+        hipError_t e = hipSetDevice(p->device);
+        e = e != hipSuccess ? e : hipMemcpy(host_offsets.data(), offsets, (n + 1) * sizeof(long long), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && host_offsets[n] > 0) {
+            host_views.resize((size_t)host_offsets[n]);
+            e = hipMemcpy(host_views.data(), views, host_views.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+        }
+        if (e != hipSuccess) {
+            return apd::set_error(err, APD_ERR_HIP, "apd_points_write_vis: download of the lists: %s", hipGetErrorString(e));
+        }
+        offsets = host_offsets.data();
+        views = host_views.data();
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        err = std::string("apd_points_write_vis: cannot write ") + path;
+        return APD_ERR_IO;
+    }
+    // uint64 number of points, then per point uint32 n and n x uint32 view index, little endian like every file of the project
+    const uint64_t count = (uint64_t)n;
+    bool ok = fwrite(&count, 8, 1, f) == 1;
+    std::vector<uint32_t> chunk;
+    const size_t kChunk = 1u << 16;  // points per fwrite
+    for (size_t k0 = 0; k0 < n && ok; k0 += kChunk) {
+        const size_t k1 = std::min(n, k0 + kChunk);
+        chunk.clear();
+        for (size_t k = k0; k < k1; ++k) {
+            chunk.push_back((uint32_t)(offsets[k + 1] - offsets[k]));
+            for (long long e = offsets[k]; e < offsets[k + 1]; ++e) {
+                chunk.push_back((uint32_t)views[e]);
+            }
+        }
+        ok = fwrite(chunk.data(), 4, chunk.size(), f) == chunk.size();
+    }
+    if (fclose(f) != 0 || !ok) {
+        err = std::string("apd_points_write_vis: short write to ") + path;
+        return APD_ERR_IO;
+    }
+    return APD_OK;
+}
 
 extern "C" int apd_points_destroy(apd_points_t p)
 {
@@ -788,11 +1129,15 @@ extern "C" int apd_points_destroy(apd_points_t p)
         const bool known = hipGetDevice(&current) == hipSuccess;
         hipSetDevice(p->device);
         apd_fusion::free_device_arrays(p->arrays);
+        hipFree(p->vis_offsets);
+        hipFree(p->vis_views);
         if (known) {
             hipSetDevice(current);
         }
     } else {
         apd_fusion::free_host_arrays(p->arrays);
+        free(p->vis_offsets);
+        free(p->vis_views);
     }
     delete p;
     return APD_OK;

@@ -43,11 +43,12 @@ inline apd_fusion_options default_options()
     return o;
 }
 
-// The seven arrays of an apd_points_t, on the device while the views are fused
+// The arrays of an apd_points_t, on the device while the views are fused
 struct PointArrays {
     float *xyz = nullptr, *normal = nullptr;
     uint8_t *bgr = nullptr, *support = nullptr;
     int32_t *view = nullptr, *pixel = nullptr;
+    uint32_t *sources = nullptr;  // bit j: source j of the point's view is one of the votes counted in support
 };
 
 // The arguments of apd_fuse_views / apd_fuse_views_variant / apd_fuse_views_opt (include/apd_mi355x.h)
@@ -97,6 +98,7 @@ protected:
     float *xyz = nullptr;   // [pixel][3] of the view being fused: the points where they are, before the compaction
     uint8_t *bgr = nullptr; // [pixel][3]
     uint8_t *support = nullptr;  // [pixel]: votes the point was accepted with
+    uint32_t *agreeing = nullptr;  // [pixel]: bit j = source j is one of those votes; null unless the points in memory are asked for
     int *block_counts = nullptr;  // points per block of 256 pixels
 
     int hip_failed(const char *expr, hipError_t e, const char *file, int line) const;  // what HIP_TRY returns
@@ -179,7 +181,7 @@ protected:
         return APD_OK;
     }
 
-    // The scratch every variant needs (xyz, bgr, support, block_counts, and what collect() uses) and the staging buffer, sized for the
+    // The scratch every variant needs (xyz, bgr, support, agreeing, block_counts, and what collect() uses) and the staging buffer, sized for the
     // largest view.  Ends the set-up: its time is taken here.
     int alloc_common();
     // View i has its points in xyz / bgr, block_counts filled, and state[p] == accepted where pixel p is a point: packs them in

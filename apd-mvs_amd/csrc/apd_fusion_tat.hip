@@ -19,8 +19,8 @@
 //                 records.
 //
 // Memory per view of n pixels and S sources: 4 n (validity words) + 8 S n / 256 (block values) + 1 n (emitted) + 30 n (the
-// points before and after compaction, as in the ETH fusion) bytes, about 36 bytes per pixel, plus one mask byte per pixel
-// of every view for the whole run.  No (pixel, source) record is stored: at 6200 x 4130 with 10 sources the records would be
+// points before and after compaction, as in the ETH fusion) bytes, about 36 bytes per pixel (4 n more for the agreeing sources
+// when the points in memory are asked for), plus one mask byte per pixel of every view for the whole run.  No (pixel, source) record is stored: at 6200 x 4130 with 10 sources the records would be
 // ~4 GB, this layout is ~0.9 GB.
 #include <hip/hip_runtime.h>
 
@@ -65,6 +65,7 @@ struct TatTask {
     float *xyz;              // [pixel][3]
     uint8_t *bgr;            // [pixel][3]
     uint8_t *support;        // [pixel]: `count` of the round that emitted the point
+    uint32_t *agreeing;      // [pixel]: bit j = source j is counted in it; null: not asked for
     int *block_counts;       // points per block
 };
 
@@ -262,6 +263,13 @@ __global__ __launch_bounds__(256) void k_tat_decide(const TatView *__restrict__ 
                 task.bgr[3 * (size_t)p + k] = static_cast<uint8_t>(colour[k]);
             }
             task.support[p] = (uint8_t)count;
+            if (task.agreeing) {
+                uint32_t used = 0;
+                for (int j = 0; j < S; ++j) {
+                    used |= (uint32_t)(first_round[j * 256 + threadIdx.x] <= round) << j;
+                }
+                task.agreeing[p] = used;
+            }
             rv.mask[p] = 1;
         }
     }
@@ -348,6 +356,7 @@ int TatFusion::run(bool intermediate)
         task.xyz = xyz;
         task.bgr = bgr;
         task.support = support;
+        task.agreeing = agreeing;
         task.block_counts = block_counts;
         hipLaunchKernelGGL(k_tat_valid, dim3(nblocks), dim3(256), 0, 0, dviews, task);
         hipLaunchKernelGGL(k_tat_scan, dim3(S), dim3(1024), 0, 0, task, nblocks);

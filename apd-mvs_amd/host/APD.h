@@ -161,6 +161,9 @@ void SetFusionVariant(int variant);
 // additive: the options of the fusion (apd_fusion_options, include/apd_mi355x.h: the ETH loop's acceptance rule as values, normals
 // in the PLY file) that RunFusion, the in-memory paths and apdhost_fuse hand to apd_fuse_views_opt; its `variant` included
 void SetFusionOptions(const apd_fusion_options &options);
+// additive: RunFusion and the in-memory paths also write <dense>/APD/APD.ply.vis, COLMAP's fused.ply.vis (apd_points_write_vis):
+// per point the views that see it, as positions in pair.txt
+void SetFusionPlyVis(bool on);
 
 class APD {
 public:

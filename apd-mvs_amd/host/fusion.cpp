@@ -28,6 +28,7 @@ namespace {
 
 int g_fusion_device = 0;
 int g_fusion_variant = APD_FUSION_ETH;  // which of the reference's loops (APD_FUSION_*, include/apd_mi355x.h)
+bool g_fusion_ply_vis = false;          // SetFusionPlyVis
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
 apd_fusion_options &fusion_options()
@@ -103,6 +104,26 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
 void SetFusionDevice(int device) { g_fusion_device = device; }
 
 void SetFusionVariant(int variant) { g_fusion_variant = variant; }
+
+void SetFusionPlyVis(bool on) { g_fusion_ply_vis = on; }
+
+namespace {
+
+// --ply-vis: <ply_path>.vis from the points of the fusion that wrote ply_path; releases them
+void write_vis_beside(const path &ply_path, apd_points_t points)
+{
+    const std::string vis_path = ply_path.string() + ".vis";
+    const int st = apd_points_write_vis(points, vis_path.c_str());
+    const std::string err = st != APD_OK ? apd_fusion_last_error() : "";
+    apd_points_destroy(points);
+    if (st != APD_OK) {
+        std::cerr << err << std::endl;
+        exit(EXIT_FAILURE);
+    }
+    std::cout << "Visibility lists in " << vis_path << std::endl;
+}
+
+}  // namespace
 
 void SetFusionOptions(const apd_fusion_options &options)
 {
@@ -245,12 +266,16 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     const path ply_path = dense_folder / path("APD") / path("APD.ply");
     const auto t_fuse = std::chrono::steady_clock::now();
     std::cout << "Fusion inputs ready: " << std::chrono::duration_cast<std::chrono::milliseconds>(t_fuse - t_inputs).count() << " ms" << std::endl;
-    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str());
+    apd_points_t points = nullptr;
+    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str(), nullptr, g_fusion_ply_vis ? &points : nullptr);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms" << std::endl;
     if (n < 0) {
         exit(EXIT_FAILURE);  // like every other device error of the reference (CudaSafeCall, APD.cpp:315-323)
     }
     std::cout << "Fused " << n << " points into " << ply_path << std::endl;
+    if (g_fusion_ply_vis) {
+        write_vis_beside(ply_path, points);
+    }
 }
 
 // The final maps are on `device` already (host/multi_device.cpp keeps every view's state there and gathers the other devices'
@@ -427,10 +452,14 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
     std::cout << "Fusion inputs ready: prepared in " << f->prepare_ms << " ms behind the passes, waited "
               << std::chrono::duration_cast<std::chrono::milliseconds>(t_fuse - t_wait).count() << " ms" << std::endl;
     long long count = 0;
-    const apd_fusion_options fusion = call_options();
+    apd_fusion_options fusion = call_options();
+    apd_points_t points = nullptr;
+    if (g_fusion_ply_vis) {
+        fusion.result_on_device = 1;  // the maps are here already: the lists are built here too and only they come down
+    }
     const int st = apd_fuse_views_opt(&fusion, f->device, V, cams.data(), f->imgs.data(), f->channels, depths.data(), normals.data(), weaks.data(),
                                       f->any_block ? f->blocks.data() : nullptr, rws.data(), cls.data(), offs.data(), idx.data(), 1,
-                                      ply_path.string().c_str(), &count, nullptr);
+                                      ply_path.string().c_str(), &count, g_fusion_ply_vis ? &points : nullptr);
     double ms_setup = 0, ms_views = 0, ms_file = 0;
     apd_fusion_last_timing(&ms_setup, &ms_views, &ms_file);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms (set-up "
@@ -442,6 +471,9 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
         exit(EXIT_FAILURE);
     }
     std::cout << "Fused " << count << " points into " << ply_path << std::endl;
+    if (g_fusion_ply_vis) {
+        write_vis_beside(ply_path, points);
+    }
 }
 
 // ---- --filtered-maps: the geometric filter (apd_filter_views, csrc/apd_filter.hip) ----

@@ -3,7 +3,7 @@
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
-//       [--ply-normals] [--filtered-maps]
+//       [--ply-normals] [--ply-vis] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -13,7 +13,8 @@
 // --fusion-*: the acceptance rule of the ETH fusion (apd_fusion_options, include/apd_mi355x.h: votes a point needs, the three
 // thresholds, the STRONG / WEAK factors); refused with another --fusion, whose loops keep their own thresholds.  --ply-normals:
 // APD.ply with nx ny nz, the reference pixel's normal, for every loop.  A bad value is refused with the usage line before
-// anything is read or written.  Without these flags APD.ply keeps its bytes.
+// anything is read or written.  Without these flags APD.ply keeps its bytes.  --ply-vis: APD/APD.ply.vis beside APD.ply, COLMAP's
+// fused.ply.vis (per point the views that see it, as positions in pair.txt), from the same fusion; APD.ply keeps its bytes.
 //
 // --masks [DIR] (default DIR: masks): <dense_folder>/DIR/<%08d>.jpg|pgm are per-view pixel masks, grey < 128 = masked out of
 // PatchMatch (apd_upload_mask: the pixels cost no NCC and leave as depth 0 / UNKNOWN); a view without a file is unmasked, a file
@@ -113,6 +114,8 @@ bool ParseOptions(int argc, char **argv, Options &o)
             o.fusion_thresholds_set = true;
         } else if (a == "--ply-normals") {
             o.fusion.ply_normals = 1;
+        } else if (a == "--ply-vis") {
+            o.ply_vis = true;
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
         } else if (a == "--seed") {
@@ -324,7 +327,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -339,6 +342,7 @@ int main(int argc, char **argv)
     APD::SetDevice(opt.gpu_index);
     SetFusionDevice(opt.gpu_index);
     SetFusionOptions(opt.fusion);
+    SetFusionPlyVis(opt.ply_vis);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

@@ -493,7 +493,31 @@ def load_colour_images(folder, ids):
 FUSION_VARIANTS = {"eth": 0, "tat_intermediate": 1, "tat_advanced": 2}  # APD_FUSION_* of include/apd_mi355x.h
 
 
-def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False):
+def read_vis(path):
+    """COLMAP's fused.ply.vis (little endian: uint64 number of points, then per point uint32 n and n x uint32 view index) as
+    (offsets int64 [N + 1], views int32): point k is seen by views[offsets[k]:offsets[k + 1]].  ValueError for a file that is
+    short or has bytes left over."""
+    raw = open(path, "rb").read()
+    if len(raw) < 8 or (len(raw) - 8) % 4:
+        raise ValueError("%s: not a .vis file (%d bytes)" % (path, len(raw)))
+    n = int(np.frombuffer(raw, "<u8", 1)[0])
+    words = np.frombuffer(raw, "<u4", offset=8)
+    offsets = np.zeros(n + 1, np.int64)
+    at = 0
+    for k in range(n):   # the position of each count depends on the counts before it
+        if at >= len(words):
+            raise ValueError("%s: ends in point %d of %d" % (path, k, n))
+        at += 1 + int(words[at])
+        offsets[k + 1] = at - (k + 1)
+    if at != len(words):
+        raise ValueError("%s: %d words for %d points, %d expected" % (path, len(words), n, at))
+    keep = np.ones(len(words), bool)
+    keep[offsets[:-1] + np.arange(n)] = False
+    return offsets, words[keep].astype(np.int32)
+
+
+def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False,
+         vis_path=None):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -505,13 +529,14 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     options: a FusionOptions (default_fusion_options(min_consistent=2, ...): the ETH loop's acceptance rule, ply_normals,
     result_on_device; its `variant` is set from `variant`), None for the reference's behaviour.  return_points: also return the
     points as a Points object (numpy views, or torch tensors on `device` with result_on_device): (count, Points); ply_path may
-    then be None and no file is written."""
+    then be None and no file is written.  vis_path: also write COLMAP's fused.ply.vis of the same fusion there (per point the
+    views that see it, as indices of the scene's views; Points.write_vis), with or without a PLY file or the points."""
     import ctypes as C
     from . import Points, default_fusion_options
     if variant not in FUSION_VARIANTS:
         raise ValueError("unknown fusion variant %r: one of %s" % (variant, ", ".join(sorted(FUSION_VARIANTS))))
-    if ply_path is None and not return_points:
-        raise ValueError("fuse: neither a PLY file nor the points are asked for")
+    if ply_path is None and not return_points and vis_path is None:
+        raise ValueError("fuse: neither a PLY file nor the points nor the visibility file are asked for")
     L = host_lib()
     L.apdhost_set_fusion_device(int(device))
     L.apdhost_set_fusion_variant(FUSION_VARIANTS[variant])
@@ -565,10 +590,21 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
         blocks = (C.c_void_p * V)(*[None if b is None else b.ctypes.data for b in keep])
     handle = C.c_void_p()
     n = L.apdhost_fuse_opt(C.byref(opt), V, C.byref(cams), ptrs(imgs), channels, ptrs(deps), ptrs(nors), ptrs(weaks), blocks, rows, cols, offs,
-                           idx, None if ply_path is None else str(ply_path).encode(), C.byref(handle) if return_points else None)
+                           idx, None if ply_path is None else str(ply_path).encode(),
+                           C.byref(handle) if return_points or vis_path is not None else None)
     if n < 0:
         raise RuntimeError("device fusion failed (apd_fuse_views_opt, %s): see stderr" % variant)
-    return (int(n), Points(handle, device)) if return_points else int(n)
+    points = Points(handle, device) if return_points else None
+    if vis_path is not None and points is not None:
+        points.write_vis(vis_path)
+    elif vis_path is not None:  # the file alone: no array is copied or wrapped
+        from . import ApdError, lib
+        rc = lib().apd_points_write_vis(handle, str(vis_path).encode())
+        why = lib().apd_fusion_last_error().decode() if rc != 0 else ""
+        lib().apd_points_destroy(handle)
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, why))
+    return (int(n), points) if return_points else int(n)
 
 
 class FilteredMaps:

@@ -393,7 +393,11 @@ void apd_fusion_default_options(apd_fusion_options *o);
  *   bgr      3 bytes: the colour of the PLY record;
  *   support  1 byte: the votes the point was accepted with (ETH: num_consistent >= min_consistent; T&T: `count` of the round
  *            that emitted it);
- *   view, pixel   int32 each: the index of the reference view and the raster index row * cols + col in it.
+ *   view, pixel   int32 each: the index of the reference view and the raster index row * cols + col in it;
+ *   sources  uint32: which sources those votes are.  Bit j is set when the j-th source of the point's view, in pair.txt order
+ *            (view pair_indices[pair_offsets[view] + j] of the call), is one of them -- the convention of the selected views of
+ *            apd_download.  ETH: the votes that survived the consumption of source pixels, the ones support counts and the
+ *            colour is averaged over; T&T: the sources counted in `count` of the emitting round.  popcount(sources) == support.
  * The arrays are host memory, or device memory on the call's device when options.result_on_device was set (then nothing is
  * downloaded unless a PLY file is asked for as well).  They belong to the object and live until apd_points_destroy; an accessor
  * of an object without points may return NULL. */
@@ -406,6 +410,20 @@ const uint8_t *apd_points_bgr(apd_points_t p);
 const uint8_t *apd_points_support(apd_points_t p);
 const int32_t *apd_points_view(apd_points_t p);
 const int32_t *apd_points_pixel(apd_points_t p);
+const uint32_t *apd_points_sources(apd_points_t p);
+/* The views that see each point, as lists in compressed form: *offsets has count + 1 entries, point k has
+ * (*views)[(*offsets)[k] .. (*offsets)[k + 1]): first its own reference view view[k], then its agreeing sources as indices of views
+ * of the fusion call, in ascending bit order of sources[k] -- support[k] + 1 entries.  The object keeps a copy of the call's
+ * pair_offsets / pair_indices for this.  The two arrays are built on the first call and kept; they live where the points live
+ * (device-resident points: built on the device, offsets by a 64-bit scan over all points, since a large run has more than 2^31
+ * entries) and belong to the object.  An object without points gives *offsets = {0}.  NULL for any argument: APD_ERR_INVALID;
+ * the message is apd_fusion_last_error's. */
+int apd_points_visibility(apd_points_t p, const long long **offsets, const int32_t **views);
+/* Writes the lists as COLMAP's fused.ply.vis (what its Delaunay mesher and Poisson trimming read beside fused.ply), little
+ * endian: uint64 number of points, then per point uint32 n and n x uint32 view index -- the entries of apd_points_visibility,
+ * i.e. positions of views in the fusion call.  Host- or device-resident points.  NULL p or path: APD_ERR_INVALID; a file that
+ * cannot be written: APD_ERR_IO. */
+int apd_points_write_vis(apd_points_t p, const char *path);
 int apd_points_destroy(apd_points_t p);
 
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
