@@ -181,6 +181,8 @@ def lib():
         getattr(L, "apd_points_" + n).restype = C.c_void_p
     L.apd_points_visibility.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.apd_points_write_vis.argtypes = [C.c_void_p, C.c_char_p]
+    L.apd_points_average.argtypes = [C.c_void_p, C.c_int, C.c_void_p, fpp, fpp, ipp, ipp, C.c_int, C.POINTER(C.c_void_p)]
+    L.apd_points_write_ply.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.apd_points_destroy.argtypes = [C.c_void_p]
     L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     _lib = L
@@ -226,8 +228,9 @@ class Points:
     of the point's view is one of those votes; a device result holds the same bit patterns as int32).  A host result gives
     read-only numpy views of the library's memory, valid while an array or this object lives; a device result gives torch tensors
     on its device, filled by device-to-device copies (no host round trip) and independent of this object.  visibility() and
-    write_vis() are the library's (apd_points_visibility, apd_points_write_vis); the object keeps the library's points for them
-    until close()."""
+    write_vis() are the library's (apd_points_visibility, apd_points_write_vis), and so are average() (apd_points_average: a new
+    Points with positions and normals averaged over the agreeing views) and write_ply() (apd_points_write_ply); the object keeps
+    the library's points for them until close()."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
                ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
@@ -284,6 +287,49 @@ class Points:
             raise ApdError("Points.write_vis: the points are closed")
         L = lib()
         rc = L.apd_points_write_vis(self._p, str(path).encode())
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+
+    def average(self, cameras, depths, normals, maps_on_device=False):
+        """apd_points_average: a new Points with every point's xyz and normal replaced by the mean over its own view and its agreeing
+        sources, sources / support reduced to the sources that contributed; these points stay as they are.  cameras: the fusion
+        call's (a ctypes array or a sequence of Camera); depths, normals: per view float32 [H, W] and [H, W, 3] at the fusion
+        call's sizes, numpy arrays or, with maps_on_device, torch tensors on the points' device.  The result lives where these points live."""
+        if not self._p:
+            raise ApdError("Points.average: the points are closed")
+        L = lib()
+        V = len(cameras)
+        if len(depths) != V or len(normals) != V:
+            raise ValueError("Points.average: %d cameras, %d depth maps, %d normal maps" % (V, len(depths), len(normals)))
+        cams = cameras if isinstance(cameras, C.Array) else (Camera * V)(*cameras)
+
+        def prepared(a):
+            if maps_on_device:
+                import torch
+                return a.to(torch.float32).contiguous()
+            return np.ascontiguousarray(a, np.float32)
+
+        deps, nors = [prepared(d) for d in depths], [prepared(n) for n in normals]
+        for d, n in zip(deps, nors):
+            if d.ndim != 2 or tuple(n.shape) != tuple(d.shape) + (3,):
+                raise ValueError("Points.average: depth maps are [H, W], normal maps [H, W, 3]")
+        rows, cols = (C.c_int * V)(*[d.shape[0] for d in deps]), (C.c_int * V)(*[d.shape[1] for d in deps])
+        if maps_on_device:
+            import torch
+            torch.cuda.synchronize(torch.device("cuda", self.device))  # the tensors' producers, before the library's stream reads them
+        out = C.c_void_p()
+        rc = L.apd_points_average(self._p, V, C.byref(cams), (C.c_void_p * V)(*[_ptr(a) for a in deps]), (C.c_void_p * V)(*[_ptr(a) for a in nors]),
+                                  rows, cols, int(bool(maps_on_device)), C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device)
+
+    def write_ply(self, path, normals=False):
+        """The PLY file of these points (apd_points_write_ply): ExportPointCloud's header and records, with nx ny nz when `normals`."""
+        if not self._p:
+            raise ApdError("Points.write_ply: the points are closed")
+        L = lib()
+        rc = L.apd_points_write_ply(self._p, str(path).encode(), int(bool(normals)))
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
 

@@ -545,17 +545,6 @@ int EthFusion::run()
 
 }  // namespace
 
-// One fusion's points (apd_points_t): the arrays are host memory (malloc) or device memory on `device`
-struct apd_points {
-    int device = 0, on_device = 0;
-    long long count = 0;
-    apd_fusion::PointArrays arrays;
-    std::vector<int> pair_offsets, pair_indices;  // the call's source lists: what bit j of sources[k] means
-    // apd_points_visibility: built on the first call, where the arrays live (host: malloc; device: hipMalloc)
-    long long *vis_offsets = nullptr;
-    int32_t *vis_views = nullptr;
-};
-
 namespace apd_fusion {
 
 int run_eth(const char *who, const Args &args) { return EthFusion(who, args).run(); }
@@ -592,6 +581,8 @@ int write_ply(const char *who, const char *ply_path, long long count, const std:
     return APD_OK;
 }
 
+}  // namespace
+
 void free_device_arrays(PointArrays &p)
 {
     hipFree(p.xyz);
@@ -615,8 +606,6 @@ void free_host_arrays(PointArrays &p)
     free(p.sources);
     p = PointArrays();
 }
-
-}  // namespace
 
 int check_options(const char *who, const apd_fusion_options *options, bool *preset_out)
 {
@@ -830,6 +819,8 @@ int Call::finish()
         pts->count = count_;
         pts->pair_offsets.assign(a.pair_offsets, a.pair_offsets + a.num_views + 1);
         pts->pair_indices.assign(a.pair_indices, a.pair_indices + a.pair_offsets[a.num_views]);
+        pts->rows.assign(a.rows, a.rows + a.num_views);
+        pts->cols.assign(a.cols, a.cols + a.num_views);
         if (pts->on_device) {
             std::swap(pts->arrays, soa_);
             soa_capacity_ = 0;

@@ -18,12 +18,24 @@
 #include <vector>
 
 #include "../../include/apd_mi355x.h"
+#include "apd_fusion_math.h"
 #include "apd_host_error.h"
 
 namespace apd_fusion {
 
 extern thread_local std::string g_fusion_error;
 extern thread_local double g_fusion_ms[3];  // last fusion: set-up (allocations, uploads), views (kernels + point downloads), PLY file
+
+// The arrays of an apd_points_t, on the device while the views are fused
+struct PointArrays {
+    float *xyz = nullptr, *normal = nullptr;
+    uint8_t *bgr = nullptr, *support = nullptr;
+    int32_t *view = nullptr, *pixel = nullptr;
+    uint32_t *sources = nullptr;  // bit j: source j of the point's view is one of the votes counted in support
+};
+
+void free_device_arrays(PointArrays &p);  // hipFree of each array (on the current device)
+void free_host_arrays(PointArrays &p);
 
 // apd_fusion_default_options: the reference's literals, a PLY of 15-byte records, host results
 inline apd_fusion_options default_options()
@@ -43,13 +55,18 @@ inline apd_fusion_options default_options()
     return o;
 }
 
-// The arrays of an apd_points_t, on the device while the views are fused
-struct PointArrays {
-    float *xyz = nullptr, *normal = nullptr;
-    uint8_t *bgr = nullptr, *support = nullptr;
-    int32_t *view = nullptr, *pixel = nullptr;
-    uint32_t *sources = nullptr;  // bit j: source j of the point's view is one of the votes counted in support
-};
+// The geometry of camera c at rows x cols: K, R, t and the centre -R^T t in float, term order of Get3DPointonWorld (APD.cpp:795-798)
+inline void view_geometry(const apd_camera &c, int rows, int cols, View &geo)
+{
+    memcpy(geo.K, c.K, sizeof(geo.K));
+    memcpy(geo.R, c.R, sizeof(geo.R));
+    memcpy(geo.t, c.t, sizeof(geo.t));
+    geo.centre[0] = -(c.R[0] * c.t[0] + c.R[3] * c.t[1] + c.R[6] * c.t[2]);
+    geo.centre[1] = -(c.R[1] * c.t[0] + c.R[4] * c.t[1] + c.R[7] * c.t[2]);
+    geo.centre[2] = -(c.R[2] * c.t[0] + c.R[5] * c.t[1] + c.R[8] * c.t[2]);
+    geo.rows = rows;
+    geo.cols = cols;
+}
 
 // The arguments of apd_fuse_views / apd_fuse_views_variant / apd_fuse_views_opt (include/apd_mi355x.h)
 struct Args {
@@ -141,16 +158,7 @@ protected:
     // The geometry of cameras[i] and the depth and normal maps: what every view of every variant and of the filter has
     template <typename V> int fill_maps(int i, V &v)
     {
-        const apd_camera &c = a.cameras[i];
-        memcpy(v.geo.K, c.K, sizeof(v.geo.K));
-        memcpy(v.geo.R, c.R, sizeof(v.geo.R));
-        memcpy(v.geo.t, c.t, sizeof(v.geo.t));
-        // -R^T t in float, term order of Get3DPointonWorld (APD.cpp:795-798)
-        v.geo.centre[0] = -(c.R[0] * c.t[0] + c.R[3] * c.t[1] + c.R[6] * c.t[2]);
-        v.geo.centre[1] = -(c.R[1] * c.t[0] + c.R[4] * c.t[1] + c.R[7] * c.t[2]);
-        v.geo.centre[2] = -(c.R[2] * c.t[0] + c.R[5] * c.t[1] + c.R[8] * c.t[2]);
-        v.geo.rows = a.rows[i];
-        v.geo.cols = a.cols[i];
+        view_geometry(a.cameras[i], a.rows[i], a.cols[i], v.geo);
         HIP_TRY(device_map(a.depths[i], (size_t)pixels(i) * 4, &v.depth));
         HIP_TRY(device_map(a.normals[i], (size_t)pixels(i) * 12, &v.normal));
         return APD_OK;
@@ -215,3 +223,16 @@ private:
 };
 
 }  // namespace apd_fusion
+
+// One fusion's points (apd_points_t): the arrays are host memory (malloc) or device memory on `device`.  apd_fusion.hip makes
+// them and builds their visibility lists; apd_points.hip averages them and writes their PLY.
+struct apd_points {
+    int device = 0, on_device = 0;
+    long long count = 0;
+    apd_fusion::PointArrays arrays;
+    std::vector<int> pair_offsets, pair_indices;  // the call's source lists: what bit j of sources[k] means
+    std::vector<int> rows, cols;                  // the call's view sizes: what pixel[k] and a projection into a source mean
+    // apd_points_visibility: built on the first call, where the arrays live (host: malloc; device: hipMalloc)
+    long long *vis_offsets = nullptr;
+    int32_t *vis_views = nullptr;
+};

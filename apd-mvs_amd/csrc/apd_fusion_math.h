@@ -210,4 +210,73 @@ APD_HD bool accept_point(int agreeing, float consistency, int weak_state)
     return accept_point(agreeing, consistency, weak_state, 1, 0.3f, 0.45f);
 }
 
+// A view as the mean below reads it: the geometry and the depth and normal maps (rows x cols of geo)
+struct MapView {
+    View geo;
+    const float *depth;   // <= 0: no estimate
+    const float *normal;  // 3 per pixel, world frame
+};
+
+// The lowest set bit of m != 0
+APD_HD int lowest_bit(uint32_t m)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __ffs((int)m) - 1;
+#else
+    return __builtin_ctz(m);
+#endif
+}
+
+// Mean position and normal of a fused point over its own view and its agreeing sources (apd_points_average): what fusibile,
+// ACMM's RunFusion and COLMAP's fusion emit.  P, n: the point's stored position and normal (the reference term: no map of the
+// point's own view is read); mask: its agreeing sources; src[0 .. num_src): the source list of its view.  Source j of the mask,
+// in ascending order, contributes the lifted point and the normal of the pixel P projects to (vote_target: the very bits the fusion
+// projected), unless P lands outside the view or the depth there is <= 0 (the fusion's predicate: NaN is not skipped); the
+// sources that contributed are `kept`, their number `used`.  Sums in that order from the reference term, one division per
+// component by used + 1; the mean normal is renormalised (left-to-right sum of squares, sqrtf), (0, 0, 0) when its length is 0
+// or NaN.  A mean position is NaN only when a contributing depth is NaN or infinite (no ETH vote has one; a Tanks and Temples
+// point can reach one through a stale entry); which NaN it is -- sign and payload -- is outside the contract, as IEEE 754 leaves
+// it to the machine.
+APD_HD void mean_point(const MapView *views, const int *src, int num_src, const float P[3], const float n[3], uint32_t mask,
+                       float meanP[3], float meanN[3], uint32_t &kept, int &used)
+{
+    float sumP[3] = {P[0], P[1], P[2]}, sumN[3] = {n[0], n[1], n[2]};
+    used = 0;
+    kept = 0;
+    uint32_t m = mask & (num_src >= 32 ? 0xFFFFFFFFu : ((1u << num_src) - 1u));
+    while (m) {  // at most 32 rounds
+        const int j = lowest_bit(m);
+        m &= m - 1;
+        const MapView &sv = views[src[j]];
+        int sc, sr;
+        if (!vote_target(sv.geo, P, sc, sr)) {
+            continue;
+        }
+        const size_t idx = (size_t)sr * (size_t)sv.geo.cols + (size_t)sc;
+        const float d = sv.depth[idx];
+        if (d <= 0.0f) {
+            continue;
+        }
+        float Q[3];
+        lift(sv.geo, sc, sr, d, Q);
+        for (int k = 0; k < 3; ++k) {
+            sumP[k] += Q[k];
+            sumN[k] += sv.normal[3 * idx + k];
+        }
+        used++;
+        kept |= 1u << j;
+    }
+    const float count = (float)(used + 1);
+    float t[3];
+    for (int k = 0; k < 3; ++k) {
+        meanP[k] = sumP[k] / count;
+        t[k] = sumN[k] / count;
+    }
+    const float len = sqrtf(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+    const bool ok = len > 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        meanN[k] = ok ? t[k] / len : 0.0f;
+    }
+}
+
 }  // namespace apd_fusion

@@ -164,6 +164,9 @@ void SetFusionOptions(const apd_fusion_options &options);
 // additive: RunFusion and the in-memory paths also write <dense>/APD/APD.ply.vis, COLMAP's fused.ply.vis (apd_points_write_vis):
 // per point the views that see it, as positions in pair.txt
 void SetFusionPlyVis(bool on);
+// additive: <dense>/APD/APD.ply holds the mean position (and, with normals in the file, the mean normal) of every point over the
+// views that agree on it (apd_points_average, apd_points_write_ply); an APD.ply.vis is then that of the averaged points
+void SetFusionPlyMean(bool on);
 
 class APD {
 public:

@@ -29,6 +29,7 @@ namespace {
 int g_fusion_device = 0;
 int g_fusion_variant = APD_FUSION_ETH;  // which of the reference's loops (APD_FUSION_*, include/apd_mi355x.h)
 bool g_fusion_ply_vis = false;          // SetFusionPlyVis
+bool g_fusion_ply_mean = false;         // SetFusionPlyMean
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
 apd_fusion_options &fusion_options()
@@ -57,10 +58,14 @@ struct FusionView {
     Mat block;     // optional uint8 mask of <dense>/blocks (APD.cpp:849-853); empty = none
 };
 
+void average_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
+                       const int *rows, const int *cols, int maps_on_device, const path &ply_path);
+
 // Device fusion through the C ABI (host pointers).  options: nullptr = those of SetFusionOptions; ply_path may be null when
-// points is not.
+// points is not.  mean_path (--ply-mean; points must be given): the fusion writes no file, *points become the averaged points
+// and their PLY goes to *mean_path.
 long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const char *ply_path,
-                        const apd_fusion_options *options = nullptr, apd_points_t *points = nullptr)
+                        const apd_fusion_options *options = nullptr, apd_points_t *points = nullptr, const path *mean_path = nullptr)
 {
     const int V = (int)views.size();
     std::vector<apd_camera> cams(V);
@@ -90,11 +95,14 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
     const int channels = (V > 0 && views[0].image.type == MAT_32FC3) ? 3 : 1;
     const apd_fusion_options opt = options ? *options : call_options();
     const int st = apd_fuse_views_opt(&opt, g_fusion_device, V, cams.data(), imgs.data(), channels, deps.data(), nors.data(), weaks.data(),
-                                      any_block ? blocks.data() : nullptr, rows.data(), cols.data(), offs.data(), idx.data(), 0, ply_path, &n,
-                                      points);
+                                      any_block ? blocks.data() : nullptr, rows.data(), cols.data(), offs.data(), idx.data(), 0,
+                                      mean_path ? nullptr : ply_path, &n, points);
     if (st != APD_OK) {
         std::cerr << apd_fusion_last_error() << std::endl;
         return -1;
+    }
+    if (mean_path) {
+        average_and_write(*points, V, cams.data(), deps.data(), nors.data(), rows.data(), cols.data(), 0, *mean_path);
     }
     return n;
 }
@@ -107,7 +115,27 @@ void SetFusionVariant(int variant) { g_fusion_variant = variant; }
 
 void SetFusionPlyVis(bool on) { g_fusion_ply_vis = on; }
 
+void SetFusionPlyMean(bool on) { g_fusion_ply_mean = on; }
+
 namespace {
+
+// --ply-mean: replaces the points of a fusion by their means over the agreeing views (apd_points_average with the fusion's own
+// cameras and maps) and writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
+void average_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
+                       const int *rows, const int *cols, int maps_on_device, const path &ply_path)
+{
+    apd_points_t mean = nullptr;
+    int st = apd_points_average(points, num_views, cameras, depths, normals, rows, cols, maps_on_device, &mean);
+    st = st != APD_OK ? st : apd_points_write_ply(mean, ply_path.string().c_str(), fusion_options().ply_normals);
+    const std::string err = st != APD_OK ? apd_fusion_last_error() : "";
+    apd_points_destroy(points);
+    points = mean;
+    if (st != APD_OK) {
+        apd_points_destroy(mean);
+        std::cerr << err << std::endl;
+        exit(EXIT_FAILURE);
+    }
+}
 
 // --ply-vis: <ply_path>.vis from the points of the fusion that wrote ply_path; releases them
 void write_vis_beside(const path &ply_path, apd_points_t points)
@@ -267,7 +295,8 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     const auto t_fuse = std::chrono::steady_clock::now();
     std::cout << "Fusion inputs ready: " << std::chrono::duration_cast<std::chrono::milliseconds>(t_fuse - t_inputs).count() << " ms" << std::endl;
     apd_points_t points = nullptr;
-    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str(), nullptr, g_fusion_ply_vis ? &points : nullptr);
+    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str(), nullptr, g_fusion_ply_vis || g_fusion_ply_mean ? &points : nullptr,
+                                      g_fusion_ply_mean ? &ply_path : nullptr);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms" << std::endl;
     if (n < 0) {
         exit(EXIT_FAILURE);  // like every other device error of the reference (CudaSafeCall, APD.cpp:315-323)
@@ -275,6 +304,8 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     std::cout << "Fused " << n << " points into " << ply_path << std::endl;
     if (g_fusion_ply_vis) {
         write_vis_beside(ply_path, points);
+    } else {
+        apd_points_destroy(points);  // --ply-mean alone
     }
 }
 
@@ -454,12 +485,13 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
     long long count = 0;
     apd_fusion_options fusion = call_options();
     apd_points_t points = nullptr;
-    if (g_fusion_ply_vis) {
-        fusion.result_on_device = 1;  // the maps are here already: the lists are built here too and only they come down
+    if (g_fusion_ply_vis || g_fusion_ply_mean) {
+        fusion.result_on_device = 1;  // the maps are here already: the lists and the means are built here too and only they come down
     }
     const int st = apd_fuse_views_opt(&fusion, f->device, V, cams.data(), f->imgs.data(), f->channels, depths.data(), normals.data(), weaks.data(),
                                       f->any_block ? f->blocks.data() : nullptr, rws.data(), cls.data(), offs.data(), idx.data(), 1,
-                                      ply_path.string().c_str(), &count, g_fusion_ply_vis ? &points : nullptr);
+                                      g_fusion_ply_mean ? nullptr : ply_path.string().c_str(), &count,
+                                      g_fusion_ply_vis || g_fusion_ply_mean ? &points : nullptr);
     double ms_setup = 0, ms_views = 0, ms_file = 0;
     apd_fusion_last_timing(&ms_setup, &ms_views, &ms_file);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms (set-up "
@@ -470,9 +502,14 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
         std::cerr << err << std::endl;
         exit(EXIT_FAILURE);
     }
+    if (g_fusion_ply_mean) {
+        average_and_write(points, V, cams.data(), depths.data(), normals.data(), rws.data(), cls.data(), 1, ply_path);
+    }
     std::cout << "Fused " << count << " points into " << ply_path << std::endl;
     if (g_fusion_ply_vis) {
         write_vis_beside(ply_path, points);
+    } else {
+        apd_points_destroy(points);  // --ply-mean alone
     }
 }
 

@@ -3,7 +3,7 @@
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
-//       [--ply-normals] [--ply-vis] [--filtered-maps]
+//       [--ply-normals] [--ply-vis] [--ply-mean] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -15,6 +15,11 @@
 // APD.ply with nx ny nz, the reference pixel's normal, for every loop.  A bad value is refused with the usage line before
 // anything is read or written.  Without these flags APD.ply keeps its bytes.  --ply-vis: APD/APD.ply.vis beside APD.ply, COLMAP's
 // fused.ply.vis (per point the views that see it, as positions in pair.txt), from the same fusion; APD.ply keeps its bytes.
+// --ply-mean: APD.ply holds every point's mean position over its own view and its agreeing sources (apd_points_average: what
+// fusibile, ACMM and COLMAP emit) instead of the reference pixel's; with --ply-normals the mean normal, renormalised, too; with
+// --ply-vis the lists of the averaged points.  With every --fusion.  A source contributes the pixel the point itself projects to;
+// the Tanks and Temples loops may count a source through a stale `diff` entry of an earlier pixel, which that projection does not
+// reach or finds without depth: such a source is skipped and no longer listed.  Without the flag nothing changes.
 //
 // --masks [DIR] (default DIR: masks): <dense_folder>/DIR/<%08d>.jpg|pgm are per-view pixel masks, grey < 128 = masked out of
 // PatchMatch (apd_upload_mask: the pixels cost no NCC and leave as depth 0 / UNKNOWN); a view without a file is unmasked, a file
@@ -116,6 +121,8 @@ bool ParseOptions(int argc, char **argv, Options &o)
             o.fusion.ply_normals = 1;
         } else if (a == "--ply-vis") {
             o.ply_vis = true;
+        } else if (a == "--ply-mean") {
+            o.ply_mean = true;
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
         } else if (a == "--seed") {
@@ -327,7 +334,9 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n");
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+                        "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
+                        "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -343,6 +352,7 @@ int main(int argc, char **argv)
     SetFusionDevice(opt.gpu_index);
     SetFusionOptions(opt.fusion);
     SetFusionPlyVis(opt.ply_vis);
+    SetFusionPlyMean(opt.ply_mean);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

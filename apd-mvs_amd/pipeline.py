@@ -516,8 +516,42 @@ def read_vis(path):
     return offsets, words[keep].astype(np.int32)
 
 
+def _fusion_views(scene, results):
+    """What fuse() hands over of every view besides its image: the camera with K scaled to the maps when the image has another
+    size (RescaleImageAndCamera, APD.cpp:729-750), the depth map and the normal map."""
+    cam_t = type(scene.cameras[0])
+    cams = (cam_t * scene.num_views)()
+    deps, nors = [], []
+    for v in range(scene.num_views):
+        st = results[v]
+        h, w = st.depth.shape
+        cam = cam_t.from_buffer_copy(scene.cameras[v])
+        img = scene.images[v]
+        if img.shape[:2] != (h, w):
+            sx = np.float32(w) / np.float32(img.shape[1])
+            sy = np.float32(h) / np.float32(img.shape[0])
+            cam.K[0] = float(np.float32(cam.K[0]) * sx)
+            cam.K[2] = float(np.float32(cam.K[2]) * sx)
+            cam.K[4] = float(np.float32(cam.K[4]) * sy)
+            cam.K[5] = float(np.float32(cam.K[5]) * sy)
+        cams[v] = cam
+        deps.append(np.ascontiguousarray(st.depth, np.float32))
+        nors.append(np.ascontiguousarray(st.normal, np.float32))
+    return cams, deps, nors
+
+
+def average_points(scene, results, points, device=0):
+    """Points.average with the cameras and the depth and normal maps fuse() passes for (scene, results): the mean position and
+    normal of every point of `points` (a Points of fuse(..., return_points=True) on the same scene and results) over the views
+    that agree on it.  Returns a new Points where `points` lives; on GPU `points.device` (`device` must name it)."""
+    if int(device) != points.device:
+        raise ValueError("average_points: the points live on device %d, not %d" % (points.device, int(device)))
+    cams, deps, nors = _fusion_views(scene, results)
+    return points.average(cams, deps, nors)
+
+
 def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False,
-         vis_path=None):
+         vis_path=None, average=False):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -530,13 +564,28 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     result_on_device; its `variant` is set from `variant`), None for the reference's behaviour.  return_points: also return the
     points as a Points object (numpy views, or torch tensors on `device` with result_on_device): (count, Points); ply_path may
     then be None and no file is written.  vis_path: also write COLMAP's fused.ply.vis of the same fusion there (per point the
-    views that see it, as indices of the scene's views; Points.write_vis), with or without a PLY file or the points."""
+    views that see it, as indices of the scene's views; Points.write_vis), with or without a PLY file or the points.
+    average: the mean geometry (average_points) -- the file (written by Points.write_ply, with normals when the options say
+    ply_normals), the returned points and the .vis file are those of the averaged points: positions and normals are means over
+    the agreeing views, and a source that did not contribute is no longer listed."""
     import ctypes as C
     from . import Points, default_fusion_options
     if variant not in FUSION_VARIANTS:
         raise ValueError("unknown fusion variant %r: one of %s" % (variant, ", ".join(sorted(FUSION_VARIANTS))))
     if ply_path is None and not return_points and vis_path is None:
         raise ValueError("fuse: neither a PLY file nor the points nor the visibility file are asked for")
+    if average:
+        n, fused = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True)
+        mean = average_points(scene, results, fused, device)
+        fused.close()
+        if ply_path is not None:
+            mean.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
+        if vis_path is not None:
+            mean.write_vis(vis_path)
+        if return_points:
+            return n, mean
+        mean.close()
+        return n
     L = host_lib()
     L.apdhost_set_fusion_device(int(device))
     L.apdhost_set_fusion_variant(FUSION_VARIANTS[variant])

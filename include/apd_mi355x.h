@@ -388,7 +388,7 @@ void apd_fusion_default_options(apd_fusion_options *o);
 
 /* The points of one fusion as a structure of arrays, in the order of the PLY file: views in order, pixels of a view in raster
  * order.  Point k has
- *   xyz      3 floats: the reference pixel's lifted point (the reference averages only colour);
+ *   xyz      3 floats: the reference pixel's lifted point (the reference averages only colour; apd_points_average gives the mean);
  *   normal   3 floats: the reference pixel's normal as given in normals[view], copied, not renormalised;
  *   bgr      3 bytes: the colour of the PLY record;
  *   support  1 byte: the votes the point was accepted with (ETH: num_consistent >= min_consistent; T&T: `count` of the round
@@ -424,6 +424,32 @@ int apd_points_visibility(apd_points_t p, const long long **offsets, const int32
  * i.e. positions of views in the fusion call.  Host- or device-resident points.  NULL p or path: APD_ERR_INVALID; a file that
  * cannot be written: APD_ERR_IO. */
 int apd_points_write_vis(apd_points_t p, const char *path);
+/* Mean geometry: a new points object with p's points in p's order, each with the mean of the points and of the normals of the views
+ * that agree on it -- what fusibile, ACMM's RunFusion and COLMAP's stereo fusion emit; p itself, like every fusion call, keeps the
+ * reference pixel's.  cameras, depths, normals, rows, cols, maps_on_device: as in the fusion call that made p (the same maps, or
+ * others of the same sizes, e.g. filtered ones); the images, weak maps and block masks are not needed.  Point k with position P =
+ * xyz[k], normal n, view v and mask m = sources[k]: for every set bit j of m in ascending order, s = pair_indices[pair_offsets[v]
+ * + j]; P is projected into view s exactly as the fusion projected it (APD.cpp:896-899); a source whose pixel lies outside the
+ * view or has depth <= 0 there is skipped; otherwise the pixel's lifted point (Get3DPointonWorld) and its normal are added to
+ * sums that start from P and n.  The result has xyz = sum / (used + 1), normal = the mean normal renormalised ((0, 0, 0) when its
+ * length is 0 or NaN), sources = the bits that were not skipped, support = their number `used`; bgr, view and pixel are copied.
+ * binary32 in that fixed order (contract C9).  With the maps of the ETH fusion that made p nothing is skipped and sources and
+ * support come back unchanged; a Tanks and Temples point may name a source through a stale `diff` entry that its own projection
+ * does not reach: that source is skipped by the rule above.  The object lives where p lives (host memory, or device memory on
+ * p's device), carries p's source lists on (apd_points_visibility and apd_points_write_vis work on it and list the views that were
+ * kept) and is released with apd_points_destroy.  The mean is computed on p's device, whatever memory p and the maps are in
+ * (host-resident points and host maps are uploaded, the result is downloaded); an object without points gives an object without
+ * points.  Refused with APD_ERR_INVALID before any device is touched, message "apd_points_average: ..." (apd_fusion_last_error):
+ * a NULL argument, num_views, rows[i] or cols[i] other than the fusion call's, a NULL depths[s] or normals[s] for a view s that
+ * some source list names.  *out is untouched when the call fails. */
+int apd_points_average(apd_points_t p, int num_views, const apd_camera *cameras, const float *const *depths,
+                       const float *const *normals, const int *rows, const int *cols, int maps_on_device, apd_points_t *out);
+/* The PLY file of any points object, a fusion's or an averaged one: the header and the records of ExportPointCloud (APD.cpp:214-254)
+ * as the fusion writes them, x y z + colour (15 bytes) or with_normals != 0: x y z nx ny nz + colour (27 bytes).  For the points
+ * of a fusion call these are the bytes that call writes to its ply_path with the same ply_normals.  Host- or device-resident
+ * points.  `element vertex` is printed from the 64-bit count.  NULL p or path: APD_ERR_INVALID; a file that cannot be written:
+ * APD_ERR_IO. */
+int apd_points_write_ply(apd_points_t p, const char *path, int with_normals);
 int apd_points_destroy(apd_points_t p);
 
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
