@@ -183,6 +183,11 @@ def lib():
     L.apd_points_write_vis.argtypes = [C.c_void_p, C.c_char_p]
     L.apd_points_average.argtypes = [C.c_void_p, C.c_int, C.c_void_p, fpp, fpp, ipp, ipp, C.c_int, C.POINTER(C.c_void_p)]
     L.apd_points_write_ply.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.apd_points_create.argtypes = [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 7 + [C.c_int, ipp, ipp, ipp, ipp, C.POINTER(C.c_void_p)]
+    L.apd_points_merge_voxels.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
+    L.apd_points_merged.argtypes = [C.c_void_p]
+    L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
+    L.apd_sort_tile_sizes.restype = None
     L.apd_points_destroy.argtypes = [C.c_void_p]
     L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     _lib = L
@@ -230,7 +235,10 @@ class Points:
     on its device, filled by device-to-device copies (no host round trip) and independent of this object.  visibility() and
     write_vis() are the library's (apd_points_visibility, apd_points_write_vis), and so are average() (apd_points_average: a new
     Points with positions and normals averaged over the agreeing views) and write_ply() (apd_points_write_ply); the object keeps
-    the library's points for them until close()."""
+    the library's points for them until close().  from_arrays() makes a Points of a caller's arrays (apd_points_create);
+    merge_voxels() gives one point per cell of a cubic grid with the union of the members' lists (apd_points_merge_voxels), and
+    `merged` says whether an object is such a result: its view, pixel and sources are its representative's alone, its lists are
+    those of visibility(), and average() refuses it."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
                ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
@@ -242,6 +250,7 @@ class Points:
         self.device = int(device)
         self.count = int(L.apd_points_count(handle))
         self.on_device = bool(L.apd_points_on_device(handle))
+        self.merged = bool(L.apd_points_merged(handle))
         self._lists = None
         for name, width, typestr, size in self._FIELDS:
             address = getattr(L, "apd_points_" + name)(handle)
@@ -261,6 +270,47 @@ class Points:
         if count:
             return np.asarray(_Borrowed(self, address, shape, typestr))
         return np.empty(shape, np.dtype(typestr))
+
+    @classmethod
+    def from_arrays(cls, xyz, normal, bgr, support, view, pixel, sources, rows, cols, pairs, device=0, on_device=False):
+        """apd_points_create: a Points of the caller's arrays (numpy or anything numpy converts; copied), as if fused over views of
+        rows[i] x cols[i] pixels with the source lists pairs[i] (view indices).  on_device: the copy lives on GPU `device`;
+        otherwise it is host memory and no device is touched.  The library checks the arrays against the views and the lists and
+        raises ApdError with its message."""
+        L = lib()
+        arrays = [np.ascontiguousarray(a, t) for a, t in zip((xyz, normal, bgr, support, view, pixel, sources),
+                                                            (np.float32, np.float32, np.uint8, np.uint8, np.int32, np.int32, np.uint32))]
+        count = len(arrays[4])
+        for a, width in zip(arrays, (3, 3, 3, 1, 1, 1, 1)):
+            if a.size != count * width:
+                raise ValueError("Points.from_arrays: %d views (one per point) and an array of %d elements, not %d" % (count, a.size, count * width))
+        V = len(rows)
+        if len(cols) != V or len(pairs) != V:
+            raise ValueError("Points.from_arrays: %d rows, %d cols, %d source lists" % (V, len(cols), len(pairs)))
+        flat = [int(s) for p in pairs for s in p]
+        offs = (C.c_int * (V + 1))(*np.cumsum([0] + [len(p) for p in pairs]).tolist())
+        idx = (C.c_int * max(len(flat), 1))(*flat)
+        out = C.c_void_p()
+        rc = L.apd_points_create(int(device), int(bool(on_device)), count, *[C.c_void_p(a.ctypes.data) for a in arrays], V,
+                                 (C.c_int * max(V, 1))(*[int(r) for r in rows]), (C.c_int * max(V, 1))(*[int(c) for c in cols]), offs, idx, C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return cls(out, device)
+
+    def merge_voxels(self, size, origin=None):
+        """apd_points_merge_voxels: (Points, dropped) -- one point per occupied cell of the cubic grid of cell size `size` with a
+        corner at `origin` (0, 0, 0 by default), in ascending cell order (z-major), each the mean of its members in input order,
+        with the distinct views of its members' lists as its visibility() list; `dropped` points had a non-finite coordinate or
+        lie more than 2^20 cells from the origin.  Computed on these points' device; the result lives where they live."""
+        if not self._p:
+            raise ApdError("Points.merge_voxels: the points are closed")
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        out, dropped = C.c_void_p(), C.c_longlong(0)
+        rc = L.apd_points_merge_voxels(self._p, float(size), org, C.byref(out), C.byref(dropped))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device), int(dropped.value)
 
     def __len__(self):
         return self.count

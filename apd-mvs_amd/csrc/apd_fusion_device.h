@@ -235,4 +235,7 @@ struct apd_points {
     // apd_points_visibility: built on the first call, where the arrays live (host: malloc; device: hipMalloc)
     long long *vis_offsets = nullptr;
     int32_t *vis_views = nullptr;
+    // a result of apd_points_merge_voxels: made with its lists (the union of its members'), view / pixel / sources are its
+    // representative's and say nothing about the lists
+    int merged = 0;
 };

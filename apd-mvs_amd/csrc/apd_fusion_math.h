@@ -227,6 +227,21 @@ APD_HD int lowest_bit(uint32_t m)
 #endif
 }
 
+// The mean of `count` normals whose sum is sumN, renormalised: one division per component, a left-to-right sum of squares, sqrtf,
+// and (0, 0, 0) when the length is 0 or NaN.  The one rule of apd_points_average and apd_points_merge_voxels.
+APD_HD void mean_normal(const float sumN[3], float count, float meanN[3])
+{
+    float t[3];
+    for (int k = 0; k < 3; ++k) {
+        t[k] = sumN[k] / count;
+    }
+    const float len = sqrtf(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+    const bool ok = len > 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        meanN[k] = ok ? t[k] / len : 0.0f;
+    }
+}
+
 // Mean position and normal of a fused point over its own view and its agreeing sources (apd_points_average): what fusibile,
 // ACMM's RunFusion and COLMAP's fusion emit.  P, n: the point's stored position and normal (the reference term: no map of the
 // point's own view is read); mask: its agreeing sources; src[0 .. num_src): the source list of its view.  Source j of the mask,
@@ -267,16 +282,10 @@ APD_HD void mean_point(const MapView *views, const int *src, int num_src, const 
         kept |= 1u << j;
     }
     const float count = (float)(used + 1);
-    float t[3];
     for (int k = 0; k < 3; ++k) {
         meanP[k] = sumP[k] / count;
-        t[k] = sumN[k] / count;
     }
-    const float len = sqrtf(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-    const bool ok = len > 0.0f;
-    for (int k = 0; k < 3; ++k) {
-        meanN[k] = ok ? t[k] / len : 0.0f;
-    }
+    mean_normal(sumN, count, meanN);
 }
 
 }  // namespace apd_fusion

@@ -1,5 +1,9 @@
 // apd_points.hip -- what is done with a fusion's points after the fusion: apd_points_average and apd_points_write_ply of
-// include/apd_mi355x.h.
+// include/apd_mi355x.h, and apd_points_create, which makes a points object of a caller's arrays.  (apd_points_merge_voxels:
+// apd_points_merge.hip.)
+//
+// apd_points_create: the checks that make the arrays a cloud some fusion could have made (every later call relies on them: a
+// view indexes the source lists, a bit of `sources` indexes a list), then one copy of each array, to host memory or to the device.
 //
 // apd_points_average: the mean position and normal of every point over its own view and its agreeing sources
 // (apd_fusion::mean_point, apd_fusion_math.h: contract C9).  A pure function of (points, maps): a point names its view and its
@@ -22,11 +26,14 @@
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_device.h"
 #include "apd_fusion_math.h"
+#include "apd_points_host.h"
 
 namespace {
 
 using apd_fusion::MapView;
 using apd_fusion::PointArrays;
+using apd_points_host::DeviceScope;
+using apd_points_host::Scratch;
 
 // Point k < n of `in` averaged into `out` (xyz, normal, sources = the sources that contributed, support = their number).  One lane
 // per point; each lane walks its mask (mean_point: at most 32 rounds) and gathers up to 32 x (4 + 12) bytes from the maps.  No
@@ -63,62 +70,15 @@ int hip_failed(const char *expr, hipError_t e, const char *, int)
     return apd::set_error(err(), APD_ERR_HIP, "apd_points_average: %s: %s", expr, hipGetErrorString(e));
 }
 
-// Selects a device for one call and puts the caller's back
-struct DeviceScope {
-    int previous = -1;
-    explicit DeviceScope(bool active)
-    {
-        if (active && hipGetDevice(&previous) != hipSuccess) {
-            previous = -1;
-        }
-    }
-    ~DeviceScope()
-    {
-        if (previous >= 0) {
-            hipSetDevice(previous);
-        }
-    }
-};
-
-// Device memory of one call: freed when the call returns, but for what it hands over
-struct Scratch {
-    std::vector<void *> owned;
-    ~Scratch()
-    {
-        for (void *q : owned) {
-            hipFree(q);
-        }
-    }
-    template <typename T> hipError_t alloc(size_t bytes, T **out)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes > 0 ? bytes : 1);
-        if (e == hipSuccess) {
-            owned.push_back(q);
-            *out = static_cast<T *>(q);
-        }
-        return e;
-    }
-    // a device copy of `bytes` host bytes
-    template <typename T> hipError_t upload(const T *host, size_t bytes, const T **out)
-    {
-        T *copy = nullptr;
-        hipError_t e = alloc(bytes, &copy);
-        if (e == hipSuccess) {
-            *out = copy;
-            e = bytes > 0 ? hipMemcpy(copy, host, bytes, hipMemcpyHostToDevice) : hipSuccess;
-        }
-        return e;
-    }
-    void keep(void *q) { owned.erase(std::find(owned.begin(), owned.end(), q)); }
-};
-
 // What apd_points_average refuses, before any device call
 int check_average(apd_points_t p, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
                   const int *rows, const int *cols, apd_points_t *out)
 {
     if (!p || !cameras || !depths || !normals || !rows || !cols || !out) {
         return apd::set_error(err(), APD_ERR_INVALID, "apd_points_average: null argument");
+    }
+    if (p->merged) {  // its sources are its representative's: there is no list of maps to average a merged point over
+        return apd::set_error(err(), APD_ERR_INVALID, "apd_points_average: merged points name no sources");
     }
     if (num_views != (int)p->rows.size()) {
         return apd::set_error(err(), APD_ERR_INVALID, "apd_points_average: %d views, the fusion of the points had %d", num_views, (int)p->rows.size());
@@ -264,6 +224,156 @@ extern "C" int apd_points_average(apd_points_t p, int num_views, const apd_camer
         }
     }
     *out = result;
+    return APD_OK;
+}
+
+namespace {
+
+int create_hip_failed(const char *expr, hipError_t e, const char *, int)
+{
+    return apd::set_error(err(), APD_ERR_HIP, "apd_points_create: %s: %s", expr, hipGetErrorString(e));
+}
+
+#define CREATE_REFUSE(...) return apd::set_error(err(), APD_ERR_INVALID, "apd_points_create: " __VA_ARGS__)
+
+// What apd_points_create refuses, before anything is allocated
+int check_create(long long count, const float *xyz, const float *normal, const uint8_t *bgr, const uint8_t *support, const int32_t *view,
+                 const int32_t *pixel, const uint32_t *sources, int num_views, const int *rows, const int *cols, const int *pair_offsets,
+                 const int *pair_indices, apd_points_t *out)
+{
+    if (!rows || !cols || !pair_offsets || !out) {
+        CREATE_REFUSE("null argument");
+    }
+    if (count < 0) {
+        CREATE_REFUSE("a count of %lld points", count);
+    }
+    if (count > 0 && !(xyz && normal && bgr && support && view && pixel && sources)) {
+        CREATE_REFUSE("null argument");
+    }
+    if (num_views < 1) {
+        CREATE_REFUSE("%d views", num_views);
+    }
+    for (int i = 0; i < num_views; ++i) {
+        if (rows[i] <= 0 || cols[i] <= 0) {
+            CREATE_REFUSE("view %d has %d x %d pixels", i, cols[i], rows[i]);
+        }
+        if ((long long)rows[i] * cols[i] > 0x7fffffffLL) {
+            CREATE_REFUSE("view %d has %d x %d pixels, more than a pixel index holds", i, cols[i], rows[i]);
+        }
+    }
+    if (pair_offsets[0] != 0) {
+        CREATE_REFUSE("pair_offsets starts at %d, not at 0", pair_offsets[0]);
+    }
+    for (int i = 0; i < num_views; ++i) {
+        const int len = pair_offsets[i + 1] - pair_offsets[i];
+        if (pair_offsets[i + 1] < pair_offsets[i]) {
+            CREATE_REFUSE("pair_offsets descends at view %d", i);
+        }
+        if (len > APD_MAX_IMAGES) {
+            CREATE_REFUSE("view %d has %d sources, more than %d", i, len, APD_MAX_IMAGES);
+        }
+    }
+    if (pair_offsets[num_views] > 0 && !pair_indices) {
+        CREATE_REFUSE("null argument");
+    }
+    for (int i = 0; i < num_views; ++i) {
+        for (int e = pair_offsets[i]; e < pair_offsets[i + 1]; ++e) {
+            if (pair_indices[e] < 0 || pair_indices[e] >= num_views) {
+                CREATE_REFUSE("source %d of view %d is view %d of %d", e - pair_offsets[i], i, pair_indices[e], num_views);
+            }
+            if (pair_indices[e] == i) {
+                CREATE_REFUSE("view %d is its own source", i);
+            }
+        }
+    }
+    for (long long k = 0; k < count; ++k) {
+        const int v = view[k];
+        if (v < 0 || v >= num_views) {
+            CREATE_REFUSE("point %lld is of view %d of %d", k, v, num_views);
+        }
+        if (pixel[k] < 0 || pixel[k] >= rows[v] * cols[v]) {
+            CREATE_REFUSE("point %lld is pixel %d of view %d, which has %d", k, pixel[k], v, rows[v] * cols[v]);
+        }
+        const int len = pair_offsets[v + 1] - pair_offsets[v];
+        if (len < 32 && (sources[k] >> len) != 0) {
+            CREATE_REFUSE("point %lld names sources 0x%x, its view %d has %d", k, sources[k], v, len);
+        }
+        if (__builtin_popcount(sources[k]) != (int)support[k]) {
+            CREATE_REFUSE("point %lld names %d sources and has a support of %d", k, __builtin_popcount(sources[k]), (int)support[k]);
+        }
+    }
+    return APD_OK;
+}
+
+#undef CREATE_REFUSE
+
+// a copy of `bytes` caller bytes where the object lives
+template <typename T> int create_copy(bool on_device, const T *from, size_t bytes, T **to)
+{
+    const auto hip_failed = create_hip_failed;
+    if (on_device) {
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, bytes));
+        *to = static_cast<T *>(q);  // the object's from here on: apd_points_destroy frees it
+        HIP_TRY(hipMemcpy(q, from, bytes, hipMemcpyHostToDevice));
+        return APD_OK;
+    }
+    *to = static_cast<T *>(malloc(bytes));
+    if (!*to) {
+        return apd::set_error(err(), APD_ERR_HIP, "apd_points_create: out of host memory");
+    }
+    memcpy(*to, from, bytes);
+    return APD_OK;
+}
+
+int create_arrays(apd_points *q, const float *xyz, const float *normal, const uint8_t *bgr, const uint8_t *support, const int32_t *view,
+                  const int32_t *pixel, const uint32_t *sources)
+{
+    const auto hip_failed = create_hip_failed;
+    const size_t n = (size_t)q->count;
+    const bool dev = q->on_device != 0;
+    if (dev) {
+        HIP_TRY(hipSetDevice(q->device));
+    }
+    PointArrays &a = q->arrays;
+    int rc = create_copy(dev, xyz, n * 12, &a.xyz);
+    rc = rc != APD_OK ? rc : create_copy(dev, normal, n * 12, &a.normal);
+    rc = rc != APD_OK ? rc : create_copy(dev, bgr, n * 3, &a.bgr);
+    rc = rc != APD_OK ? rc : create_copy(dev, support, n, &a.support);
+    rc = rc != APD_OK ? rc : create_copy(dev, view, n * 4, &a.view);
+    rc = rc != APD_OK ? rc : create_copy(dev, pixel, n * 4, &a.pixel);
+    return rc != APD_OK ? rc : create_copy(dev, sources, n * 4, &a.sources);
+}
+
+}  // namespace
+
+extern "C" int apd_points_create(int device, int on_device, long long count, const float *xyz, const float *normal, const uint8_t *bgr,
+                                 const uint8_t *support, const int32_t *view, const int32_t *pixel, const uint32_t *sources, int num_views,
+                                 const int *rows, const int *cols, const int *pair_offsets, const int *pair_indices, apd_points_t *out)
+{
+    err().clear();
+    if (const int rc = check_create(count, xyz, normal, bgr, support, view, pixel, sources, num_views, rows, cols, pair_offsets, pair_indices, out);
+        rc != APD_OK) {
+        return rc;
+    }
+    apd_points *q = new apd_points();
+    q->device = device;
+    q->on_device = on_device ? 1 : 0;
+    q->count = count;
+    q->pair_offsets.assign(pair_offsets, pair_offsets + num_views + 1);
+    q->pair_indices.assign(pair_indices, pair_indices + pair_offsets[num_views]);
+    q->rows.assign(rows, rows + num_views);
+    q->cols.assign(cols, cols + num_views);
+    if (count > 0) {
+        DeviceScope scope(q->on_device != 0);
+        if (const int rc = create_arrays(q, xyz, normal, bgr, support, view, pixel, sources); rc != APD_OK) {
+            const std::string why = err();
+            apd_points_destroy(q);  // the arrays made so far
+            err() = why;
+            return rc;
+        }
+    }
+    *out = q;
     return APD_OK;
 }
 

@@ -167,6 +167,9 @@ void SetFusionPlyVis(bool on);
 // additive: <dense>/APD/APD.ply holds the mean position (and, with normals in the file, the mean normal) of every point over the
 // views that agree on it (apd_points_average, apd_points_write_ply); an APD.ply.vis is then that of the averaged points
 void SetFusionPlyMean(bool on);
+// additive: size > 0: <dense>/APD/APD.ply holds one point per occupied cell of a cubic grid of that cell size (apd_points_merge_voxels,
+// after the averaging if that is asked for too); an APD.ply.vis is then that of the merged points.  0: off
+void SetFusionPlyVoxel(float size);
 
 class APD {
 public:

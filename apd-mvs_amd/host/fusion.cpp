@@ -30,6 +30,10 @@ int g_fusion_device = 0;
 int g_fusion_variant = APD_FUSION_ETH;  // which of the reference's loops (APD_FUSION_*, include/apd_mi355x.h)
 bool g_fusion_ply_vis = false;          // SetFusionPlyVis
 bool g_fusion_ply_mean = false;         // SetFusionPlyMean
+float g_fusion_ply_voxel = 0.0f;        // SetFusionPlyVoxel; 0: off
+
+// --ply-mean or --ply-voxel: APD.ply is written from the points after the fusion, not by it
+bool ply_from_points() { return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f; }
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
 apd_fusion_options &fusion_options()
@@ -58,12 +62,12 @@ struct FusionView {
     Mat block;     // optional uint8 mask of <dense>/blocks (APD.cpp:849-853); empty = none
 };
 
-void average_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
-                       const int *rows, const int *cols, int maps_on_device, const path &ply_path);
+void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
+                      const int *rows, const int *cols, int maps_on_device, const path &ply_path);
 
 // Device fusion through the C ABI (host pointers).  options: nullptr = those of SetFusionOptions; ply_path may be null when
-// points is not.  mean_path (--ply-mean; points must be given): the fusion writes no file, *points become the averaged points
-// and their PLY goes to *mean_path.
+// points is not.  mean_path (--ply-mean, --ply-voxel; points must be given): the fusion writes no file, *points become the
+// averaged and / or merged points and their PLY goes to *mean_path.
 long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const char *ply_path,
                         const apd_fusion_options *options = nullptr, apd_points_t *points = nullptr, const path *mean_path = nullptr)
 {
@@ -102,7 +106,7 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
         return -1;
     }
     if (mean_path) {
-        average_and_write(*points, V, cams.data(), deps.data(), nors.data(), rows.data(), cols.data(), 0, *mean_path);
+        rework_and_write(*points, V, cams.data(), deps.data(), nors.data(), rows.data(), cols.data(), 0, *mean_path);
     }
     return n;
 }
@@ -117,21 +121,43 @@ void SetFusionPlyVis(bool on) { g_fusion_ply_vis = on; }
 
 void SetFusionPlyMean(bool on) { g_fusion_ply_mean = on; }
 
+void SetFusionPlyVoxel(float size) { g_fusion_ply_voxel = size; }
+
 namespace {
 
 // --ply-mean: replaces the points of a fusion by their means over the agreeing views (apd_points_average with the fusion's own
-// cameras and maps) and writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
-void average_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
-                       const int *rows, const int *cols, int maps_on_device, const path &ply_path)
+// cameras and maps); --ply-voxel: replaces them -- the means, with both -- by one point per cell (apd_points_merge_voxels) and
+// prints the cells and the dropped points.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
+void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
+                      const int *rows, const int *cols, int maps_on_device, const path &ply_path)
 {
-    apd_points_t mean = nullptr;
-    int st = apd_points_average(points, num_views, cameras, depths, normals, rows, cols, maps_on_device, &mean);
-    st = st != APD_OK ? st : apd_points_write_ply(mean, ply_path.string().c_str(), fusion_options().ply_normals);
-    const std::string err = st != APD_OK ? apd_fusion_last_error() : "";
-    apd_points_destroy(points);
-    points = mean;
+    int st = APD_OK;
+    if (g_fusion_ply_mean) {
+        apd_points_t mean = nullptr;
+        st = apd_points_average(points, num_views, cameras, depths, normals, rows, cols, maps_on_device, &mean);
+        if (st == APD_OK) {
+            apd_points_destroy(points);
+            points = mean;
+        }
+    }
+    if (st == APD_OK && g_fusion_ply_voxel > 0.0f) {
+        apd_points_t merged = nullptr;
+        long long dropped = 0;
+        st = apd_points_merge_voxels(points, g_fusion_ply_voxel, nullptr, &merged, &dropped);
+        if (st == APD_OK) {
+            double ms_setup = 0, ms_kernels = 0;
+            apd_fusion_last_timing(&ms_setup, &ms_kernels, nullptr);
+            std::cout << "Merged " << apd_points_count(points) << " points into " << apd_points_count(merged) << " cells of size " << g_fusion_ply_voxel
+                      << ", dropped " << dropped << ": " << (long long)(ms_setup + ms_kernels) << " ms (set-up " << (long long)ms_setup << ", kernels "
+                      << (long long)ms_kernels << ")" << std::endl;
+            apd_points_destroy(points);
+            points = merged;
+        }
+    }
+    st = st != APD_OK ? st : apd_points_write_ply(points, ply_path.string().c_str(), fusion_options().ply_normals);
     if (st != APD_OK) {
-        apd_points_destroy(mean);
+        const std::string err = apd_fusion_last_error();
+        apd_points_destroy(points);
         std::cerr << err << std::endl;
         exit(EXIT_FAILURE);
     }
@@ -295,8 +321,8 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     const auto t_fuse = std::chrono::steady_clock::now();
     std::cout << "Fusion inputs ready: " << std::chrono::duration_cast<std::chrono::milliseconds>(t_fuse - t_inputs).count() << " ms" << std::endl;
     apd_points_t points = nullptr;
-    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str(), nullptr, g_fusion_ply_vis || g_fusion_ply_mean ? &points : nullptr,
-                                      g_fusion_ply_mean ? &ply_path : nullptr);
+    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str(), nullptr, g_fusion_ply_vis || ply_from_points() ? &points : nullptr,
+                                      ply_from_points() ? &ply_path : nullptr);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms" << std::endl;
     if (n < 0) {
         exit(EXIT_FAILURE);  // like every other device error of the reference (CudaSafeCall, APD.cpp:315-323)
@@ -305,7 +331,7 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     if (g_fusion_ply_vis) {
         write_vis_beside(ply_path, points);
     } else {
-        apd_points_destroy(points);  // --ply-mean alone
+        apd_points_destroy(points);  // --ply-mean or --ply-voxel alone
     }
 }
 
@@ -485,13 +511,13 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
     long long count = 0;
     apd_fusion_options fusion = call_options();
     apd_points_t points = nullptr;
-    if (g_fusion_ply_vis || g_fusion_ply_mean) {
+    if (g_fusion_ply_vis || ply_from_points()) {
         fusion.result_on_device = 1;  // the maps are here already: the lists and the means are built here too and only they come down
     }
     const int st = apd_fuse_views_opt(&fusion, f->device, V, cams.data(), f->imgs.data(), f->channels, depths.data(), normals.data(), weaks.data(),
                                       f->any_block ? f->blocks.data() : nullptr, rws.data(), cls.data(), offs.data(), idx.data(), 1,
-                                      g_fusion_ply_mean ? nullptr : ply_path.string().c_str(), &count,
-                                      g_fusion_ply_vis || g_fusion_ply_mean ? &points : nullptr);
+                                      ply_from_points() ? nullptr : ply_path.string().c_str(), &count,
+                                      g_fusion_ply_vis || ply_from_points() ? &points : nullptr);
     double ms_setup = 0, ms_views = 0, ms_file = 0;
     apd_fusion_last_timing(&ms_setup, &ms_views, &ms_file);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms (set-up "
@@ -502,14 +528,14 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
         std::cerr << err << std::endl;
         exit(EXIT_FAILURE);
     }
-    if (g_fusion_ply_mean) {
-        average_and_write(points, V, cams.data(), depths.data(), normals.data(), rws.data(), cls.data(), 1, ply_path);
+    if (ply_from_points()) {
+        rework_and_write(points, V, cams.data(), depths.data(), normals.data(), rws.data(), cls.data(), 1, ply_path);
     }
     std::cout << "Fused " << count << " points into " << ply_path << std::endl;
     if (g_fusion_ply_vis) {
         write_vis_beside(ply_path, points);
     } else {
-        apd_points_destroy(points);  // --ply-mean alone
+        apd_points_destroy(points);  // --ply-mean or --ply-voxel alone
     }
 }
 

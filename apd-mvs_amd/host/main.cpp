@@ -3,7 +3,7 @@
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
-//       [--ply-normals] [--ply-vis] [--ply-mean] [--filtered-maps]
+//       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -20,6 +20,10 @@
 // --ply-vis the lists of the averaged points.  With every --fusion.  A source contributes the pixel the point itself projects to;
 // the Tanks and Temples loops may count a source through a stale `diff` entry of an earlier pixel, which that projection does not
 // reach or finds without depth: such a source is skipped and no longer listed.  Without the flag nothing changes.
+// --ply-voxel SIZE: APD.ply holds one point per occupied cell of a cubic grid of that cell size at the origin
+// (apd_points_merge_voxels: the mean of the cell's points, the union of their lists) and, with --ply-vis, APD.ply.vis those
+// lists; with --ply-mean the points are averaged first.  With every --fusion; the cells and the dropped points (non-finite, or
+// 2^20 cells from the origin) are printed.  SIZE must be a positive finite number, or the usage line is all that happens.
 //
 // --masks [DIR] (default DIR: masks): <dense_folder>/DIR/<%08d>.jpg|pgm are per-view pixel masks, grey < 128 = masked out of
 // PatchMatch (apd_upload_mask: the pixels cost no NCC and leave as depth 0 / UNKNOWN); a view without a file is unmasked, a file
@@ -123,6 +127,12 @@ bool ParseOptions(int argc, char **argv, Options &o)
             o.ply_vis = true;
         } else if (a == "--ply-mean") {
             o.ply_mean = true;
+        } else if (a == "--ply-voxel") {
+            const char *text = i + 1 < argc ? argv[++i] : "";
+            if (!real(text, o.ply_voxel) || !(o.ply_voxel > 0.0f)) {
+                fprintf(stderr, "bad value '%s' of %s: a positive number\n", text, a.c_str());
+                return false;
+            }
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
         } else if (a == "--seed") {
@@ -334,9 +344,10 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
-                        "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n");
+                        "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
+                        "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -353,6 +364,7 @@ int main(int argc, char **argv)
     SetFusionOptions(opt.fusion);
     SetFusionPlyVis(opt.ply_vis);
     SetFusionPlyMean(opt.ply_mean);
+    SetFusionPlyVoxel(opt.ply_voxel);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

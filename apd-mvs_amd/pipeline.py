@@ -551,7 +551,7 @@ def average_points(scene, results, points, device=0):
 
 
 def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False,
-         vis_path=None, average=False):
+         vis_path=None, average=False, voxel=None, voxel_origin=None):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -567,13 +567,29 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     views that see it, as indices of the scene's views; Points.write_vis), with or without a PLY file or the points.
     average: the mean geometry (average_points) -- the file (written by Points.write_ply, with normals when the options say
     ply_normals), the returned points and the .vis file are those of the averaged points: positions and normals are means over
-    the agreeing views, and a source that did not contribute is no longer listed."""
+    the agreeing views, and a source that did not contribute is no longer listed.
+    voxel: a cell size -- the file, the returned points and the .vis file are those of Points.merge_voxels(voxel, voxel_origin): one
+    point per occupied cell of the cubic grid, the mean of the cell's points (of the averaged ones with average=True) with the
+    union of their lists; the count returned is that of the cells."""
     import ctypes as C
     from . import Points, default_fusion_options
     if variant not in FUSION_VARIANTS:
         raise ValueError("unknown fusion variant %r: one of %s" % (variant, ", ".join(sorted(FUSION_VARIANTS))))
     if ply_path is None and not return_points and vis_path is None:
         raise ValueError("fuse: neither a PLY file nor the points nor the visibility file are asked for")
+    if voxel is not None:
+        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average)
+        merged, _ = whole.merge_voxels(voxel, voxel_origin)
+        whole.close()
+        if ply_path is not None:
+            merged.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
+        if vis_path is not None:
+            merged.write_vis(vis_path)
+        if return_points:
+            return merged.count, merged
+        n = merged.count
+        merged.close()
+        return n
     if average:
         n, fused = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True)
         mean = average_points(scene, results, fused, device)

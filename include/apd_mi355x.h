@@ -450,6 +450,54 @@ int apd_points_average(apd_points_t p, int num_views, const apd_camera *cameras,
  * points.  `element vertex` is printed from the 64-bit count.  NULL p or path: APD_ERR_INVALID; a file that cannot be written:
  * APD_ERR_IO. */
 int apd_points_write_ply(apd_points_t p, const char *path, int with_normals);
+/* A points object from caller arrays: a cloud that was not fused in this call, to be merged, listed or written like one that
+ * was.  The arrays are HOST pointers with the layout of the accessors above (xyz and normal 3 floats, bgr 3 bytes per point) and
+ * are copied; rows, cols, pair_offsets (num_views + 1 entries) and pair_indices are those of a fusion call and say what view,
+ * pixel and the bits of sources mean.  on_device != 0: the copy is device memory on `device`; otherwise it is host memory and no
+ * device is touched -- with the host paths of apd_points_visibility, apd_points_write_vis and apd_points_write_ply such an object
+ * works on a machine without a GPU.  Refused with APD_ERR_INVALID before anything is allocated, message "apd_points_create: ..."
+ * (apd_fusion_last_error): a NULL argument (count == 0 may pass NULL arrays, and pair_indices may be NULL when no view has a
+ * source), a negative count, num_views < 1, a rows or cols entry that is not positive, pair_offsets not ascending from 0, a
+ * pair_indices entry outside 0 .. num_views - 1 or equal to its own view, a source list longer than APD_MAX_IMAGES, a view[k]
+ * outside the views, a pixel[k] outside its view, a bit of sources[k] at or above the length of its view's source list,
+ * popcount(sources[k]) != support[k].  *out is untouched when the call fails. */
+int apd_points_create(int device, int on_device, long long count, const float *xyz, const float *normal, const uint8_t *bgr,
+                      const uint8_t *support, const int32_t *view, const int32_t *pixel, const uint32_t *sources, int num_views,
+                      const int *rows, const int *cols, const int *pair_offsets, const int *pair_indices, apd_points_t *out);
+/* One point per occupied cell of a cubic grid, with the union of the members' visibility lists: the form COLMAP's fusion gives
+ * (one point per surface element with all the views that see it) and its Delaunay mesher reads.  binary32, IEEE operations in
+ * the order given (contract C10; csrc/apd_voxel_math.h).
+ *   Cell and key.  Per axis c: t = (xyz[c] - origin[c]) / voxel_size (a subtraction, then a division), f = floorf(t).  A point is
+ *   DROPPED when for any axis f is not in [-1048576, 1048576) -- NaN fails the test, so points with a non-finite coordinate are
+ *   dropped; *dropped (may be NULL) receives their number.  Otherwise i_c = (int)f and the key is
+ *   ((iz + 2^20) << 42) | ((iy + 2^20) << 21) | (ix + 2^20).
+ *   Output.  One point per distinct key, in ascending key order.  The members of a cell are taken in ascending input index; a
+ *   merged point with m members and representative r (the first member) has
+ *     xyz      per component the binary32 sum of the members' values in member order, starting from r's, divided by (float)m;
+ *     normal   the same sum and division, then renormalised by the rule of apd_points_average (left-to-right sum of squares,
+ *              sqrtf, (0, 0, 0) when the length is 0 or NaN);
+ *     bgr      per channel (sum + m / 2) / m in unsigned 64-bit integers;
+ *     view, pixel, sources   those of r, copied.  They describe r ALONE: sources does not name the views of the list below;
+ *     support  min(255, L - 1), L the length of the list below.
+ *   Visibility.  The list of a merged point holds the distinct views of the union of its members' lists, ascending; the
+ *   members' lists are the input's apd_points_visibility lists (not its sources bits, so a merged object can be merged again on
+ *   a coarser grid).  The result carries these lists as its own: apd_points_visibility and apd_points_write_vis return them,
+ *   apd_points_write_ply writes the merged points.
+ * The means are unweighted: merging a merged object again weighs every earlier cell as one point, whatever it had absorbed.
+ * apd_points_average refuses a merged object (APD_ERR_INVALID, "merged points name no sources").
+ * The result lives where p lives and is released with apd_points_destroy.  The merge is computed on p's device whatever memory p
+ * is in (host-resident points and lists are uploaded, the result is downloaded); there is no host implementation.  An object
+ * without points gives an object without points, with no device touched.  Refused, message "apd_points_merge_voxels: ...":
+ * APD_ERR_INVALID for a NULL p or out, a voxel_size that is not finite or not above 0, a non-finite origin component (origin3
+ * NULL: 0, 0, 0); APD_ERR_UNSUPPORTED for 2^31 or more points (the sort carries a 32-bit index) or 2^32 or more list entries in
+ * total.  All of these before any device is touched, but for the entry total of device-resident points, which is known once
+ * their lists are built on their device.  *out and *dropped are untouched when the call fails.  apd_fusion_last_timing reports
+ * the call: set-up (uploads, allocations), the kernels (and the download of a host result) as "views", file 0. */
+int apd_points_merge_voxels(apd_points_t p, float voxel_size, const float *origin3, apd_points_t *out, long long *dropped);
+int apd_points_merged(apd_points_t p);   /* 1 for a result of apd_points_merge_voxels, else 0 */
+/* The tile sizes of the device sort under apd_points_merge_voxels (csrc/apd_sort.h): elements per workgroup of a sort pass and
+ * entries per workgroup of its scan.  For tests that choose sizes around them. */
+void apd_sort_tile_sizes(int *sort_tile, int *scan_tile);
 int apd_points_destroy(apd_points_t p);
 
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
