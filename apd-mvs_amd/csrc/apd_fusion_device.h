@@ -1,5 +1,5 @@
 // apd_fusion_device.h -- the host driver the device fusions share (apd_fusion.hip: ETH, apd_fusion_tat.hip: Tanks and Temples).
-// Implemented once, in apd_fusion.hip, together with the two kernels only it launches (k_fusion_scan, k_fusion_compact): argument
+// Implemented once, in apd_fusion_call.hip, together with the kernels only it launches (k_fusion_scan, k_fusion_compact): argument
 // checks, the device memory of a call, the per-view geometry and maps, the scratch of the point compaction, the download of a
 // view's points, the PLY file, the points in memory (apd_points_t), and the per-thread error / timing that apd_fusion_last_error
 // and apd_fusion_last_timing report.
@@ -20,22 +20,12 @@
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_math.h"
 #include "apd_host_error.h"
+#include "apd_points_host.h"
 
 namespace apd_fusion {
 
 extern thread_local std::string g_fusion_error;
 extern thread_local double g_fusion_ms[3];  // last fusion: set-up (allocations, uploads), views (kernels + point downloads), PLY file
-
-// The arrays of an apd_points_t, on the device while the views are fused
-struct PointArrays {
-    float *xyz = nullptr, *normal = nullptr;
-    uint8_t *bgr = nullptr, *support = nullptr;
-    int32_t *view = nullptr, *pixel = nullptr;
-    uint32_t *sources = nullptr;  // bit j: source j of the point's view is one of the votes counted in support
-};
-
-void free_device_arrays(PointArrays &p);  // hipFree of each array (on the current device)
-void free_host_arrays(PointArrays &p);
 
 // apd_fusion_default_options: the reference's literals, a PLY of 15-byte records, host results
 inline apd_fusion_options default_options()
@@ -123,16 +113,7 @@ protected:
     size_t max_blocks() const { return (max_px + 255) / 256; }  // blocks of 256 pixels of the largest view
     int sources(int i) const { return a.pair_offsets[i + 1] - a.pair_offsets[i]; }
 
-    template <typename T> hipError_t alloc(size_t bytes, T **out)
-    {
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes > 0 ? bytes : 1);
-        if (e == hipSuccess) {
-            owned_.push_back(p);
-            *out = static_cast<T *>(p);
-        }
-        return e;
-    }
+    template <typename T> hipError_t alloc(size_t bytes, T **out) { return scratch_.alloc(bytes, out); }
 
     // First step of every variant.  Clears the last error and checks the arguments: APD_ERR_INVALID with "<who>: ..." before any
     // device is touched.  eth: the weak maps are required, and a view that is its own source is pointed to the host fusion.  Then
@@ -143,16 +124,7 @@ protected:
     template <typename T> hipError_t device_map(const T *map, size_t bytes, const T **out)
     {
         *out = map;
-        if (a.maps_on_device) {
-            return hipSuccess;
-        }
-        T *copy;
-        hipError_t e = alloc(bytes, &copy);
-        if (e == hipSuccess) {
-            *out = copy;
-            e = hipMemcpy(copy, map, bytes, hipMemcpyHostToDevice);
-        }
-        return e;
+        return a.maps_on_device ? hipSuccess : scratch_.upload(map, bytes, out);
     }
 
     // The geometry of cameras[i] and the depth and normal maps: what every view of every variant and of the filter has
@@ -209,7 +181,7 @@ private:
     int reserve_points(long long need);  // room for `need` points in soa_, kept across a growth
     void release_points();
 
-    std::vector<void *> owned_;
+    apd_points_host::Scratch scratch_;  // every device allocation of the call but soa_
     void *staging_ = nullptr;  // page-locked buffer of the point downloads
     int *total_ = nullptr;     // points of the view
     uint8_t *records_ = nullptr;
@@ -217,25 +189,9 @@ private:
     // and copies hundreds of megabytes at Tanks&Temples scale), downloaded through one page-locked staging buffer
     std::vector<std::vector<uint8_t>> body_;
     long long count_ = 0;
-    PointArrays soa_;            // the points in memory so far, device memory outside owned_: handed to the apd_points_t or freed
+    PointArrays soa_;            // the points in memory so far, device memory outside scratch_: handed to the apd_points_t or freed
     long long soa_capacity_ = 0;
     std::chrono::steady_clock::time_point t_lap_;
 };
 
 }  // namespace apd_fusion
-
-// One fusion's points (apd_points_t): the arrays are host memory (malloc) or device memory on `device`.  apd_fusion.hip makes
-// them and builds their visibility lists; apd_points.hip averages them and writes their PLY.
-struct apd_points {
-    int device = 0, on_device = 0;
-    long long count = 0;
-    apd_fusion::PointArrays arrays;
-    std::vector<int> pair_offsets, pair_indices;  // the call's source lists: what bit j of sources[k] means
-    std::vector<int> rows, cols;                  // the call's view sizes: what pixel[k] and a projection into a source mean
-    // apd_points_visibility: built on the first call, where the arrays live (host: malloc; device: hipMalloc)
-    long long *vis_offsets = nullptr;
-    int32_t *vis_views = nullptr;
-    // a result of apd_points_merge_voxels: made with its lists (the union of its members'), view / pixel / sources are its
-    // representative's and say nothing about the lists
-    int merged = 0;
-};

@@ -15,7 +15,7 @@
 //   k_tat_decide  one lane per pixel: the last valid pixel q_j <= p of every source (own wave's ballot, the earlier waves of
 //                 the block, then the block prefix), the costs recomputed at q_j (apd_fusion_math.h: the very arithmetic of the
 //                 scan's pixel, so the same bits the reference stored in diff[j]), the k loop, and the point;
-//   Call::collect (apd_fusion_device.h; k_fusion_scan + k_fusion_compact of apd_fusion.hip): the points in raster order as PLY
+//   Call::collect (apd_fusion_device.h; k_fusion_scan + k_fusion_compact of apd_fusion_call.hip): the points in raster order as PLY
 //                 records.
 //
 // Memory per view of n pixels and S sources: 4 n (validity words) + 8 S n / 256 (block values) + 1 n (emitted) + 30 n (the

@@ -1,233 +1,131 @@
-// apd_points.hip -- what is done with a fusion's points after the fusion: apd_points_average and apd_points_write_ply of
-// include/apd_mi355x.h, and apd_points_create, which makes a points object of a caller's arrays.  (apd_points_merge_voxels:
-// apd_points_merge.hip.)
+// apd_points.hip -- the life and the files of a points object (apd_points_t of include/apd_mi355x.h, struct apd_points of
+// apd_points_host.h): the operations on the table of its arrays, the one function that makes a new object, the accessors,
+// apd_points_create, apd_points_destroy, apd_points_write_ply and apd_points_write_vis.  Who fills one: the fusions
+// (apd_fusion_call.hip), apd_points_average.hip, apd_points_merge.hip; its visibility lists: apd_points_vis.hip.
 //
 // apd_points_create: the checks that make the arrays a cloud some fusion could have made (every later call relies on them: a
 // view indexes the source lists, a bit of `sources` indexes a list), then one copy of each array, to host memory or to the device.
 //
-// apd_points_average: the mean position and normal of every point over its own view and its agreeing sources
-// (apd_fusion::mean_point, apd_fusion_math.h: contract C9).  A pure function of (points, maps): a point names its view and its
-// agreeing sources, its stored xyz is the very P the fusion projected into them, and the source pixel is a function of P
-// (vote_target) -- so the mean is computed after the fact, one lane per point, in no order, by k_points_average.  There is no host
-// path: host-resident points and host maps go up, the kernel runs on the points' device, the four arrays it writes come down.
-//
 // apd_points_write_ply: ExportPointCloud's file (APD.cpp:214-254) of any points object, the fusion's own or an averaged one: the
-// header, then the 15-byte or 27-byte records k_fusion_compact packs (apd_fusion.hip), packed here on the host from the arrays
-// (device-resident points come down in chunks).
+// header, then the 15-byte or 27-byte records k_fusion_compact packs (apd_fusion_call.hip), packed here on the host from the
+// arrays (device-resident points come down in chunks).
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_device.h"
-#include "apd_fusion_math.h"
 #include "apd_points_host.h"
 
-namespace {
+namespace apd_fusion {
 
-using apd_fusion::MapView;
-using apd_fusion::PointArrays;
-using apd_points_host::DeviceScope;
-using apd_points_host::Scratch;
-
-// Point k < n of `in` averaged into `out` (xyz, normal, sources = the sources that contributed, support = their number).  One lane
-// per point; each lane walks its mask (mean_point: at most 32 rounds) and gathers up to 32 x (4 + 12) bytes from the maps.  No
-// LDS, no atomics; every offset is a size_t.
-__global__ __launch_bounds__(256) void k_points_average(const MapView *__restrict__ views, const int *__restrict__ pair_offsets,
-                                                         const int *__restrict__ pair_indices, size_t n, const float *__restrict__ xyz,
-                                                         const float *__restrict__ normal, const int32_t *__restrict__ view,
-                                                         const uint32_t *__restrict__ sources, PointArrays out)
+hipError_t alloc_arrays(apd_points_host::Scratch &scratch, PointArrays &p, size_t n, unsigned which)
 {
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) {
-        return;
-    }
-    const int v = view[k];
-    const int first = pair_offsets[v];
-    const float P[3] = {xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]};
-    const float nr[3] = {normal[3 * k], normal[3 * k + 1], normal[3 * k + 2]};
-    float meanP[3], meanN[3];
-    uint32_t kept;
-    int used;
-    apd_fusion::mean_point(views, pair_indices + first, pair_offsets[v + 1] - first, P, nr, sources[k], meanP, meanN, kept, used);
-    for (int c = 0; c < 3; ++c) {
-        out.xyz[3 * k + c] = meanP[c];
-        out.normal[3 * k + c] = meanN[c];
-    }
-    out.sources[k] = kept;
-    out.support[k] = (uint8_t)used;
-}
-
-std::string &err() { return apd_fusion::g_fusion_error; }
-
-int hip_failed(const char *expr, hipError_t e, const char *, int)
-{
-    return apd::set_error(err(), APD_ERR_HIP, "apd_points_average: %s: %s", expr, hipGetErrorString(e));
-}
-
-// What apd_points_average refuses, before any device call
-int check_average(apd_points_t p, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
-                  const int *rows, const int *cols, apd_points_t *out)
-{
-    if (!p || !cameras || !depths || !normals || !rows || !cols || !out) {
-        return apd::set_error(err(), APD_ERR_INVALID, "apd_points_average: null argument");
-    }
-    if (p->merged) {  // its sources are its representative's: there is no list of maps to average a merged point over
-        return apd::set_error(err(), APD_ERR_INVALID, "apd_points_average: merged points name no sources");
-    }
-    if (num_views != (int)p->rows.size()) {
-        return apd::set_error(err(), APD_ERR_INVALID, "apd_points_average: %d views, the fusion of the points had %d", num_views, (int)p->rows.size());
-    }
-    for (int i = 0; i < num_views; ++i) {
-        if (rows[i] != p->rows[(size_t)i] || cols[i] != p->cols[(size_t)i]) {
-            return apd::set_error(err(), APD_ERR_INVALID, "apd_points_average: view %d has %d x %d pixels, in the fusion of the points it had %d x %d", i,
-                                  cols[i], rows[i], p->cols[(size_t)i], p->rows[(size_t)i]);
+    hipError_t e = hipSuccess;
+    for_each_array([&](auto member, size_t bytes, unsigned bit) {
+        if ((which & bit) && e == hipSuccess) {
+            e = scratch.alloc(n * bytes, &(p.*member));
         }
-    }
-    for (int s : p->pair_indices) {
-        if (!depths[s] || !normals[s]) {
-            return apd::set_error(err(), APD_ERR_INVALID, "apd_points_average: view %d is a source and has no %s map", s, depths[s] ? "normal" : "depth");
-        }
-    }
-    return APD_OK;
+    });
+    return e;
 }
 
-// The object apd_points_average returns, without its arrays: where p lives, with p's source lists and view sizes
-apd_points *like(const apd_points *p)
+void keep_arrays(apd_points_host::Scratch &scratch, const PointArrays &p)
+{
+    for_each_array([&](auto member, size_t, unsigned) {
+        if (p.*member) {
+            scratch.keep(p.*member);
+        }
+    });
+}
+
+bool alloc_host_arrays(PointArrays &p, size_t n)
+{
+    bool ok = true;
+    for_each_array([&](auto member, size_t bytes, unsigned) {
+        p.*member = static_cast<std::remove_reference_t<decltype(p.*member)>>(malloc(n * bytes > 0 ? n * bytes : 1));
+        ok = ok && p.*member;
+    });
+    return ok;
+}
+
+void free_arrays(PointArrays &p, bool on_device)
+{
+    for_each_array([&](auto member, size_t, unsigned) {
+        if (on_device) {
+            hipFree(p.*member);
+        } else {
+            free(p.*member);
+        }
+    });
+    p = PointArrays();
+}
+
+hipError_t copy_arrays(const PointArrays &to, const PointArrays &from, size_t n, hipMemcpyKind kind, unsigned which, size_t first)
+{
+    hipError_t e = hipSuccess;
+    for_each_array([&](auto member, size_t bytes, unsigned bit) {
+        if (!(which & bit) || e != hipSuccess) {
+            return;
+        }
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(from.*member) + first * bytes;
+        if (kind == hipMemcpyHostToHost) {
+            memcpy(to.*member, src, n * bytes);
+        } else {
+            e = hipMemcpy(to.*member, src, n * bytes, kind);
+        }
+    });
+    return e;
+}
+
+}  // namespace apd_fusion
+
+namespace apd_points_host {
+
+void write_ply_header(FILE *f, long long count, bool normals)
+{
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n%s"
+               "property uchar diffuse_blue\nproperty uchar diffuse_green\nproperty uchar diffuse_red\nend_header\n", count,
+            normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "");
+}
+
+apd_points *new_points(int device, int on_device, int num_views, const int *rows, const int *cols, const int *pair_offsets, const int *pair_indices)
 {
     apd_points *q = new apd_points();
-    q->device = p->device;
-    q->on_device = p->on_device;
-    q->count = p->count;
-    q->pair_offsets = p->pair_offsets;
-    q->pair_indices = p->pair_indices;
-    q->rows = p->rows;
-    q->cols = p->cols;
+    q->device = device;
+    q->on_device = on_device ? 1 : 0;
+    q->pair_offsets.assign(pair_offsets, pair_offsets + num_views + 1);
+    q->pair_indices.assign(pair_indices, pair_indices + pair_offsets[num_views]);
+    q->rows.assign(rows, rows + num_views);
+    q->cols.assign(cols, cols + num_views);
     return q;
 }
 
-int average(apd_points_t p, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
-            int maps_on_device, apd_points *result)
-{
-    const size_t n = (size_t)p->count;
-    const size_t nblocks = (n + 255) / 256;
-    if (nblocks > 0x7fffffffull) {
-        return apd::set_error(err(), APD_ERR_UNSUPPORTED, "apd_points_average: %lld points are more than one launch takes", p->count);
-    }
-    HIP_TRY(hipSetDevice(p->device));
-    Scratch scratch;
-    // the view table, built and uploaded once: geometry, and the maps of the views some list names
-    std::vector<char> named((size_t)num_views, 0);
-    for (int s : p->pair_indices) {
-        named[(size_t)s] = 1;
-    }
-    std::vector<MapView> hv((size_t)num_views);
-    for (int i = 0; i < num_views; ++i) {
-        MapView &v = hv[(size_t)i];
-        apd_fusion::view_geometry(cameras[i], p->rows[(size_t)i], p->cols[(size_t)i], v.geo);
-        v.depth = nullptr;
-        v.normal = nullptr;
-        if (!named[(size_t)i]) {
-            continue;
-        }
-        if (maps_on_device) {
-            v.depth = depths[i];
-            v.normal = normals[i];
-        } else {
-            const size_t px = (size_t)p->rows[(size_t)i] * (size_t)p->cols[(size_t)i];
-            HIP_TRY(scratch.upload(depths[i], px * 4, &v.depth));
-            HIP_TRY(scratch.upload(normals[i], px * 12, &v.normal));
-        }
-    }
-    const MapView *dviews = nullptr;
-    const int *pair_offsets = nullptr, *pair_indices = nullptr;
-    HIP_TRY(scratch.upload(hv.data(), sizeof(MapView) * hv.size(), &dviews));
-    HIP_TRY(scratch.upload(p->pair_offsets.data(), p->pair_offsets.size() * sizeof(int), &pair_offsets));
-    HIP_TRY(scratch.upload(p->pair_indices.data(), p->pair_indices.size() * sizeof(int), &pair_indices));
-    // the points the kernel reads, and the arrays it writes at their final size
-    const PointArrays &in = p->arrays;
-    const float *xyz = in.xyz, *normal = in.normal;
-    const int32_t *view = in.view;
-    const uint32_t *sources = in.sources;
-    if (!p->on_device) {
-        HIP_TRY(scratch.upload(in.xyz, n * 12, &xyz));
-        HIP_TRY(scratch.upload(in.normal, n * 12, &normal));
-        HIP_TRY(scratch.upload(in.view, n * 4, &view));
-        HIP_TRY(scratch.upload(in.sources, n * 4, &sources));
-    }
-    PointArrays dev;
-    HIP_TRY(scratch.alloc(n * 12, &dev.xyz));
-    HIP_TRY(scratch.alloc(n * 12, &dev.normal));
-    HIP_TRY(scratch.alloc(n * 4, &dev.sources));
-    HIP_TRY(scratch.alloc(n, &dev.support));
-    if (p->on_device) {  // what is copied, device to device
-        HIP_TRY(scratch.alloc(n * 3, &dev.bgr));
-        HIP_TRY(scratch.alloc(n * 4, &dev.view));
-        HIP_TRY(scratch.alloc(n * 4, &dev.pixel));
-        HIP_TRY(hipMemcpy(dev.bgr, in.bgr, n * 3, hipMemcpyDeviceToDevice));
-        HIP_TRY(hipMemcpy(dev.view, in.view, n * 4, hipMemcpyDeviceToDevice));
-        HIP_TRY(hipMemcpy(dev.pixel, in.pixel, n * 4, hipMemcpyDeviceToDevice));
-    }
-    hipLaunchKernelGGL(k_points_average, dim3((unsigned)nblocks), dim3(256), 0, 0, dviews, pair_offsets, pair_indices, n, xyz, normal, view, sources,
-                       dev);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (p->on_device) {
-        for (void *q : {(void *)dev.xyz, (void *)dev.normal, (void *)dev.sources, (void *)dev.support, (void *)dev.bgr, (void *)dev.view, (void *)dev.pixel}) {
-            scratch.keep(q);
-        }
-        result->arrays = dev;
-        return APD_OK;
-    }
-    PointArrays &h = result->arrays;  // freed with `result` by the caller if anything below fails
-    h.xyz = (float *)malloc(n * 12);
-    h.normal = (float *)malloc(n * 12);
-    h.bgr = (uint8_t *)malloc(n * 3);
-    h.support = (uint8_t *)malloc(n);
-    h.view = (int32_t *)malloc(n * 4);
-    h.pixel = (int32_t *)malloc(n * 4);
-    h.sources = (uint32_t *)malloc(n * 4);
-    if (!(h.xyz && h.normal && h.bgr && h.support && h.view && h.pixel && h.sources)) {
-        return apd::set_error(err(), APD_ERR_HIP, "apd_points_average: out of host memory");
-    }
-    HIP_TRY(hipMemcpy(h.xyz, dev.xyz, n * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h.normal, dev.normal, n * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h.sources, dev.sources, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h.support, dev.support, n, hipMemcpyDeviceToHost));
-    memcpy(h.bgr, in.bgr, n * 3);
-    memcpy(h.view, in.view, n * 4);
-    memcpy(h.pixel, in.pixel, n * 4);
-    return APD_OK;
-}
+}  // namespace apd_points_host
 
-}  // namespace
-
-extern "C" int apd_points_average(apd_points_t p, int num_views, const apd_camera *cameras, const float *const *depths,
-                                  const float *const *normals, const int *rows, const int *cols, int maps_on_device, apd_points_t *out)
-{
-    err().clear();
-    if (const int rc = check_average(p, num_views, cameras, depths, normals, rows, cols, out); rc != APD_OK) {
-        return rc;
-    }
-    apd_points *result = like(p);
-    if (p->count > 0) {
-        DeviceScope scope(true);
-        const int rc = average(p, num_views, cameras, depths, normals, maps_on_device, result);
-        if (rc != APD_OK) {
-            apd_points_destroy(result);  // its arrays are host memory, or none yet
-            return rc;
-        }
-    }
-    *out = result;
-    return APD_OK;
-}
+extern "C" long long apd_points_count(apd_points_t p) { return p ? p->count : 0; }
+extern "C" int apd_points_on_device(apd_points_t p) { return p ? p->on_device : 0; }
+extern "C" const float *apd_points_xyz(apd_points_t p) { return p ? p->arrays.xyz : nullptr; }
+extern "C" const float *apd_points_normal(apd_points_t p) { return p ? p->arrays.normal : nullptr; }
+extern "C" const uint8_t *apd_points_bgr(apd_points_t p) { return p ? p->arrays.bgr : nullptr; }
+extern "C" const uint8_t *apd_points_support(apd_points_t p) { return p ? p->arrays.support : nullptr; }
+extern "C" const int32_t *apd_points_view(apd_points_t p) { return p ? p->arrays.view : nullptr; }
+extern "C" const int32_t *apd_points_pixel(apd_points_t p) { return p ? p->arrays.pixel : nullptr; }
+extern "C" const uint32_t *apd_points_sources(apd_points_t p) { return p ? p->arrays.sources : nullptr; }
 
 namespace {
+
+using apd_fusion::PointArrays;
+using namespace apd_points_host;
+
+std::string &err() { return apd_fusion::g_fusion_error; }
 
 int create_hip_failed(const char *expr, hipError_t e, const char *, int)
 {
@@ -307,42 +205,26 @@ int check_create(long long count, const float *xyz, const float *normal, const u
 
 #undef CREATE_REFUSE
 
-// a copy of `bytes` caller bytes where the object lives
-template <typename T> int create_copy(bool on_device, const T *from, size_t bytes, T **to)
-{
-    const auto hip_failed = create_hip_failed;
-    if (on_device) {
-        void *q = nullptr;
-        HIP_TRY(hipMalloc(&q, bytes));
-        *to = static_cast<T *>(q);  // the object's from here on: apd_points_destroy frees it
-        HIP_TRY(hipMemcpy(q, from, bytes, hipMemcpyHostToDevice));
-        return APD_OK;
-    }
-    *to = static_cast<T *>(malloc(bytes));
-    if (!*to) {
-        return apd::set_error(err(), APD_ERR_HIP, "apd_points_create: out of host memory");
-    }
-    memcpy(*to, from, bytes);
-    return APD_OK;
-}
-
-int create_arrays(apd_points *q, const float *xyz, const float *normal, const uint8_t *bgr, const uint8_t *support, const int32_t *view,
-                  const int32_t *pixel, const uint32_t *sources)
+// one copy of each of the caller's arrays where the object lives
+int create_arrays(apd_points *q, const PointArrays &from)
 {
     const auto hip_failed = create_hip_failed;
     const size_t n = (size_t)q->count;
-    const bool dev = q->on_device != 0;
-    if (dev) {
+    PointArrays a;
+    if (q->on_device) {
+        Scratch scratch;  // of the arrays until every copy is made
         HIP_TRY(hipSetDevice(q->device));
+        HIP_TRY(alloc_arrays(scratch, a, n));
+        HIP_TRY(copy_arrays(a, from, n, hipMemcpyHostToDevice));
+        keep_arrays(scratch, a);
+    } else if (!alloc_host_arrays(a, n)) {
+        free_arrays(a, false);
+        return apd::set_error(err(), APD_ERR_HIP, "apd_points_create: out of host memory");
+    } else {
+        copy_arrays(a, from, n, hipMemcpyHostToHost);
     }
-    PointArrays &a = q->arrays;
-    int rc = create_copy(dev, xyz, n * 12, &a.xyz);
-    rc = rc != APD_OK ? rc : create_copy(dev, normal, n * 12, &a.normal);
-    rc = rc != APD_OK ? rc : create_copy(dev, bgr, n * 3, &a.bgr);
-    rc = rc != APD_OK ? rc : create_copy(dev, support, n, &a.support);
-    rc = rc != APD_OK ? rc : create_copy(dev, view, n * 4, &a.view);
-    rc = rc != APD_OK ? rc : create_copy(dev, pixel, n * 4, &a.pixel);
-    return rc != APD_OK ? rc : create_copy(dev, sources, n * 4, &a.sources);
+    q->arrays = a;
+    return APD_OK;
 }
 
 }  // namespace
@@ -356,24 +238,38 @@ extern "C" int apd_points_create(int device, int on_device, long long count, con
         rc != APD_OK) {
         return rc;
     }
-    apd_points *q = new apd_points();
-    q->device = device;
-    q->on_device = on_device ? 1 : 0;
+    apd_points *q = new_points(device, on_device, num_views, rows, cols, pair_offsets, pair_indices);
     q->count = count;
-    q->pair_offsets.assign(pair_offsets, pair_offsets + num_views + 1);
-    q->pair_indices.assign(pair_indices, pair_indices + pair_offsets[num_views]);
-    q->rows.assign(rows, rows + num_views);
-    q->cols.assign(cols, cols + num_views);
     if (count > 0) {
         DeviceScope scope(q->on_device != 0);
-        if (const int rc = create_arrays(q, xyz, normal, bgr, support, view, pixel, sources); rc != APD_OK) {
-            const std::string why = err();
-            apd_points_destroy(q);  // the arrays made so far
-            err() = why;
+        // the caller's arrays, in the order of PointArrays: read only
+        const PointArrays from = {const_cast<float *>(xyz),      const_cast<float *>(normal),  const_cast<uint8_t *>(bgr),     const_cast<uint8_t *>(support),
+                                  const_cast<int32_t *>(view), const_cast<int32_t *>(pixel), const_cast<uint32_t *>(sources)};
+        if (const int rc = create_arrays(q, from); rc != APD_OK) {
+            apd_points_destroy(q);  // it has no arrays yet; keeps the message
             return rc;
         }
     }
     *out = q;
+    return APD_OK;
+}
+
+extern "C" int apd_points_destroy(apd_points_t p)
+{
+    if (!p) {
+        return APD_OK;
+    }
+    DeviceScope scope(p->on_device != 0);
+    if (p->on_device) {
+        hipSetDevice(p->device);
+        hipFree(p->vis_offsets);
+        hipFree(p->vis_views);
+    } else {
+        free(p->vis_offsets);
+        free(p->vis_views);
+    }
+    apd_fusion::free_arrays(p->arrays, p->on_device != 0);
+    delete p;
     return APD_OK;
 }
 
@@ -404,18 +300,19 @@ extern "C" int apd_points_write_ply(apd_points_t p, const char *path, int with_n
         err() = std::string("apd_points_write_ply: cannot write ") + path;  // no length limit: not through set_error
         return APD_ERR_IO;
     }
-    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n%s"
-               "property uchar diffuse_blue\nproperty uchar diffuse_green\nproperty uchar diffuse_red\nend_header\n", p->count,
-            with_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "");
+    write_ply_header(f, p->count, with_normals != 0);
     bool ok = true;
     for (size_t k0 = 0; k0 < n && ok; k0 += kChunk) {
         const size_t m = std::min(n - k0, kChunk);
         const float *cx = a.xyz + 3 * k0, *cn = a.normal + 3 * k0;
         const uint8_t *cb = a.bgr + 3 * k0;
         if (p->on_device) {
-            hipError_t e = hipMemcpy(xyz.data(), cx, m * 12, hipMemcpyDeviceToHost);
-            e = e != hipSuccess || !with_normals ? e : hipMemcpy(normal.data(), cn, m * 12, hipMemcpyDeviceToHost);
-            e = e != hipSuccess ? e : hipMemcpy(bgr.data(), cb, m * 3, hipMemcpyDeviceToHost);
+            PointArrays chunk;
+            chunk.xyz = xyz.data();
+            chunk.normal = normal.data();
+            chunk.bgr = bgr.data();
+            const unsigned which = apd_fusion::kXyz | apd_fusion::kBgr | (with_normals ? apd_fusion::kNormal : 0u);
+            const hipError_t e = copy_arrays(chunk, a, m, hipMemcpyDeviceToHost, which, k0);
             if (e != hipSuccess) {
                 fclose(f);
                 return apd::set_error(err(), APD_ERR_HIP, "apd_points_write_ply: download of the points: %s", hipGetErrorString(e));
@@ -437,6 +334,63 @@ extern "C" int apd_points_write_ply(apd_points_t p, const char *path, int with_n
     }
     if (fclose(f) != 0 || !ok) {
         err() = std::string("apd_points_write_ply: short write to ") + path;
+        return APD_ERR_IO;
+    }
+    return APD_OK;
+}
+
+extern "C" int apd_points_write_vis(apd_points_t p, const char *path)
+{
+    err().clear();
+    if (!p || !path) {
+        return apd::set_error(err(), APD_ERR_INVALID, "apd_points_write_vis: null argument");
+    }
+    const long long *offsets = nullptr;
+    const int32_t *views = nullptr;
+    if (const int rc = apd_points_visibility(p, &offsets, &views); rc != APD_OK) {
+        return rc;
+    }
+    const size_t n = (size_t)p->count;
+    std::vector<long long> host_offsets;
+    std::vector<int32_t> host_views;
+    if (p->on_device) {  // one download of each array
+        DeviceScope scope(true);
+        host_offsets.resize(n + 1);
+        hipError_t e = hipSetDevice(p->device);
+        e = e != hipSuccess ? e : hipMemcpy(host_offsets.data(), offsets, (n + 1) * sizeof(long long), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && host_offsets[n] > 0) {
+            host_views.resize((size_t)host_offsets[n]);
+            e = hipMemcpy(host_views.data(), views, host_views.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+        }
+        if (e != hipSuccess) {
+            return apd::set_error(err(), APD_ERR_HIP, "apd_points_write_vis: download of the lists: %s", hipGetErrorString(e));
+        }
+        offsets = host_offsets.data();
+        views = host_views.data();
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        err() = std::string("apd_points_write_vis: cannot write ") + path;
+        return APD_ERR_IO;
+    }
+    // uint64 number of points, then per point uint32 n and n x uint32 view index, little endian like every file of the project
+    const uint64_t count = (uint64_t)n;
+    bool ok = fwrite(&count, 8, 1, f) == 1;
+    std::vector<uint32_t> chunk;
+    const size_t kChunk = 1u << 16;  // points per fwrite
+    for (size_t k0 = 0; k0 < n && ok; k0 += kChunk) {
+        const size_t k1 = std::min(n, k0 + kChunk);
+        chunk.clear();
+        for (size_t k = k0; k < k1; ++k) {
+            chunk.push_back((uint32_t)(offsets[k + 1] - offsets[k]));
+            for (long long e = offsets[k]; e < offsets[k + 1]; ++e) {
+                chunk.push_back((uint32_t)views[e]);
+            }
+        }
+        ok = fwrite(chunk.data(), 4, chunk.size(), f) == chunk.size();
+    }
+    if (fclose(f) != 0 || !ok) {
+        err() = std::string("apd_points_write_vis: short write to ") + path;
         return APD_ERR_IO;
     }
     return APD_OK;

@@ -30,6 +30,7 @@ namespace {
 using apd_fusion::PointArrays;
 using apd_points_host::DeviceScope;
 using apd_points_host::Scratch;
+using apd_points_host::ms_since;
 
 struct Grid {
     float origin[3];
@@ -192,11 +193,6 @@ int hip_failed(const char *expr, hipError_t e, const char *, int)
 
 dim3 grid_of(size_t n) { return dim3((unsigned)((n + 255) / 256)); }  // n < 2^32: fits
 
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 constexpr long long kMaxEntries = 1LL << 32;
 
 int too_many_entries(long long entries)
@@ -226,12 +222,9 @@ int merge(apd_points_t p, const Grid &grid, const long long *offsets, const int3
     PointArrays in = p->arrays;
     if (!p->on_device) {
         long long entries = offsets[n];
-        HIP_TRY(scratch.upload((const float *)p->arrays.xyz, n * 12, (const float **)&in.xyz));
-        HIP_TRY(scratch.upload((const float *)p->arrays.normal, n * 12, (const float **)&in.normal));
-        HIP_TRY(scratch.upload((const uint8_t *)p->arrays.bgr, n * 3, (const uint8_t **)&in.bgr));
-        HIP_TRY(scratch.upload((const int32_t *)p->arrays.view, n * 4, (const int32_t **)&in.view));
-        HIP_TRY(scratch.upload((const int32_t *)p->arrays.pixel, n * 4, (const int32_t **)&in.pixel));
-        HIP_TRY(scratch.upload((const uint32_t *)p->arrays.sources, n * 4, (const uint32_t **)&in.sources));
+        constexpr unsigned kRead = apd_fusion::kAllArrays & ~apd_fusion::kSupport;  // the merge counts its own support
+        HIP_TRY(alloc_arrays(scratch, in, n, kRead));
+        HIP_TRY(copy_arrays(in, p->arrays, n, hipMemcpyHostToDevice, kRead));
         HIP_TRY(scratch.upload(offsets, (n + 1) * sizeof(long long), &offsets));
         HIP_TRY(scratch.upload(views, (size_t)entries * sizeof(int32_t), &views));
     }
@@ -283,13 +276,7 @@ int merge(apd_points_t p, const Grid &grid, const long long *offsets, const int3
 
     // 5: the merged points
     PointArrays out;
-    HIP_TRY(scratch.alloc(cells * 12, &out.xyz));
-    HIP_TRY(scratch.alloc(cells * 12, &out.normal));
-    HIP_TRY(scratch.alloc(cells * 3, &out.bgr));
-    HIP_TRY(scratch.alloc(cells, &out.support));
-    HIP_TRY(scratch.alloc(cells * 4, &out.view));
-    HIP_TRY(scratch.alloc(cells * 4, &out.pixel));
-    HIP_TRY(scratch.alloc(cells * 4, &out.sources));
+    HIP_TRY(alloc_arrays(scratch, out, cells));
     HIP_TRY(scratch.alloc((cells + 1) * 4, &start));
     hipLaunchKernelGGL(k_cell_starts, grid_of(m), dim3(256), 0, 0, (const uint32_t *)head, (const uint64_t *)before, m, start);
     hipLaunchKernelGGL(k_cell_merge, grid_of(cells), dim3(256), 0, 0, cells, (const uint32_t *)start, member, in, out);
@@ -338,23 +325,18 @@ int merge(apd_points_t p, const Grid &grid, const long long *offsets, const int3
 
     result->count = (long long)cells;
     if (p->on_device) {
-        for (void *q : {(void *)out.xyz, (void *)out.normal, (void *)out.bgr, (void *)out.support, (void *)out.view, (void *)out.pixel,
-                        (void *)out.sources, (void *)vis_offsets, (void *)vis_views}) {
-            scratch.keep(q);
-        }
+        keep_arrays(scratch, out);
+        scratch.keep(vis_offsets);
+        scratch.keep(vis_views);
         result->arrays = out;
         result->vis_offsets = vis_offsets;
         result->vis_views = vis_views;
     } else {  // freed with `result` by the caller if a download fails
-        PointArrays &h = result->arrays;
-        int rc = download(out.xyz, cells * 12, &h.xyz);
-        rc = rc != APD_OK ? rc : download(out.normal, cells * 12, &h.normal);
-        rc = rc != APD_OK ? rc : download(out.bgr, cells * 3, &h.bgr);
-        rc = rc != APD_OK ? rc : download(out.support, cells, &h.support);
-        rc = rc != APD_OK ? rc : download(out.view, cells * 4, &h.view);
-        rc = rc != APD_OK ? rc : download(out.pixel, cells * 4, &h.pixel);
-        rc = rc != APD_OK ? rc : download(out.sources, cells * 4, &h.sources);
-        rc = rc != APD_OK ? rc : download(vis_offsets, (cells + 1) * sizeof(long long), &result->vis_offsets);
+        if (!alloc_host_arrays(result->arrays, cells)) {
+            return apd::set_error(err(), APD_ERR_HIP, "apd_points_merge_voxels: out of host memory");
+        }
+        HIP_TRY(copy_arrays(result->arrays, out, cells, hipMemcpyDeviceToHost));
+        int rc = download(vis_offsets, (cells + 1) * sizeof(long long), &result->vis_offsets);
         rc = rc != APD_OK ? rc : download(vis_views, (size_t)distinct * sizeof(int32_t), &result->vis_views);
         if (rc != APD_OK) {
             return rc;
@@ -385,13 +367,7 @@ extern "C" int apd_points_merge_voxels(apd_points_t p, float voxel_size, const f
     if (p->count >= (1LL << 31)) {
         return apd::set_error(err(), APD_ERR_UNSUPPORTED, "apd_points_merge_voxels: %lld points, 2^31 or more (the sort carries a 32-bit index)", p->count);
     }
-    apd_points *result = new apd_points();
-    result->device = p->device;
-    result->on_device = p->on_device;
-    result->pair_offsets = p->pair_offsets;
-    result->pair_indices = p->pair_indices;
-    result->rows = p->rows;
-    result->cols = p->cols;
+    apd_points *result = apd_points_host::new_points_like(p);
     result->merged = 1;
     long long lost = 0;
     apd_fusion::g_fusion_ms[0] = apd_fusion::g_fusion_ms[1] = apd_fusion::g_fusion_ms[2] = 0.0;
@@ -432,9 +408,3 @@ extern "C" int apd_points_merge_voxels(apd_points_t p, float voxel_size, const f
 }
 
 extern "C" int apd_points_merged(apd_points_t p) { return p && p->merged ? 1 : 0; }
-
-extern "C" void apd_sort_tile_sizes(int *sort_tile, int *scan_tile)
-{
-    *sort_tile = apd_sort::kSortTile;
-    *scan_tile = apd_sort::kScanTile;
-}

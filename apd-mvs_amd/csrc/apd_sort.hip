@@ -1,7 +1,7 @@
 // apd_sort.hip -- the device scan and the device radix sort of apd_sort.h.
 //
 // The scan (exclusive_scan): three kernels.  k_scan_sums adds up each block of kScanTile entries; k_scan_top, one workgroup, turns
-// the block sums into block prefixes (every lane over a run of consecutive sums, as k_vis_scan of apd_fusion.hip does);
+// the block sums into block prefixes (every lane over a run of consecutive sums: scan_sums_in_place of apd_scan.h);
 // k_scan_apply repeats a block's own scan in LDS and adds its prefix.  Sums and outputs are 64-bit.
 //
 // The sort (sort_pairs): least significant digit first, 8 bits a pass.  A pass is k_sort_histogram (per block of kSortTile
@@ -14,6 +14,9 @@
 // count, they do not place.  Destinations of a wave are runs of one digit each, so the stores are scattered over up to 256
 // streams per block; nothing is staged through LDS to widen them (the merge this sort serves is a small part of a fusion).
 #include "apd_sort.h"
+
+#include "../../include/apd_mi355x.h"
+#include "apd_scan.h"
 
 namespace apd_sort {
 
@@ -47,29 +50,9 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_sums(const uint32_t *__re
 __global__ __launch_bounds__(kScanTopThreads) void k_scan_top(uint64_t *__restrict__ sums, size_t nblocks)
 {
     __shared__ uint64_t part[kScanTopThreads];
-    const size_t t = threadIdx.x;
-    const size_t per = (nblocks + kScanTopThreads - 1) / kScanTopThreads;
-    const size_t b0 = t * per < nblocks ? t * per : nblocks, b1 = b0 + per < nblocks ? b0 + per : nblocks;
-    uint64_t sum = 0;
-    for (size_t b = b0; b < b1; ++b) {
-        sum += sums[b];
-    }
-    part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < kScanTopThreads; off <<= 1) {
-        const uint64_t v = ((int)t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = part[t] - sum;
-    for (size_t b = b0; b < b1; ++b) {
-        const uint64_t c = sums[b];
-        sums[b] = run;
-        run += c;
-    }
-    if (t == kScanTopThreads - 1) {
-        sums[nblocks] = part[kScanTopThreads - 1];
+    const uint64_t total = apd_scan::scan_sums_in_place(sums, nblocks, part);
+    if (threadIdx.x == kScanTopThreads - 1) {
+        sums[nblocks] = total;
     }
 }
 
@@ -85,15 +68,8 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_apply(const uint32_t *__r
         item[j] = first + j < n ? in[first + j] : 0u;
         sum += item[j];
     }
-    part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < kScanThreads; off <<= 1) {
-        const uint64_t v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = sums[blockIdx.x] + part[t] - sum;
+    const uint64_t upto = apd_scan::block_inclusive_scan(part, t, sum);
+    uint64_t run = sums[blockIdx.x] + upto - sum;
     for (int j = 0; j < kScanItems; ++j) {
         if (first + j < n) {
             out[first + j] = run;
@@ -297,3 +273,9 @@ hipError_t sort_pairs(uint64_t *keys, uint64_t *keys_alt, uint32_t *vals, uint32
 }
 
 }  // namespace apd_sort
+
+extern "C" void apd_sort_tile_sizes(int *sort_tile, int *scan_tile)
+{
+    *sort_tile = apd_sort::kSortTile;
+    *scan_tile = apd_sort::kScanTile;
+}

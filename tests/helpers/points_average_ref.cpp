@@ -2,7 +2,7 @@
 // the points: for every point the masked loop over its view's source list, the sums from the stored position and normal, the
 // divisions by the number of contributions and the renormalisation of the mean normal, all written out here.
 //
-// TEST INFRASTRUCTURE ONLY: the checker of apd_points_average (apd-mvs_amd/csrc/apd_points.hip), compiled by
+// TEST INFRASTRUCTURE ONLY: the checker of apd_points_average (apd-mvs_amd/csrc/apd_points_average.hip), compiled by
 // tests/points_average_checker.py.  From the product it takes lift, drop and vote_target of the arithmetic contract
 // (apd_fusion_math.h) and nothing else: it does not call apd_fusion::mean_point, the code under test.
 #include <cmath>

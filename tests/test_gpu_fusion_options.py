@@ -15,6 +15,7 @@ import pytest
 import eth_fusion_checker as E
 import fusion_cases
 import tat_checker
+import vis_checker as VC
 from test_fusion_cases import VARIANTS
 from test_fusion_options import CASES_OF_SET
 from test_gpu_dropin_binary import APD_BIN, _read_dmb, _write_dense_folder
@@ -218,6 +219,40 @@ def test_result_across_views_with_an_empty_view_between(gpu_pkg, ob, checker, tm
     for field in ("xyz", "normal", "bgr", "support", "view", "pixel"):
         assert getattr(host, field).tobytes() == getattr(want, field).tobytes(), field
         assert getattr(dev, field).cpu().numpy().tobytes() == getattr(want, field).tobytes(), field
+
+
+# The first pixels of every view of full_frame kept as reference pixels, and the points the sequential ETH loop then makes per
+# view (counted with the checker on the CPU before the cuts were chosen).  The points in memory start without room, and room for
+# `need` points is max(need, twice the room, 4096): view 0 asks for none, view 1 gets the floor of 4096, view 2 passes it and
+# doubles it to 8192, view 3 passes 8192 and 16384 at once and gets what it needs.
+GROWTH_CUTS = [0, 40000, 1200000, 100000]
+GROWTH_POINTS = [0, 3395, 1002, 17275]
+
+
+def test_points_grow_across_views(gpu_pkg, ob, tmp_path):
+    """The seven arrays, the visibility lists and the PLY bytes of a fusion whose device arrays grow three times, kept across
+    every growth: host result and device result against the sequential checker, bit for bit."""
+    case = VC.first_pixels(fusion_cases.case("full_frame"), "growth", GROWTH_CUTS)
+    vis = VC.build(tmp_path)
+    want = VC.fuse_case(vis, ob, "eth", case, tmp_path / "ref.ply", ply_normals=True, vis_path=tmp_path / "ref.vis")
+    assert np.bincount(want.view, minlength=4).tolist() == GROWTH_POINTS
+    totals = np.cumsum(GROWTH_POINTS)
+    assert totals[0] == 0 and 0 < totals[1] < 4096 < totals[2] < 8192 and totals[3] > 16384
+    for on_device in (False, True):
+        tag = "dev" if on_device else "host"
+        options = gpu_pkg.default_fusion_options(ply_normals=1, result_on_device=int(on_device))
+        n, pts = _fuse(gpu_pkg, ob, case, options, tmp_path / (tag + ".ply"), points=True, on_device=on_device)
+        assert n == want.count == pts.count and pts.on_device == on_device
+        assert (tmp_path / (tag + ".ply")).read_bytes() == (tmp_path / "ref.ply").read_bytes(), tag
+        host = lambda a: a.cpu().numpy() if on_device else np.asarray(a)
+        for field in ("xyz", "normal", "bgr", "support", "view", "pixel", "sources"):
+            assert host(getattr(pts, field)).tobytes() == getattr(want, field).tobytes(), (field, tag)
+        offsets, views = [host(a) for a in pts.visibility()]
+        assert offsets.tobytes() == want.offsets.tobytes() and views.tobytes() == want.views.tobytes(), tag
+        pts.write_ply(tmp_path / (tag + "_points.ply"), normals=True)
+        assert (tmp_path / (tag + "_points.ply")).read_bytes() == (tmp_path / "ref.ply").read_bytes(), tag
+        pts.write_vis(tmp_path / (tag + ".vis"))
+        assert (tmp_path / (tag + ".vis")).read_bytes() == (tmp_path / "ref.vis").read_bytes(), tag
 
 
 # --------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """The three device fusions (apd_fuse_views_variant: ETH, csrc/apd_fusion.hip; Tanks and Temples, csrc/apd_fusion_tat.hip;
-the shared scan and compaction of csrc/apd_fusion.hip) against their sequential loops (oracle/fusion_oracle.cpp,
+the shared scan and compaction of csrc/apd_fusion_call.hip) against their sequential loops (oracle/fusion_oracle.cpp,
 tests/helpers/tat_fusion_ref.cpp) on the committed cases of tests/fusion_cases.py: full frames whose scans split the blocks
 over partitions, the block counts at the partitions' boundaries, the generated edge cases and non-finite inputs.  Every case
 runs through the C ABI with maps on the host and on the device; the PLY files must be byte-identical, but for the sign and

@@ -1,5 +1,5 @@
 """The agreeing sources of every fused point and the visibility lists on the device (apd_points_sources, apd_points_visibility,
-apd_points_write_vis; csrc/apd_fusion.hip, csrc/apd_fusion_tat.hip), bitwise against the sequential checker that keeps them
+apd_points_write_vis; csrc/apd_points_vis.hip, csrc/apd_points.hip), bitwise against the sequential checker that keeps them
 (tests/helpers/fusion_vis_ref.cpp): host- and device-resident points, all three loops and option set "a", the edges of the
 64-bit scan behind the offsets, a view without points between two with points, a vote from source 30, the Python layer and the
 drop-in binary's --ply-vis."""

@@ -1,4 +1,4 @@
-"""The mean geometry of fused points on the device (apd_points_average, apd_points_write_ply; csrc/apd_points.hip), bitwise against
+"""The mean geometry of fused points on the device (apd_points_average, apd_points_write_ply; csrc/apd_points_average.hip, csrc/apd_points.hip), bitwise against
 the sequential checker (tests/helpers/points_average_ref.cpp): host- and device-resident points, host and device maps, all three
 loops, the skip path over filtered depth maps, the refusals that need a points object, the PLY writer against the file the same
 fusion wrote, the Python layer and the drop-in binary's --ply-mean."""

@@ -297,6 +297,37 @@ def test_created_host_object_returns_lists_and_writes_itself(pkg, ob, vis, tmp_p
     pts.close()
 
 
+@pytest.mark.parametrize("count", [0, 1, 257])
+def test_created_host_object_of_a_few_points_keeps_every_byte(pkg, tmp_path, count):
+    """apd_points_create of host-resident points over 3 views of 4 x 5 pixels with 2 sources each, with no point, one point and
+    one more than a block of 256: every accessor returns the bytes given, apd_points_write_ply (both record forms) writes the
+    bytes packed here, apd_points_visibility and apd_points_write_vis give the lists that view / sources / pairs imply, and
+    apd_points_destroy returns APD_OK.  No device."""
+    rng = np.random.RandomState(7 + count)
+    rows, cols, pairs = views_of(3, nsrc=2)
+    sources = rng.randint(0, 4, count).astype(np.uint32)
+    want = cloud(rng.standard_normal((count, 3)).astype(np.float32), normal=rng.standard_normal((count, 3)).astype(np.float32),
+                 bgr=rng.randint(0, 256, (count, 3)).astype(np.uint8), view=rng.randint(0, 3, count), sources=sources, pairs=pairs)
+    assert want.count == count and len(want.offsets) == count + 1 and want.offsets[-1] == count + int(want.support.sum())
+    pts = from_cloud(pkg, want, rows, cols, pairs)
+    assert not pts.on_device and not pts.merged and pts.count == count == len(pts)
+    for f in PV.FIELDS:
+        got = np.asarray(getattr(pts, f))
+        assert got.dtype == getattr(want, f).dtype and got.tobytes() == getattr(want, f).tobytes(), f
+    offsets, views = pts.visibility()
+    assert offsets.dtype == np.int64 and offsets.tobytes() == np.asarray(want.offsets, np.int64).tobytes()
+    assert views.dtype == np.int32 and views.tobytes() == np.asarray(want.views, np.int32).tobytes()
+    for normals in (False, True):
+        path = tmp_path / ("n%d.ply" % normals)
+        pts.write_ply(path, normals=normals)
+        assert path.read_bytes() == ply_bytes(want, normals)
+    pts.write_vis(tmp_path / "a.vis")
+    assert (tmp_path / "a.vis").read_bytes() == VC.vis_bytes(want.offsets, want.views)
+    handle, pts._p = pts._p, None
+    del offsets, views, got
+    assert pkg.lib().apd_points_destroy(handle) == 0
+
+
 def test_merge_refusals_that_need_no_device(pkg):
     L = pkg.lib()
     c = cloud([[0.5, 0, 0], [0.6, 0, 0]])

@@ -13,7 +13,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 if len(sys.argv) > 1 and sys.argv[1] == "--all":
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     per_file = {"apd_kernels_k67w.hip": ["-mllvm", "-amdgpu-promote-alloca-to-vector-limit=2048"]}   # build.py: FILE_FLAGS
-    for f in ("apd_kernels_k67w.hip", "apd_kernels_k1415w.hip", "apd_kernels_weak.hip", "apd_kernels.hip", "apd_fusion.hip", "apd_filter.hip", "apd_exchange.hip"):
+    for f in ("apd_kernels_k67w.hip", "apd_kernels_k1415w.hip", "apd_kernels_weak.hip", "apd_kernels.hip", "apd_fusion.hip", "apd_fusion_call.hip", "apd_filter.hip", "apd_exchange.hip"):
         print("== csrc/%s %s" % (f, " ".join(per_file.get(f, []))))
         sys.stdout.flush()
         subprocess.call([sys.executable, os.path.abspath(__file__), os.path.join(root, "apd-mvs_amd", "csrc", f)] + per_file.get(f, []))
