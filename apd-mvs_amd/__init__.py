@@ -186,6 +186,8 @@ def lib():
     L.apd_points_create.argtypes = [C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 7 + [C.c_int, ipp, ipp, ipp, ipp, C.POINTER(C.c_void_p)]
     L.apd_points_merge_voxels.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
     L.apd_points_merged.argtypes = [C.c_void_p]
+    L.apd_points_neighbour_counts.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p]
+    L.apd_points_remove_sparse.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
     L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
     L.apd_sort_tile_sizes.restype = None
     L.apd_points_destroy.argtypes = [C.c_void_p]
@@ -238,7 +240,9 @@ class Points:
     the library's points for them until close().  from_arrays() makes a Points of a caller's arrays (apd_points_create);
     merge_voxels() gives one point per cell of a cubic grid with the union of the members' lists (apd_points_merge_voxels), and
     `merged` says whether an object is such a result: its view, pixel and sources are its representative's alone, its lists are
-    those of visibility(), and average() refuses it."""
+    those of visibility(), and average() refuses it.  neighbour_counts() counts every point's neighbours within a radius
+    (apd_points_neighbour_counts) and remove_sparse() gives the points that have enough of them (apd_points_remove_sparse), with
+    everything else an object carries."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
                ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
@@ -311,6 +315,50 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Points(out, self.device), int(dropped.value)
+
+    def neighbour_counts(self, radius, cap=0, origin=None):
+        """apd_points_neighbour_counts: per point the number of other points within `radius` of it (contract C11: on the grid of cell
+        size `radius` with a corner at `origin`, 0, 0, 0 by default), at most `cap` (0: no cap); a point with a non-finite
+        coordinate or more than 2^20 cells from the origin counts 0 and is counted by nobody.  uint32 [N]: a numpy array for host
+        points; for device points a torch tensor on their device holding the same bit patterns as int32, like `sources`.
+        Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.neighbour_counts: the points are closed")
+        if not 0 <= int(cap) <= 0xFFFFFFFF:
+            raise ValueError("Points.neighbour_counts: a cap of %r, not in 0 .. 2^32 - 1" % (cap,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        nothing = (C.c_uint32 * 1)()   # where an object without points gets its no counts: the library refuses NULL
+        if self.on_device:
+            import torch
+            counts = torch.empty((self.count,), dtype=torch.int32, device=torch.device("cuda", self.device))
+            torch.cuda.synchronize(counts.device)
+            address = counts.data_ptr() if self.count else C.addressof(nothing)
+        else:
+            counts = np.zeros(self.count, np.uint32)
+            address = counts.ctypes.data if self.count else C.addressof(nothing)
+        rc = L.apd_points_neighbour_counts(self._p, float(radius), org, int(cap), C.c_void_p(address))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return counts
+
+    def remove_sparse(self, radius, min_neighbours, origin=None):
+        """apd_points_remove_sparse: (Points, removed) -- the points with at least `min_neighbours` other points within `radius`
+        (the relation of neighbour_counts), in their order, with all seven arrays; `removed` is the number left out.
+        min_neighbours = 0 keeps every point.  The result lists, writes and averages itself like these points; the result of a
+        merged object is a merged object with the kept points' lists.  Computed on these points' device; the result lives where
+        they live."""
+        if not self._p:
+            raise ApdError("Points.remove_sparse: the points are closed")
+        if not 0 <= int(min_neighbours) <= 0xFFFFFFFF:
+            raise ValueError("Points.remove_sparse: a minimum of %r neighbours, not in 0 .. 2^32 - 1" % (min_neighbours,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        out, removed = C.c_void_p(), C.c_longlong(0)
+        rc = L.apd_points_remove_sparse(self._p, float(radius), org, int(min_neighbours), C.byref(out), C.byref(removed))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device), int(removed.value)
 
     def __len__(self):
         return self.count

@@ -1,7 +1,8 @@
 // apd_points.hip -- the life and the files of a points object (apd_points_t of include/apd_mi355x.h, struct apd_points of
 // apd_points_host.h): the operations on the table of its arrays, the one function that makes a new object, the accessors,
-// apd_points_create, apd_points_destroy, apd_points_write_ply and apd_points_write_vis.  Who fills one: the fusions
-// (apd_fusion_call.hip), apd_points_average.hip, apd_points_merge.hip; its visibility lists: apd_points_vis.hip.
+// apd_points_create, apd_points_destroy, apd_points_write_ply and apd_points_write_vis, and compact_points: an object without some
+// of its points.  Who fills one: the fusions (apd_fusion_call.hip), apd_points_average.hip, apd_points_merge.hip,
+// apd_points_radius.hip (through compact_points); its visibility lists: apd_points_vis.hip.
 //
 // apd_points_create: the checks that make the arrays a cloud some fusion could have made (every later call relies on them: a
 // view indexes the source lists, a bit of `sources` indexes a list), then one copy of each array, to host memory or to the device.
@@ -23,6 +24,7 @@
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_device.h"
 #include "apd_points_host.h"
+#include "apd_sort.h"
 
 namespace apd_fusion {
 
@@ -392,6 +394,156 @@ extern "C" int apd_points_write_vis(apd_points_t p, const char *path)
     if (fclose(f) != 0 || !ok) {
         err() = std::string("apd_points_write_vis: short write to ") + path;
         return APD_ERR_IO;
+    }
+    return APD_OK;
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// compact_points
+// --------------------------------------------------------------------------------------------------------------------
+
+namespace {
+
+// `width` elements per point: those of the kept points k go to point at[k] (the kept points before k)
+template <typename T>
+__global__ __launch_bounds__(256) void k_compact_array(const T *__restrict__ in, int width, const uint32_t *__restrict__ keep,
+                                                        const uint64_t *__restrict__ at, size_t n, T *__restrict__ out)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n && keep[k]) {
+        const size_t to = (size_t)at[k];
+        for (int c = 0; c < width; ++c) {
+            out[to * width + c] = in[k * width + c];
+        }
+    }
+}
+
+// length[k]: entries of the list of point k if it is kept, else 0
+__global__ __launch_bounds__(256) void k_kept_list_lengths(const long long *__restrict__ offsets, const uint32_t *__restrict__ keep, size_t n,
+                                                            uint32_t *__restrict__ length)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n) {
+        length[k] = keep[k] ? (uint32_t)(offsets[k + 1] - offsets[k]) : 0u;
+    }
+}
+
+// The list of kept point k starts at entry_at[k] (the kept entries before it) and belongs to point at[k]; [kept] = all of them
+__global__ __launch_bounds__(256) void k_compact_lists(const long long *__restrict__ offsets, const int32_t *__restrict__ views,
+                                                        const uint32_t *__restrict__ keep, const uint64_t *__restrict__ at,
+                                                        const uint64_t *__restrict__ entry_at, size_t n, long long *__restrict__ out_offsets,
+                                                        int32_t *__restrict__ out_views)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) {
+        return;
+    }
+    if (keep[k]) {
+        out_offsets[at[k]] = (long long)entry_at[k];
+        int32_t *to = out_views + entry_at[k];
+        for (long long e = offsets[k]; e < offsets[k + 1]; ++e) {
+            *to++ = views[e];
+        }
+    }
+    if (k == 0) {
+        out_offsets[at[n]] = (long long)entry_at[n];
+    }
+}
+
+}  // namespace
+
+int apd_points_host::compact_points(const char *who, const apd_points *p, const apd_fusion::PointArrays &in, const uint32_t *keep,
+                                    apd_points *result)
+{
+    using apd_fusion::PointArrays;
+    const auto hip_failed = [who](const char *expr, hipError_t e, const char *, int) {  // what HIP_TRY returns here
+        return apd::set_error(apd_fusion::g_fusion_error, APD_ERR_HIP, "%s: %s: %s", who, expr, hipGetErrorString(e));
+    };
+    const auto no_host_memory = [who] { return apd::set_error(apd_fusion::g_fusion_error, APD_ERR_HIP, "%s: out of host memory", who); };
+    const size_t n = (size_t)p->count;
+    const dim3 blocks((unsigned)((n + 255) / 256));  // n < 2^31: fits
+    Scratch scratch;
+    // p's lists where p lives, before anything of the result exists: a merged object's are all it has
+    const long long *offsets = nullptr;
+    const int32_t *views = nullptr;
+    if (p->merged) {
+        if (const int rc = apd_points_visibility(const_cast<apd_points *>(p), &offsets, &views); rc != APD_OK) {
+            return rc;
+        }
+    }
+    uint64_t *at = nullptr;
+    HIP_TRY(scratch.alloc((n + 1) * 8, &at));
+    HIP_TRY(apd_sort::exclusive_scan(keep, at, n));
+    uint64_t kept = 0;
+    HIP_TRY(hipMemcpy(&kept, at + n, 8, hipMemcpyDeviceToHost));
+    const size_t m = (size_t)kept;
+    result->merged = p->merged;
+    result->count = (long long)m;
+    if (m == 0) {  // an object without points
+        return APD_OK;
+    }
+    PointArrays out;
+    HIP_TRY(alloc_arrays(scratch, out, m));
+    apd_fusion::for_each_array([&](auto member, size_t bytes, unsigned) {
+        if (bytes % 4 == 0) {
+            hipLaunchKernelGGL(k_compact_array<uint32_t>, blocks, dim3(256), 0, 0, reinterpret_cast<const uint32_t *>(in.*member), (int)(bytes / 4), keep,
+                               (const uint64_t *)at, n, reinterpret_cast<uint32_t *>(out.*member));
+        } else {
+            hipLaunchKernelGGL(k_compact_array<uint8_t>, blocks, dim3(256), 0, 0, reinterpret_cast<const uint8_t *>(in.*member), (int)bytes, keep,
+                               (const uint64_t *)at, n, reinterpret_cast<uint8_t *>(out.*member));
+        }
+    });
+    HIP_TRY(hipGetLastError());
+    long long *out_offsets = nullptr;
+    int32_t *out_views = nullptr;
+    size_t entries = 0;
+    if (p->merged) {
+        if (!p->on_device) {
+            const size_t total = (size_t)offsets[n];
+            HIP_TRY(scratch.upload(offsets, (n + 1) * sizeof(long long), &offsets));
+            HIP_TRY(scratch.upload(views, total * sizeof(int32_t), &views));
+        }
+        uint32_t *length = nullptr;
+        uint64_t *entry_at = nullptr;
+        HIP_TRY(scratch.alloc(n * 4, &length));
+        HIP_TRY(scratch.alloc((n + 1) * 8, &entry_at));
+        hipLaunchKernelGGL(k_kept_list_lengths, blocks, dim3(256), 0, 0, offsets, keep, n, length);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(apd_sort::exclusive_scan(length, entry_at, n));
+        uint64_t total = 0;
+        HIP_TRY(hipMemcpy(&total, entry_at + n, 8, hipMemcpyDeviceToHost));
+        entries = (size_t)total;
+        HIP_TRY(scratch.alloc((m + 1) * sizeof(long long), &out_offsets));
+        HIP_TRY(scratch.alloc(entries * sizeof(int32_t), &out_views));
+        hipLaunchKernelGGL(k_compact_lists, blocks, dim3(256), 0, 0, offsets, views, keep, (const uint64_t *)at, (const uint64_t *)entry_at, n, out_offsets,
+                           out_views);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    if (p->on_device) {
+        keep_arrays(scratch, out);
+        result->arrays = out;
+        if (p->merged) {
+            scratch.keep(out_offsets);
+            scratch.keep(out_views);
+            result->vis_offsets = out_offsets;
+            result->vis_views = out_views;
+        }
+        return APD_OK;
+    }
+    // host memory: freed with `result` by the caller if a download fails
+    if (!alloc_host_arrays(result->arrays, m)) {
+        return no_host_memory();
+    }
+    HIP_TRY(copy_arrays(result->arrays, out, m, hipMemcpyDeviceToHost));
+    if (p->merged) {
+        result->vis_offsets = static_cast<long long *>(malloc((m + 1) * sizeof(long long)));
+        result->vis_views = static_cast<int32_t *>(malloc(entries > 0 ? entries * sizeof(int32_t) : sizeof(int32_t)));
+        if (!result->vis_offsets || !result->vis_views) {
+            return no_host_memory();
+        }
+        HIP_TRY(hipMemcpy(result->vis_offsets, out_offsets, (m + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(result->vis_views, out_views, entries * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     return APD_OK;
 }

@@ -138,4 +138,12 @@ inline apd_points *new_points_like(const apd_points *p)
     return new_points(p->device, p->on_device, (int)p->rows.size(), p->rows.data(), p->cols.data(), p->pair_offsets.data(), p->pair_indices.data());
 }
 
+// The points k of p (count > 0, fewer than 2^31) with keep[k] != 0 -- `keep`: count flags of 0 or 1 in device memory on p's device,
+// which is the current one; `in`: p's arrays on that device, its own or the caller's upload of them -- in p's order into `result`
+// (of new_points_like(p), without arrays so far): a scan of the flags and one gather per array of the table, on the null stream.
+// The result of host-resident points comes down.  A merged p hands the kept points' lists on (new offsets by a 64-bit scan of the
+// kept lengths) and result->merged = 1; any other result builds its lists from its sources like p.  Messages start with `who`;
+// on failure the caller destroys `result`.
+int compact_points(const char *who, const apd_points *p, const apd_fusion::PointArrays &in, const uint32_t *keep, apd_points *result);
+
 }  // namespace apd_points_host

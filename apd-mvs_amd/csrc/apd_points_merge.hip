@@ -1,7 +1,8 @@
 // apd_points_merge.hip -- apd_points_merge_voxels of include/apd_mi355x.h: one point per occupied cell of a cubic grid, with the
 // union of its members' visibility lists (arithmetic contract C10; the cell and the key: apd_voxel_math.h).
 //
-// On the points' device, on top of the sort and the scan of apd_sort.h:
+// On the points' device, on top of the sort and the scan of apd_sort.h (steps 1 and 2: apd_points_grid.h, shared with
+// apd_points_radius.hip):
 //   1. k_voxel_keys: the key of every point and whether it is kept.
 //   2. scan of the keep flags, k_voxel_compact: (key, input index) of the kept points, in input order.
 //   3. sort_pairs: stable, so the members of a cell stand in ascending input index.
@@ -21,6 +22,7 @@
 
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_device.h"
+#include "apd_points_grid.h"
 #include "apd_points_host.h"
 #include "apd_sort.h"
 #include "apd_voxel_math.h"
@@ -28,40 +30,13 @@
 namespace {
 
 using apd_fusion::PointArrays;
+using apd_points_grid::Grid;
+using apd_points_grid::grid_of;
+using apd_points_grid::k_voxel_compact;
+using apd_points_grid::k_voxel_keys;
 using apd_points_host::DeviceScope;
 using apd_points_host::Scratch;
 using apd_points_host::ms_since;
-
-struct Grid {
-    float origin[3];
-    float size;
-};
-
-__global__ __launch_bounds__(256) void k_voxel_keys(const float *__restrict__ xyz, size_t n, Grid grid, uint64_t *__restrict__ key,
-                                                     uint32_t *__restrict__ keep)
-{
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) {
-        return;
-    }
-    const float P[3] = {xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]};
-    uint64_t code = 0;
-    const bool kept = apd_fusion::voxel_key(P, grid.origin, grid.size, code);
-    key[k] = code;
-    keep[k] = kept ? 1u : 0u;
-}
-
-// at[k]: kept points before point k
-__global__ __launch_bounds__(256) void k_voxel_compact(const uint64_t *__restrict__ key, const uint32_t *__restrict__ keep,
-                                                        const uint64_t *__restrict__ at, size_t n, uint64_t *__restrict__ keys,
-                                                        uint32_t *__restrict__ index)
-{
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n && keep[k]) {
-        keys[at[k]] = key[k];
-        index[at[k]] = (uint32_t)k;
-    }
-}
 
 // head[i] = 1 where sorted key i differs from its predecessor: the first element of a cell, or of a (cell, view) run of the lists
 __global__ __launch_bounds__(256) void k_run_heads(const uint64_t *__restrict__ keys, size_t n, uint32_t *__restrict__ head)
@@ -190,8 +165,6 @@ int hip_failed(const char *expr, hipError_t e, const char *, int)
 {
     return apd::set_error(err(), APD_ERR_HIP, "apd_points_merge_voxels: %s: %s", expr, hipGetErrorString(e));
 }
-
-dim3 grid_of(size_t n) { return dim3((unsigned)((n + 255) / 256)); }  // n < 2^32: fits
 
 constexpr long long kMaxEntries = 1LL << 32;
 

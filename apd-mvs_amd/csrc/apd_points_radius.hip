@@ -1,0 +1,289 @@
+// apd_points_radius.hip -- apd_points_neighbour_counts and apd_points_remove_sparse of include/apd_mi355x.h: how many other points
+// every point has within a radius, and the object without the points that have too few (arithmetic contract C11; the
+// relation: apd_radius_math.h).
+//
+// On the points' device, on its null stream, on top of the sort and the scan of apd_sort.h:
+//   1. k_voxel_keys, scan, k_voxel_compact (apd_points_grid.h): (key, input index) of the points inside the grid of cell size
+//      `radius`, in input order.
+//   2. sort_pairs: the points of a cell together, the cells in key order -- x fastest, so the three x-adjacent cells of a (y, z)
+//      row are one contiguous run of the sorted keys.
+//   3. k_gather_xyz: the positions in sorted order.
+//   4. k_neighbour_count: one lane per point in sorted order; for each of the 9 (dz, dy) rows around its cell a binary search for
+//      the start of the run and a walk to its end.  Lanes of a wave stand next to each other in sorted order: they mostly share
+//      their cell, so their searches take the same branches and their candidate loads go to the same address.  A lane leaves the
+//      loops at `cap`.  No LDS, no atomics; the count goes to the point's input index, a point outside the grid keeps 0.
+//   5. removal: k_keep_flags, compact_points (apd_points.hip).
+// The work is the number of (point, candidate in the 27 cells) pairs: with cap == 0 a cell of m members costs m * m distance
+// tests, each lane of the cell walking all m; the removal runs with cap = min_neighbours and is bounded by that early exit in
+// dense regions.  There is no host path: host-resident points go up, the result comes down.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include <string>
+
+#include "../../include/apd_mi355x.h"
+#include "apd_fusion_device.h"
+#include "apd_points_grid.h"
+#include "apd_points_host.h"
+#include "apd_radius_math.h"
+#include "apd_sort.h"
+
+namespace {
+
+using apd_fusion::PointArrays;
+using apd_points_grid::Grid;
+using apd_points_grid::grid_of;
+using apd_points_grid::k_voxel_compact;
+using apd_points_grid::k_voxel_keys;
+using apd_points_host::DeviceScope;
+using apd_points_host::Scratch;
+
+__global__ __launch_bounds__(256) void k_gather_xyz(const float *__restrict__ xyz, const uint32_t *__restrict__ member, size_t m,
+                                                     float *__restrict__ sorted_xyz)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) {
+        const size_t k = member[i];
+        sorted_xyz[3 * i] = xyz[3 * k];
+        sorted_xyz[3 * i + 1] = xyz[3 * k + 1];
+        sorted_xyz[3 * i + 2] = xyz[3 * k + 2];
+    }
+}
+
+// the first position in [from, m) whose key is not below `want`
+__device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ keys, uint32_t from, uint32_t m, uint64_t want)
+{
+    uint32_t lo = from, hi = m;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < want) {
+            lo = mid + 1;
+        } else {
+            hi = mid;
+        }
+    }
+    return lo;
+}
+
+// Sorted element i < m: counts[member[i]] = min(neighbours, cap) by contract C11.  keys: ascending; xyz: in the same order.
+// The rows are visited in ascending key order, so a row's run starts at or after the end of the one before it.  The x range is
+// clamped and a row whose y or z cell leaves the grid is skipped: a search bound never borrows into the next field of the key.
+// Every candidate of a run lies in a cell adjacent to the lane's by construction; what is left of the relation is the index and
+// the distance.
+__global__ __launch_bounds__(256) void k_neighbour_count(const uint64_t *__restrict__ keys, const float *__restrict__ xyz,
+                                                          const uint32_t *__restrict__ member, uint32_t m, float r2, uint32_t cap,
+                                                          uint32_t *__restrict__ counts)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;  // m < 2^31
+    if (i >= m) {
+        return;
+    }
+    int cell[3];
+    apd_fusion::radius_cells_of_key(keys[i], cell);
+    const float P[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
+    const int lo = -apd_fusion::kVoxelHalf, hi = apd_fusion::kVoxelHalf - 1;
+    const int x0 = cell[0] > lo ? cell[0] - 1 : lo, x1 = cell[0] < hi ? cell[0] + 1 : hi;
+    uint32_t count = 0, at = 0;
+    bool full = false;
+    for (int dz = -1; dz <= 1 && !full; ++dz) {
+        const int cz = cell[2] + dz;
+        if (cz < lo || cz > hi) {
+            continue;
+        }
+        for (int dy = -1; dy <= 1 && !full; ++dy) {
+            const int cy = cell[1] + dy;
+            if (cy < lo || cy > hi) {
+                continue;
+            }
+            const uint64_t last = apd_fusion::radius_key(x1, cy, cz);
+            at = lower_bound(keys, at, m, apd_fusion::radius_key(x0, cy, cz));
+            for (; at < m && keys[at] <= last; ++at) {
+                const float Q[3] = {xyz[3 * (size_t)at], xyz[3 * (size_t)at + 1], xyz[3 * (size_t)at + 2]};
+                if (at != i && apd_fusion::radius_within(P, Q, r2)) {
+                    ++count;
+                    if (count == cap) {  // cap == 0: never
+                        full = true;
+                        break;
+                    }
+                }
+            }
+        }
+    }
+    counts[member[i]] = count;
+}
+
+// keep[k] = 1 where counts[k] (capped at min_neighbours) reaches min_neighbours
+__global__ __launch_bounds__(256) void k_keep_flags(const uint32_t *__restrict__ counts, size_t n, uint32_t min_neighbours,
+                                                     uint32_t *__restrict__ keep)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n) {
+        keep[k] = counts[k] >= min_neighbours ? 1u : 0u;
+    }
+}
+
+std::string &err() { return apd_fusion::g_fusion_error; }
+
+// One call of either entry point: its name, which starts every message, and the steps the two share
+struct Call {
+    const char *const who;
+    Grid grid = {{0.0f, 0.0f, 0.0f}, 0.0f};
+
+    int hip_failed(const char *expr, hipError_t e, const char *, int) const  // what HIP_TRY returns
+    {
+        return apd::set_error(err(), APD_ERR_HIP, "%s: %s: %s", who, expr, hipGetErrorString(e));
+    }
+
+    // What both calls refuse before any device is touched; fills `grid`
+    int check(apd_points_t p, const void *output, float radius, const float *origin3)
+    {
+        err().clear();
+        if (!p || !output) {
+            return apd::set_error(err(), APD_ERR_INVALID, "%s: null argument", who);
+        }
+        if (!(isfinite(radius) && radius > 0.0f)) {
+            return apd::set_error(err(), APD_ERR_INVALID, "%s: a radius of %g, not a positive finite number", who, (double)radius);
+        }
+        const float r2 = radius * radius;
+        if (!(isfinite(r2) && r2 > 0.0f)) {
+            return apd::set_error(err(), APD_ERR_INVALID, "%s: a radius of %g, whose square %g is not a positive finite number", who, (double)radius,
+                                  (double)r2);
+        }
+        grid.size = radius;
+        for (int a = 0; origin3 && a < 3; ++a) {
+            if (!isfinite(origin3[a])) {
+                return apd::set_error(err(), APD_ERR_INVALID, "%s: origin component %d is %g", who, a, (double)origin3[a]);
+            }
+            grid.origin[a] = origin3[a];
+        }
+        if (p->count >= (1LL << 31)) {
+            return apd::set_error(err(), APD_ERR_UNSUPPORTED, "%s: %lld points, 2^31 or more (the sort carries a 32-bit index)", who, p->count);
+        }
+        return APD_OK;
+    }
+
+    // counts[k] for the n > 0 points at xyz; both in device memory on the current device
+    int count_neighbours(const float *xyz, size_t n, uint32_t cap, uint32_t *counts) const
+    {
+        Scratch scratch;
+        uint64_t *key = nullptr, *at = nullptr, *keys[2] = {nullptr, nullptr};
+        uint32_t *keep = nullptr, *index[2] = {nullptr, nullptr};
+        HIP_TRY(scratch.alloc(n * 8, &key));
+        HIP_TRY(scratch.alloc(n * 4, &keep));
+        HIP_TRY(scratch.alloc((n + 1) * 8, &at));
+        HIP_TRY(hipMemsetAsync(counts, 0, n * 4, 0));  // the points outside the grid
+        hipLaunchKernelGGL(k_voxel_keys, grid_of(n), dim3(256), 0, 0, xyz, n, grid, key, keep);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(apd_sort::exclusive_scan(keep, at, n));
+        uint64_t inside = 0;
+        HIP_TRY(hipMemcpy(&inside, at + n, 8, hipMemcpyDeviceToHost));
+        const size_t m = (size_t)inside;
+        if (m == 0) {
+            return APD_OK;
+        }
+        for (int b = 0; b < 2; ++b) {
+            HIP_TRY(scratch.alloc(m * 8, &keys[b]));
+            HIP_TRY(scratch.alloc(m * 4, &index[b]));
+        }
+        hipLaunchKernelGGL(k_voxel_compact, grid_of(n), dim3(256), 0, 0, (const uint64_t *)key, (const uint32_t *)keep, (const uint64_t *)at, n, keys[0],
+                           index[0]);
+        HIP_TRY(hipGetLastError());
+        int side = 0;
+        HIP_TRY(apd_sort::sort_pairs(keys[0], keys[1], index[0], index[1], m, &side, nullptr));
+        float *sorted_xyz = nullptr;
+        HIP_TRY(scratch.alloc(m * 12, &sorted_xyz));
+        hipLaunchKernelGGL(k_gather_xyz, grid_of(m), dim3(256), 0, 0, xyz, (const uint32_t *)index[side], m, sorted_xyz);
+        hipLaunchKernelGGL(k_neighbour_count, grid_of(m), dim3(256), 0, 0, (const uint64_t *)keys[side], (const float *)sorted_xyz,
+                           (const uint32_t *)index[side], (uint32_t)m, grid.size * grid.size, cap, counts);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        return APD_OK;
+    }
+
+    // apd_points_neighbour_counts of p (count > 0): host-resident points send their positions up and get the counts down
+    int counts_of(apd_points_t p, uint32_t cap, uint32_t *counts) const
+    {
+        const size_t n = (size_t)p->count;
+        Scratch scratch;
+        HIP_TRY(hipSetDevice(p->device));
+        const float *xyz = p->arrays.xyz;
+        uint32_t *device_counts = counts;
+        if (!p->on_device) {
+            HIP_TRY(scratch.upload((const float *)p->arrays.xyz, n * 12, &xyz));
+            HIP_TRY(scratch.alloc(n * 4, &device_counts));
+        }
+        if (const int rc = count_neighbours(xyz, n, cap, device_counts); rc != APD_OK) {
+            return rc;
+        }
+        if (!p->on_device) {
+            HIP_TRY(hipMemcpy(counts, device_counts, n * 4, hipMemcpyDeviceToHost));
+        }
+        return APD_OK;
+    }
+
+    // apd_points_remove_sparse of p (count > 0) into `result`: host-resident points send every array up once, for the count and
+    // for the compaction
+    int remove_sparse(apd_points_t p, uint32_t min_neighbours, apd_points *result) const
+    {
+        const size_t n = (size_t)p->count;
+        Scratch scratch;
+        HIP_TRY(hipSetDevice(p->device));
+        PointArrays in = p->arrays;
+        if (!p->on_device) {
+            HIP_TRY(alloc_arrays(scratch, in, n));
+            HIP_TRY(copy_arrays(in, p->arrays, n, hipMemcpyHostToDevice));
+        }
+        uint32_t *counts = nullptr, *keep = nullptr;
+        HIP_TRY(scratch.alloc(n * 4, &counts));
+        HIP_TRY(scratch.alloc(n * 4, &keep));
+        if (min_neighbours == 0) {  // every point stays, those outside the grid too: nothing to count
+            HIP_TRY(hipMemsetAsync(counts, 0, n * 4, 0));
+        } else if (const int rc = count_neighbours(in.xyz, n, min_neighbours, counts); rc != APD_OK) {
+            return rc;
+        }
+        hipLaunchKernelGGL(k_keep_flags, grid_of(n), dim3(256), 0, 0, (const uint32_t *)counts, n, min_neighbours, keep);
+        HIP_TRY(hipGetLastError());
+        return apd_points_host::compact_points(who, p, in, keep, result);
+    }
+};
+
+}  // namespace
+
+extern "C" int apd_points_neighbour_counts(apd_points_t p, float radius, const float *origin3, unsigned cap, uint32_t *counts)
+{
+    Call call{"apd_points_neighbour_counts"};
+    if (const int rc = call.check(p, counts, radius, origin3); rc != APD_OK) {
+        return rc;
+    }
+    if (p->count == 0) {
+        return APD_OK;
+    }
+    DeviceScope scope(true);
+    return call.counts_of(p, cap, counts);
+}
+
+extern "C" int apd_points_remove_sparse(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, apd_points_t *out,
+                                        long long *removed)
+{
+    Call call{"apd_points_remove_sparse"};
+    if (const int rc = call.check(p, out, radius, origin3); rc != APD_OK) {
+        return rc;
+    }
+    apd_points *result = apd_points_host::new_points_like(p);
+    result->merged = p->merged;
+    if (p->count > 0) {
+        DeviceScope scope(true);
+        if (const int rc = call.remove_sparse(p, min_neighbours, result); rc != APD_OK) {
+            const std::string why = err();
+            apd_points_destroy(result);  // its arrays are host memory, or none yet
+            err() = why;
+            return rc;
+        }
+    }
+    *out = result;
+    if (removed) {
+        *removed = p->count - result->count;
+    }
+    return APD_OK;
+}

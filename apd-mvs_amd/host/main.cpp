@@ -3,7 +3,7 @@
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
-//       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--filtered-maps]
+//       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-radius-filter RADIUS,MIN] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -24,6 +24,10 @@
 // (apd_points_merge_voxels: the mean of the cell's points, the union of their lists) and, with --ply-vis, APD.ply.vis those
 // lists; with --ply-mean the points are averaged first.  With every --fusion; the cells and the dropped points (non-finite, or
 // 2^20 cells from the origin) are printed.  SIZE must be a positive finite number, or the usage line is all that happens.
+// --ply-radius-filter RADIUS,MIN: APD.ply holds the points that have at least MIN other points within RADIUS
+// (apd_points_remove_sparse: the radius outlier filter, on the grid of cell size RADIUS at the origin) and, with --ply-vis,
+// APD.ply.vis their lists; applied last, after --ply-mean and --ply-voxel.  With every --fusion; the number removed is printed.
+// RADIUS must be a positive finite number whose square is one too, MIN a count, or the usage line is all that happens.
 //
 // --masks [DIR] (default DIR: masks): <dense_folder>/DIR/<%08d>.jpg|pgm are per-view pixel masks, grey < 128 = masked out of
 // PatchMatch (apd_upload_mask: the pixels cost no NCC and leave as depth 0 / UNKNOWN); a view without a file is unmasked, a file
@@ -133,6 +137,20 @@ bool ParseOptions(int argc, char **argv, Options &o)
                 fprintf(stderr, "bad value '%s' of %s: a positive number\n", text, a.c_str());
                 return false;
             }
+        } else if (a == "--ply-radius-filter") {
+            const std::string both = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = both.find(',');
+            const std::string count = comma == std::string::npos ? "" : both.substr(comma + 1);
+            char *end = nullptr;
+            const unsigned long long k = strtoull(count.c_str(), &end, 10);
+            const bool digits = !count.empty() && count.find_first_not_of("0123456789") == std::string::npos && *end == '\0' && k <= 0xffffffffull;
+            float r = 0.0f;
+            if (!digits || !real(both.substr(0, comma).c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
+                fprintf(stderr, "bad value '%s' of %s: RADIUS,MIN, a positive number and a count\n", both.c_str(), a.c_str());
+                return false;
+            }
+            o.ply_radius = r;
+            o.ply_radius_min = (unsigned)k;
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
         } else if (a == "--seed") {
@@ -344,10 +362,11 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-radius-filter RADIUS,MIN] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
-                        "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n");
+                        "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
+                        "  --ply-radius-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points that have fewer than MIN other points within RADIUS, after --ply-mean and --ply-voxel.\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -365,6 +384,7 @@ int main(int argc, char **argv)
     SetFusionPlyVis(opt.ply_vis);
     SetFusionPlyMean(opt.ply_mean);
     SetFusionPlyVoxel(opt.ply_voxel);
+    SetFusionPlyRadiusFilter(opt.ply_radius, opt.ply_radius_min);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

@@ -38,6 +38,8 @@ struct Options {
     bool ply_vis = false;                 // --ply-vis: APD/APD.ply.vis beside APD.ply (apd_points_write_vis)
     bool ply_mean = false;                // --ply-mean: APD.ply (and APD.ply.vis) of the points averaged over their agreeing views (apd_points_average)
     float ply_voxel = 0.0f;               // --ply-voxel SIZE: APD.ply (and APD.ply.vis) of the points merged per cell of that size (apd_points_merge_voxels); 0: off
+    float ply_radius = 0.0f;              // --ply-radius-filter RADIUS,MIN: APD.ply (and APD.ply.vis) of the points with at least MIN others within
+    unsigned ply_radius_min = 0;          // RADIUS (apd_points_remove_sparse), after --ply-mean and --ply-voxel; radius 0: off
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)

@@ -494,7 +494,38 @@ int apd_points_create(int device, int on_device, long long count, const float *x
  * their lists are built on their device.  *out and *dropped are untouched when the call fails.  apd_fusion_last_timing reports
  * the call: set-up (uploads, allocations), the kernels (and the download of a host result) as "views", file 0. */
 int apd_points_merge_voxels(apd_points_t p, float voxel_size, const float *origin3, apd_points_t *out, long long *dropped);
-int apd_points_merged(apd_points_t p);   /* 1 for a result of apd_points_merge_voxels, else 0 */
+int apd_points_merged(apd_points_t p);   /* 1 for a result of apd_points_merge_voxels (or of a removal from one), else 0 */
+/* Neighbours within a radius, and the removal of points that have too few of them: the radius outlier filter that is run between
+ * fusion and meshing, here on the points object, so that sources, support, view / pixel and the visibility lists survive it.
+ * binary32, IEEE operations in the order given (contract C11; csrc/apd_radius_math.h).
+ *   Grid.  Cubic, cell size `radius`, origin origin3 (NULL: 0, 0, 0); the cell of a point on each axis is that of
+ *   apd_points_merge_voxels.  A point that the merge would drop (a non-finite coordinate, a cell outside [-2^20, 2^20)) is outside
+ *   the grid: it has no neighbours and is nobody's neighbour.
+ *   Neighbour.  Point j is a neighbour of point i when j != i as indices (coincident points are each other's neighbours), both
+ *   are inside the grid, their cells differ by at most 1 on every axis, and (dx * dx + dy * dy) + dz * dz <= radius * radius
+ *   with dx = x_i - x_j and so on.  The cell condition is part of the definition: the search of the 27 cells around a point is
+ *   exact, not an approximation; in real arithmetic it follows from the distance test, in binary32 it can only turn away a pair
+ *   within the rounding of the cell quotient (2^-24 of a cell near the origin, about 1/8 at cell 2^20) of exactly one radius apart.
+ *   counts[i] = min(neighbours of i, cap); cap == 0: no cap.  Kept by apd_points_remove_sparse: the points with at least
+ *   min_neighbours neighbours; min_neighbours == 0 keeps every point, those outside the grid too.
+ * apd_points_neighbour_counts: `counts` has apd_points_count(p) entries, host memory for host-resident points, device memory on
+ * p's device for device-resident ones.
+ * apd_points_remove_sparse: *out is a new object with the kept points in p's order, every array copied; *removed (may be NULL)
+ * the number of points left out.  The result of a fusion's or an averaged object carries its source lists and view sizes on:
+ * apd_points_visibility, apd_points_write_vis and apd_points_average work on it as on p.  The result of a merged object is a merged
+ * object (apd_points_merged) with the kept points' lists.  It lives where p lives and is released with apd_points_destroy.
+ * Both are computed on p's device, on its null stream, whatever memory p is in (host-resident points are uploaded, the result is
+ * downloaded); there is no host implementation.  An object without points gives no counts, or an object without points, with no
+ * device touched.  The work is the number of (point, candidate in the 27 cells around it) pairs: with cap == 0 a cell of m
+ * members costs m * m distance tests, one lane per point; the removal runs with cap = min_neighbours and leaves a dense
+ * neighbourhood after that many hits.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_neighbour_counts: ..." or
+ * "apd_points_remove_sparse: ..." (apd_fusion_last_error): a NULL p, a NULL counts or out, a radius that is not finite or not
+ * above 0, a radius whose square is not finite or is zero, a non-finite origin component; APD_ERR_UNSUPPORTED for 2^31 or more
+ * points (the sort carries a 32-bit index).  *out and *removed are untouched when the call fails. */
+int apd_points_neighbour_counts(apd_points_t p, float radius, const float *origin3, unsigned cap, uint32_t *counts);
+int apd_points_remove_sparse(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, apd_points_t *out,
+                             long long *removed);
 /* The tile sizes of the device sort under apd_points_merge_voxels (csrc/apd_sort.h): elements per workgroup of a sort pass and
  * entries per workgroup of its scan.  For tests that choose sizes around them. */
 void apd_sort_tile_sizes(int *sort_tile, int *scan_tile);
