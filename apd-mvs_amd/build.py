@@ -160,16 +160,19 @@ TOOLS_DIR = os.path.join(HERE, "..", "tools")
 
 def build_tools(force=False):
     """tools/_build/: valu_rates (exhaustive ISA checks of the arithmetic contract), valu_issue (issue cost per VALU instruction
-    class, the basis of bench.py's roofline peak), unaligned_gather (cost of dword gathers at 2-byte alignment), lds_addr_bits (ds_read does not ignore high address bits), tcp_patterns (L1 tag accesses per gather by lane address pattern), tcp_mix (cost of gathers whose lanes partly miss the L1), rccl_init_time (what RCCL's set-up consists of)."""
+    class, the basis of bench.py's roofline peak), unaligned_gather (cost of dword gathers at 2-byte alignment), lds_addr_bits (ds_read does not ignore high address bits), tcp_patterns (L1 tag accesses per gather by lane address pattern), tcp_mix (cost of gathers whose lanes partly miss the L1), rccl_init_time (what RCCL's set-up consists of), sort_check (the sort and the scan of csrc/apd_sort.h against host references; it calls the library
+    this tree built and is relinked when that is)."""
     out_dir = os.path.join(TOOLS_DIR, "_build")
     os.makedirs(out_dir, exist_ok=True)
     outs = []
     for name, flags in (("valu_rates", ["-ffp-contract=off", "-fno-slp-vectorize"]), ("valu_issue", []), ("unaligned_gather", []),
                         ("lds_addr_bits", ["-Wno-unused-value"]), ("tcp_patterns", []), ("tcp_mix", []),
-                        ("rccl_init_time", ["-Wno-unused-result", "-Wno-unused-value", "-ldl", "-pthread"])):
+                        ("rccl_init_time", ["-Wno-unused-result", "-Wno-unused-value", "-ldl", "-pthread"]),
+                        ("sort_check", ["-Wall", "-L" + OUT_DIR, "-lapd_mi355x", "-Wl,-rpath,$ORIGIN/../../apd-mvs_amd/_build", "-Wl,-rpath," + OUT_DIR])):
         src = os.path.join(TOOLS_DIR, name + ".hip")
         out = os.path.join(out_dir, name)
-        if force or _newer(out, [src]):
+        deps = [src] + ([LIB_PATH, os.path.join(CSRC, "apd_sort.h")] if name == "sort_check" else [])
+        if force or _newer(out, deps):
             r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17"] + flags + [src, "-o", out],
                                stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
             if r.returncode != 0:

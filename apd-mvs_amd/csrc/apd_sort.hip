@@ -24,6 +24,13 @@ namespace {
 
 constexpr int kWaves = kSortThreads / 64;
 
+// k_sort_histogram and k_sort_scatter index count[t], base[t] and wave_count[w][t] by thread; the reductions and the Hillis-Steele
+// scan of apd_scan.h halve or double their stride
+static_assert(kSortThreads == kDigits, "one thread of a sort block per digit of the [kDigits] tables in LDS");
+static_assert(kSortThreads % 64 == 0, "a sort block is whole waves: the ballots rank 64 lanes");
+static_assert(kScanThreads > 0 && (kScanThreads & (kScanThreads - 1)) == 0, "k_scan_sums reduces with strides kScanThreads / 2, / 4, ... 1");
+static_assert(kScanTopThreads > 0 && (kScanTopThreads & (kScanTopThreads - 1)) == 0, "kScanTopThreads is a power of two");
+
 __global__ __launch_bounds__(kScanThreads) void k_scan_sums(const uint32_t *__restrict__ in, size_t n, uint64_t *__restrict__ sums)
 {
     __shared__ uint64_t part[kScanThreads];

@@ -356,6 +356,7 @@ def test_exports_equal_the_host_postprocessing(gpu_pkg, synth, W, H):
     assert np.array_equal(canon(d_depth.cpu().numpy()), canon(rp[..., 3]))
     d_normal = torch.empty((H, W, 3), device="cuda", dtype=torch.float32)
     d_depth.zero_()
+    torch.cuda.synchronize()   # the export runs on the handle's own non-blocking stream: torch's fill must have ended before it
     h.export_depth_normal(d_depth, d_normal)
     assert np.array_equal(canon(d_depth.cpu().numpy()), canon(rp[..., 3]))
     assert np.array_equal(canon(d_normal.cpu().numpy()), canon(rp[..., :3]))

@@ -190,6 +190,7 @@ def test_masked_pass_equals_frozen_pixel_emulation(gpu_pkg, synth, kind, W, H, N
     assert np.array_equal(depth.cpu().numpy().view(np.uint32), np.ascontiguousarray(rp[..., 3]).view(np.uint32))
     normal = torch.empty((H, W, 3), device="cuda", dtype=torch.float32)
     depth.zero_()
+    torch.cuda.synchronize()   # the export runs on the handle's own non-blocking stream: torch's fill must have ended before it
     a.export_depth_normal(depth, normal)
     assert np.array_equal(depth.cpu().numpy().view(np.uint32), np.ascontiguousarray(rp[..., 3]).view(np.uint32))
     assert np.array_equal(normal.cpu().numpy().view(np.uint32), np.ascontiguousarray(rp[..., :3]).view(np.uint32))

@@ -94,6 +94,35 @@ def test_a_table_scan_of_several_blocks(gpu_pkg, checker, tiles):
     assert 1 < want.count <= n // 4
 
 
+def ring_lists(view, sources, num_views, nsrc):
+    """PV.source_lists for the ring source lists of views_of(num_views, nsrc), without a Python loop over the points."""
+    view = np.asarray(view, np.int64)[:, None]
+    candidates = np.concatenate([view, (view + 1 + np.arange(nsrc)) % num_views], axis=1)
+    listed = np.concatenate([np.ones_like(view), (np.asarray(sources, np.int64)[:, None] >> np.arange(nsrc)) & 1], axis=1).astype(bool)
+    return np.concatenate([[0], np.cumsum(listed.sum(1))]).astype(np.int64), candidates[listed].astype(np.int32)
+
+
+def test_scans_with_two_block_sums_in_a_lane_of_the_top_scan(gpu_pkg, checker, tiles):
+    """S * 1024 + S + 17 kept points, device-resident: the scan of the keep flags and the scans of `head` and `length` over the kept
+    points have more blocks than the 1024 lanes of the workgroup that scans the block sums, so every lane owns two sums and the
+    upper lanes none.  (The sort and the scan on their own at this boundary and past it: tools/sort_check.hip, test_gpu_sort_scan.py.)"""
+    T, S = tiles
+    n = S * 1024 + S + 17
+    assert n > S * 1024
+    rng = np.random.default_rng(16)
+    num_views, nsrc = 3, 2
+    rows, cols, pairs = views_of(num_views, nsrc)
+    view = rng.integers(0, num_views, n).astype(np.int32)
+    sources = rng.integers(0, 1 << nsrc, n).astype(np.uint32)
+    lists = ring_lists(view, sources, num_views, nsrc)
+    few = PV.source_lists(view[:1000], sources[:1000], pairs)
+    assert np.array_equal(lists[0][:1001], few[0]) and np.array_equal(lists[1][:few[0][-1]], few[1])
+    c = cloud(cells_from_a_pool(rng, n, -2 ** 20, 2 ** 20, n // 4), normal=rng.normal(size=(n, 3)).astype(np.float32),
+              bgr=rng.integers(0, 256, (n, 3)).astype(np.uint8), view=view, sources=sources, pairs=pairs, lists=lists)
+    want = check(gpu_pkg, checker, c, (rows, cols, pairs), 1.0, on_device=(True,))
+    assert want.dropped == 0 and 1 < want.count <= n // 4
+
+
 def test_one_varying_digit(gpu_pkg, checker, tiles):
     """x cells 0 .. 255, y and z fixed: only the lowest digit differs between keys and seven passes are skipped.  And 0 .. 255 in
     z alone: the digits in between are skipped, a high one is not."""
