@@ -188,6 +188,9 @@ def lib():
     L.apd_points_merged.argtypes = [C.c_void_p]
     L.apd_points_neighbour_counts.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p]
     L.apd_points_remove_sparse.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
+    L.apd_points_knn_mean_distances.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p]
+    L.apd_points_remove_statistical.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_float, C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
     L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
     L.apd_sort_tile_sizes.restype = None
     L.apd_points_destroy.argtypes = [C.c_void_p]
@@ -242,7 +245,9 @@ class Points:
     `merged` says whether an object is such a result: its view, pixel and sources are its representative's alone, its lists are
     those of visibility(), and average() refuses it.  neighbour_counts() counts every point's neighbours within a radius
     (apd_points_neighbour_counts) and remove_sparse() gives the points that have enough of them (apd_points_remove_sparse), with
-    everything else an object carries."""
+    everything else an object carries.  knn_mean_distances() gives every point's mean distance to its k nearest neighbours within
+    a radius (apd_points_knn_mean_distances) and remove_statistical() the points whose value is no outlier of the cloud's own
+    distribution of it (apd_points_remove_statistical), likewise."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
                ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
@@ -359,6 +364,50 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Points(out, self.device), int(removed.value)
+
+    def knn_mean_distances(self, radius, k, origin=None):
+        """apd_points_knn_mean_distances: per point the mean distance to its `k` (1 .. 64) nearest neighbours among the other points
+        within `radius` of it (contract C12: the neighbours of neighbour_counts, the k smallest squared distances, their square
+        roots summed in ascending order and divided by k, in binary32); +inf for a point with fewer than k neighbours, an isolated
+        point and a point outside the grid among them.  float32 [N]: a numpy array for host points, a torch tensor on their device
+        for device points.  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.knn_mean_distances: the points are closed")
+        if not 0 <= int(k) <= 0xFFFFFFFF:
+            raise ValueError("Points.knn_mean_distances: k = %r, not in 0 .. 2^32 - 1" % (k,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        nothing = (C.c_float * 1)()   # where an object without points gets its no scores: the library refuses NULL
+        if self.on_device:
+            import torch
+            mean = torch.empty((self.count,), dtype=torch.float32, device=torch.device("cuda", self.device))
+            torch.cuda.synchronize(mean.device)
+            address = mean.data_ptr() if self.count else C.addressof(nothing)
+        else:
+            mean = np.zeros(self.count, np.float32)
+            address = mean.ctypes.data if self.count else C.addressof(nothing)
+        rc = L.apd_points_knn_mean_distances(self._p, float(radius), org, int(k), C.c_void_p(address))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return mean
+
+    def remove_statistical(self, radius, k, std_ratio, origin=None):
+        """apd_points_remove_statistical: (Points, removed, threshold) -- the points whose knn_mean_distances(radius, k) value is
+        finite and at most threshold = mu + std_ratio * sigma, mu and sigma the mean and the sample standard deviation of the
+        finite values (binary64, summed in a fixed order: contract C12), in their order, with all seven arrays; `removed` is the
+        number left out.  std_ratio may be zero or negative.  The result carries what the result of remove_sparse carries.
+        Computed on these points' device; the result lives where they live."""
+        if not self._p:
+            raise ApdError("Points.remove_statistical: the points are closed")
+        if not 0 <= int(k) <= 0xFFFFFFFF:
+            raise ValueError("Points.remove_statistical: k = %r, not in 0 .. 2^32 - 1" % (k,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        out, removed, threshold = C.c_void_p(), C.c_longlong(0), C.c_double(0.0)
+        rc = L.apd_points_remove_statistical(self._p, float(radius), org, int(k), float(std_ratio), C.byref(out), C.byref(removed), C.byref(threshold))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device), int(removed.value), float(threshold.value)
 
     def __len__(self):
         return self.count

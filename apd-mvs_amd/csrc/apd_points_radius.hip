@@ -2,7 +2,8 @@
 // every point has within a radius, and the object without the points that have too few (arithmetic contract C11; the
 // relation: apd_radius_math.h).
 //
-// On the points' device, on its null stream, on top of the sort and the scan of apd_sort.h:
+// On the points' device, on its null stream, on top of the sort and the scan of apd_sort.h (the refusals and
+// steps 1 to 3: apd_points_search.h, shared with apd_points_knn.hip):
 //   1. k_voxel_keys, scan, k_voxel_compact (apd_points_grid.h): (key, input index) of the points inside the grid of cell size
 //      `radius`, in input order.
 //   2. sort_pairs: the points of a cell together, the cells in key order -- x fastest, so the three x-adjacent cells of a (y, z)
@@ -24,47 +25,20 @@
 
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_device.h"
-#include "apd_points_grid.h"
 #include "apd_points_host.h"
+#include "apd_points_search.h"
 #include "apd_radius_math.h"
-#include "apd_sort.h"
 
 namespace {
 
 using apd_fusion::PointArrays;
-using apd_points_grid::Grid;
 using apd_points_grid::grid_of;
-using apd_points_grid::k_voxel_compact;
-using apd_points_grid::k_voxel_keys;
 using apd_points_host::DeviceScope;
 using apd_points_host::Scratch;
-
-__global__ __launch_bounds__(256) void k_gather_xyz(const float *__restrict__ xyz, const uint32_t *__restrict__ member, size_t m,
-                                                     float *__restrict__ sorted_xyz)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < m) {
-        const size_t k = member[i];
-        sorted_xyz[3 * i] = xyz[3 * k];
-        sorted_xyz[3 * i + 1] = xyz[3 * k + 1];
-        sorted_xyz[3 * i + 2] = xyz[3 * k + 2];
-    }
-}
-
-// the first position in [from, m) whose key is not below `want`
-__device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ keys, uint32_t from, uint32_t m, uint64_t want)
-{
-    uint32_t lo = from, hi = m;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (keys[mid] < want) {
-            lo = mid + 1;
-        } else {
-            hi = mid;
-        }
-    }
-    return lo;
-}
+using apd_points_search::err;
+using apd_points_search::lower_bound;
+using apd_points_search::Search;
+using apd_points_search::Sorted;
 
 // Sorted element i < m: counts[member[i]] = min(neighbours, cap) by contract C11.  keys: ascending; xyz: in the same order.
 // The rows are visited in ascending key order, so a row's run starts at or after the end of the one before it.  The x range is
@@ -123,79 +97,18 @@ __global__ __launch_bounds__(256) void k_keep_flags(const uint32_t *__restrict__
     }
 }
 
-std::string &err() { return apd_fusion::g_fusion_error; }
-
-// One call of either entry point: its name, which starts every message, and the steps the two share
-struct Call {
-    const char *const who;
-    Grid grid = {{0.0f, 0.0f, 0.0f}, 0.0f};
-
-    int hip_failed(const char *expr, hipError_t e, const char *, int) const  // what HIP_TRY returns
-    {
-        return apd::set_error(err(), APD_ERR_HIP, "%s: %s: %s", who, expr, hipGetErrorString(e));
-    }
-
-    // What both calls refuse before any device is touched; fills `grid`
-    int check(apd_points_t p, const void *output, float radius, const float *origin3)
-    {
-        err().clear();
-        if (!p || !output) {
-            return apd::set_error(err(), APD_ERR_INVALID, "%s: null argument", who);
-        }
-        if (!(isfinite(radius) && radius > 0.0f)) {
-            return apd::set_error(err(), APD_ERR_INVALID, "%s: a radius of %g, not a positive finite number", who, (double)radius);
-        }
-        const float r2 = radius * radius;
-        if (!(isfinite(r2) && r2 > 0.0f)) {
-            return apd::set_error(err(), APD_ERR_INVALID, "%s: a radius of %g, whose square %g is not a positive finite number", who, (double)radius,
-                                  (double)r2);
-        }
-        grid.size = radius;
-        for (int a = 0; origin3 && a < 3; ++a) {
-            if (!isfinite(origin3[a])) {
-                return apd::set_error(err(), APD_ERR_INVALID, "%s: origin component %d is %g", who, a, (double)origin3[a]);
-            }
-            grid.origin[a] = origin3[a];
-        }
-        if (p->count >= (1LL << 31)) {
-            return apd::set_error(err(), APD_ERR_UNSUPPORTED, "%s: %lld points, 2^31 or more (the sort carries a 32-bit index)", who, p->count);
-        }
-        return APD_OK;
-    }
-
+// One call of either entry point: the refusals and the cell order of apd_points_search.h, and the steps the two share
+struct Call : Search {
     // counts[k] for the n > 0 points at xyz; both in device memory on the current device
     int count_neighbours(const float *xyz, size_t n, uint32_t cap, uint32_t *counts) const
     {
         Scratch scratch;
-        uint64_t *key = nullptr, *at = nullptr, *keys[2] = {nullptr, nullptr};
-        uint32_t *keep = nullptr, *index[2] = {nullptr, nullptr};
-        HIP_TRY(scratch.alloc(n * 8, &key));
-        HIP_TRY(scratch.alloc(n * 4, &keep));
-        HIP_TRY(scratch.alloc((n + 1) * 8, &at));
         HIP_TRY(hipMemsetAsync(counts, 0, n * 4, 0));  // the points outside the grid
-        hipLaunchKernelGGL(k_voxel_keys, grid_of(n), dim3(256), 0, 0, xyz, n, grid, key, keep);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(apd_sort::exclusive_scan(keep, at, n));
-        uint64_t inside = 0;
-        HIP_TRY(hipMemcpy(&inside, at + n, 8, hipMemcpyDeviceToHost));
-        const size_t m = (size_t)inside;
-        if (m == 0) {
-            return APD_OK;
+        Sorted s;
+        if (const int rc = sort_into_cells(scratch, xyz, n, s); rc != APD_OK || s.m == 0) {
+            return rc;
         }
-        for (int b = 0; b < 2; ++b) {
-            HIP_TRY(scratch.alloc(m * 8, &keys[b]));
-            HIP_TRY(scratch.alloc(m * 4, &index[b]));
-        }
-        hipLaunchKernelGGL(k_voxel_compact, grid_of(n), dim3(256), 0, 0, (const uint64_t *)key, (const uint32_t *)keep, (const uint64_t *)at, n, keys[0],
-                           index[0]);
-        HIP_TRY(hipGetLastError());
-        int side = 0;
-        HIP_TRY(apd_sort::sort_pairs(keys[0], keys[1], index[0], index[1], m, &side, nullptr));
-        float *sorted_xyz = nullptr;
-        HIP_TRY(scratch.alloc(m * 12, &sorted_xyz));
-        hipLaunchKernelGGL(k_gather_xyz, grid_of(m), dim3(256), 0, 0, xyz, (const uint32_t *)index[side], m, sorted_xyz);
-        hipLaunchKernelGGL(k_neighbour_count, grid_of(m), dim3(256), 0, 0, (const uint64_t *)keys[side], (const float *)sorted_xyz,
-                           (const uint32_t *)index[side], (uint32_t)m, grid.size * grid.size, cap, counts);
+        hipLaunchKernelGGL(k_neighbour_count, grid_of(s.m), dim3(256), 0, 0, s.keys, s.xyz, s.member, (uint32_t)s.m, grid.size * grid.size, cap, counts);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
         return APD_OK;
@@ -252,7 +165,7 @@ struct Call {
 
 extern "C" int apd_points_neighbour_counts(apd_points_t p, float radius, const float *origin3, unsigned cap, uint32_t *counts)
 {
-    Call call{"apd_points_neighbour_counts"};
+    Call call{{"apd_points_neighbour_counts"}};
     if (const int rc = call.check(p, counts, radius, origin3); rc != APD_OK) {
         return rc;
     }
@@ -266,7 +179,7 @@ extern "C" int apd_points_neighbour_counts(apd_points_t p, float radius, const f
 extern "C" int apd_points_remove_sparse(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, apd_points_t *out,
                                         long long *removed)
 {
-    Call call{"apd_points_remove_sparse"};
+    Call call{{"apd_points_remove_sparse"}};
     if (const int rc = call.check(p, out, radius, origin3); rc != APD_OK) {
         return rc;
     }

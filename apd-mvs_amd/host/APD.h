@@ -170,6 +170,10 @@ void SetFusionPlyMean(bool on);
 // additive: size > 0: <dense>/APD/APD.ply holds one point per occupied cell of a cubic grid of that cell size (apd_points_merge_voxels,
 // after the averaging if that is asked for too); an APD.ply.vis is then that of the merged points.  0: off
 void SetFusionPlyVoxel(float size);
+// additive: radius > 0: <dense>/APD/APD.ply holds the points whose mean distance to their k nearest neighbours within that radius is
+// at most mean + std_ratio * deviation of the cloud's (apd_points_remove_statistical, after the averaging and the merge and before
+// the radius filter if those are asked for too); an APD.ply.vis is then that of the points kept.  0: off
+void SetFusionPlyStatFilter(float radius, unsigned k, float std_ratio);
 // additive: radius > 0: <dense>/APD/APD.ply holds the points that have at least min_neighbours other points within that radius
 // (apd_points_remove_sparse, after the averaging and the merge if those are asked for too); an APD.ply.vis is then that of the
 // points kept.  0: off

@@ -3,7 +3,8 @@
 //   APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion]
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
-//       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-radius-filter RADIUS,MIN] [--filtered-maps]
+//       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN]
+//       [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -24,6 +25,12 @@
 // (apd_points_merge_voxels: the mean of the cell's points, the union of their lists) and, with --ply-vis, APD.ply.vis those
 // lists; with --ply-mean the points are averaged first.  With every --fusion; the cells and the dropped points (non-finite, or
 // 2^20 cells from the origin) are printed.  SIZE must be a positive finite number, or the usage line is all that happens.
+// --ply-stat-filter RADIUS,K,RATIO: APD.ply holds the points whose mean distance to their K nearest neighbours within RADIUS is at
+// most mu + RATIO * sigma of the cloud's own distribution of that value (apd_points_remove_statistical: the statistical outlier
+// filter; a point with fewer than K neighbours within RADIUS goes) and, with --ply-vis, APD.ply.vis their lists; applied after
+// --ply-mean and --ply-voxel and before --ply-radius-filter.  With every --fusion; the number removed and the threshold are
+// printed.  RADIUS as for --ply-radius-filter, K 1 .. 64, RATIO a finite number (zero and negative allowed), or the usage line is
+// all that happens.
 // --ply-radius-filter RADIUS,MIN: APD.ply holds the points that have at least MIN other points within RADIUS
 // (apd_points_remove_sparse: the radius outlier filter, on the grid of cell size RADIUS at the origin) and, with --ply-vis,
 // APD.ply.vis their lists; applied last, after --ply-mean and --ply-voxel.  With every --fusion; the number removed is printed.
@@ -137,6 +144,23 @@ bool ParseOptions(int argc, char **argv, Options &o)
                 fprintf(stderr, "bad value '%s' of %s: a positive number\n", text, a.c_str());
                 return false;
             }
+        } else if (a == "--ply-stat-filter") {
+            const std::string all = i + 1 < argc ? argv[++i] : "";
+            const size_t c1 = all.find(','), c2 = c1 == std::string::npos ? c1 : all.find(',', c1 + 1);
+            const std::string count = c2 == std::string::npos ? "" : all.substr(c1 + 1, c2 - c1 - 1), ratio = c2 == std::string::npos ? "" : all.substr(c2 + 1);
+            char *end = nullptr;
+            const unsigned long long k = strtoull(count.c_str(), &end, 10);
+            const bool digits = !count.empty() && count.size() <= 9 && count.find_first_not_of("0123456789") == std::string::npos && k >= 1 && k <= 64;
+            const float t = strtof(ratio.c_str(), &end);
+            const bool number = !ratio.empty() && end != ratio.c_str() && *end == '\0' && t >= -3.402823466e+38f && t <= 3.402823466e+38f;
+            float r = 0.0f;
+            if (!digits || !number || !real(all.substr(0, c1).c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
+                fprintf(stderr, "bad value '%s' of %s: RADIUS,K,RATIO, a positive number, a count of 1 .. 64 and a number\n", all.c_str(), a.c_str());
+                return false;
+            }
+            o.ply_stat_radius = r;
+            o.ply_stat_k = (unsigned)k;
+            o.ply_stat_ratio = t;
         } else if (a == "--ply-radius-filter") {
             const std::string both = i + 1 < argc ? argv[++i] : "";
             const size_t comma = both.find(',');
@@ -362,10 +386,11 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-radius-filter RADIUS,MIN] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
+                        "  --ply-stat-filter RADIUS,K,RATIO: APD.ply (and APD.ply.vis) without the points whose mean distance to their K nearest neighbours within RADIUS is above mean + RATIO * deviation of the cloud's, after --ply-mean and --ply-voxel, before --ply-radius-filter.\n"
                         "  --ply-radius-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points that have fewer than MIN other points within RADIUS, after --ply-mean and --ply-voxel.\n");
         return EXIT_FAILURE;
     }
@@ -384,6 +409,7 @@ int main(int argc, char **argv)
     SetFusionPlyVis(opt.ply_vis);
     SetFusionPlyMean(opt.ply_mean);
     SetFusionPlyVoxel(opt.ply_voxel);
+    SetFusionPlyStatFilter(opt.ply_stat_radius, opt.ply_stat_k, opt.ply_stat_ratio);
     SetFusionPlyRadiusFilter(opt.ply_radius, opt.ply_radius_min);
 
     std::vector<Problem> problems;

@@ -38,6 +38,9 @@ struct Options {
     bool ply_vis = false;                 // --ply-vis: APD/APD.ply.vis beside APD.ply (apd_points_write_vis)
     bool ply_mean = false;                // --ply-mean: APD.ply (and APD.ply.vis) of the points averaged over their agreeing views (apd_points_average)
     float ply_voxel = 0.0f;               // --ply-voxel SIZE: APD.ply (and APD.ply.vis) of the points merged per cell of that size (apd_points_merge_voxels); 0: off
+    float ply_stat_radius = 0.0f;         // --ply-stat-filter RADIUS,K,RATIO: APD.ply (and APD.ply.vis) of the points whose mean distance to their K
+    unsigned ply_stat_k = 0;              // nearest neighbours within RADIUS is at most mean + RATIO * deviation (apd_points_remove_statistical), after
+    float ply_stat_ratio = 0.0f;          // --ply-mean and --ply-voxel, before --ply-radius-filter; radius 0: off
     float ply_radius = 0.0f;              // --ply-radius-filter RADIUS,MIN: APD.ply (and APD.ply.vis) of the points with at least MIN others within
     unsigned ply_radius_min = 0;          // RADIUS (apd_points_remove_sparse), after --ply-mean and --ply-voxel; radius 0: off
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)

@@ -526,6 +526,36 @@ int apd_points_merged(apd_points_t p);   /* 1 for a result of apd_points_merge_v
 int apd_points_neighbour_counts(apd_points_t p, float radius, const float *origin3, unsigned cap, uint32_t *counts);
 int apd_points_remove_sparse(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, apd_points_t *out,
                              long long *removed);
+/* The mean distance to the k nearest neighbours, and the removal of the points whose value is an outlier of the cloud's own
+ * distribution of it: the statistical outlier filter that is run between fusion and meshing (PCL's StatisticalOutlierRemoval,
+ * Open3D's remove_statistical_outlier), here on the points object, so that sources, support, view / pixel and the visibility lists
+ * survive it.  IEEE operations in the order given (contract C12; csrc/apd_knn_math.h).
+ *   Neighbours.  Those of apd_points_neighbour_counts, on the grid of cell size `radius` at origin3 (NULL: 0, 0, 0): the search is
+ *   bounded by the radius, which keeps it exact and bounds the work of an isolated point.
+ *   Score.  mean[i] of a point with at least k neighbours: the k smallest (dx * dx + dy * dy) + dz * dz over its neighbours,
+ *   sqrtf of each, summed in ascending order in binary32 from 0, divided by (float)k.  With fewer than k neighbours -- an isolated
+ *   point, a point outside the grid --: +inf.  k is 1 .. 64.
+ *   Threshold.  Over the points with a finite score, in input order, in binary64: n_f their number, S1 the sum of the scores and
+ *   S2 of their squares, each summed in chunks of 256 consecutive input indices (a chunk sequentially from 0, then the chunk
+ *   sums sequentially); mu = S1 / n_f, var = (S2 - S1 * S1 / n_f) / (n_f - 1) clamped below at 0 (0 for n_f < 2),
+ *   T = mu + (double)std_ratio * sqrt(var); n_f == 0: T = 0.
+ *   Kept by apd_points_remove_statistical: the points with a finite score and (double)score <= T, in p's order.
+ * apd_points_knn_mean_distances: `mean` has apd_points_count(p) entries, host memory for host-resident points, device memory on
+ * p's device for device-resident ones.
+ * apd_points_remove_statistical: *out is a new object with the kept points, every array copied, and carries what the result of
+ * apd_points_remove_sparse carries (source lists and view sizes; a merged object gives a merged object with the kept points'
+ * lists); *removed (may be NULL) the number of points left out, *threshold (may be NULL) T.  std_ratio may be zero or negative.
+ * Both are computed on p's device, on its null stream, whatever memory p is in; there is no host implementation.  The scores of
+ * device-resident points never leave the device for the removal: n / 256 chunk sums do.  An object without points gives no
+ * scores, or an object without points and T = 0, with no device touched.  The work is that of apd_points_neighbour_counts
+ * without a cap plus the selection: k LDS reads for every candidate that displaces one of the k held.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_knn_mean_distances: ..." or
+ * "apd_points_remove_statistical: ..." (apd_fusion_last_error): what apd_points_neighbour_counts refuses, a k outside 1 .. 64, a
+ * std_ratio that is not finite; APD_ERR_UNSUPPORTED for 2^31 or more points.  *out, *removed and *threshold are untouched when
+ * the call fails. */
+int apd_points_knn_mean_distances(apd_points_t p, float radius, const float *origin3, unsigned k, float *mean);
+int apd_points_remove_statistical(apd_points_t p, float radius, const float *origin3, unsigned k, float std_ratio,
+                                  apd_points_t *out, long long *removed, double *threshold);
 /* The tile sizes of the device sort under apd_points_merge_voxels (csrc/apd_sort.h): elements per workgroup of a sort pass and
  * entries per workgroup of its scan.  For tests that choose sizes around them. */
 void apd_sort_tile_sizes(int *sort_tile, int *scan_tile);
