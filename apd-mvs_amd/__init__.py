@@ -191,6 +191,9 @@ def lib():
     L.apd_points_knn_mean_distances.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p]
     L.apd_points_remove_statistical.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_float, C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
+    L.apd_points_components.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+    L.apd_points_remove_small_components.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
     L.apd_sort_tile_sizes.restype = None
     L.apd_points_destroy.argtypes = [C.c_void_p]
@@ -247,7 +250,9 @@ class Points:
     (apd_points_neighbour_counts) and remove_sparse() gives the points that have enough of them (apd_points_remove_sparse), with
     everything else an object carries.  knn_mean_distances() gives every point's mean distance to its k nearest neighbours within
     a radius (apd_points_knn_mean_distances) and remove_statistical() the points whose value is no outlier of the cloud's own
-    distribution of it (apd_points_remove_statistical), likewise."""
+    distribution of it (apd_points_remove_statistical), likewise.  components() labels the connected components of the points within
+    a radius of each other (apd_points_components) and remove_small_components() gives the points of the components that are large
+    enough (apd_points_remove_small_components), likewise."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
                ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
@@ -408,6 +413,49 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Points(out, self.device), int(removed.value), float(threshold.value)
+
+    def components(self, radius, origin=None):
+        """apd_points_components: (label, size, components) -- the connected components of the graph in which two points share an edge
+        when they are neighbours within `radius` (contract C13: the relation of neighbour_counts, on the grid of cell size `radius`
+        with a corner at `origin`, 0, 0, 0 by default).  label[i] is the smallest index among the points of i's component, size[i]
+        their number, `components` the number of components; a point with a non-finite coordinate or more than 2^20 cells from
+        the origin is a component of its own.  label and size are uint32 [N]: numpy arrays for host points; for device points
+        torch tensors on their device holding the same bit patterns as int32, like `sources`.  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.components: the points are closed")
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        nothing = (C.c_uint32 * 1)()   # where an object without points gets its no labels: the library refuses NULL
+        if self.on_device:
+            import torch
+            label, size = (torch.empty((self.count,), dtype=torch.int32, device=torch.device("cuda", self.device)) for _ in range(2))
+            torch.cuda.synchronize(label.device)
+            addresses = [a.data_ptr() if self.count else C.addressof(nothing) for a in (label, size)]
+        else:
+            label, size = np.zeros(self.count, np.uint32), np.zeros(self.count, np.uint32)
+            addresses = [a.ctypes.data if self.count else C.addressof(nothing) for a in (label, size)]
+        components = C.c_longlong(0)
+        rc = L.apd_points_components(self._p, float(radius), org, C.c_void_p(addresses[0]), C.c_void_p(addresses[1]), C.byref(components))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return label, size, int(components.value)
+
+    def remove_small_components(self, radius, min_size, origin=None):
+        """apd_points_remove_small_components: (Points, removed, components) -- the points whose connected component (the relation of
+        components()) has at least `min_size` points, in their order, with all seven arrays; `removed` is the number left out,
+        `components` the number of components of these points.  min_size 0 and 1 keep every point.  The result carries what the
+        result of remove_sparse carries.  Computed on these points' device; the result lives where they live."""
+        if not self._p:
+            raise ApdError("Points.remove_small_components: the points are closed")
+        if not 0 <= int(min_size) <= 0xFFFFFFFF:
+            raise ValueError("Points.remove_small_components: a minimum of %r points, not in 0 .. 2^32 - 1" % (min_size,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        out, removed, components = C.c_void_p(), C.c_longlong(0), C.c_longlong(0)
+        rc = L.apd_points_remove_small_components(self._p, float(radius), org, int(min_size), C.byref(out), C.byref(removed), C.byref(components))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device), int(removed.value), int(components.value)
 
     def __len__(self):
         return self.count

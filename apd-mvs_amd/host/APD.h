@@ -178,6 +178,10 @@ void SetFusionPlyStatFilter(float radius, unsigned k, float std_ratio);
 // (apd_points_remove_sparse, after the averaging and the merge if those are asked for too); an APD.ply.vis is then that of the
 // points kept.  0: off
 void SetFusionPlyRadiusFilter(float radius, unsigned min_neighbours);
+// additive: radius > 0: <dense>/APD/APD.ply holds the points whose connected component -- two points are joined when they are within
+// that radius of each other -- has at least min_size points (apd_points_remove_small_components, after everything above that is
+// asked for too); an APD.ply.vis is then that of the points kept.  0: off
+void SetFusionPlyComponentFilter(float radius, unsigned min_size);
 
 class APD {
 public:

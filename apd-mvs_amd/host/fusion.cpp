@@ -36,9 +36,16 @@ unsigned g_fusion_ply_stat_k = 0;
 float g_fusion_ply_stat_ratio = 0.0f;
 float g_fusion_ply_radius = 0.0f;       // SetFusionPlyRadiusFilter; 0: off
 unsigned g_fusion_ply_radius_min = 0;
+float g_fusion_ply_component_radius = 0.0f;  // SetFusionPlyComponentFilter; 0: off
+unsigned g_fusion_ply_component_min = 0;
 
-// --ply-mean, --ply-voxel, --ply-stat-filter or --ply-radius-filter: APD.ply is written from the points after the fusion, not by it
-bool ply_from_points() { return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f; }
+// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter or --ply-component-filter: APD.ply is written from the points after
+// the fusion, not by it
+bool ply_from_points()
+{
+    return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f ||
+           g_fusion_ply_component_radius > 0.0f;
+}
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
 apd_fusion_options &fusion_options()
@@ -71,7 +78,7 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
                       const int *rows, const int *cols, int maps_on_device, const path &ply_path);
 
 // Device fusion through the C ABI (host pointers).  options: nullptr = those of SetFusionOptions; ply_path may be null when
-// points is not.  mean_path (--ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter; points must be given): the fusion writes no file, *points
+// points is not.  mean_path (--ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter; points must be given): the fusion writes no file, *points
 // become the averaged and / or merged and / or filtered points and their PLY goes to *mean_path.
 long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const char *ply_path,
                         const apd_fusion_options *options = nullptr, apd_points_t *points = nullptr, const path *mean_path = nullptr)
@@ -141,13 +148,20 @@ void SetFusionPlyRadiusFilter(float radius, unsigned min_neighbours)
     g_fusion_ply_radius_min = min_neighbours;
 }
 
+void SetFusionPlyComponentFilter(float radius, unsigned min_size)
+{
+    g_fusion_ply_component_radius = radius;
+    g_fusion_ply_component_min = min_size;
+}
+
 namespace {
 
 // --ply-mean: replaces the points of a fusion by their means over the agreeing views (apd_points_average with the fusion's own
 // cameras and maps); --ply-voxel: replaces them -- the means, with both -- by one point per cell (apd_points_merge_voxels) and
 // prints the cells and the dropped points; --ply-stat-filter: replaces what these left by the points whose k-nearest mean distance
 // is no outlier (apd_points_remove_statistical) and prints how many went and the threshold; --ply-radius-filter: replaces what these left by the points with enough neighbours
-// (apd_points_remove_sparse) and prints how many went.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
+// (apd_points_remove_sparse) and prints how many went; --ply-component-filter: replaces what these left by the points of the connected
+// components that are large enough (apd_points_remove_small_components) and prints the components and how many points went.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
 void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
                       const int *rows, const int *cols, int maps_on_device, const path &ply_path)
 {
@@ -194,6 +208,17 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
         if (st == APD_OK) {
             std::cout << "Removed " << removed << " of " << apd_points_count(points) << " points with fewer than " << g_fusion_ply_radius_min
                       << " neighbours within " << g_fusion_ply_radius << std::endl;
+            apd_points_destroy(points);
+            points = kept;
+        }
+    }
+    if (st == APD_OK && g_fusion_ply_component_radius > 0.0f) {
+        apd_points_t kept = nullptr;
+        long long removed = 0, components = 0;
+        st = apd_points_remove_small_components(points, g_fusion_ply_component_radius, nullptr, g_fusion_ply_component_min, &kept, &removed, &components);
+        if (st == APD_OK) {
+            std::cout << "Removed " << removed << " of " << apd_points_count(points) << " points in connected components of fewer than "
+                      << g_fusion_ply_component_min << " points, of " << components << " components within " << g_fusion_ply_component_radius << std::endl;
             apd_points_destroy(points);
             points = kept;
         }
@@ -375,7 +400,7 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     if (g_fusion_ply_vis) {
         write_vis_beside(ply_path, points);
     } else {
-        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter or --ply-radius-filter alone
+        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter or --ply-component-filter alone
     }
 }
 
@@ -579,7 +604,7 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
     if (g_fusion_ply_vis) {
         write_vis_beside(ply_path, points);
     } else {
-        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter or --ply-radius-filter alone
+        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter or --ply-component-filter alone
     }
 }
 

@@ -556,6 +556,35 @@ int apd_points_remove_sparse(apd_points_t p, float radius, const float *origin3,
 int apd_points_knn_mean_distances(apd_points_t p, float radius, const float *origin3, unsigned k, float *mean);
 int apd_points_remove_statistical(apd_points_t p, float radius, const float *origin3, unsigned k, float std_ratio,
                                   apd_points_t *out, long long *removed, double *threshold);
+/* The connected components of the points within a radius of each other, and the removal of the small ones: the filter that is run
+ * after the radius and the statistical filter (PCL's EuclideanClusterExtraction, Open3D's cluster_dbscan and a size cut, MeshLab's
+ * "remove isolated pieces"), here on the points object, so that sources, support, view / pixel and the visibility lists survive it.
+ * A detached clump of 200 points passes both other filters, which judge a point by its own neighbourhood; this one judges the clump.
+ * Integers only (contract C13; csrc/apd_points_clusters.hip).
+ *   Graph.  The vertices are the points of p.  Points i and j share an edge exactly when they are neighbours by the relation of
+ *   apd_points_neighbour_counts, on the grid of cell size `radius` at origin3 (NULL: 0, 0, 0); the relation is symmetric.  A point
+ *   outside the grid has no edges.
+ *   Component.  A connected component of that graph; a point outside the grid is a component of its own.
+ *   label[i] is the smallest index among the points of i's component, size[i] their number (below 2^31).  Both are functions of
+ *   the input alone: no visiting order, launch shape or race outcome shows in them.
+ *   Kept by apd_points_remove_small_components: the points with size[i] >= min_size, in p's order.  min_size 0 and 1 keep every
+ *   point, those outside the grid too; from 2 on a point outside the grid goes.
+ * apd_points_components: `label` and `size` have apd_points_count(p) entries each, host memory for host-resident points, device
+ * memory on p's device for device-resident ones; `size` may be NULL, `label` may not.  *components (may be NULL) receives the
+ * number of components, which is the number of i with label[i] == i.
+ * apd_points_remove_small_components: *out is a new object with the kept points, every array copied, and carries what the result
+ * of apd_points_remove_sparse carries (source lists and view sizes; a merged object gives a merged object with the kept points'
+ * lists); *removed (may be NULL) the number of points left out, *components (may be NULL) the number of components of p.  With
+ * min_size <= 1 and components == NULL nothing is labelled.
+ * Both are computed on p's device, on its null stream, whatever memory p is in; there is no host implementation.  An object
+ * without points gives no labels, or an object without points, and *components = 0, with no device touched.  The work is half
+ * the distance tests of apd_points_neighbour_counts without a cap, plus a concurrent union-find over the edges found.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_components: ..." or
+ * "apd_points_remove_small_components: ..." (apd_fusion_last_error): what apd_points_neighbour_counts refuses;
+ * APD_ERR_UNSUPPORTED for 2^31 or more points.  *out, *removed and *components are untouched when the call fails. */
+int apd_points_components(apd_points_t p, float radius, const float *origin3, uint32_t *label, uint32_t *size, long long *components);
+int apd_points_remove_small_components(apd_points_t p, float radius, const float *origin3, unsigned min_size, apd_points_t *out,
+                                       long long *removed, long long *components);
 /* The tile sizes of the device sort under apd_points_merge_voxels (csrc/apd_sort.h): elements per workgroup of a sort pass and
  * entries per workgroup of its scan.  For tests that choose sizes around them. */
 void apd_sort_tile_sizes(int *sort_tile, int *scan_tile);
