@@ -194,6 +194,9 @@ def lib():
     L.apd_points_components.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
     L.apd_points_remove_small_components.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.POINTER(C.c_void_p),
                                                      C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.apd_points_estimate_normals.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p, C.c_void_p]
+    L.apd_points_with_estimated_normals.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_longlong)]
     L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
     L.apd_sort_tile_sizes.restype = None
     L.apd_points_destroy.argtypes = [C.c_void_p]
@@ -252,7 +255,9 @@ class Points:
     a radius (apd_points_knn_mean_distances) and remove_statistical() the points whose value is no outlier of the cloud's own
     distribution of it (apd_points_remove_statistical), likewise.  components() labels the connected components of the points within
     a radius of each other (apd_points_components) and remove_small_components() gives the points of the components that are large
-    enough (apd_points_remove_small_components), likewise."""
+    enough (apd_points_remove_small_components), likewise.  estimate_normals() gives every point's normal and surface variation
+    from its neighbourhood within a radius (apd_points_estimate_normals) and with_estimated_normals() these points with those
+    normals in place of the stored ones (apd_points_with_estimated_normals), likewise."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
                ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
@@ -456,6 +461,51 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Points(out, self.device), int(removed.value), int(components.value)
+
+    def estimate_normals(self, radius, min_neighbours, origin=None):
+        """apd_points_estimate_normals: (normals float32 [N, 3], variation float32 [N]) -- for a point with at least
+        `min_neighbours` (2 .. 2^31 - 1) other points within `radius` (the relation of neighbour_counts) the direction of least
+        variance of the point and those neighbours (contract C14: binary64 moment sums in cell order, a cyclic Jacobi eigen-solve),
+        signed like the stored normal, and the smallest eigenvalue's share of the variance, 0 on a plane and at most 1/3; for any
+        other point, one outside the grid among them, the stored normal and +inf.  numpy arrays for host points, torch tensors on
+        their device for device points.  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.estimate_normals: the points are closed")
+        if not 0 <= int(min_neighbours) <= 0xFFFFFFFF:
+            raise ValueError("Points.estimate_normals: a minimum of %r neighbours, not in 0 .. 2^32 - 1" % (min_neighbours,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        nothing = (C.c_float * 3)()   # where an object without points gets its no results: the library refuses NULL for both
+        if self.on_device:
+            import torch
+            normals = torch.empty((self.count, 3), dtype=torch.float32, device=torch.device("cuda", self.device))
+            variation = torch.empty((self.count,), dtype=torch.float32, device=torch.device("cuda", self.device))
+            torch.cuda.synchronize(normals.device)
+            addresses = [a.data_ptr() if self.count else C.addressof(nothing) for a in (normals, variation)]
+        else:
+            normals, variation = np.zeros((self.count, 3), np.float32), np.zeros(self.count, np.float32)
+            addresses = [a.ctypes.data if self.count else C.addressof(nothing) for a in (normals, variation)]
+        rc = L.apd_points_estimate_normals(self._p, float(radius), org, int(min_neighbours), C.c_void_p(addresses[0]), C.c_void_p(addresses[1]))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return normals, variation
+
+    def with_estimated_normals(self, radius, min_neighbours, origin=None):
+        """apd_points_with_estimated_normals: (Points, estimated) -- these points in their order with `normal` replaced by the
+        normals of estimate_normals(radius, min_neighbours) and every other array and the lists as they are; `estimated` is the
+        number of points that got an estimate, the others keep their stored normal.  A merged object gives a merged object.
+        Computed on these points' device; the result lives where they live."""
+        if not self._p:
+            raise ApdError("Points.with_estimated_normals: the points are closed")
+        if not 0 <= int(min_neighbours) <= 0xFFFFFFFF:
+            raise ValueError("Points.with_estimated_normals: a minimum of %r neighbours, not in 0 .. 2^32 - 1" % (min_neighbours,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        out, estimated = C.c_void_p(), C.c_longlong(0)
+        rc = L.apd_points_with_estimated_normals(self._p, float(radius), org, int(min_neighbours), C.byref(out), C.byref(estimated))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device), int(estimated.value)
 
     def __len__(self):
         return self.count

@@ -38,13 +38,15 @@ float g_fusion_ply_radius = 0.0f;       // SetFusionPlyRadiusFilter; 0: off
 unsigned g_fusion_ply_radius_min = 0;
 float g_fusion_ply_component_radius = 0.0f;  // SetFusionPlyComponentFilter; 0: off
 unsigned g_fusion_ply_component_min = 0;
+float g_fusion_ply_normals_radius = 0.0f;  // SetFusionPlyEstimateNormals; 0: off
+unsigned g_fusion_ply_normals_min = 0;
 
-// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter or --ply-component-filter: APD.ply is written from the points after
-// the fusion, not by it
+// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter or --ply-estimate-normals: APD.ply is written
+// from the points after the fusion, not by it
 bool ply_from_points()
 {
     return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f ||
-           g_fusion_ply_component_radius > 0.0f;
+           g_fusion_ply_component_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f;
 }
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
@@ -78,7 +80,7 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
                       const int *rows, const int *cols, int maps_on_device, const path &ply_path);
 
 // Device fusion through the C ABI (host pointers).  options: nullptr = those of SetFusionOptions; ply_path may be null when
-// points is not.  mean_path (--ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter; points must be given): the fusion writes no file, *points
+// points is not.  mean_path (--ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-estimate-normals; points must be given): the fusion writes no file, *points
 // become the averaged and / or merged and / or filtered points and their PLY goes to *mean_path.
 long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const char *ply_path,
                         const apd_fusion_options *options = nullptr, apd_points_t *points = nullptr, const path *mean_path = nullptr)
@@ -154,6 +156,12 @@ void SetFusionPlyComponentFilter(float radius, unsigned min_size)
     g_fusion_ply_component_min = min_size;
 }
 
+void SetFusionPlyEstimateNormals(float radius, unsigned min_neighbours)
+{
+    g_fusion_ply_normals_radius = radius;
+    g_fusion_ply_normals_min = min_neighbours;
+}
+
 namespace {
 
 // --ply-mean: replaces the points of a fusion by their means over the agreeing views (apd_points_average with the fusion's own
@@ -161,7 +169,9 @@ namespace {
 // prints the cells and the dropped points; --ply-stat-filter: replaces what these left by the points whose k-nearest mean distance
 // is no outlier (apd_points_remove_statistical) and prints how many went and the threshold; --ply-radius-filter: replaces what these left by the points with enough neighbours
 // (apd_points_remove_sparse) and prints how many went; --ply-component-filter: replaces what these left by the points of the connected
-// components that are large enough (apd_points_remove_small_components) and prints the components and how many points went.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
+// components that are large enough (apd_points_remove_small_components) and prints the components and how many points went;
+// --ply-estimate-normals: replaces the normals of what these left by those of each point's neighbourhood
+// (apd_points_with_estimated_normals) and prints how many points got one.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
 void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
                       const int *rows, const int *cols, int maps_on_device, const path &ply_path)
 {
@@ -219,6 +229,17 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
         if (st == APD_OK) {
             std::cout << "Removed " << removed << " of " << apd_points_count(points) << " points in connected components of fewer than "
                       << g_fusion_ply_component_min << " points, of " << components << " components within " << g_fusion_ply_component_radius << std::endl;
+            apd_points_destroy(points);
+            points = kept;
+        }
+    }
+    if (st == APD_OK && g_fusion_ply_normals_radius > 0.0f) {
+        apd_points_t kept = nullptr;
+        long long estimated = 0;
+        st = apd_points_with_estimated_normals(points, g_fusion_ply_normals_radius, nullptr, g_fusion_ply_normals_min, &kept, &estimated);
+        if (st == APD_OK) {
+            std::cout << "Estimated the normals of " << estimated << " of " << apd_points_count(points) << " points from at least "
+                      << g_fusion_ply_normals_min << " neighbours within " << g_fusion_ply_normals_radius << std::endl;
             apd_points_destroy(points);
             points = kept;
         }
@@ -400,7 +421,7 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     if (g_fusion_ply_vis) {
         write_vis_beside(ply_path, points);
     } else {
-        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter or --ply-component-filter alone
+        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter or --ply-estimate-normals alone
     }
 }
 
@@ -604,7 +625,7 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
     if (g_fusion_ply_vis) {
         write_vis_beside(ply_path, points);
     } else {
-        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter or --ply-component-filter alone
+        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter or --ply-estimate-normals alone
     }
 }
 

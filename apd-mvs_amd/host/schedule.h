@@ -45,6 +45,8 @@ struct Options {
     unsigned ply_radius_min = 0;          // RADIUS (apd_points_remove_sparse), after --ply-mean and --ply-voxel; radius 0: off
     float ply_component_radius = 0.0f;    // --ply-component-filter RADIUS,MIN: APD.ply (and APD.ply.vis) of the points whose connected component within
     unsigned ply_component_min = 0;       // RADIUS has at least MIN points (apd_points_remove_small_components), after --ply-radius-filter; radius 0: off
+    float ply_normals_radius = 0.0f;      // --ply-estimate-normals RADIUS,MIN: the points of APD.ply with normals estimated from the neighbourhood within
+    unsigned ply_normals_min = 0;         // RADIUS of each point that has at least MIN others there (apd_points_with_estimated_normals), last; radius 0: off
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)

@@ -585,6 +585,37 @@ int apd_points_remove_statistical(apd_points_t p, float radius, const float *ori
 int apd_points_components(apd_points_t p, float radius, const float *origin3, uint32_t *label, uint32_t *size, long long *components);
 int apd_points_remove_small_components(apd_points_t p, float radius, const float *origin3, unsigned min_size, apd_points_t *out,
                                        long long *removed, long long *components);
+/* Normals and surface variation from each point's neighbourhood: the step a Poisson mesher depends on (PCL's NormalEstimation,
+ * Open3D's estimate_normals), here on the points object, so that sources, support, view / pixel and the visibility lists survive
+ * it.  The stored normal -- the PatchMatch normal of one pixel, or a mean of such -- only chooses the sign.  IEEE operations in
+ * the order given (contract C14; csrc/apd_normal_math.h).
+ *   Neighbours.  Those of apd_points_neighbour_counts, on the grid of cell size `radius` at origin3 (NULL: 0, 0, 0).
+ *   Estimate.  A point with at least min_neighbours neighbours (itself not counted; min_neighbours is 2 .. 2^31 - 1): over the
+ *   point and its neighbours in ascending (cell, index) order, with d = Q - P in binary32, the binary64 sums n, of d and of the
+ *   six products d_a * d_b; the covariance C_ab = S_ab / n - (S_a / n) * (S_b / n); its eigenvalues l0 <= l1 <= l2 (clamped
+ *   below at 0) and vectors by cyclic Jacobi rotations in binary64, in the order (0,1), (0,2), (1,2), at most 5 sweeps.  The
+ *   normal is the eigenvector of l0 (the lowest column among equal eigenvalues), renormalised, flipped when its binary64 dot
+ *   product with the stored normal is < 0; when that product is neither < 0 nor > 0 (a zero, NaN or orthogonal stored normal)
+ *   its first non-zero component is made positive; converted to binary32 last.  variation = (float)(l0 / (l0 + l1 + l2)), the
+ *   "surface variation", between 0 (a plane) and 1/3; 0 when the sum is 0 (coincident points).
+ *   No estimate.  A point with fewer neighbours and a point outside the grid: its normal is the stored normal, copied, and its
+ *   variation +inf.  A result is never NaN unless the stored normal was.
+ * apd_points_estimate_normals: normal3 takes 3 * apd_points_count(p) floats and variation apd_points_count(p), host memory for
+ * host-resident points, device memory on p's device for device-resident ones; either may be NULL, not both.
+ * apd_points_with_estimated_normals: *out is a new object with p's points in p's order, every array copied and `normal`
+ * replaced; it lives where p lives, is merged when p is and then carries p's lists; *estimated (may be NULL) is the number of
+ * points that got an estimate.  p is left as it is.
+ * Both are computed on p's device, on its null stream, whatever memory p is in; there is no host implementation.  An object
+ * without points gives no results, or an object without points and *estimated = 0, with no device touched.  The work is that of
+ * apd_points_neighbour_counts without a cap, with sixteen binary64 operations per neighbour, plus one eigen-solve per point.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_estimate_normals: ..." or
+ * "apd_points_with_estimated_normals: ..." (apd_fusion_last_error): what apd_points_neighbour_counts refuses, both of normal3
+ * and variation NULL, a min_neighbours outside 2 .. 2^31 - 1; APD_ERR_UNSUPPORTED for 2^31 or more points.  *out and *estimated
+ * are untouched when the call fails. */
+int apd_points_estimate_normals(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, float *normal3,
+                                float *variation);
+int apd_points_with_estimated_normals(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, apd_points_t *out,
+                                      long long *estimated);
 /* The tile sizes of the device sort under apd_points_merge_voxels (csrc/apd_sort.h): elements per workgroup of a sort pass and
  * entries per workgroup of its scan.  For tests that choose sizes around them. */
 void apd_sort_tile_sizes(int *sort_tile, int *scan_tile);
