@@ -666,9 +666,9 @@ class Handle:
 
     def reset(self, params):
         """Re-arms the handle for another (view, pass) of the same size (apd_reset): same initial state as a new one."""
+        _check(lib().apd_reset(self._h, C.byref(params)))   # a refused reset leaves the handle, and this object, as they were
         self.params = params
         self._keep = []
-        _check(lib().apd_reset(self._h, C.byref(params)))
 
     def __del__(self):
         try:

@@ -449,6 +449,14 @@ static bool frame_area_supported(int width, int height)
     return ((uint64_t)width + 1u) * ((uint64_t)height + 1u) * 16u < (1ull << 32);
 }
 
+// K3 numbers its rays slot = direction * 4 + rotation for short2 strong_pts[32] and a 32-bit mask (k3_gen_neighbours): a
+// rotate_time above 4 would write past both.  The reference's schedule produces 1, 2 and 4 ("max is 4 from [1, 2, 4]",
+// APD.cu:1790); zero or less leaves K3 without a ray and the angle constants without a divisor.
+static bool rotate_time_supported(int rotate_time)
+{
+    return rotate_time >= 1 && rotate_time <= 4;
+}
+
 int apd_create(apd_handle *out, int device, int width, int height, const apd_params *params)
 {
     if (!out || !params || width <= 0 || height <= 0) {
@@ -463,6 +471,9 @@ int apd_create(apd_handle *out, int device, int width, int height, const apd_par
     if (params->strong_radius != 5 || params->strong_increment != 2 || params->weak_radius != 5 || params->weak_increment != 5) {
         // the reference never changes these (main.h:84-87); the kernels are specialised for them
         return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_create: only strong 5/2 and weak 5/5 patch geometry is built");
+    }
+    if (!rotate_time_supported(params->rotate_time)) {
+        return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_create: rotate_time %d is outside 1..4 (K3 has 8 x 4 ray slots)", params->rotate_time);
     }
     if (device >= 0) {
         HIP_TRY(hipSetDevice(device));
@@ -484,6 +495,9 @@ int apd_reset(apd_handle c, const apd_params *params)
     }
     if (params->strong_radius != 5 || params->strong_increment != 2 || params->weak_radius != 5 || params->weak_increment != 5) {
         return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_reset: only strong 5/2 and weak 5/5 patch geometry is built");
+    }
+    if (!rotate_time_supported(params->rotate_time)) {
+        return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_reset: rotate_time %d is outside 1..4 (K3 has 8 x 4 ray slots)", params->rotate_time);
     }
     HIP_TRY(hipSetDevice(c->device));
     c->params = *params;

@@ -69,7 +69,8 @@ typedef struct apd_params {
     int weak_increment;     /* 5 */
     int use_APD;            /* bool */
     int weak_peak_radius;   /* 2 */
-    int rotate_time;        /* 4 */
+    int rotate_time;        /* 4; 1..4 only (K3 keeps 8 x 4 ray slots): apd_create / apd_reset refuse any other value
+                               with APD_ERR_UNSUPPORTED */
     float ransac_threshold; /* 0.005 */
     float geom_factor;      /* 0.2 */
     int state;              /* apd_run_state */
@@ -121,8 +122,8 @@ void apd_default_params(apd_params *p);
  * (APD.cpp:636-666).  `device` < 0 keeps the current device (reference: cudaSetDevice, main.cpp:153).
  * Limits (APD_ERR_UNSUPPORTED otherwise): width, height <= 16384 (16-bit neighbour coordinates, 24-bit index
  * arithmetic) and (width + 1) * (height + 1) * 16 < 2^32 (32-bit byte offsets into the float texel-quad copy of a source:
- * 16384 x 16382 is the largest frame with a 16384-px axis); patch geometry strong 5/2, weak 5/5.  Non-positive sizes are
- * APD_ERR_INVALID.  No handle is returned on failure. */
+ * 16384 x 16382 is the largest frame with a 16384-px axis); patch geometry strong 5/2, weak 5/5; rotate_time 1..4.  These
+ * are answered before any device call.  Non-positive sizes are APD_ERR_INVALID.  No handle is returned on failure. */
 int apd_create(apd_handle *out, int device, int width, int height, const apd_params *params);
 
 /* ~APD (APD.cpp:361-397). */
@@ -131,7 +132,8 @@ int apd_destroy(apd_handle h);
 /* Re-arms a handle for another (view, pass) of the same width x height with new parameters: the state arrays return to
  * what apd_create leaves (so a recycled handle gives the same bits as a new one), uploads are forgotten, device buffers
  * are kept.  Saves the ~25 hipMalloc/hipFree pairs per (view, pass) of the construct-run-destroy cycle of
- * ProcessProblem (main.cpp:91-138). */
+ * ProcessProblem (main.cpp:91-138).  Parameters apd_create would refuse (patch geometry, rotate_time) are refused here
+ * too, with APD_ERR_UNSUPPORTED, and leave the handle as it was: armed for the pass it was armed for. */
 int apd_reset(apd_handle h, const apd_params *params);
 
 /* Image / depth / camera upload of CudaSpaceInitialization (APD.cpp:588-634).  images[0] is the

@@ -123,3 +123,15 @@ def test_frame_sizes_are_refused_before_any_device_call(pkg, W, H, status):
     assert L.apd_create(C.byref(out), 0, W, H, C.byref(params)) == status
     assert out.value is None and b"apd_create" in L.apd_last_error()
     assert ((W + 1) * (H + 1) * 16 >= 2 ** 32) == (W <= 16384 and H <= 16384 and status == -5)
+
+
+@pytest.mark.parametrize("rotate_time", [0, -1, 5, 8])
+def test_rotate_time_outside_1_to_4_is_refused_before_any_device_call(pkg, rotate_time):
+    """K3 keeps 8 x 4 ray slots: apd_create refuses any other rotate_time as an argument check -- it answers APD_ERR_UNSUPPORTED
+    with or without a device, returns no handle (so nothing was allocated for one) and names the value."""
+    L = pkg.lib()
+    out = C.c_void_p()
+    params = pkg.default_params(rotate_time=rotate_time)
+    assert L.apd_create(C.byref(out), 0, 32, 32, C.byref(params)) == -5
+    assert out.value is None
+    assert b"apd_create" in L.apd_last_error() and ("rotate_time %d" % rotate_time).encode() in L.apd_last_error()

@@ -1,4 +1,6 @@
 """Error behaviour of the C ABI: the reference exit()s (APD.cpp:321, 430); the library returns codes."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -43,6 +45,56 @@ def test_geometric_pass_needs_depth_maps(gpu_pkg, synth):
 def test_unsupported_patch_geometry(gpu_pkg):
     with pytest.raises(gpu_pkg.ApdError, match="patch geometry"):
         gpu_pkg.Handle(32, 32, gpu_pkg.default_params(strong_radius=7))
+
+
+APD_ERR_UNSUPPORTED = -5
+
+
+@pytest.mark.parametrize("rotate_time", [0, -1, 5, 8])
+def test_rotate_time_outside_1_to_4_is_refused_by_apd_create(gpu_pkg, rotate_time):
+    """K3 keeps 8 x 4 ray slots (short2 strong_pts[32] and a 32-bit mask): rotate_time = 5 would write slot 32.  The value is
+    refused before any device work; no kernel is ever launched with it."""
+    L = gpu_pkg.lib()
+    params = gpu_pkg.default_params(rotate_time=rotate_time)
+    out = C.c_void_p()
+    assert L.apd_create(C.byref(out), 0, 32, 32, C.byref(params)) == APD_ERR_UNSUPPORTED
+    assert out.value is None, "no handle may be returned"
+    message = L.apd_last_error().decode()
+    assert "apd_create" in message and "rotate_time %d" % rotate_time in message, message
+    with pytest.raises(gpu_pkg.ApdError, match="rotate_time"):
+        gpu_pkg.Handle(32, 32, params)
+
+
+@pytest.mark.parametrize("rotate_time", [0, -1, 5, 8])
+def test_rotate_time_outside_1_to_4_is_refused_by_apd_reset(gpu_pkg, ob, synth, rotate_time):
+    """... and a refused apd_reset leaves the handle as it was: its parameters, its uploaded views, its state -- the pass it was
+    armed for still gives the oracle's bits, and so does the next one after an accepted apd_reset."""
+    W, H, N = 40, 33, 2
+    sc, imgs = common.scene_inputs(synth, W, H, N)
+    p = common.base_params(sc, N, max_iterations=1, weak_peak_radius=6)
+    h = common.make_handle(gpu_pkg, sc, imgs, N, p)
+    L = gpu_pkg.lib()
+    bad = gpu_pkg.default_params(**dict(p, rotate_time=rotate_time, seed=99))
+    assert L.apd_reset(h._h, C.byref(bad)) == APD_ERR_UNSUPPORTED
+    message = L.apd_last_error().decode()
+    assert "apd_reset" in message and "rotate_time %d" % rotate_time in message, message
+    with pytest.raises(gpu_pkg.ApdError, match="rotate_time"):
+        h.reset(bad)
+    o = common.make_oracle(ob, sc, imgs, N, p)
+    h.run()
+    o.run()
+    common.assert_state_equal(gpu_pkg, h, o, "the armed pass after a refused apd_reset")
+    o.close()
+    p2 = dict(p, seed=8, rotate_time=1)
+    h.reset(gpu_pkg.default_params(**p2))
+    cams = [gpu_pkg.make_camera(sc.K[i], sc.R[i], sc.t[i], W, H, sc.depth_min, sc.depth_max) for i in range(N + 1)]
+    h.upload_views(cams, imgs)
+    o = common.make_oracle(ob, sc, imgs, N, p2)
+    h.run()
+    o.run()
+    common.assert_state_equal(gpu_pkg, h, o, "an accepted apd_reset after a refused one")
+    h.close()
+    o.close()
 
 
 def test_camera_size_mismatch(gpu_pkg, synth):
