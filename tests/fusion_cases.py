@@ -21,6 +21,7 @@ TAG_CLASSES = {
     "invalid": ["holes", "zero_band", "long_carry", "all_zero_view", "all_blocked_view"],
     "images": ["grey", "colour", "near_255", "blocks", "blocks_none"],
     "maps": ["maps_host", "maps_device", "blocks_device"],
+    "cameras": ["rolled", "aniso", "offcentre", "source_behind"],
     "non_finite": ["nan_depth", "inf_depth", "neg_inf_depth", "neg_zero_depth", "denormal_depth", "huge_depth", "nan_normal"],
 }
 
@@ -80,6 +81,9 @@ def _derived_tags(c):
             tags.add("asymmetric")
     if any(v not in listed for v in range(c.num_views)) and listed:
         tags.add("unlisted_view")
+    for v in c.views:
+        tags |= {t for t, ok in (("rolled", abs(float(v["R"][1])) > 0.5), ("aniso", float(v["K"][0]) != float(v["K"][4])),
+                                 ("offcentre", float(v["K"][2]) != 0.5 * v["W"] and float(v["K"][2]) != (v["W"] - 1) / 2.0)) if ok}
     for d in c.depths:
         if (d == 0).mean() >= 0.01 and (d != 0).any():
             tags.add("holes")
@@ -298,6 +302,72 @@ def non_finite(seed):
     return c
 
 
+def _rig_views(W, H, rig):
+    """[(K, R, c)] of tests/camera_space_cases.py as the view dicts of this module."""
+    return [dict(K=K.astype(np.float32), R=R.reshape(9).astype(np.float32), t=(-R @ c).astype(np.float32), W=W, H=H) for K, R, c in rig]
+
+
+def _world_normals(c, seed):
+    """_ring_maps turns (0, 0, -1) of each CAMERA into the world frame, which agrees between views only while their optical axes are
+    near parallel (the ring).  Here every view gets the normal of one world direction, the ring's optical axis, with the same noise."""
+    rng = np.random.RandomState(seed)
+    for v in range(c.num_views):
+        n = np.zeros(c.depths[v].shape + (3,), np.float64)
+        n[..., 2] = -1.0
+        n[..., 0] = 0.01 * rng.standard_normal(c.depths[v].shape)
+        c.normals[v] = np.ascontiguousarray((n / np.linalg.norm(n, axis=-1, keepdims=True)).astype(np.float32))
+
+
+def projected_z(c, i, j):
+    """Camera-frame z in view j of every pixel of view i with a depth above zero (float64)."""
+    vi, vj = c.views[i], c.views[j]
+    K, R, t = vi["K"].astype(np.float64), vi["R"].astype(np.float64).reshape(3, 3), vi["t"].astype(np.float64)
+    ys, xs = np.nonzero(c.depths[i] > 0)
+    d = c.depths[i][ys, xs].astype(np.float64)
+    world = (np.stack([(xs - K[2]) / K[0] * d, (ys - K[5]) / K[4] * d, d], -1) - t) @ R
+    return world @ vj["R"].astype(np.float64).reshape(3, 3)[2] + float(vj["t"][2])
+
+
+ROLLED_VIEWS = (0, 1)   # of rolled_aniso; first in the list, so that no other view has consumed their pixels before them
+
+
+def rolled_aniso(seed):
+    """96 x 72, 5 views of the ring's scene, every view a source of every other: view 0 rolled by 90 degrees, view 1 rolled with
+    fy = 0.5 fx and the principal point at (0.3 W, 0.7 H), view 2 the upright ring camera, view 3 fy = 0.5 fx, view 4 the principal
+    point at (0.7 W, 0.25 H).  The off-centre views are aimed so that the target still lands on their frame centre."""
+    import camera_space_cases as cc
+    W, H = 96, 72
+    mid = (0.5 * W, 0.5 * H)
+    f = cc.focal(W)
+    rig = [cc.ring_source(W, H, 1, roll=90.0),
+           cc.ring_source(W, H, 2, K=cc.intrinsics(W, H, fx=1.2 * f, fy=0.6 * f, cx=0.3 * W, cy=0.7 * H), roll=90.0, pixel=mid),
+           cc.reference_view(W, H),
+           cc.ring_source(W, H, 3, K=cc.intrinsics(W, H, fx=1.2 * f, fy=0.6 * f)),
+           cc.ring_source(W, H, 4, K=cc.intrinsics(W, H, cx=0.7 * W, cy=0.25 * H), pixel=mid)]
+    c = ring_case("rolled_aniso", seed, W, H, 5, 4, views=_rig_views(W, H, rig))
+    _world_normals(c, seed + 1)
+    return c
+
+
+BEHIND_PART, BEHIND_ALL = 3, 4   # of source_behind: the views that have part of the cloud, and all of it, behind them
+
+
+def source_behind(seed):
+    """96 x 72, 5 views, every view a source of every other: three ring cameras, one camera between the ring and the nearer plane that
+    looks along the surface (part of the others' points have z <= 0 in it) and one that faces away (every point has z < 0 in it, and
+    its own rays meet no surface: its depth map is zero)."""
+    import camera_space_cases as cc
+    W, H = 96, 72
+    rig = cc.rig_behind(W, H)
+    rig = rig[:2] + [cc.ring_source(W, H, 2)] + rig[2:]
+    c = ring_case("source_behind", seed, W, H, 5, 4, views=_rig_views(W, H, rig), tags=("source_behind",))
+    _world_normals(c, seed + 1)
+    for d in c.depths:
+        d[d > 1e6] = 0.0   # rays that meet no surface
+    c.retag()
+    return c
+
+
 # group: which test of test_gpu_fusion_scale.py runs the case
 CASES = {
     "full_frame": ("full_frame", lambda: full_frame(5)),
@@ -318,6 +388,8 @@ CASES = {
     "source_lists": ("generated", lambda: source_lists(41)),
     "mixed_sizes": ("generated", lambda: mixed_sizes(42)),
     "all_blocked": ("generated", lambda: all_blocked(43)),
+    "rolled_aniso": ("generated", lambda: rolled_aniso(44)),
+    "source_behind": ("generated", lambda: source_behind(45)),
     "non_finite": ("non_finite", lambda: non_finite(5)),
 }
 

@@ -2,6 +2,8 @@
 RunFusion) and the Tanks and Temples checker (tests/helpers/tat_fusion_ref.cpp).  These tests keep the inputs of
 test_gpu_fusion_scale.py honest: every edge they are meant to cover occurs, every case that can emit points does, the long carry
 is long and the non-finite case does emit non-finite points.  No GPU needed."""
+import copy
+
 import numpy as np
 import pytest
 
@@ -58,3 +60,30 @@ def test_committed_case_on_the_sequential_loops(ob, checker, tmp_path, name):
             assert stats["max_gap"] > 1024 * 256, stats
         if variant != "eth" and name in fusion_cases.names("non_finite"):
             assert (~np.isfinite(xyz)).any(1).sum() >= 1, variant
+
+
+def test_source_behind_has_points_behind_its_sources():
+    """What `vote_target` and the loops' projections meet in this case: z <= 0 for part of the other views' points in one source, for
+    every point in the other, which has no depth of its own."""
+    case = fusion_cases.case("source_behind")
+    assert "source_behind" in case.tags and not case.depths[fusion_cases.BEHIND_ALL].any()
+    for i in (0, 1):
+        z_part, z_all = fusion_cases.projected_z(case, i, fusion_cases.BEHIND_PART), fusion_cases.projected_z(case, i, fusion_cases.BEHIND_ALL)
+        print("source_behind: view %d, %d points, %.1f %% with z <= 0 in view %d, all z < 0 in view %d: %s"
+              % (i, len(z_part), 100 * (z_part <= 0).mean(), fusion_cases.BEHIND_PART, fusion_cases.BEHIND_ALL, bool((z_all < 0).all())))
+        assert len(z_part) > 1000 and 0.05 <= (z_part <= 0).mean() <= 0.95 and (z_all < 0).all()
+        assert fusion_cases.BEHIND_PART in case.pairs[i] and fusion_cases.BEHIND_ALL in case.pairs[i]
+
+
+def test_rolled_aniso_emits_points_from_the_rolled_views(ob, checker, tmp_path):
+    """Every loop emits points whose reference is a rolled view: the case with the source lists of all other views emptied."""
+    case = fusion_cases.case("rolled_aniso")
+    assert {"rolled", "aniso", "offcentre"} <= case.tags
+    for v in fusion_cases.ROLLED_VIEWS:
+        assert abs(float(case.views[v]["R"][1])) > 0.5
+        only = copy.copy(case)
+        only.pairs = [list(p) if i == v else [] for i, p in enumerate(case.pairs)]
+        for variant in VARIANTS:
+            n = reference(ob, checker, only, variant, tmp_path / ("%s_%d.ply" % (variant, v)))
+            print("rolled_aniso: view %d alone, %s: %d points" % (v, variant, n))
+            assert n > 100, (v, variant)

@@ -19,7 +19,7 @@ from test_gpu_fusion_options import _fuse, _scene
 pytestmark = pytest.mark.gpu
 
 RULES = dict(E.OPTION_SETS, default={})
-NAMES = ["tiny_9x7", "blocks_641x409", "mixed_sizes", "all_blocked", "sources_32", "empty_between"]
+NAMES = ["tiny_9x7", "blocks_641x409", "mixed_sizes", "all_blocked", "sources_32", "empty_between", "rolled_aniso", "source_behind"]
 
 
 def _case(name):

@@ -71,7 +71,7 @@ def _fuse(pkg, ob, case, options, ply=None, points=False, on_device=False, expec
 # --------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("name", ["tiny_9x7", "blocks_641x409", "mixed_sizes", "all_blocked", "full_frame"])
+@pytest.mark.parametrize("name", ["tiny_9x7", "blocks_641x409", "mixed_sizes", "all_blocked", "full_frame", "rolled_aniso", "source_behind"])
 def test_default_options_write_the_bytes_of_the_variant_entry(gpu_pkg, ob, tmp_path, name, variant):
     """tiny: fewer pixels than a wave; 641 x 409 = 1024 * 256 + 25 pixels; views of two sizes; no point at all; a full frame."""
     case = fusion_cases.case(name)

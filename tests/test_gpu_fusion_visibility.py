@@ -68,7 +68,7 @@ def both(pkg, ob, vis, case, run, tmp_path):
 
 
 @pytest.mark.parametrize("run", sorted(RUNS))
-@pytest.mark.parametrize("name", ["tiny_9x7", "mixed_sizes", "blocks_641x409", "all_blocked", "sources_31"])
+@pytest.mark.parametrize("name", ["tiny_9x7", "mixed_sizes", "blocks_641x409", "all_blocked", "sources_31", "rolled_aniso", "source_behind"])
 def test_sources_and_lists_equal_the_checker(gpu_pkg, ob, vis, tmp_path, name, run):
     """Fewer pixels than a wave; views of two sizes; 1024 * 256 + 25 pixels; no point at all (offsets == [0], a .vis file of eight
     zero bytes); 31 sources."""

@@ -211,6 +211,14 @@ def test_fuzz_sweep_hard(gpu_pkg, ob, synth, case):
     assert "hard(" in _fuzz().run_case(case, hard=True)
 
 
+@pytest.mark.parametrize("case", list(range(82000, 82016)))
+def test_fuzz_sweep_rig(gpu_pkg, ob, synth, case):
+    """16 cases of the sweep's third family (run_rig_case): random camera rigs off synth's ring -- per source a roll, a focal ratio
+    in [0.5, 3], fy / fx in [0.5, 2], a principal point anywhere in the frame, a ring, forward, wide or partial pose -- rendered by
+    tests/camera_space_cases.py, the geometric pass on the rendered depth maps.  Seeds of their own: the cases above keep theirs."""
+    assert "rig(" in _fuzz().run_rig_case(case)
+
+
 @pytest.mark.parametrize("W,H,N,float_images", [(80, 60, 20, False), (72, 56, 12, True), (64, 48, 31, False)])
 def test_many_source_views_three_pass(gpu_pkg, ob, synth, W, H, N, float_images):
     """The 16- and 32-view instantiations of the sweep kernels (the reference allows MAX_IMAGES = 32 including the

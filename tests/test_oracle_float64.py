@@ -7,7 +7,19 @@ rounding order, which the HIP-vs-oracle tests pin."""
 import numpy as np
 import pytest
 
+import camera_space_cases as cc
 import common
+
+# rigs of tests/camera_space_cases.py on which every test of this file runs again: fx != fy, principal points off the centre and
+# different per view, a roll that is no multiple of 90 degrees -- an fx-for-fy or cx-for-cy slip changes nothing on synth's ring
+GENERAL = ["aniso", "offcentre", "roll37"]
+
+
+def _general_scene(synth, rig, W, H, seed, textureless=0.0):
+    case = cc.BY_NAME[rig]
+    sc, _ = cc.make_scene(synth, W, H, case.rig(W, H), seed=seed, textureless=textureless)
+    assert sc.num_src == 3
+    return sc, sc.images_numpy()
 
 
 def _cams(sc, i):
@@ -83,8 +95,16 @@ def _random_planes(rng, sc, gt, px, py, n):
 
 
 def test_ncc_old_against_float64(ob, synth):
+    _check_ncc_old(ob, *common.scene_inputs(synth, 96, 72, 3, seed=5))
+
+
+@pytest.mark.parametrize("rig", GENERAL)
+def test_ncc_old_against_float64_on_general_cameras(ob, synth, rig):
+    _check_ncc_old(ob, *_general_scene(synth, rig, 96, 72, seed=5))
+
+
+def _check_ncc_old(ob, sc, imgs):
     W, H, N = 96, 72, 3
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=5)
     o = common.make_oracle(ob, sc, imgs, N, common.base_params(sc, N))
     gt = sc.gt_depth.numpy()
     rng = np.random.RandomState(0)
@@ -109,8 +129,16 @@ def test_ncc_new_against_float64(ob, synth):
     """The deformable cost of WEAK pixels: 0.25 * centre (6x6, stride 2) + 0.75 * mean over the reliable neighbours of a 3x3
     (stride 5) sub-patch cost, all under the centre pixel's homography; a neighbour that projects outside the image costs 2 if
     that view is selected there, and is skipped otherwise (:436-449)."""
+    _check_ncc_new(ob, *common.scene_inputs(synth, 96, 72, 3, seed=3, textureless=0.3))
+
+
+@pytest.mark.parametrize("rig", GENERAL)
+def test_ncc_new_against_float64_on_general_cameras(ob, synth, rig):
+    _check_ncc_new(ob, *_general_scene(synth, rig, 96, 72, seed=3, textureless=0.3))
+
+
+def _check_ncc_new(ob, sc, imgs):
     W, H, N = 96, 72, 3
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=3, textureless=0.3)
     p0 = common.base_params(sc, N, max_iterations=2, weak_peak_radius=6)
     o0 = common.make_oracle(ob, sc, imgs, N, p0)
     o0.run()
@@ -168,8 +196,16 @@ def test_ncc_new_against_float64(ob, synth):
 def test_geometric_cost_against_float64(ob, synth):
     """Forward-backward reprojection error against the source view's depth map, truncated pixel look-up, 3 if that depth is 0,
     capped at 3 (:760-789)."""
+    _check_geometric_cost(ob, *common.scene_inputs(synth, 96, 72, 3, seed=4))
+
+
+@pytest.mark.parametrize("rig", GENERAL)
+def test_geometric_cost_against_float64_on_general_cameras(ob, synth, rig):
+    _check_geometric_cost(ob, *_general_scene(synth, rig, 96, 72, seed=4))
+
+
+def _check_geometric_cost(ob, sc, imgs):
     W, H, N = 96, 72, 3
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=4)
     deps = common.fake_depth_maps(W, H, N + 1)
     o = common.make_oracle(ob, sc, imgs, N, common.base_params(sc, N, state=2, geom_consistency=1), depths=deps)
     gt = sc.gt_depth.numpy()

@@ -28,9 +28,33 @@ import math
 
 import numpy as np
 
+import pytest
+
+import camera_space_cases as cc
 import common
 
 f32 = np.float32
+
+
+def ring_scene(synth):
+    """scene(W, H, N, seed, textureless) -> (scene, images) on synth's ring: what every stage's own test runs on."""
+    return lambda W, H, N, seed=1, textureless=0.0: common.scene_inputs(synth, W, H, N, seed=seed, textureless=textureless)
+
+
+def rig_scene(synth, rig):
+    """The same on a rig of tests/camera_space_cases.py with N sources, rendered at the size, seed and textureless share asked for."""
+    def scene(W, H, N, seed=1, textureless=0.0):
+        sc, _ = cc.make_scene(synth, W, H, cc.general_rig(rig, W, H, N), seed=seed, textureless=textureless)
+        return sc, sc.images_numpy()
+    return scene
+
+
+def populated(strict, ring_bounds, some):
+    """The non-vacuity of a stage: on the ring (strict) the counts meet the bounds set for synth's scenes; on another rig, whose
+    scenes hold other shares of WEAK and moving pixels, each branch the bounds are about must still occur at all."""
+    return ring_bounds if strict else some
+
+
 FLT_EPSILON = f32(1.1920929e-07)
 FLT_MAX = f32(3.4028234663852886e38)
 WEAK, STRONG, UNKNOWN = 0, 1, 2
@@ -231,8 +255,12 @@ def view_selection_of_pixel(ob, o, snap, W, H, nsrc, px, py, it):
 
 
 def test_arm_search_and_view_selection(synth, ob):
+    _check_arm_search_and_view_selection(ob, ring_scene(synth))
+
+
+def _check_arm_search_and_view_selection(ob, scene, strict=True):
     W, H, N = 40, 30, 3
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=21)
+    sc, imgs = scene(W, H, N, seed=21)
     o = common.make_oracle(ob, sc, imgs, N, common.base_params(sc, N, seed=77, max_iterations=2))
     for kid in (1, 2, 5):
         o.run_kernel(kid)
@@ -396,9 +424,9 @@ def gen_neighbours_pixel(ob, W, H, K, params, weak, nearest, planes, rng_words, 
     return out, 1, rng.words()
 
 
-def _apd_oracle(synth, ob, W, H, N, seed):
+def _apd_oracle(scene, ob, W, H, N, seed):
     """A REFINE_INIT + APD oracle whose prior comes from a complete FIRST_INIT pass of the same scene."""
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=seed, textureless=0.3)
+    sc, imgs = scene(W, H, N, seed=seed, textureless=0.3)
     p0 = common.base_params(sc, N, seed=5, max_iterations=2, weak_peak_radius=6)
     o0 = common.make_oracle(ob, sc, imgs, N, p0)
     o0.run()
@@ -409,12 +437,16 @@ def _apd_oracle(synth, ob, W, H, N, seed):
 
 
 def test_gen_neighbours(synth, ob):
+    _check_gen_neighbours(ob, ring_scene(synth))
+
+
+def _check_gen_neighbours(ob, scene, strict=True):
     W, H, N = 128, 96, 3   # a textureless region wide enough for the radius sequence to leave its doubling phase (57, 82, ...)
-    sc, p1, o = _apd_oracle(synth, ob, W, H, N, seed=12)
+    sc, p1, o = _apd_oracle(scene, ob, W, H, N, seed=12)
     for kid in (1, 2):
         o.run_kernel(kid)
     weak = o.weak_info.copy()
-    assert (weak == WEAK).sum() > 40, "the scene must have a textureless region"
+    assert (weak == WEAK).sum() > populated(strict, 40, 0), "the scene must have a textureless region"
     snap = dict(weak=weak, nearest=o.nearest_strong.copy(), planes=o.planes.copy(), rng=o.rng.copy())
     nmap = o.neighbours_map.copy()
     o.run_kernel(3)
@@ -432,7 +464,7 @@ def test_gen_neighbours(synth, ob):
             assert int(reliable[py, px]) == want_rel, (px, py)
             assert np.array_equal(rng_after[py, px], want_rng), (px, py)
             n_reliable += want_rel
-    assert n_reliable > 10, "some pixels must get a full neighbour set, or the RANSAC half is not exercised"
+    assert n_reliable > populated(strict, 10, 0), "some pixels must get a full neighbour set, or the RANSAC half is not exercised"
     # NeigbourUpdate, K4 (:1971-1987): a WEAK pixel that K3 did not mark reliable becomes UNKNOWN
     ys, xs = np.nonzero(weak == WEAK)
     o.weak_reliable[ys[::3], xs[::3]] = 0   # every pixel of this scene found its neighbours: make a third of them unreliable
@@ -446,8 +478,12 @@ def test_gen_neighbours(synth, ob):
 def test_gen_neighbours_long_rays(synth, ob):
     """The same on a hand-made WEAK block 150 px wide: the rays leave the doubling phase of the radius sequence
     (2, 4, 8, 16, 32, 57, 82, ...; :1807) and run into the substitution by the nearest STRONG pixel; every 7th WEAK pixel."""
+    _check_gen_neighbours_long_rays(ob, ring_scene(synth))
+
+
+def _check_gen_neighbours_long_rays(ob, scene, strict=True):
     W, H, N = 200, 140, 2
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=4)
+    sc, imgs = scene(W, H, N, seed=4)
     p0 = common.base_params(sc, N, seed=5, max_iterations=1, weak_peak_radius=6)
     o0 = common.make_oracle(ob, sc, imgs, N, p0)
     o0.run()
@@ -546,8 +582,12 @@ def depth_to_weak_pixel(o, cams_c, K, R, params, planes, sel, vweight, nsrc, W, 
 
 
 def test_depth_to_weak_classifier(synth, ob):
+    _check_depth_to_weak_classifier(ob, ring_scene(synth))
+
+
+def _check_depth_to_weak_classifier(ob, scene, strict=True):
     W, H, N = 56, 40, 3
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=14, textureless=0.25)
+    sc, imgs = scene(W, H, N, seed=14, textureless=0.25)
     for geom in (0, 1):
         kw = dict(seed=9, max_iterations=2, weak_peak_radius=4 if geom else 6)
         depths = None
@@ -660,8 +700,12 @@ def ransac_fit_plane_pixel(ob, W, K, weak, planes, neighbours_row, rng_words, px
 
 
 def test_ransac_fit_plane(synth, ob):
+    _check_ransac_fit_plane(ob, ring_scene(synth))
+
+
+def _check_ransac_fit_plane(ob, scene, strict=True):
     W, H, N = 128, 96, 3
-    sc, p1, o = _apd_oracle(synth, ob, W, H, N, seed=12)
+    sc, p1, o = _apd_oracle(scene, ob, W, H, N, seed=12)
     for kid in (1, 2, 3, 4, 5, 6, 7):   # RunPatchMatch's order up to the first K8 (:2407-2451)
         o.run_kernel(kid, 0)
     weak, planes, rng0 = o.weak_info.copy(), o.planes.copy(), o.rng.copy()
@@ -681,7 +725,7 @@ def test_ransac_fit_plane(synth, ob):
                     zero = not np.any(got.view(np.uint32) & 0x7FFFFFFF)
                     zeroed += int(zero)
                     fitted += int(not zero and not np.array_equal(got.view(np.uint32), planes[py, px].view(np.uint32)))
-    assert fitted > 20 and zeroed > 0, (fitted, zeroed)   # both outcomes of the RANSAC loop occur
+    assert fitted > populated(strict, 20, 0) and zeroed > populated(strict, 0, -1), (fitted, zeroed)   # both outcomes of the RANSAC loop occur
     o.close()
 
 
@@ -735,8 +779,12 @@ def local_refine_pixel(o, cams_c, K, R, params, planes, sel, vweight, nsrc, px, 
 
 
 def test_local_refine(synth, ob):
+    _check_local_refine(ob, ring_scene(synth))
+
+
+def _check_local_refine(ob, scene, strict=True):
     W, H, N = 56, 40, 3
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=14, textureless=0.25)
+    sc, imgs = scene(W, H, N, seed=14, textureless=0.25)
     for geom in (0, 1):
         kw = dict(seed=9, max_iterations=1, weak_peak_radius=4 if geom else 6)   # one iteration: planes far enough from converged to move
         depths = None
@@ -771,7 +819,7 @@ def test_local_refine(synth, ob):
                     assert np.array_equal(got[py, px, :3].view(np.uint32), planes[py, px, :3].view(np.uint32)), (geom, px, py)  # only w is written
                     assert np.float32(want).view(np.uint32) == got[py, px, 3].view(np.uint32), (geom, px, py, float(want), float(got[py, px, 3]))
                     moved += int(got[py, px, 3].view(np.uint32) != planes[py, px, 3].view(np.uint32))
-        assert moved > 5, (geom, moved)   # some depths are adopted
+        assert moved > populated(strict, 5, 0), (geom, moved)   # some depths are adopted
         o.close()
 
 
@@ -794,8 +842,12 @@ def nearest_strong_pixel(weak, W, H, px, py):
 
 
 def test_find_nearest_strong_point(synth, ob):
+    _check_find_nearest_strong_point(ob, ring_scene(synth))
+
+
+def _check_find_nearest_strong_point(ob, scene, strict=True):
     W, H, N = 128, 96, 2
-    sc, p1, o = _apd_oracle(synth, ob, W, H, N, seed=12)
+    sc, p1, o = _apd_oracle(scene, ob, W, H, N, seed=12)
     o.run_kernel(1)
     weak = o.weak_info.copy()
     # a hand-made WEAK block wider than the search radius, with UNKNOWN pixels on part of its border: pixels without any STRONG
@@ -871,8 +923,12 @@ def filter_strong_pixel(planes, costs, weak, W, H, px, py):
 
 
 def test_depth_normal_and_median_filter(synth, ob):
+    _check_depth_normal_and_median_filter(ob, ring_scene(synth))
+
+
+def _check_depth_normal_and_median_filter(ob, scene, strict=True):
     W, H, N = 89, 65, 3   # odd height: grid_size_half.y = ((65 / 2) + 15) / 16 = 2 blocks of 16 row pairs -> row 64 is never filtered
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=21, textureless=0.3)
+    sc, imgs = scene(W, H, N, seed=21, textureless=0.3)
     o0 = common.make_oracle(ob, sc, imgs, N, common.base_params(sc, N, seed=3, max_iterations=2, weak_peak_radius=6))
     o0.run()
     p0 = common.base_params(sc, N)
@@ -884,7 +940,7 @@ def test_depth_normal_and_median_filter(synth, ob):
         o.run_kernel(kid)
     o.run_sweeps(0, 1)
     before, costs, weak = o.planes.copy(), o.costs.copy(), o.weak_info.copy()
-    assert (weak == WEAK).sum() > 20 and (weak == STRONG).sum() > 200
+    assert (weak == WEAK).sum() > populated(strict, 20, 0) and (weak == STRONG).sum() > 200
     K = [f32(v) for v in sc.K[0].reshape(-1)]
     R = [f32(v) for v in sc.R[0].reshape(-1)]
     # K11, :1587-1600: depth first, then the normal to the world frame (w keeps the depth)
@@ -911,7 +967,7 @@ def test_depth_normal_and_median_filter(synth, ob):
                 changed += int(np.float32(v).view(np.uint32) != snap[py, px, 3].view(np.uint32))
                 want[py, px, 3] = v
         assert np.array_equal(o.planes.view(np.uint32), want.view(np.uint32)), colour
-    assert changed > 50, changed
+    assert changed > populated(strict, 50, 0), changed
     assert rows == H - 1   # the last row of the odd-height frame stays as K11 left it
     o.close()
 
@@ -1027,8 +1083,12 @@ def strong_update_pixel(ob, o, snap, W, H, nsrc, params, K, px, py, it):
 
 
 def test_strong_update(synth, ob):
+    _check_strong_update(ob, ring_scene(synth))
+
+
+def _check_strong_update(ob, scene, strict=True):
     W, H, N = 36, 28, 3
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=23)
+    sc, imgs = scene(W, H, N, seed=23)
     for state in (0, 1):
         prior = None
         params = common.base_params(sc, N, seed=41 + state, max_iterations=2, state=state)
@@ -1060,7 +1120,7 @@ def test_strong_update(synth, ob):
                         adopted += int(ws != int(snap[2][py, px]))
                         refined += int(not np.array_equal(planes[py, px].view(np.uint32), snap[1][py, px].view(np.uint32)))
         # REFINE_INIT only commits an improvement of more than 0.1 (:1312): few pixels move, both branches occur
-        assert (adopted > 20 and refined > 100) if state == 0 else (adopted > 3 and refined > 20), (state, adopted, refined)
+        assert ((adopted > 20 and refined > 100) if state == 0 else (adopted > 3 and refined > 20)) if strict else (adopted > 0 and refined > 0), (state, adopted, refined)
         o.close()
 
 
@@ -1113,8 +1173,12 @@ def random_initialization_pixel(ob, o, K, R, params, planes, sel, rng_words, nsr
 
 
 def test_random_initialization(synth, ob):
+    _check_random_initialization(ob, ring_scene(synth))
+
+
+def _check_random_initialization(ob, scene, strict=True):
     W, H, N = 48, 36, 5
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=31, textureless=0.2)
+    sc, imgs = scene(W, H, N, seed=31, textureless=0.2)
     K = [f32(v) for v in sc.K[0].reshape(-1)]
     R = [f32(v) for v in sc.R[0].reshape(-1)]
     prior = None
@@ -1268,8 +1332,12 @@ def weak_update_pixel(ob, o, snap, nb_row, fit_plane, W, H, nsrc, params, K, px,
 
 
 def test_weak_update(synth, ob):
+    _check_weak_update(ob, ring_scene(synth))
+
+
+def _check_weak_update(ob, scene, strict=True):
     W, H, N = 96, 72, 3
-    sc, imgs = common.scene_inputs(synth, W, H, N, seed=12, textureless=0.3)
+    sc, imgs = scene(W, H, N, seed=12, textureless=0.3)
     o0 = common.make_oracle(ob, sc, imgs, N, common.base_params(sc, N, seed=5, max_iterations=2, weak_peak_radius=6))
     o0.run()
     p0 = common.base_params(sc, N)
@@ -1308,7 +1376,23 @@ def test_weak_update(synth, ob):
                         nofit += int(not np.any(fit[py, px, :3]))
         checked = int((snap[2] == WEAK).sum())
         # REFINE_INIT only commits an improvement of more than 0.1: few planes move there
-        assert checked > 150 and refined > (3 if state == 1 else 20), (state, checked, moved, refined, nofit)
+        assert (checked > 150 and refined > (3 if state == 1 else 20)) if strict else (checked > 50 and refined > 0), (state, checked, moved, refined, nofit)
         nofit_total += nofit
         o.close()
     assert nofit_total > 0, "no WEAK pixel without a fit plane: the early return of the refinement is not exercised"
+
+
+# ---- every stage again on general cameras -----------------------------------------------------------------------------------------
+# fx != fy, principal points off the centre and different per view, a roll that is no multiple of 90 degrees: on synth's ring an
+# fx-for-fy or a cx-for-cy slip in either entry changes nothing.  Same frame sizes, seeds and passes as each stage's own test; the
+# bit comparisons are the same, the population counts are held to `populated`.
+
+STAGES = [_check_arm_search_and_view_selection, _check_gen_neighbours, _check_gen_neighbours_long_rays, _check_depth_to_weak_classifier,
+          _check_ransac_fit_plane, _check_local_refine, _check_find_nearest_strong_point, _check_depth_normal_and_median_filter,
+          _check_strong_update, _check_random_initialization, _check_weak_update]
+
+
+@pytest.mark.parametrize("rig", ["aniso", "offcentre", "roll37"])
+@pytest.mark.parametrize("stage", STAGES, ids=[f.__name__[7:] for f in STAGES])
+def test_stage_on_general_cameras(synth, ob, stage, rig):
+    stage(ob, rig_scene(synth, rig), strict=False)

@@ -1,6 +1,7 @@
 """Randomised bit-exact parity sweep: HIP path vs CPU oracle over random sizes, view counts, scenes and seeds through the
 three pass kinds (FIRST_INIT, REFINE_INIT + APD, REFINE_ITER + APD + geometric term), 8-bit and float images, compared
-after every pass (all state arrays).  Usage: [APD_FUZZ_SCALE=3] [APD_FUZZ_HARD=1] python tools/parity_fuzz.py [cases] [first_seed]
+after every pass (all state arrays).  Usage: [APD_FUZZ_SCALE=3] [APD_FUZZ_HARD=1] [APD_FUZZ_RIG=1] python tools/parity_fuzz.py [cases] [first_seed]
+APD_FUZZ_RIG=1: every case on a random camera rig off synth's ring (run_rig_case).
 APD_FUZZ_HARD=1: every case on synth.HARD-like scenes (slabs in front of the planes: depth steps and occlusions; per-view gain /
 offset; sources aiming off the target), with the clutter, gain and aim drawn per case."""
 import os, sys, time
@@ -12,6 +13,85 @@ pkg = ge.load_package()
 from apd_mvs_amd import synth
 from oracle import binding as ob
 import common
+
+
+def _three_passes(label, sc, imgs, deps, N, case, iters, passes, recycle, split, share, equal=common.assert_state_equal):
+    """The three pass kinds on the HIP path and the oracle, every state array compared with `equal` after each pass."""
+    W, H = sc.width, sc.height
+    cams = [pkg.make_camera(sc.K[i], sc.R[i], sc.t[i], W, H, sc.depth_min, sc.depth_max) for i in range(N + 1)]
+    shared = [pkg.SharedImage(W, H, im) for im in imgs] if share else None
+    h, prior = None, None
+    try:
+        for pi, extra in enumerate(passes):
+            p = common.base_params(sc, N, seed=100 + case, max_iterations=iters, **extra)
+            geom = bool(p.get("geom_consistency"))
+            if h is None:
+                h = pkg.Handle(W, H, pkg.default_params(**p), device=0)
+            else:
+                h.reset(pkg.default_params(**p))
+            if share:
+                h.upload_views_shared(cams, shared)
+            elif split:
+                h.upload_views_split(cams, imgs)
+            else:
+                h.upload_views(cams, imgs, deps if geom else None)
+            if prior is not None:
+                h.upload_prior(*prior)
+            o = common.make_oracle(ob, sc, imgs, N, p, depths=deps if geom else None, prior=prior)
+            try:
+                assert h.weak_count == o.weak_count, label
+                if split:
+                    h.run_before_depths()
+                    if geom:
+                        h.upload_depths(deps)
+                    h.run_after_depths()
+                else:
+                    h.run()
+                o.run()
+                equal(pkg, h, o, "%s pass %d" % (label, pi))
+                planes, weak, views = h.download()
+                prior = common.postprocess(planes, weak, views, p["depth_min"], p["depth_max"])
+            finally:
+                o.close()
+            if not recycle:
+                h.close()
+                h = None
+    finally:
+        if h is not None:
+            h.close()
+        for im in shared or []:
+            im.close()
+
+
+def run_rig_case(case):
+    """One random RIG through the three pass kinds (tests/camera_space_cases.py: random_rig and the renderer): per source a roll
+    from {0, 90, 180, any}, a focal ratio in [0.5, 3], fy / fx in [0.5, 2], a principal point anywhere in the frame and a pose from
+    {ring, forward, wide, partial}; the geometric pass reads the rendered depth map of every view.  A pixel that no source sees sums no
+    view and the sweep divides 0 by 0: arrays in which the oracle holds a NaN compare through common.canon_nan, all others as raw bits.  Seeds of its own stream: the
+    easy and hard cases keep their draws."""
+    import camera_space_cases as cc
+    rng = np.random.RandomState(55000 + case)
+    W, H = int(rng.randint(40, 131)), int(rng.randint(32, 97))
+    N = int(rng.randint(2, 7))
+    tl = float(rng.choice([0.0, 0.15, 0.3]))
+    iters = int(rng.randint(1, 3))
+    float_images = bool(rng.rand() < 0.35)
+    views, kinds = cc.random_rig(rng, W, H, N)
+    sc, deps = cc.make_scene(synth, W, H, views, seed=case, textureless=tl)
+    imgs = sc.images_numpy()
+    if float_images:
+        imgs = [(im * np.float32(0.731) + np.float32(1.5)).astype(np.float32) for im in imgs]
+    passes = [dict(state=0, use_APD=0, weak_peak_radius=6),
+              dict(state=1, use_APD=1, weak_peak_radius=6, rotate_time=2, ransac_threshold=0.01 - 0.00125),
+              dict(state=2, use_APD=1, weak_peak_radius=4, rotate_time=4, ransac_threshold=0.01 - 0.0025, geom_consistency=1)]
+    recycle = bool(rng.rand() < 0.5)
+    split = bool(rng.rand() < 0.5)
+    share = bool(split and rng.rand() < 0.5)
+    label = "rig case %d: %dx%d N=%d textureless=%.2f iters=%d %s%s%s rig(%s)" % (
+        case, W, H, N, tl, iters, "float" if float_images else "8-bit", " recycled" if recycle else "",
+        (" shared" if share else " split") if split else "", ", ".join(kinds))
+    _three_passes(label, sc, imgs, deps, N, case, iters, passes, recycle, split, share, equal=common.assert_state_equal_nan_canonical)
+    return label
 
 
 def run_case(case, hard=None):
@@ -45,7 +125,6 @@ def run_case(case, hard=None):
     if rng.rand() < 0.5:  # the schedule's other radii (main.cpp:176-186: 6, 4, 2, 2) and values no schedule uses (K14's peak test, its end samples)
         for q in passes:
             q["weak_peak_radius"] = int(rng.choice([2, 2, 2, 4, 0, 1, 3, 5, 12, 29, 30, 40]))
-    prior = None
     # how the HIP side is driven (the oracle always runs the plain schedule): one handle per pass (the reference's object per
     # view and pass), or ONE handle recycled with apd_reset for all three passes; the whole pass in one call, or split around the
     # depth maps (apd_upload_views_split / apd_run_before_depths / apd_upload_depths / apd_run_after_depths) as the scheduler
@@ -58,49 +137,7 @@ def run_case(case, hard=None):
                                                                                (" shared" if share else " split") if split else "",
                                                                                (" hard(clutter %d gain %.2f baseline %.2f aim %.1f)" % (
                                                                                    scene_kw["clutter"], scene_kw["gain"], scene_kw["baseline"], scene_kw["aim_jitter"])) if hard else "")
-    cams = [pkg.make_camera(sc.K[i], sc.R[i], sc.t[i], W, H, sc.depth_min, sc.depth_max) for i in range(N + 1)]
-    shared = [pkg.SharedImage(W, H, im) for im in imgs] if share else None
-    h = None
-    try:
-        for pi, extra in enumerate(passes):
-            p = common.base_params(sc, N, seed=100 + case, max_iterations=iters, **extra)
-            geom = bool(p.get("geom_consistency"))
-            if h is None:
-                h = pkg.Handle(W, H, pkg.default_params(**p), device=0)
-            else:
-                h.reset(pkg.default_params(**p))
-            if share:
-                h.upload_views_shared(cams, shared)
-            elif split:
-                h.upload_views_split(cams, imgs)
-            else:
-                h.upload_views(cams, imgs, deps if geom else None)
-            if prior is not None:
-                h.upload_prior(*prior)
-            o = common.make_oracle(ob, sc, imgs, N, p, depths=deps if geom else None, prior=prior)
-            try:
-                assert h.weak_count == o.weak_count, label
-                if split:
-                    h.run_before_depths()
-                    if geom:
-                        h.upload_depths(deps)
-                    h.run_after_depths()
-                else:
-                    h.run()
-                o.run()
-                common.assert_state_equal(pkg, h, o, "%s pass %d" % (label, pi))
-                planes, weak, views = h.download()
-                prior = common.postprocess(planes, weak, views, p["depth_min"], p["depth_max"])
-            finally:
-                o.close()
-            if not recycle:
-                h.close()
-                h = None
-    finally:
-        if h is not None:
-            h.close()
-        for im in shared or []:
-            im.close()
+    _three_passes(label, sc, imgs, deps, N, case, iters, passes, recycle, split, share)
     return label
 
 
@@ -111,7 +148,7 @@ if __name__ == "__main__":
     t0 = time.time()
     for case in range(first, first + cases):
         try:
-            print("ok   " + run_case(case), flush=True)
+            print("ok   " + (run_rig_case(case) if os.environ.get("APD_FUZZ_RIG", "0") == "1" else run_case(case)), flush=True)
         except AssertionError as e:
             bad += 1
             print("FAIL case %d: %s" % (case, e), flush=True)
