@@ -197,6 +197,8 @@ def lib():
     L.apd_points_estimate_normals.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p, C.c_void_p]
     L.apd_points_with_estimated_normals.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.POINTER(C.c_void_p),
                                                     C.POINTER(C.c_longlong)]
+    L.apd_points_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_void_p, C.c_void_p]
+    L.apd_points_rendered_visibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
     L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
     L.apd_sort_tile_sizes.restype = None
     L.apd_points_destroy.argtypes = [C.c_void_p]
@@ -257,7 +259,10 @@ class Points:
     a radius of each other (apd_points_components) and remove_small_components() gives the points of the components that are large
     enough (apd_points_remove_small_components), likewise.  estimate_normals() gives every point's normal and surface variation
     from its neighbourhood within a radius (apd_points_estimate_normals) and with_estimated_normals() these points with those
-    normals in place of the stored ones (apd_points_with_estimated_normals), likewise."""
+    normals in place of the stored ones (apd_points_with_estimated_normals), likewise.  render() draws the points into a camera
+    with a z-buffer: the depth and the index of the nearest point per pixel (apd_points_render); with_rendered_visibility() gives
+    these points as a merged object whose lists name the cameras that see each point, occlusion included
+    (apd_points_rendered_visibility)."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
                ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
@@ -506,6 +511,49 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Points(out, self.device), int(estimated.value)
+
+    def render(self, camera, splat=0):
+        """apd_points_render: (depth float32 [height, width], index uint32 [height, width]) -- these points drawn into `camera` (a
+        Camera: K, R, t, width, height) with a z-buffer (contract C15): per pixel the depth of the nearest point whose footprint of
+        (2 * splat + 1)^2 pixels covers it and that point's index, the lowest among equal depths; 0 and 0xFFFFFFFF where no
+        footprint reaches.  numpy arrays for host points; for device points torch tensors on their device, the index holding the
+        same bit patterns as int32, like `sources`.  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.render: the points are closed")
+        L = lib()
+        cam = Camera.from_buffer_copy(camera)
+        shape = (max(int(cam.height), 0), max(int(cam.width), 0))
+        if self.on_device:
+            import torch
+            depth = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self.device))
+            index = torch.empty(shape, dtype=torch.int32, device=torch.device("cuda", self.device))
+            torch.cuda.synchronize(depth.device)
+            addresses = [depth.data_ptr(), index.data_ptr()]
+        else:
+            depth, index = np.zeros(shape, np.float32), np.zeros(shape, np.uint32)
+            addresses = [depth.ctypes.data, index.ctypes.data]
+        nothing = (C.c_uint32 * 1)()   # where a camera without pixels gets its no maps: the library refuses NULL for both, then the camera
+        rc = L.apd_points_render(self._p, C.byref(cam), int(splat), *[C.c_void_p(a if shape[0] * shape[1] else C.addressof(nothing)) for a in addresses])
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return depth, index
+
+    def with_rendered_visibility(self, cameras, splat=1, rel_tolerance=0.01):
+        """apd_points_rendered_visibility: (Points, unseen) -- these points in their order, every array copied, as a merged object
+        whose visibility() list of a point holds the cameras (indices into `cameras`, a ctypes array or a sequence of Camera, not
+        necessarily the fusion's) that see it: the point is drawn into the camera and lies within rel_tolerance * z behind the
+        depth z that render(camera, splat) has at its own pixel.  support is min(255, length - 1), 0 for an empty list; `unseen`
+        is the number of points no camera sees.  Computed on these points' device; the result lives where they live."""
+        if not self._p:
+            raise ApdError("Points.with_rendered_visibility: the points are closed")
+        L = lib()
+        V = len(cameras)
+        cams = cameras if isinstance(cameras, C.Array) else (Camera * max(V, 1))(*[Camera.from_buffer_copy(c) for c in cameras])
+        out, unseen = C.c_void_p(), C.c_longlong(0)
+        rc = L.apd_points_rendered_visibility(self._p, V, C.byref(cams), int(splat), float(rel_tolerance), C.byref(out), C.byref(unseen))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device), int(unseen.value)
 
     def __len__(self):
         return self.count

@@ -82,3 +82,12 @@ static __device__ unsigned long long g_weak_stats[8];
 #else
 #define APD_CLUSTER_REDUCE_COMBINED 1
 #endif
+
+// -DAPD_LAB_RENDER_NO_LOAD (tools/points_render_time.py --library): k_render_scatter of apd_points_render.hip issues its atomic min
+// for every pixel of every footprint, without the load that skips it where the pixel already holds a smaller key: the form the
+// load is measured against.  Same results, the product build loads first.
+#ifdef APD_LAB_RENDER_NO_LOAD
+#define APD_RENDER_LOAD_BEFORE_MIN 0
+#else
+#define APD_RENDER_LOAD_BEFORE_MIN 1
+#endif

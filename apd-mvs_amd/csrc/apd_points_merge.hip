@@ -9,7 +9,8 @@
 //   4. k_run_heads, scan: the first element of every cell, and from the scan the rank of every element's cell.
 //   5. k_cell_starts, k_cell_merge: one lane per cell adds its members up in member order.
 //   6. the lists: k_list_lengths, scan, k_list_expand write rank * num_views + view for every entry of every member's input list;
-//      sort_pairs (keys only); k_run_heads, scan, k_list_emit keep the first of every run: per cell its distinct views, ascending.
+//      sort_pairs (keys only); k_run_heads, scan, k_list_emit keep the first of every run: per cell its distinct views, ascending;
+//      k_cell_offsets: every cell's offset, also of a cell whose members have no entries.
 //   7. k_cell_support: support from the length of a cell's list.
 // There is no host path: host-resident points go up, the result comes down.
 #include <hip/hip_runtime.h>
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(256) void k_list_expand(const uint32_t *__restrict_
 }
 
 // The first entry of every (cell, view) run of the sorted list keys goes to position before[i] of the merged lists; the first of
-// a cell is the cell's offset.  Every cell has an entry: a member's list holds at least its own view.
+// a cell is the cell's offset (k_cell_offsets writes the same, and that of a cell without entries).
 __global__ __launch_bounds__(256) void k_list_emit(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ head,
                                                     const uint64_t *__restrict__ before, size_t entries, uint64_t num_views, size_t cells,
                                                     long long *__restrict__ vis_offsets, int32_t *__restrict__ vis_views)
@@ -148,6 +149,30 @@ __global__ __launch_bounds__(256) void k_list_emit(const uint64_t *__restrict__ 
     if (i == 0) {
         vis_offsets[cells] = (long long)before[entries];
     }
+}
+
+// vis_offsets[c] for c <= cells: the distinct (cell, view) runs before the first sorted key of cell c or a later one, by binary
+// search; that key starts a run, so before[] at its position counts exactly those.  k_list_emit writes the offset of every cell
+// that has an entry; a cell whose members all have empty lists (a rendered visibility can have them) has none, and gets its
+// offset here, like every other cell.
+__global__ __launch_bounds__(256) void k_cell_offsets(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ before, size_t entries,
+                                                       uint64_t num_views, size_t cells, long long *__restrict__ vis_offsets)
+{
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > cells) {
+        return;
+    }
+    const uint64_t want = (uint64_t)c * num_views;
+    size_t lo = 0, hi = entries;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < want) {
+            lo = mid + 1;
+        } else {
+            hi = mid;
+        }
+    }
+    vis_offsets[c] = (long long)before[lo];
 }
 
 __global__ __launch_bounds__(256) void k_cell_support(const long long *__restrict__ vis_offsets, size_t cells, uint8_t *__restrict__ support)
@@ -278,10 +303,14 @@ int merge(apd_points_t p, const Grid &grid, const long long *offsets, const int3
     hipLaunchKernelGGL(k_list_expand, grid_of(m), dim3(256), 0, 0, member, m, offsets, views, (const uint64_t *)before, (const uint64_t *)entry_at,
                        num_views, list_keys[0]);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(apd_sort::sort_pairs(list_keys[0], list_keys[1], nullptr, nullptr, entries, &side, nullptr));
-    const uint64_t *list_sorted = list_keys[side];
-    hipLaunchKernelGGL(k_run_heads, grid_of(entries), dim3(256), 0, 0, list_sorted, entries, list_head);
-    HIP_TRY(hipGetLastError());
+    if (entries > 0) {  // every list may be empty: a rendered visibility that no camera sees
+        HIP_TRY(apd_sort::sort_pairs(list_keys[0], list_keys[1], nullptr, nullptr, entries, &side, nullptr));
+    }
+    const uint64_t *list_sorted = list_keys[entries > 0 ? side : 0];
+    if (entries > 0) {
+        hipLaunchKernelGGL(k_run_heads, grid_of(entries), dim3(256), 0, 0, list_sorted, entries, list_head);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(apd_sort::exclusive_scan(list_head, list_before, entries));
     uint64_t distinct = 0;
     HIP_TRY(hipMemcpy(&distinct, list_before + entries, 8, hipMemcpyDeviceToHost));
@@ -289,8 +318,11 @@ int merge(apd_points_t p, const Grid &grid, const long long *offsets, const int3
     int32_t *vis_views = nullptr;
     HIP_TRY(scratch.alloc((cells + 1) * sizeof(long long), &vis_offsets));
     HIP_TRY(scratch.alloc((size_t)distinct * sizeof(int32_t), &vis_views));
-    hipLaunchKernelGGL(k_list_emit, grid_of(entries), dim3(256), 0, 0, list_sorted, (const uint32_t *)list_head, (const uint64_t *)list_before, entries,
-                       num_views, cells, vis_offsets, vis_views);
+    if (entries > 0) {
+        hipLaunchKernelGGL(k_list_emit, grid_of(entries), dim3(256), 0, 0, list_sorted, (const uint32_t *)list_head, (const uint64_t *)list_before, entries,
+                           num_views, cells, vis_offsets, vis_views);
+    }
+    hipLaunchKernelGGL(k_cell_offsets, grid_of(cells + 1), dim3(256), 0, 0, list_sorted, (const uint64_t *)list_before, entries, num_views, cells, vis_offsets);
     // 7
     hipLaunchKernelGGL(k_cell_support, grid_of(cells), dim3(256), 0, 0, (const long long *)vis_offsets, cells, out.support);
     HIP_TRY(hipGetLastError());

@@ -186,6 +186,11 @@ void SetFusionPlyComponentFilter(float radius, unsigned min_size);
 // where it has at least min_neighbours other points (apd_points_with_estimated_normals, after everything above that is asked for
 // too); the file shows them with normals in it, and without them keeps its bytes.  0: off
 void SetFusionPlyEstimateNormals(float radius, unsigned min_neighbours);
+// additive: splat >= 0: the lists of <dense>/APD/APD.ply.vis are the rendered ones: per point the views that see it when the cloud that
+// is written is drawn into every view's full-resolution camera with footprints of that splat, within rel_tolerance of the nearest
+// depth at the point's pixel (apd_points_rendered_visibility, after everything above that is asked for too); APD.ply keeps its
+// bytes.  -1: off
+void SetFusionPlyRenderVis(int splat, float rel_tolerance);
 
 class APD {
 public:

@@ -40,13 +40,15 @@ float g_fusion_ply_component_radius = 0.0f;  // SetFusionPlyComponentFilter; 0: 
 unsigned g_fusion_ply_component_min = 0;
 float g_fusion_ply_normals_radius = 0.0f;  // SetFusionPlyEstimateNormals; 0: off
 unsigned g_fusion_ply_normals_min = 0;
+int g_fusion_ply_render_splat = -1;        // SetFusionPlyRenderVis; -1: off
+float g_fusion_ply_render_tolerance = 0.0f;
 
-// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter or --ply-estimate-normals: APD.ply is written
-// from the points after the fusion, not by it
+// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-estimate-normals or --ply-render-vis:
+// APD.ply is written from the points after the fusion, not by it
 bool ply_from_points()
 {
     return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f ||
-           g_fusion_ply_component_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f;
+           g_fusion_ply_component_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f || g_fusion_ply_render_splat >= 0;
 }
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
@@ -69,6 +71,7 @@ apd_fusion_options call_options()
 
 struct FusionView {
     Camera cam;
+    Camera full;   // the camera at the size of the image, before it is scaled to the maps: what --ply-render-vis draws into
     Mat image;     // float 0..255: 3 channels (blue, green, red, cv::imread(IMREAD_COLOR), APD.cpp:859) or 1 (grey)
     Mat depth;     // float, <= 0: no estimate
     Mat normal;    // 3 x float, world frame
@@ -76,8 +79,8 @@ struct FusionView {
     Mat block;     // optional uint8 mask of <dense>/blocks (APD.cpp:849-853); empty = none
 };
 
-void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
-                      const int *rows, const int *cols, int maps_on_device, const path &ply_path);
+void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const apd_camera *full_cameras, const float *const *depths,
+                      const float *const *normals, const int *rows, const int *cols, int maps_on_device, const path &ply_path);
 
 // Device fusion through the C ABI (host pointers).  options: nullptr = those of SetFusionOptions; ply_path may be null when
 // points is not.  mean_path (--ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-estimate-normals; points must be given): the fusion writes no file, *points
@@ -86,13 +89,14 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
                         const apd_fusion_options *options = nullptr, apd_points_t *points = nullptr, const path *mean_path = nullptr)
 {
     const int V = (int)views.size();
-    std::vector<apd_camera> cams(V);
+    std::vector<apd_camera> cams(V), full(V);
     std::vector<const float *> imgs(V), deps(V), nors(V);
     std::vector<const uint8_t *> weaks(V), blocks(V, nullptr);
     bool any_block = false;
     std::vector<int> rows(V), cols(V), offs(V + 1, 0), idx;
     for (int i = 0; i < V; ++i) {
         cams[i] = views[i].cam;
+        full[i] = views[i].full;
         imgs[i] = views[i].image.ptr<float>();
         deps[i] = views[i].depth.ptr<float>();
         nors[i] = views[i].normal.ptr<float>();
@@ -120,7 +124,7 @@ long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::v
         return -1;
     }
     if (mean_path) {
-        rework_and_write(*points, V, cams.data(), deps.data(), nors.data(), rows.data(), cols.data(), 0, *mean_path);
+        rework_and_write(*points, V, cams.data(), full.data(), deps.data(), nors.data(), rows.data(), cols.data(), 0, *mean_path);
     }
     return n;
 }
@@ -162,6 +166,12 @@ void SetFusionPlyEstimateNormals(float radius, unsigned min_neighbours)
     g_fusion_ply_normals_min = min_neighbours;
 }
 
+void SetFusionPlyRenderVis(int splat, float rel_tolerance)
+{
+    g_fusion_ply_render_splat = splat;
+    g_fusion_ply_render_tolerance = rel_tolerance;
+}
+
 namespace {
 
 // --ply-mean: replaces the points of a fusion by their means over the agreeing views (apd_points_average with the fusion's own
@@ -171,9 +181,11 @@ namespace {
 // (apd_points_remove_sparse) and prints how many went; --ply-component-filter: replaces what these left by the points of the connected
 // components that are large enough (apd_points_remove_small_components) and prints the components and how many points went;
 // --ply-estimate-normals: replaces the normals of what these left by those of each point's neighbourhood
-// (apd_points_with_estimated_normals) and prints how many points got one.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
-void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *normals,
-                      const int *rows, const int *cols, int maps_on_device, const path &ply_path)
+// (apd_points_with_estimated_normals) and prints how many points got one; --ply-render-vis: replaces the lists of what these left by
+// the views that see each point when the cloud is drawn into full_cameras, the views' cameras at the size of their images
+// (apd_points_rendered_visibility), and prints how many points no view sees.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
+void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const apd_camera *full_cameras, const float *const *depths,
+                      const float *const *normals, const int *rows, const int *cols, int maps_on_device, const path &ply_path)
 {
     int st = APD_OK;
     if (g_fusion_ply_mean) {
@@ -240,6 +252,18 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
         if (st == APD_OK) {
             std::cout << "Estimated the normals of " << estimated << " of " << apd_points_count(points) << " points from at least "
                       << g_fusion_ply_normals_min << " neighbours within " << g_fusion_ply_normals_radius << std::endl;
+            apd_points_destroy(points);
+            points = kept;
+        }
+    }
+    if (st == APD_OK && g_fusion_ply_render_splat >= 0) {
+        apd_points_t kept = nullptr;
+        long long unseen = 0;
+        st = apd_points_rendered_visibility(points, num_views, full_cameras, g_fusion_ply_render_splat, g_fusion_ply_render_tolerance, &kept, &unseen);
+        if (st == APD_OK) {
+            std::cout << "Rendered the visibility of " << apd_points_count(points) << " points in " << num_views << " views with a splat of "
+                      << g_fusion_ply_render_splat << " and a tolerance of " << g_fusion_ply_render_tolerance << ": " << unseen << " points are seen by no view"
+                      << std::endl;
             apd_points_destroy(points);
             points = kept;
         }
@@ -315,6 +339,9 @@ bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> 
         }
         memset(&v.cam, 0, sizeof(v.cam));
         ReadCamera(dense_folder / path("cams") / path(ToFormatIndex(problem.ref_image_id) + "_cam.txt"), v.cam);
+        v.full = v.cam;
+        v.full.width = v.image.cols;
+        v.full.height = v.image.rows;
         int cols = map_cols, rows = map_rows;
         if (!on_device) {
             if (maps) {
@@ -583,10 +610,11 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
         exit(EXIT_FAILURE);
     }
     const int V = (int)f->views.size();
-    std::vector<apd_camera> cams(V);
+    std::vector<apd_camera> cams(V), full(V);
     std::vector<int> rws(V, f->rows), cls(V, f->cols), offs(V + 1, 0), idx;
     for (int i = 0; i < V; ++i) {
         cams[i] = f->views[i].cam;
+        full[i] = f->views[i].full;
         idx.insert(idx.end(), f->sources[i].begin(), f->sources[i].end());
         offs[i + 1] = (int)idx.size();
     }
@@ -619,7 +647,7 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
         exit(EXIT_FAILURE);
     }
     if (ply_from_points()) {
-        rework_and_write(points, V, cams.data(), depths.data(), normals.data(), rws.data(), cls.data(), 1, ply_path);
+        rework_and_write(points, V, cams.data(), full.data(), depths.data(), normals.data(), rws.data(), cls.data(), 1, ply_path);
     }
     std::cout << "Fused " << count << " points into " << ply_path << std::endl;
     if (g_fusion_ply_vis) {

@@ -4,7 +4,7 @@
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
 //       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN]
-//       [--ply-component-filter RADIUS,MIN] [--ply-estimate-normals RADIUS,MIN] [--filtered-maps]
+//       [--ply-component-filter RADIUS,MIN] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -39,9 +39,15 @@
 // --ply-estimate-normals RADIUS,MIN: the points of APD.ply carry, where a point has at least MIN other points within RADIUS, the
 // normal of that neighbourhood -- its direction of least variance, signed like the point's own normal
 // (apd_points_with_estimated_normals, on the grid of cell size RADIUS at the origin) -- instead of the reference pixel's or the mean
-// one; applied last, after --ply-component-filter.  With every --fusion; the number of points estimated is printed.  The flag
+// one; applied after --ply-component-filter.  With every --fusion; the number of points estimated is printed.  The flag
 // implies nothing else: the normals are in the file with --ply-normals, and without it APD.ply keeps its bytes.  RADIUS as for
 // --ply-radius-filter, MIN a count of 2 or more, or the usage line is all that happens.
+// --ply-render-vis SPLAT,TOL: APD.ply.vis (the flag implies --ply-vis) lists per point the views that see it, occlusion included:
+// the cloud that APD.ply holds is drawn into every view's camera at the size of its image with a z-buffer, each point over the
+// (2 SPLAT + 1)^2 pixels around its own, and a view sees a point that lies within TOL times the nearest depth behind that depth at
+// its pixel (apd_points_rendered_visibility); applied last, after --ply-estimate-normals.  With every --fusion; APD.ply keeps the
+// bytes it has without the flag, and the number of points no view sees is printed.  SPLAT must be a count of 0 .. 8 and TOL a
+// non-negative finite number, or the usage line is all that happens.
 // --ply-radius-filter RADIUS,MIN: APD.ply holds the points that have at least MIN other points within RADIUS
 // (apd_points_remove_sparse: the radius outlier filter, on the grid of cell size RADIUS at the origin) and, with --ply-vis,
 // APD.ply.vis their lists; applied after --ply-mean, --ply-voxel and --ply-stat-filter.  With every --fusion; the number removed is printed.
@@ -214,6 +220,19 @@ bool ParseOptions(int argc, char **argv, Options &o)
             }
             o.ply_normals_radius = r;
             o.ply_normals_min = (unsigned)k;
+        } else if (a == "--ply-render-vis") {
+            const std::string both = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = both.find(',');
+            const std::string count = comma == std::string::npos ? "" : both.substr(0, comma);
+            const bool digits = count.size() == 1 && count[0] >= '0' && count[0] <= '8';
+            float t = 0.0f;
+            if (!digits || !real(both.substr(comma + 1).c_str(), t)) {
+                fprintf(stderr, "bad value '%s' of %s: SPLAT,TOL, a count of 0 .. 8 and a non-negative number\n", both.c_str(), a.c_str());
+                return false;
+            }
+            o.ply_render_splat = count[0] - '0';
+            o.ply_render_tolerance = t;
+            o.ply_vis = true;
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
         } else if (a == "--seed") {
@@ -425,14 +444,15 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-estimate-normals RADIUS,MIN] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
                         "  --ply-stat-filter RADIUS,K,RATIO: APD.ply (and APD.ply.vis) without the points whose mean distance to their K nearest neighbours within RADIUS is above mean + RATIO * deviation of the cloud's, after --ply-mean and --ply-voxel, before --ply-radius-filter.\n"
                         "  --ply-radius-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points that have fewer than MIN other points within RADIUS, after --ply-mean and --ply-voxel.\n"
                         "  --ply-component-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points of connected components of fewer than MIN points, two points being joined when they are within RADIUS of each other, after --ply-radius-filter.\n"
-                        "  --ply-estimate-normals RADIUS,MIN: the normals of the points of APD.ply (shown with --ply-normals) estimated from the other points within RADIUS of each, where there are at least MIN (2 or more) of them, after every other --ply-* flag.\n");
+                        "  --ply-estimate-normals RADIUS,MIN: the normals of the points of APD.ply (shown with --ply-normals) estimated from the other points within RADIUS of each, where there are at least MIN (2 or more) of them, after every other --ply-* flag but --ply-render-vis.\n"
+                        "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag.\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -454,6 +474,7 @@ int main(int argc, char **argv)
     SetFusionPlyRadiusFilter(opt.ply_radius, opt.ply_radius_min);
     SetFusionPlyComponentFilter(opt.ply_component_radius, opt.ply_component_min);
     SetFusionPlyEstimateNormals(opt.ply_normals_radius, opt.ply_normals_min);
+    SetFusionPlyRenderVis(opt.ply_render_splat, opt.ply_render_tolerance);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

@@ -47,6 +47,8 @@ struct Options {
     unsigned ply_component_min = 0;       // RADIUS has at least MIN points (apd_points_remove_small_components), after --ply-radius-filter; radius 0: off
     float ply_normals_radius = 0.0f;      // --ply-estimate-normals RADIUS,MIN: the points of APD.ply with normals estimated from the neighbourhood within
     unsigned ply_normals_min = 0;         // RADIUS of each point that has at least MIN others there (apd_points_with_estimated_normals), last; radius 0: off
+    int ply_render_splat = -1;            // --ply-render-vis SPLAT,TOL: APD.ply.vis (the flag implies --ply-vis) lists per point the views that see it when the
+    float ply_render_tolerance = 0.0f;    // cloud is drawn into them with footprints of SPLAT (apd_points_rendered_visibility), last; splat -1: off
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)

@@ -618,6 +618,45 @@ int apd_points_estimate_normals(apd_points_t p, float radius, const float *origi
                                 float *variation);
 int apd_points_with_estimated_normals(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, apd_points_t *out,
                                       long long *estimated);
+/* The cloud drawn into a camera with a z-buffer, and from such maps the views that see each point, occlusion included: what the
+ * cleaned cloud looks like from a camera (a depth map and a point-index map, to inspect holes, to derive a mask, to compare with a
+ * view's own depth map), and the visibility lists COLMAP's Delaunay mesher and Poisson trimming read, rebuilt for the cloud as it
+ * is now.  The lists of a fusion only record which sources agreed with one reference pixel; these name every camera of the call
+ * that sees the point.  binary32, IEEE operations in the order given (contract C15; csrc/apd_render_math.h).
+ *   Draw.  Point k at P and a camera (K, R, t, width, height; the other fields are not read): u, w and the depth d by the fusion's
+ *   projection (ProjectCamera, APD.cpp:805-815), c = int(u + 0.5f) and r = int(w + 0.5f) where that conversion is defined.  The
+ *   point is drawn when d > 0 and finite, both conversions are defined, and 0 <= c < width, 0 <= r < height.  A point whose centre
+ *   pixel is outside the image is not drawn at all.
+ *   Footprint.  The pixels (c + dc, r + dr) with |dc|, |dr| <= splat (0 .. 8), clipped to the image.
+ *   Maps.  Per pixel over the points whose footprint covers it: the smallest key ((uint64)bits(d) << 32) | k, i.e. the nearest
+ *   point, and among equal depths the lowest index.  depth is that point's d, or 0.0f where no footprint reaches; index is its
+ *   k, or 0xFFFFFFFF.  Both are functions of the input alone: no launch shape, order of arrival or race outcome shows in them.
+ *   Seen.  Point k is seen by a camera when it is drawn and d - z <= rel_tolerance * z, z the depth of the map (rendered with the
+ *   call's splat) at the point's own centre pixel: one subtraction, one multiplication, one comparison.  With rel_tolerance 0 only
+ *   the winner of the pixel and exact ties are seen.
+ * apd_points_render: depth and index have camera->width * camera->height entries in row-major order, host memory for
+ * host-resident points, device memory on p's device for device-resident ones; either may be NULL, not both.  Host-resident points
+ * without any give all-empty maps with no device touched; device-resident ones have their maps filled on their device.
+ * apd_points_rendered_visibility: *out is a new object with p's points in p's order, every array copied, and it is a merged
+ * object (apd_points_merged): it carries explicit lists, the rendered ones.  The list of point k holds the cameras of the call
+ * that see it, as indices 0 .. num_views - 1, ascending, and may be empty; support[k] is 0 for an empty list, else
+ * min(255, L - 1); view, pixel and sources are copied and describe the original point alone, as after a merge.  num_views is the
+ * call's own and need not be the fusion's; the result names max(num_views, the views of p) views, a view past p's own with the size
+ * of its camera.  apd_points_visibility, apd_points_write_vis, apd_points_write_ply, the filters and apd_points_merge_voxels work
+ * on it as on any merged object, and apd_points_average refuses it.  *unseen (may be NULL) is the number of points with an empty
+ * list.  The result lives where p lives.  An object without points gives an object without points and *unseen = 0, with no device
+ * touched.  p may itself be a merged object: its lists are not read.
+ * Both are computed on p's device, on its null stream, whatever memory p is in; there is no host implementation.  One image of
+ * 64-bit keys is alive at a time, allocated once at the largest camera of the call.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_render: ..." or
+ * "apd_points_rendered_visibility: ..." (apd_fusion_last_error): a NULL p, camera, cameras or out, both maps NULL, a splat outside
+ * 0 .. 8, a width or height that is not positive or whose product is 2^31 or more, num_views < 1, a rel_tolerance that is negative
+ * or not finite; APD_ERR_UNSUPPORTED for 2^31 or more points and for 2^32 or more list entries (known once the lists are counted
+ * on the device).  *out and *unseen are untouched when the call fails.  apd_fusion_last_timing reports the call like the merge:
+ * set-up, the kernels (and the download of a host result) as "views", file 0. */
+int apd_points_render(apd_points_t p, const apd_camera *camera, int splat, float *depth, uint32_t *index);
+int apd_points_rendered_visibility(apd_points_t p, int num_views, const apd_camera *cameras, int splat, float rel_tolerance,
+                                   apd_points_t *out, long long *unseen);
 /* The tile sizes of the device sort under apd_points_merge_voxels (csrc/apd_sort.h): elements per workgroup of a sort pass and
  * entries per workgroup of its scan.  For tests that choose sizes around them. */
 void apd_sort_tile_sizes(int *sort_tile, int *scan_tile);
