@@ -10,10 +10,10 @@
 // On the points' device, on its null stream, after the refusals and the cell order of apd_points_search.h.  Everything between
 // the sort and the last step works on SORTED POSITIONS: lanes of a wave are neighbours in space.
 //   1. k_cluster_init: parent[v] = v, root_min[v] = 2^32 - 1, root_size[v] = 0.
-//   2. k_cluster_link: one lane per sorted position i.  The 9-row walk of k_neighbour_count, stopped at the first candidate
-//      position `at` >= i: the rows ascend in key order and so do the positions, so everything after that is above i too, and
-//      since the relation is symmetric every edge is seen exactly once, from its higher end.  Every candidate within the radius
-//      is unite(i, at) on parent[], a lock-free union-find:
+//   2. k_cluster_link: one lane per sorted position i.  The walk over the 27 cells (for_each_candidate of apd_points_search.h, the
+//      one of the other three searches) with end = i: it visits the positions in ascending order and stops before the first one
+//      >= i, everything after that being above i too, and since the relation is symmetric every edge is seen exactly once, from
+//      its higher end.  Every candidate within the radius is unite(i, at) on parent[], a lock-free union-find:
 //        find(v)      follows parent[] to the slot that names itself, halving the path on the way (fetch_min of the
 //                     grandparent into the slot it came from);
 //        unite(a, b)  finds both roots, and hooks the larger under the smaller with a compare-and-swap on parent[larger] that
@@ -45,8 +45,8 @@
 //   5. k_cluster_fill: label[k] = k, size[k] = 1 (what a point outside the grid keeps); k_cluster_emit: label[member[i]] =
 //      root_min[root[i]], size[member[i]] = root_size[root[i]].
 //   6. the number of components: the flags label[k] == k through apd_sort::exclusive_scan.
-//   7. removal: flags size[k] >= min_size, compact_points (apd_points.hip).  With min_size <= 1 and no caller for the number of
-//      components nothing is labelled.
+//   7. removal: flags size[k] >= min_size (k_keep_flags of apd_points_search.h), compact_points (apd_points.hip).  With
+//      min_size <= 1 and no caller for the number of components nothing is labelled.
 // No LDS, no scratch memory.  The work of the link step is half that of apd_points_neighbour_counts without a cap.  There is no
 // host path: host-resident points go up, the result comes down.
 #include <hip/hip_runtime.h>
@@ -68,10 +68,11 @@ using apd_fusion::PointArrays;
 using apd_points_grid::grid_of;
 using apd_points_host::DeviceScope;
 using apd_points_host::Scratch;
-using apd_points_search::err;
-using apd_points_search::lower_bound;
+using apd_points_search::for_each_candidate;
+using apd_points_search::k_keep_flags;
 using apd_points_search::Search;
 using apd_points_search::Sorted;
+using apd_points_search::Staged;
 
 __device__ __forceinline__ uint32_t parent_of(uint32_t *parent, uint32_t v)
 {
@@ -126,8 +127,8 @@ __global__ __launch_bounds__(256) void k_cluster_init(uint32_t m, uint32_t *__re
 }
 
 // Sorted element i < m: unites i with every neighbour (contract C11) at a sorted position below i.  keys: ascending; xyz: in the
-// same order; parent: k_cluster_init's.  The rows, the clamped x range and the skipped rows are those of k_neighbour_count
-// (apd_points_radius.hip); the searches and the walks end at position i, which no read reaches or passes.
+// same order; parent: k_cluster_init's.  The walk's searches and runs end at position i, which no read of a candidate reaches or
+// passes.
 __global__ __launch_bounds__(256) void k_cluster_link(const uint64_t *__restrict__ keys, const float *__restrict__ xyz, uint32_t m, float r2,
                                                        uint32_t *parent)
 {
@@ -135,32 +136,13 @@ __global__ __launch_bounds__(256) void k_cluster_link(const uint64_t *__restrict
     if (i >= m) {
         return;
     }
-    int cell[3];
-    apd_fusion::radius_cells_of_key(keys[i], cell);
     const float P[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
-    const int lo = -apd_fusion::kVoxelHalf, hi = apd_fusion::kVoxelHalf - 1;
-    const int x0 = cell[0] > lo ? cell[0] - 1 : lo, x1 = cell[0] < hi ? cell[0] + 1 : hi;
-    uint32_t at = 0;
-    for (int dz = -1; dz <= 1 && at < i; ++dz) {
-        const int cz = cell[2] + dz;
-        if (cz < lo || cz > hi) {
-            continue;
+    for_each_candidate(keys, xyz, i, i, [&](uint32_t at, const float Q[3]) {
+        if (apd_fusion::radius_within(P, Q, r2) && parent_of(parent, i) != parent_of(parent, at)) {
+            unite(parent, i, at);
         }
-        for (int dy = -1; dy <= 1 && at < i; ++dy) {
-            const int cy = cell[1] + dy;
-            if (cy < lo || cy > hi) {
-                continue;
-            }
-            const uint64_t last = apd_fusion::radius_key(x1, cy, cz);
-            at = lower_bound(keys, at, i, apd_fusion::radius_key(x0, cy, cz));
-            for (; at < i && keys[at] <= last; ++at) {
-                const float Q[3] = {xyz[3 * (size_t)at], xyz[3 * (size_t)at + 1], xyz[3 * (size_t)at + 2]};
-                if (apd_fusion::radius_within(P, Q, r2) && parent_of(parent, i) != parent_of(parent, at)) {
-                    unite(parent, i, at);
-                }
-            }
-        }
-    }
+        return false;
+    });
 }
 
 __global__ __launch_bounds__(256) void k_cluster_flatten(uint32_t m, uint32_t *parent, uint32_t *__restrict__ root)
@@ -237,16 +219,6 @@ __global__ __launch_bounds__(256) void k_cluster_own_flags(const uint32_t *__res
     }
 }
 
-// keep[k] = 1 where size[k] reaches min_size
-__global__ __launch_bounds__(256) void k_cluster_keep_flags(const uint32_t *__restrict__ size, size_t n, uint32_t min_size,
-                                                             uint32_t *__restrict__ keep)
-{
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n) {
-        keep[k] = size[k] >= min_size ? 1u : 0u;
-    }
-}
-
 // One call of either entry point: the refusals and the cell order of apd_points_search.h, and the steps the two share
 struct Call : Search {
     // label[k] = k and size[k] = 1 for the n > 0 points; all in device memory on the current device
@@ -303,44 +275,35 @@ struct Call : Search {
         return APD_OK;
     }
 
-    // apd_points_components of p (count > 0): host-resident points send their positions up and get labels and sizes down
+    // apd_points_components of p (count > 0); the sizes are computed whether the caller wants them or not
     int components_of(apd_points_t p, uint32_t *label, uint32_t *size, long long *components) const
     {
         const size_t n = (size_t)p->count;
         Scratch scratch;
-        HIP_TRY(hipSetDevice(p->device));
-        const float *xyz = p->arrays.xyz;
-        uint32_t *device_label = label, *device_size = size;
-        if (!p->on_device) {
-            HIP_TRY(scratch.upload((const float *)p->arrays.xyz, n * 12, &xyz));
-            HIP_TRY(scratch.alloc(n * 4, &device_label));
-        }
-        if (!p->on_device || !size) {
-            HIP_TRY(scratch.alloc(n * 4, &device_size));
-        }
-        if (const int rc = label_points(xyz, n, device_label, device_size, components); rc != APD_OK) {
+        const float *xyz = nullptr;
+        Staged<uint32_t> out_label, out_size;
+        int rc = positions(scratch, p, &xyz);
+        rc = rc != APD_OK ? rc : stage(scratch, p, label, n * 4, out_label);
+        rc = rc != APD_OK ? rc : stage(scratch, p, size, n * 4, out_size);
+        if (rc != APD_OK) {
             return rc;
         }
-        if (!p->on_device) {
-            HIP_TRY(hipMemcpy(label, device_label, n * 4, hipMemcpyDeviceToHost));
-            if (size) {
-                HIP_TRY(hipMemcpy(size, device_size, n * 4, hipMemcpyDeviceToHost));
-            }
+        if (!size) {  // not wanted and so not staged, but label_points writes the sizes: scratch that nothing brings down (host is null)
+            HIP_TRY(scratch.alloc(n * 4, &out_size.device));
         }
-        return APD_OK;
+        rc = label_points(xyz, n, out_label.device, out_size.device, components);
+        rc = rc != APD_OK ? rc : download(out_label);
+        return rc != APD_OK ? rc : download(out_size);
     }
 
-    // apd_points_remove_small_components of p (count > 0) into `result`: host-resident points send every array up once, for the
-    // labelling and for the compaction
+    // apd_points_remove_small_components of p (count > 0) into `result`
     int remove_small(apd_points_t p, uint32_t min_size, apd_points *result, long long *components) const
     {
         const size_t n = (size_t)p->count;
         Scratch scratch;
-        HIP_TRY(hipSetDevice(p->device));
-        PointArrays in = p->arrays;
-        if (!p->on_device) {
-            HIP_TRY(alloc_arrays(scratch, in, n));
-            HIP_TRY(copy_arrays(in, p->arrays, n, hipMemcpyHostToDevice));
+        PointArrays in;
+        if (const int rc = device_arrays(scratch, p, in); rc != APD_OK) {
+            return rc;
         }
         uint32_t *label = nullptr, *size = nullptr, *keep = nullptr;
         HIP_TRY(scratch.alloc(n * 4, &label));
@@ -353,7 +316,7 @@ struct Call : Search {
         } else if (const int rc = label_points(in.xyz, n, label, size, components); rc != APD_OK) {
             return rc;
         }
-        hipLaunchKernelGGL(k_cluster_keep_flags, grid_of(n), dim3(256), 0, 0, (const uint32_t *)size, n, min_size, keep);
+        hipLaunchKernelGGL(k_keep_flags, grid_of(n), dim3(256), 0, 0, (const uint32_t *)size, n, min_size, keep);
         HIP_TRY(hipGetLastError());
         return apd_points_host::compact_points(who, p, in, keep, result);
     }
@@ -387,24 +350,11 @@ extern "C" int apd_points_remove_small_components(apd_points_t p, float radius, 
     if (const int rc = call.check(p, out, radius, origin3); rc != APD_OK) {
         return rc;
     }
-    apd_points *result = apd_points_host::new_points_like(p);
-    result->merged = p->merged;
     long long found = 0;
-    if (p->count > 0) {
-        DeviceScope scope(true);
-        if (const int rc = call.remove_small(p, min_size, result, components ? &found : nullptr); rc != APD_OK) {
-            const std::string why = err();
-            apd_points_destroy(result);  // its arrays are host memory, or none yet
-            err() = why;
-            return rc;
-        }
-    }
-    *out = result;
-    if (removed) {
-        *removed = p->count - result->count;
-    }
-    if (components) {
+    const auto body = [&](apd_points *result) { return call.remove_small(p, min_size, result, components ? &found : nullptr); };
+    const int rc = call.into_new_points(p, out, removed, body);
+    if (rc == APD_OK && components) {
         *components = found;
     }
-    return APD_OK;
+    return rc;
 }

@@ -4,10 +4,11 @@
 // apd_knn_math.h).
 //
 // On the points' device, on its null stream:
-//   1. k_fill: +inf for every point -- what a point outside the grid and a point with fewer than k neighbours keep.
-//   2. the points inside the grid in cell order (apd_points_search.h, shared with apd_points_radius.hip).
-//   3. k_knn_mean: one lane per point in sorted order, the 9-row walk of k_neighbour_count, and in it the selection of the k
-//      smallest d2 the lane has seen.
+//   1. k_fill (apd_points_search.h, like steps 2 and 3's walk and the host frame of both entry points): +inf for every point --
+//      what a point outside the grid and a point with fewer than k neighbours keep.
+//   2. the points inside the grid in cell order.
+//   3. k_knn_mean: one lane per point in sorted order, the walk over the 27 cells (for_each_candidate), and for each of its
+//      candidates the selection of the k smallest d2 the lane has seen.
 //   4. removal: k_chunk_sums (one lane per chunk of 256 input indices, binary64, sequential: the order is the contract), the
 //      chunk sums -- n / 256 triples, never the n scores -- come down and the host adds them in order and forms T;
 //      k_keep_flags; compact_points (apd_points.hip).
@@ -52,23 +53,16 @@ using apd_points_grid::grid_of;
 using apd_points_host::DeviceScope;
 using apd_points_host::Scratch;
 using apd_points_search::err;
-using apd_points_search::lower_bound;
+using apd_points_search::for_each_candidate;
+using apd_points_search::k_fill;
 using apd_points_search::Search;
 using apd_points_search::Sorted;
+using apd_points_search::Staged;
 
 constexpr int kLanes = 64;  // of a workgroup of k_knn_mean: one wave
 
-__global__ __launch_bounds__(256) void k_fill(float *__restrict__ out, size_t n, float value)
-{
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n) {
-        out[k] = value;
-    }
-}
-
 // Sorted element i < m with at least k neighbours: mean[member[i]] = its score by contract C12; the others keep what they have.
-// keys: ascending; xyz: in the same order; dynamic LDS: k * kLanes floats.  The walk is k_neighbour_count's: the rows in
-// ascending key order, the x range clamped, a row outside the grid skipped.
+// keys: ascending; xyz: in the same order; dynamic LDS: k * kLanes floats.
 __global__ __launch_bounds__(kLanes) void k_knn_mean(const uint64_t *__restrict__ keys, const float *__restrict__ xyz,
                                                       const uint32_t *__restrict__ member, uint32_t m, float r2, uint32_t k,
                                                       float *__restrict__ mean)
@@ -79,53 +73,35 @@ __global__ __launch_bounds__(kLanes) void k_knn_mean(const uint64_t *__restrict_
         return;
     }
     float *const mine = slots + threadIdx.x;  // slot s: mine[kLanes * s]
-    int cell[3];
-    apd_fusion::radius_cells_of_key(keys[i], cell);
     const float P[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
-    const int lo = -apd_fusion::kVoxelHalf, hi = apd_fusion::kVoxelHalf - 1;
-    const int x0 = cell[0] > lo ? cell[0] - 1 : lo, x1 = cell[0] < hi ? cell[0] + 1 : hi;
-    uint32_t at = 0, have = 0, worst_at = 0;
+    uint32_t have = 0, worst_at = 0;
     float worst = 0.0f;  // the largest of the values held, in slot worst_at
-    for (int dz = -1; dz <= 1; ++dz) {
-        const int cz = cell[2] + dz;
-        if (cz < lo || cz > hi) {
-            continue;
+    for_each_candidate(keys, xyz, i, m, [&](uint32_t at, const float Q[3]) {
+        const float d2 = apd_fusion::radius_d2(P, Q);
+        if (at == i || !(d2 <= r2)) {
+            return false;
         }
-        for (int dy = -1; dy <= 1; ++dy) {
-            const int cy = cell[1] + dy;
-            if (cy < lo || cy > hi) {
-                continue;
+        if (have < k) {
+            mine[kLanes * have] = d2;
+            if (have == 0 || d2 >= worst) {
+                worst = d2;
+                worst_at = have;
             }
-            const uint64_t last = apd_fusion::radius_key(x1, cy, cz);
-            at = lower_bound(keys, at, m, apd_fusion::radius_key(x0, cy, cz));
-            for (; at < m && keys[at] <= last; ++at) {
-                const float Q[3] = {xyz[3 * (size_t)at], xyz[3 * (size_t)at + 1], xyz[3 * (size_t)at + 2]};
-                const float d2 = apd_fusion::radius_d2(P, Q);
-                if (at == i || !(d2 <= r2)) {
-                    continue;
-                }
-                if (have < k) {
-                    mine[kLanes * have] = d2;
-                    if (have == 0 || d2 >= worst) {
-                        worst = d2;
-                        worst_at = have;
-                    }
-                    ++have;
-                } else if (d2 < worst) {
-                    mine[kLanes * worst_at] = d2;
-                    worst = mine[0];
-                    worst_at = 0;
-                    for (uint32_t s = 1; s < k; ++s) {
-                        const float v = mine[kLanes * s];
-                        if (v > worst) {
-                            worst = v;
-                            worst_at = s;
-                        }
-                    }
+            ++have;
+        } else if (d2 < worst) {
+            mine[kLanes * worst_at] = d2;
+            worst = mine[0];
+            worst_at = 0;
+            for (uint32_t s = 1; s < k; ++s) {
+                const float v = mine[kLanes * s];
+                if (v > worst) {
+                    worst = v;
+                    worst_at = s;
                 }
             }
         }
-    }
+        return false;
+    });
     if (have < k) {
         return;  // +inf from k_fill
     }
@@ -190,7 +166,7 @@ struct Call : Search {
     int scores(const float *xyz, size_t n, float *mean) const
     {
         Scratch scratch;
-        hipLaunchKernelGGL(k_fill, grid_of(n), dim3(256), 0, 0, mean, n, apd_fusion::knn_none());
+        hipLaunchKernelGGL(k_fill<float>, grid_of(n), dim3(256), 0, 0, mean, n, apd_fusion::knn_none());
         HIP_TRY(hipGetLastError());
         Sorted s;
         if (const int rc = sort_into_cells(scratch, xyz, n, s); rc != APD_OK || s.m == 0) {
@@ -204,25 +180,16 @@ struct Call : Search {
         return APD_OK;
     }
 
-    // apd_points_knn_mean_distances of p (count > 0): host-resident points send their positions up and get the scores down
+    // apd_points_knn_mean_distances of p (count > 0)
     int scores_of(apd_points_t p, float *mean) const
     {
-        const size_t n = (size_t)p->count;
         Scratch scratch;
-        HIP_TRY(hipSetDevice(p->device));
-        const float *xyz = p->arrays.xyz;
-        float *device_mean = mean;
-        if (!p->on_device) {
-            HIP_TRY(scratch.upload((const float *)p->arrays.xyz, n * 12, &xyz));
-            HIP_TRY(scratch.alloc(n * 4, &device_mean));
-        }
-        if (const int rc = scores(xyz, n, device_mean); rc != APD_OK) {
-            return rc;
-        }
-        if (!p->on_device) {
-            HIP_TRY(hipMemcpy(mean, device_mean, n * 4, hipMemcpyDeviceToHost));
-        }
-        return APD_OK;
+        const float *xyz = nullptr;
+        Staged<float> out;
+        int rc = positions(scratch, p, &xyz);
+        rc = rc != APD_OK ? rc : stage(scratch, p, mean, (size_t)p->count * 4, out);
+        rc = rc != APD_OK ? rc : scores(xyz, (size_t)p->count, out.device);
+        return rc != APD_OK ? rc : download(out);
     }
 
     // T of the n scores at `mean` (device memory): the chunk sums on the device, their totals and the threshold on the host
@@ -253,17 +220,14 @@ struct Call : Search {
         return APD_OK;
     }
 
-    // apd_points_remove_statistical of p (count > 0) into `result`: host-resident points send every array up once, for the scores
-    // and for the compaction
+    // apd_points_remove_statistical of p (count > 0) into `result`
     int remove_statistical(apd_points_t p, float std_ratio, apd_points *result, double *T) const
     {
         const size_t n = (size_t)p->count;
         Scratch scratch;
-        HIP_TRY(hipSetDevice(p->device));
-        PointArrays in = p->arrays;
-        if (!p->on_device) {
-            HIP_TRY(alloc_arrays(scratch, in, n));
-            HIP_TRY(copy_arrays(in, p->arrays, n, hipMemcpyHostToDevice));
+        PointArrays in;
+        if (const int rc = device_arrays(scratch, p, in); rc != APD_OK) {
+            return rc;
         }
         float *mean = nullptr;
         uint32_t *keep = nullptr;
@@ -312,24 +276,11 @@ extern "C" int apd_points_remove_statistical(apd_points_t p, float radius, const
     if (!isfinite(std_ratio)) {
         return apd::set_error(err(), APD_ERR_INVALID, "%s: a ratio of %g, not a finite number", call.who, (double)std_ratio);
     }
-    apd_points *result = apd_points_host::new_points_like(p);
-    result->merged = p->merged;
     double T = 0.0;  // no points: no full points
-    if (p->count > 0) {
-        DeviceScope scope(true);
-        if (const int rc = call.remove_statistical(p, std_ratio, result, &T); rc != APD_OK) {
-            const std::string why = err();
-            apd_points_destroy(result);  // its arrays are host memory, or none yet
-            err() = why;
-            return rc;
-        }
-    }
-    *out = result;
-    if (removed) {
-        *removed = p->count - result->count;
-    }
-    if (threshold) {
+    const auto body = [&](apd_points *result) { return call.remove_statistical(p, std_ratio, result, &T); };
+    const int rc = call.into_new_points(p, out, removed, body);
+    if (rc == APD_OK && threshold) {
         *threshold = T;
     }
-    return APD_OK;
+    return rc;
 }

@@ -6,11 +6,13 @@
 // On the points' device, on its null stream:
 //   1. k_normal_fill: the stored normal and +inf for every point -- what a point outside the grid and a point with fewer than
 //      min_neighbours neighbours keep.
-//   2. the points inside the grid in cell order (apd_points_search.h, shared with the radius, the statistical and the cluster filter).
-//   3. k_point_normals: one lane per point in sorted order, the 9-row walk of k_neighbour_count without a cap, and in it the ten
-//      binary64 sums of the lane's neighbourhood; then, in the same lane, the covariance and the cyclic Jacobi solve of
-//      apd_normal_math.h, its three rotations written out on named scalars, so that no array is indexed by a runtime value and
-//      the matrix, the vectors and the sums stay in registers.  The result goes to the point's input index.  No LDS, no atomics.
+//   2. the points inside the grid in cell order (apd_points_search.h, shared with the radius, the statistical and the cluster filter,
+//      like step 3's walk, step 4's fill and the host frame of both entry points).
+//   3. k_point_normals: one lane per point in sorted order, the walk over the 27 cells (for_each_candidate), which never ends early,
+//      and for each of its candidates the ten binary64 sums of the lane's neighbourhood; then, in the same lane, the covariance
+//      and the cyclic Jacobi solve of apd_normal_math.h, its three rotations written out on named scalars, so that no array is
+//      indexed by a runtime value and the matrix, the vectors and the sums stay in registers.  The result goes to the point's
+//      input index.  No LDS, no atomics.
 //   4. with_estimated_normals: k_estimated_flags, a scan for their number, and compact_points (apd_points.hip) with every flag set
 //      and the new normals in the place of the stored ones: the copy of the other six arrays and of a merged object's lists is
 //      the one every filter makes.
@@ -41,9 +43,11 @@ using apd_points_grid::grid_of;
 using apd_points_host::DeviceScope;
 using apd_points_host::Scratch;
 using apd_points_search::err;
-using apd_points_search::lower_bound;
+using apd_points_search::for_each_candidate;
+using apd_points_search::k_fill;
 using apd_points_search::Search;
 using apd_points_search::Sorted;
+using apd_points_search::Staged;
 
 // "No estimate" for every point: the stored normal and +inf; either output may be null
 __global__ __launch_bounds__(256) void k_normal_fill(const float *__restrict__ stored, size_t n, float *__restrict__ normal,
@@ -65,9 +69,9 @@ __global__ __launch_bounds__(256) void k_normal_fill(const float *__restrict__ s
 
 // Sorted element i < m with at least min_neighbours neighbours: normal[member[i]] and variation[member[i]] by contract C14 (either
 // may be null), estimated[member[i]] = 1 (may be null); the others keep what they have.  keys: ascending; xyz: in the same
-// order; stored: the stored normals by input index.  The walk is k_neighbour_count's: the rows in ascending key order, the x range
-// clamped, a row outside the grid skipped.  The lane's own position is one of the candidates and its term, d = 0, is added where the
-// walk meets it: the sums run in ascending (cell key, input index) over the point and its neighbours.
+// order; stored: the stored normals by input index.  The lane's own position is one of the walk's candidates and its term, d = 0, is
+// added where the walk meets it: the sums run in the walk's order, ascending (cell key, input index), over the point and its
+// neighbours.
 __global__ __launch_bounds__(256) void k_point_normals(const uint64_t *__restrict__ keys, const float *__restrict__ xyz,
                                                         const uint32_t *__restrict__ member, uint32_t m, float r2, uint32_t min_neighbours,
                                                         const float *__restrict__ stored, float *__restrict__ normal,
@@ -77,35 +81,16 @@ __global__ __launch_bounds__(256) void k_point_normals(const uint64_t *__restric
     if (i >= m) {
         return;
     }
-    int cell[3];
-    apd_fusion::radius_cells_of_key(keys[i], cell);
     const float P[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
-    const int lo = -apd_fusion::kVoxelHalf, hi = apd_fusion::kVoxelHalf - 1;
-    const int x0 = cell[0] > lo ? cell[0] - 1 : lo, x1 = cell[0] < hi ? cell[0] + 1 : hi;
-    uint32_t count = 0, at = 0;
+    uint32_t count = 0;
     apd_fusion::NormalSums sums;
-    for (int dz = -1; dz <= 1; ++dz) {
-        const int cz = cell[2] + dz;
-        if (cz < lo || cz > hi) {
-            continue;
+    for_each_candidate(keys, xyz, i, m, [&](uint32_t at, const float Q[3]) {
+        if (apd_fusion::radius_within(P, Q, r2)) {  // the lane's own position passes: d2 = 0
+            count += at != i ? 1u : 0u;
+            apd_fusion::normal_add(sums, P, Q);
         }
-        for (int dy = -1; dy <= 1; ++dy) {
-            const int cy = cell[1] + dy;
-            if (cy < lo || cy > hi) {
-                continue;
-            }
-            const uint64_t last = apd_fusion::radius_key(x1, cy, cz);
-            at = lower_bound(keys, at, m, apd_fusion::radius_key(x0, cy, cz));
-            for (; at < m && keys[at] <= last; ++at) {
-                const float Q[3] = {xyz[3 * (size_t)at], xyz[3 * (size_t)at + 1], xyz[3 * (size_t)at + 2]};
-                if (!apd_fusion::radius_within(P, Q, r2)) {  // the lane's own position passes: d2 = 0
-                    continue;
-                }
-                count += at != i ? 1u : 0u;
-                apd_fusion::normal_add(sums, P, Q);
-            }
-        }
-    }
+        return false;
+    });
     if (count < min_neighbours) {
         return;  // the fill
     }
@@ -125,14 +110,6 @@ __global__ __launch_bounds__(256) void k_point_normals(const uint64_t *__restric
     }
     if (estimated) {
         estimated[k] = 1u;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_fill_flags(uint32_t *__restrict__ flags, size_t n, uint32_t value)
-{
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n) {
-        flags[k] = value;
     }
 }
 
@@ -172,49 +149,30 @@ struct Call : Search {
         return APD_OK;
     }
 
-    // apd_points_estimate_normals of p (count > 0): host-resident points send positions and normals up and get the results down
+    // apd_points_estimate_normals of p (count > 0): host-resident points send positions and normals up
     int estimate_of(apd_points_t p, float *normal, float *variation) const
     {
         const size_t n = (size_t)p->count;
         Scratch scratch;
-        HIP_TRY(hipSetDevice(p->device));
-        const float *xyz = p->arrays.xyz, *stored = p->arrays.normal;
-        float *device_normal = normal, *device_variation = variation;
-        if (!p->on_device) {
-            HIP_TRY(scratch.upload((const float *)p->arrays.xyz, n * 12, &xyz));
-            HIP_TRY(scratch.upload((const float *)p->arrays.normal, n * 12, &stored));
-            if (normal) {
-                HIP_TRY(scratch.alloc(n * 12, &device_normal));
-            }
-            if (variation) {
-                HIP_TRY(scratch.alloc(n * 4, &device_variation));
-            }
-        }
-        if (const int rc = estimate(xyz, stored, n, device_normal, device_variation, nullptr); rc != APD_OK) {
-            return rc;
-        }
-        if (!p->on_device) {
-            if (normal) {
-                HIP_TRY(hipMemcpy(normal, device_normal, n * 12, hipMemcpyDeviceToHost));
-            }
-            if (variation) {
-                HIP_TRY(hipMemcpy(variation, device_variation, n * 4, hipMemcpyDeviceToHost));
-            }
-        }
-        return APD_OK;
+        const float *xyz = nullptr, *stored = nullptr;
+        Staged<float> out_normal, out_variation;
+        int rc = positions(scratch, p, &xyz);
+        rc = rc != APD_OK ? rc : readable(scratch, p, (const float *)p->arrays.normal, n * 12, &stored);
+        rc = rc != APD_OK ? rc : stage(scratch, p, normal, n * 12, out_normal);
+        rc = rc != APD_OK ? rc : stage(scratch, p, variation, n * 4, out_variation);
+        rc = rc != APD_OK ? rc : estimate(xyz, stored, n, out_normal.device, out_variation.device, nullptr);
+        rc = rc != APD_OK ? rc : download(out_normal);
+        return rc != APD_OK ? rc : download(out_variation);
     }
 
-    // apd_points_with_estimated_normals of p (count > 0) into `result`: host-resident points send every array up once, for the
-    // estimate and for the copy
+    // apd_points_with_estimated_normals of p (count > 0) into `result`
     int with_normals(apd_points_t p, apd_points *result, long long *estimated) const
     {
         const size_t n = (size_t)p->count;
         Scratch scratch;
-        HIP_TRY(hipSetDevice(p->device));
-        PointArrays in = p->arrays;
-        if (!p->on_device) {
-            HIP_TRY(alloc_arrays(scratch, in, n));
-            HIP_TRY(copy_arrays(in, p->arrays, n, hipMemcpyHostToDevice));
+        PointArrays in;
+        if (const int rc = device_arrays(scratch, p, in); rc != APD_OK) {
+            return rc;
         }
         float *normal = nullptr;
         uint32_t *flags = nullptr;
@@ -229,7 +187,7 @@ struct Call : Search {
         uint64_t total = 0;
         HIP_TRY(hipMemcpy(&total, before + n, 8, hipMemcpyDeviceToHost));
         *estimated = (long long)total;
-        hipLaunchKernelGGL(k_fill_flags, grid_of(n), dim3(256), 0, 0, flags, n, 1u);  // every point stays
+        hipLaunchKernelGGL(k_fill<uint32_t>, grid_of(n), dim3(256), 0, 0, flags, n, 1u);  // every point stays
         HIP_TRY(hipGetLastError());
         in.normal = normal;
         return apd_points_host::compact_points(who, p, in, flags, result);
@@ -265,21 +223,11 @@ extern "C" int apd_points_with_estimated_normals(apd_points_t p, float radius, c
     if (const int rc = call.check_min(min_neighbours); rc != APD_OK) {
         return rc;
     }
-    apd_points *result = apd_points_host::new_points_like(p);
-    result->merged = p->merged;
     long long count = 0;
-    if (p->count > 0) {
-        DeviceScope scope(true);
-        if (const int rc = call.with_normals(p, result, &count); rc != APD_OK) {
-            const std::string why = err();
-            apd_points_destroy(result);  // its arrays are host memory, or none yet
-            err() = why;
-            return rc;
-        }
-    }
-    *out = result;
-    if (estimated) {
+    const auto body = [&](apd_points *result) { return call.with_normals(p, result, &count); };
+    const int rc = call.into_new_points(p, out, nullptr, body);
+    if (rc == APD_OK && estimated) {
         *estimated = count;
     }
-    return APD_OK;
+    return rc;
 }

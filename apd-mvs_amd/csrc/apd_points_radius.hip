@@ -2,17 +2,18 @@
 // every point has within a radius, and the object without the points that have too few (arithmetic contract C11; the
 // relation: apd_radius_math.h).
 //
-// On the points' device, on its null stream, on top of the sort and the scan of apd_sort.h (the refusals and
-// steps 1 to 3: apd_points_search.h, shared with apd_points_knn.hip):
+// On the points' device, on its null stream, on top of the sort and the scan of apd_sort.h (the refusals, steps 1 to 3, the walk
+// of step 4, the flags of step 5 and the host frame of both entry points: apd_points_search.h, shared with the statistical filter,
+// the clusters and the normals):
 //   1. k_voxel_keys, scan, k_voxel_compact (apd_points_grid.h): (key, input index) of the points inside the grid of cell size
 //      `radius`, in input order.
 //   2. sort_pairs: the points of a cell together, the cells in key order -- x fastest, so the three x-adjacent cells of a (y, z)
 //      row are one contiguous run of the sorted keys.
 //   3. k_gather_xyz: the positions in sorted order.
-//   4. k_neighbour_count: one lane per point in sorted order; for each of the 9 (dz, dy) rows around its cell a binary search for
-//      the start of the run and a walk to its end.  Lanes of a wave stand next to each other in sorted order: they mostly share
+//   4. k_neighbour_count: one lane per point in sorted order; for_each_candidate: for each of the 9 (dz, dy) rows around its cell
+//      a binary search for the start of the run and a walk to its end.  Lanes of a wave stand next to each other in sorted order: they mostly share
 //      their cell, so their searches take the same branches and their candidate loads go to the same address.  A lane leaves the
-//      loops at `cap`.  No LDS, no atomics; the count goes to the point's input index, a point outside the grid keeps 0.
+//      walk at `cap`.  No LDS, no atomics; the count goes to the point's input index, a point outside the grid keeps 0.
 //   5. removal: k_keep_flags, compact_points (apd_points.hip).
 // The work is the number of (point, candidate in the 27 cells) pairs: with cap == 0 a cell of m members costs m * m distance
 // tests, each lane of the cell walking all m; the removal runs with cap = min_neighbours and is bounded by that early exit in
@@ -35,16 +36,15 @@ using apd_fusion::PointArrays;
 using apd_points_grid::grid_of;
 using apd_points_host::DeviceScope;
 using apd_points_host::Scratch;
-using apd_points_search::err;
-using apd_points_search::lower_bound;
+using apd_points_search::for_each_candidate;
+using apd_points_search::k_keep_flags;
 using apd_points_search::Search;
 using apd_points_search::Sorted;
+using apd_points_search::Staged;
 
 // Sorted element i < m: counts[member[i]] = min(neighbours, cap) by contract C11.  keys: ascending; xyz: in the same order.
-// The rows are visited in ascending key order, so a row's run starts at or after the end of the one before it.  The x range is
-// clamped and a row whose y or z cell leaves the grid is skipped: a search bound never borrows into the next field of the key.
-// Every candidate of a run lies in a cell adjacent to the lane's by construction; what is left of the relation is the index and
-// the distance.
+// The walk (apd_points_search.h) hands over every point of the 27 cells around the lane's; what is left of the relation is the
+// index and the distance.  The walk ends where the count reaches `cap`.
 __global__ __launch_bounds__(256) void k_neighbour_count(const uint64_t *__restrict__ keys, const float *__restrict__ xyz,
                                                           const uint32_t *__restrict__ member, uint32_t m, float r2, uint32_t cap,
                                                           uint32_t *__restrict__ counts)
@@ -53,51 +53,19 @@ __global__ __launch_bounds__(256) void k_neighbour_count(const uint64_t *__restr
     if (i >= m) {
         return;
     }
-    int cell[3];
-    apd_fusion::radius_cells_of_key(keys[i], cell);
     const float P[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
-    const int lo = -apd_fusion::kVoxelHalf, hi = apd_fusion::kVoxelHalf - 1;
-    const int x0 = cell[0] > lo ? cell[0] - 1 : lo, x1 = cell[0] < hi ? cell[0] + 1 : hi;
-    uint32_t count = 0, at = 0;
-    bool full = false;
-    for (int dz = -1; dz <= 1 && !full; ++dz) {
-        const int cz = cell[2] + dz;
-        if (cz < lo || cz > hi) {
-            continue;
+    uint32_t count = 0;
+    for_each_candidate(keys, xyz, i, m, [&](uint32_t at, const float Q[3]) {
+        if (at != i && apd_fusion::radius_within(P, Q, r2)) {
+            ++count;
+            return count == cap;  // cap == 0: never
         }
-        for (int dy = -1; dy <= 1 && !full; ++dy) {
-            const int cy = cell[1] + dy;
-            if (cy < lo || cy > hi) {
-                continue;
-            }
-            const uint64_t last = apd_fusion::radius_key(x1, cy, cz);
-            at = lower_bound(keys, at, m, apd_fusion::radius_key(x0, cy, cz));
-            for (; at < m && keys[at] <= last; ++at) {
-                const float Q[3] = {xyz[3 * (size_t)at], xyz[3 * (size_t)at + 1], xyz[3 * (size_t)at + 2]};
-                if (at != i && apd_fusion::radius_within(P, Q, r2)) {
-                    ++count;
-                    if (count == cap) {  // cap == 0: never
-                        full = true;
-                        break;
-                    }
-                }
-            }
-        }
-    }
+        return false;
+    });
     counts[member[i]] = count;
 }
 
-// keep[k] = 1 where counts[k] (capped at min_neighbours) reaches min_neighbours
-__global__ __launch_bounds__(256) void k_keep_flags(const uint32_t *__restrict__ counts, size_t n, uint32_t min_neighbours,
-                                                     uint32_t *__restrict__ keep)
-{
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n) {
-        keep[k] = counts[k] >= min_neighbours ? 1u : 0u;
-    }
-}
-
-// One call of either entry point: the refusals and the cell order of apd_points_search.h, and the steps the two share
+// One call of either entry point: the refusals, the cell order and the host frame of apd_points_search.h, and the step the two share
 struct Call : Search {
     // counts[k] for the n > 0 points at xyz; both in device memory on the current device
     int count_neighbours(const float *xyz, size_t n, uint32_t cap, uint32_t *counts) const
@@ -114,38 +82,26 @@ struct Call : Search {
         return APD_OK;
     }
 
-    // apd_points_neighbour_counts of p (count > 0): host-resident points send their positions up and get the counts down
+    // apd_points_neighbour_counts of p (count > 0)
     int counts_of(apd_points_t p, uint32_t cap, uint32_t *counts) const
     {
-        const size_t n = (size_t)p->count;
         Scratch scratch;
-        HIP_TRY(hipSetDevice(p->device));
-        const float *xyz = p->arrays.xyz;
-        uint32_t *device_counts = counts;
-        if (!p->on_device) {
-            HIP_TRY(scratch.upload((const float *)p->arrays.xyz, n * 12, &xyz));
-            HIP_TRY(scratch.alloc(n * 4, &device_counts));
-        }
-        if (const int rc = count_neighbours(xyz, n, cap, device_counts); rc != APD_OK) {
-            return rc;
-        }
-        if (!p->on_device) {
-            HIP_TRY(hipMemcpy(counts, device_counts, n * 4, hipMemcpyDeviceToHost));
-        }
-        return APD_OK;
+        const float *xyz = nullptr;
+        Staged<uint32_t> out;
+        int rc = positions(scratch, p, &xyz);
+        rc = rc != APD_OK ? rc : stage(scratch, p, counts, (size_t)p->count * 4, out);
+        rc = rc != APD_OK ? rc : count_neighbours(xyz, (size_t)p->count, cap, out.device);
+        return rc != APD_OK ? rc : download(out);
     }
 
-    // apd_points_remove_sparse of p (count > 0) into `result`: host-resident points send every array up once, for the count and
-    // for the compaction
+    // apd_points_remove_sparse of p (count > 0) into `result`
     int remove_sparse(apd_points_t p, uint32_t min_neighbours, apd_points *result) const
     {
         const size_t n = (size_t)p->count;
         Scratch scratch;
-        HIP_TRY(hipSetDevice(p->device));
-        PointArrays in = p->arrays;
-        if (!p->on_device) {
-            HIP_TRY(alloc_arrays(scratch, in, n));
-            HIP_TRY(copy_arrays(in, p->arrays, n, hipMemcpyHostToDevice));
+        PointArrays in;
+        if (const int rc = device_arrays(scratch, p, in); rc != APD_OK) {
+            return rc;
         }
         uint32_t *counts = nullptr, *keep = nullptr;
         HIP_TRY(scratch.alloc(n * 4, &counts));
@@ -183,20 +139,6 @@ extern "C" int apd_points_remove_sparse(apd_points_t p, float radius, const floa
     if (const int rc = call.check(p, out, radius, origin3); rc != APD_OK) {
         return rc;
     }
-    apd_points *result = apd_points_host::new_points_like(p);
-    result->merged = p->merged;
-    if (p->count > 0) {
-        DeviceScope scope(true);
-        if (const int rc = call.remove_sparse(p, min_neighbours, result); rc != APD_OK) {
-            const std::string why = err();
-            apd_points_destroy(result);  // its arrays are host memory, or none yet
-            err() = why;
-            return rc;
-        }
-    }
-    *out = result;
-    if (removed) {
-        *removed = p->count - result->count;
-    }
-    return APD_OK;
+    const auto body = [&](apd_points *result) { return call.remove_sparse(p, min_neighbours, result); };
+    return call.into_new_points(p, out, removed, body);
 }

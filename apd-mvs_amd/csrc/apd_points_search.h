@@ -1,8 +1,13 @@
 // apd_points_search.h -- what every search of the 27 cells around a point shares (apd_points_radius.hip: contract C11,
-// apd_points_knn.hip: contract C12): what such a call refuses before any device is touched, and the points inside the grid of
-// cell size `radius` brought into cell order -- keys, scan, compaction (apd_points_grid.h), the stable sort of (key, input index)
-// and the positions gathered into sorted order -- ready for a kernel with one lane per point in sorted order; and the binary
-// search such a kernel finds a (dz, dy) row's run with.  Device code: hipcc only.
+// apd_points_knn.hip: C12, apd_points_clusters.hip: C13, apd_points_normals.hip: C14).
+// Device: the positions gathered into cell order (k_gather_xyz), the binary search for a (dz, dy) row's run (lower_bound), THE walk
+// over the 27 cells (for_each_candidate: the one place where a key is decoded, the x range clamped, a row outside the grid skipped),
+// a typed fill and the flags "v[k] >= bound" of the removals.
+// Host, as methods of Search, one call of an entry point: what such a call refuses before any device is touched (check); the points
+// inside the grid of cell size `radius` brought into cell order -- keys, scan, compaction (apd_points_grid.h), the stable sort of
+// (key, input index), the gather -- ready for a kernel with one lane per point in sorted order (sort_into_cells); where a query
+// reads the points and writes its answer when they are host-resident (positions, readable, stage, download); the seven arrays a
+// removal compacts (device_arrays); and the tail of an entry point that hands a new object back (into_new_points).  Device code: hipcc only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +20,7 @@
 #include "apd_fusion_device.h"
 #include "apd_points_grid.h"
 #include "apd_points_host.h"
+#include "apd_radius_math.h"
 #include "apd_sort.h"
 
 namespace apd_points_search {
@@ -25,6 +31,23 @@ using apd_points_grid::grid_of;
 using apd_points_grid::k_voxel_compact;
 using apd_points_grid::k_voxel_keys;
 using apd_points_host::Scratch;
+
+template <typename T> __global__ __launch_bounds__(256) void k_fill(T *__restrict__ out, size_t n, T value)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n) {
+        out[k] = value;
+    }
+}
+
+// keep[k] = 1 where v[k] reaches `bound`: a count capped at min_neighbours, the size of a component
+__global__ __launch_bounds__(256) void k_keep_flags(const uint32_t *__restrict__ v, size_t n, uint32_t bound, uint32_t *__restrict__ keep)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n) {
+        keep[k] = v[k] >= bound ? 1u : 0u;
+    }
+}
 
 __global__ __launch_bounds__(256) void k_gather_xyz(const float *__restrict__ xyz, const uint32_t *__restrict__ member, size_t m,
                                                      float *__restrict__ sorted_xyz)
@@ -53,6 +76,45 @@ __device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ key
     return lo;
 }
 
+// The walk.  Sorted element i (keys: ascending; xyz: in the same order): f(at, Q) for every sorted position at < end in the 27
+// cells around i's, Q its position, i itself included when i < end; f returns true to end the walk.  The positions are visited in
+// ASCENDING order, each once -- contract C14 adds its binary64 sums in this order, and the link of C13 relies on everything
+// after the first position >= end being above it too: the 9 (dz, dy) rows are taken in ascending key order -- x is the fastest field
+// of a key, so the three x-adjacent cells of a row are one run of the sorted keys, found by one binary search that starts where
+// the row before ended.  The x range is clamped and a row whose y or z cell leaves the grid is skipped: a search bound never
+// borrows into the next field of the key.  Every candidate lies in a cell adjacent to i's by construction; what is left of the
+// relation of apd_radius_math.h is the index and the distance, which are f's.  No read of keys or xyz reaches position `end` but
+// that of keys[i]: end = m walks all 27 cells, end = i the part of them below i.
+template <typename F>
+__device__ __forceinline__ void for_each_candidate(const uint64_t *__restrict__ keys, const float *__restrict__ xyz, uint32_t i, uint32_t end, F &&f)
+{
+    int cell[3];
+    apd_fusion::radius_cells_of_key(keys[i], cell);
+    const int lo = -apd_fusion::kVoxelHalf, hi = apd_fusion::kVoxelHalf - 1;
+    const int x0 = cell[0] > lo ? cell[0] - 1 : lo, x1 = cell[0] < hi ? cell[0] + 1 : hi;
+    uint32_t at = 0;
+    for (int dz = -1; dz <= 1 && at < end; ++dz) {
+        const int cz = cell[2] + dz;
+        if (cz < lo || cz > hi) {
+            continue;
+        }
+        for (int dy = -1; dy <= 1 && at < end; ++dy) {
+            const int cy = cell[1] + dy;
+            if (cy < lo || cy > hi) {
+                continue;
+            }
+            const uint64_t last = apd_fusion::radius_key(x1, cy, cz);
+            at = lower_bound(keys, at, end, apd_fusion::radius_key(x0, cy, cz));
+            for (; at < end && keys[at] <= last; ++at) {
+                const float Q[3] = {xyz[3 * (size_t)at], xyz[3 * (size_t)at + 1], xyz[3 * (size_t)at + 2]};
+                if (f(at, Q)) {
+                    return;
+                }
+            }
+        }
+    }
+}
+
 std::string &err() { return apd_fusion::g_fusion_error; }
 
 // The m points inside the grid in cell order: device memory of the call's Scratch
@@ -61,6 +123,14 @@ struct Sorted {
     const uint64_t *keys = nullptr;    // ascending
     const uint32_t *member = nullptr;  // the input index of sorted element i
     const float *xyz = nullptr;        // its position
+};
+
+// An output of a query on p, where the kernels write it and where the caller wants it
+template <typename T> struct Staged {
+    T *device = nullptr;  // the caller's own pointer when p is device-resident, scratch otherwise; null: the caller wants none, and what
+                          // the call needs all the same (the sizes of apd_points_components) it allocates itself
+    T *host = nullptr;    // where download() brings it: null when `device` is the caller's
+    size_t bytes = 0;
 };
 
 // One call of an entry point: its name, which starts every message, and the steps the searches share
@@ -135,6 +205,81 @@ struct Search {
         s.keys = keys[side];
         s.member = index[side];
         s.xyz = sorted_xyz;
+        return APD_OK;
+    }
+
+    // *out = `own`, one of p's arrays of `bytes` bytes, where a kernel can read it: itself if p is device-resident, an upload owned by
+    // `scratch` otherwise.  p's device is the current one
+    template <typename T> int readable(Scratch &scratch, apd_points_t p, const T *own, size_t bytes, const T **out) const
+    {
+        *out = own;
+        if (!p->on_device) {
+            HIP_TRY(scratch.upload(own, bytes, out));
+        }
+        return APD_OK;
+    }
+
+    // A query's first step: selects p's device; *xyz = p's positions, readable
+    int positions(Scratch &scratch, apd_points_t p, const float **xyz) const
+    {
+        HIP_TRY(hipSetDevice(p->device));
+        return readable(scratch, p, (const float *)p->arrays.xyz, (size_t)p->count * 12, xyz);
+    }
+
+    // A removal's first step: selects p's device; in = p's seven arrays, readable: host-resident points send every array up once,
+    // for the search and for the compaction
+    int device_arrays(Scratch &scratch, apd_points_t p, apd_fusion::PointArrays &in) const
+    {
+        const size_t n = (size_t)p->count;
+        HIP_TRY(hipSetDevice(p->device));
+        in = p->arrays;
+        if (!p->on_device) {
+            HIP_TRY(alloc_arrays(scratch, in, n));
+            HIP_TRY(copy_arrays(in, p->arrays, n, hipMemcpyHostToDevice));
+        }
+        return APD_OK;
+    }
+
+    // The caller's output `out` of `bytes` bytes (null: not wanted, and s.device stays null) as a query on p writes it
+    template <typename T> int stage(Scratch &scratch, apd_points_t p, T *out, size_t bytes, Staged<T> &s) const
+    {
+        s.device = out;
+        s.bytes = bytes;
+        s.host = out && !p->on_device ? out : nullptr;
+        if (s.host) {
+            HIP_TRY(scratch.alloc(bytes, &s.device));
+        }
+        return APD_OK;
+    }
+
+    template <typename T> int download(const Staged<T> &s) const
+    {
+        if (s.host) {
+            HIP_TRY(hipMemcpy(s.host, s.device, s.bytes, hipMemcpyDeviceToHost));
+        }
+        return APD_OK;
+    }
+
+    // The tail of an entry point that answers with a new object like p: body(result) fills it from p (count > 0) with p's device
+    // current or fails with its message set, which stays the last error; an empty p gives an empty object and touches no device.
+    // *removed (may be null): how many points fewer the result has
+    template <typename Body> int into_new_points(apd_points_t p, apd_points_t *out, long long *removed, Body &&body) const
+    {
+        apd_points *result = apd_points_host::new_points_like(p);
+        result->merged = p->merged;
+        if (p->count > 0) {
+            apd_points_host::DeviceScope scope(true);
+            if (const int rc = body(result); rc != APD_OK) {
+                const std::string why = err();
+                apd_points_destroy(result);  // its arrays are host memory, or none yet
+                err() = why;
+                return rc;
+            }
+        }
+        *out = result;
+        if (removed) {
+            *removed = p->count - result->count;
+        }
         return APD_OK;
     }
 };

@@ -1,5 +1,50 @@
 """Shared scene / handle / oracle construction for the tests."""
+import os
+import re
+import subprocess
+
 import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WALK_KERNELS = {"k_neighbour_count": "apd_points_radius.hip", "k_knn_mean": "apd_points_knn.hip", "k_point_normals": "apd_points_normals.hip",
+                "k_cluster_link": "apd_points_clusters.hip"}
+
+
+def kernel_resources(source, tmp_path):
+    """One source of the library compiled for the device alone, with the library's flags: what the compiler's resource remarks say
+    of every kernel in it, {mangled name: {"VGPRs": "27", "ScratchSize [bytes/lane]": "0", ...}}.  Needs no GPU."""
+    from importlib import util
+    spec = util.spec_from_file_location("apd_build_for_flags", os.path.join(ROOT, "apd-mvs_amd", "build.py"))
+    builder = util.module_from_spec(spec)
+    spec.loader.exec_module(builder)
+    assert source in builder.SOURCES
+    flags = [f for f in builder.FLAGS if not f.startswith("-W")]
+    r = subprocess.run([builder.HIPCC] + flags + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+                                                  os.path.join(builder.CSRC, source), "-o", str(tmp_path / (source + ".o"))],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    found, name = {}, None
+    for line in r.stdout.splitlines():
+        m = re.search(r"remark:.*?\s(Function Name|VGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|Occupancy \[waves/SIMD\]|"
+                      r"LDS Size \[bytes/block\]): (\S+)", line)
+        if m and m.group(1) == "Function Name":
+            name = m.group(2)
+        elif m and name is not None:
+            found.setdefault(name, {})[m.group(1)] = m.group(2)
+    return found
+
+
+def walk_kernel_resources(kernel, tmp_path):
+    """kernel_resources of the file of one of the four kernels that walk the 27 cells (csrc/apd_points_search.h: for_each_candidate),
+    after the four things each of them keeps: no scratch memory, no spilled register, no static LDS, 8 waves per SIMD."""
+    found = kernel_resources(WALK_KERNELS[kernel], tmp_path)
+    mine = [v for k, v in found.items() if kernel in k]
+    assert len(mine) == 1, sorted(found)
+    print(kernel, "VGPRs", mine[0]["VGPRs"], "SGPRs", mine[0]["TotalSGPRs"])
+    assert mine[0]["ScratchSize [bytes/lane]"] == "0" and mine[0]["VGPRs Spill"] == "0" and mine[0]["SGPRs Spill"] == "0", mine[0]
+    assert mine[0]["LDS Size [bytes/block]"] == "0", mine[0]
+    assert mine[0]["Occupancy [waves/SIMD]"] == "8", mine[0]
+    return found
 
 
 def scene_inputs(synth, W, H, N, seed=1, textureless=0.0, rotate=True):

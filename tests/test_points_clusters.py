@@ -6,12 +6,12 @@ checkers alone; and the scratch size of the kernels."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import fusion_cases
+from common import walk_kernel_resources
 import points_cluster_checker as PC
 import points_radius_checker as PR
 import points_voxel_checker as PV
@@ -350,9 +350,9 @@ def test_no_gpu_means_the_components_fail_loudly(pkg):
     out, removed, components = C.c_void_p(1234), C.c_longlong(-7), C.c_longlong(-8)
     for min_size in (0, 2):
         assert L.apd_points_remove_small_components(pts._p, 1.0, None, min_size, C.byref(out), C.byref(removed), C.byref(components)) != 0
-        assert L.apd_fusion_last_error().startswith(b"apd_points_remove_small_components: ")
+        assert L.apd_fusion_last_error().startswith(b"apd_points_remove_small_components: hipSetDevice(")
         assert out.value == 1234 and removed.value == -7 and components.value == -8
-    with pytest.raises(pkg.ApdError, match="apd_points_components: "):
+    with pytest.raises(pkg.ApdError, match=r"apd_points_components: hipSetDevice\("):
         pts.components(1.0)
     pts.close()
 
@@ -391,23 +391,7 @@ def test_real_cloud_choice_removes_some_points_and_not_all(ob, vis, radius_check
 def test_the_kernels_use_no_scratch_memory_and_no_lds(tmp_path):
     """apd_points_clusters.hip compiled for gfx950 with the library's flags: the compiler reports 0 bytes of scratch per lane, no
     spilled register and no LDS for every kernel of the file, the union-find and the per-wave combining among them."""
-    from importlib import util
-    spec = util.spec_from_file_location("apd_build_for_flags", os.path.join(ROOT, "apd-mvs_amd", "build.py"))
-    builder = util.module_from_spec(spec)
-    spec.loader.exec_module(builder)
-    assert "apd_points_clusters.hip" in builder.SOURCES
-    flags = [f for f in builder.FLAGS if not f.startswith("-W")]
-    r = subprocess.run([builder.HIPCC] + flags + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                                                  os.path.join(builder.CSRC, "apd_points_clusters.hip"), "-o", str(tmp_path / "clusters.o")],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    found, name = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"remark:.*?\s(Function Name|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
-        if m and m.group(1) == "Function Name":
-            name = m.group(2)
-        elif m and name is not None:
-            found.setdefault(name, {})[m.group(1)] = m.group(2)
+    found = walk_kernel_resources("k_cluster_link", tmp_path)
     for kernel in ("k_cluster_link", "k_cluster_flatten", "k_cluster_reduce", "k_cluster_emit"):
         assert len([k for k in found if kernel in k]) == 1, (kernel, sorted(found))
     for name, v in found.items():

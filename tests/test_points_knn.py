@@ -7,12 +7,12 @@ import ctypes as C
 import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import fusion_cases
+from common import walk_kernel_resources
 import points_knn_checker as PK
 import points_radius_checker as PR
 import points_voxel_checker as PV
@@ -397,9 +397,9 @@ def test_no_gpu_means_the_scores_fail_loudly(pkg):
     pts = from_cloud(pkg, cloud([[0.5, 0, 0], [0.6, 0, 0]]), [4], [5], [[]])
     out, removed, threshold = C.c_void_p(1234), C.c_longlong(-7), C.c_double(-3.5)
     assert L.apd_points_remove_statistical(pts._p, 1.0, None, 1, 1.0, C.byref(out), C.byref(removed), C.byref(threshold)) != 0
-    assert L.apd_fusion_last_error().startswith(b"apd_points_remove_statistical: ")
+    assert L.apd_fusion_last_error().startswith(b"apd_points_remove_statistical: hipSetDevice(")
     assert out.value == 1234 and removed.value == -7 and threshold.value == -3.5
-    with pytest.raises(pkg.ApdError, match="apd_points_knn_mean_distances: "):
+    with pytest.raises(pkg.ApdError, match=r"apd_points_knn_mean_distances: hipSetDevice\("):
         pts.knn_mean_distances(1.0, 1)
     pts.close()
 
@@ -424,25 +424,6 @@ def test_real_cloud_choice_is_not_vacuous(ob, vis, radius_checker, checker, name
 def test_the_selection_kernel_uses_no_scratch_memory(tmp_path):
     """k_knn_mean keeps a lane's k values in LDS: the compiler reports 0 bytes of scratch per lane for it (k is a runtime argument
     of the one kernel, so this holds for every k), and no spilled register."""
-    from importlib import util
-    spec = util.spec_from_file_location("apd_build_for_flags", os.path.join(ROOT, "apd-mvs_amd", "build.py"))
-    builder = util.module_from_spec(spec)
-    spec.loader.exec_module(builder)
-    flags = [f for f in builder.FLAGS if not f.startswith("-W")]
-    r = subprocess.run([builder.HIPCC] + flags + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                                                  os.path.join(builder.CSRC, "apd_points_knn.hip"), "-o", str(tmp_path / "knn.o")],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    found, name = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"remark:.*?\s(Function Name|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
-        if m and m.group(1) == "Function Name":
-            name = m.group(2)
-        elif m and name is not None:
-            found.setdefault(name, {})[m.group(1)] = m.group(2)
-    mine = [v for k, v in found.items() if "k_knn_mean" in k]
-    assert len(mine) == 1, sorted(found)
-    assert mine[0]["ScratchSize [bytes/lane]"] == "0" and mine[0]["VGPRs Spill"] == "0" and mine[0]["SGPRs Spill"] == "0", mine[0]
-    assert mine[0]["LDS Size [bytes/block]"] == "0"   # no static LDS: the k * 64 slots are the dynamic region
+    found = walk_kernel_resources("k_knn_mean", tmp_path)   # no static LDS: the k * 64 slots are the dynamic region
     for name, v in found.items():
         assert v["ScratchSize [bytes/lane]"] == "0", name

@@ -6,12 +6,12 @@ apd_points_with_estimated_normals, which need no device; objects without points;
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import fusion_cases
+from common import walk_kernel_resources
 import points_normals_checker as PN
 import points_radius_checker as PR
 import points_voxel_checker as PV
@@ -509,9 +509,9 @@ def test_no_gpu_means_the_estimate_fails_loudly(pkg):
     pts = from_cloud(pkg, cloud([[0.5, 0, 0], [0.6, 0, 0], [0.6, 0.1, 0]]), [4], [5], [[]])
     out, estimated = C.c_void_p(1234), C.c_longlong(-7)
     assert L.apd_points_with_estimated_normals(pts._p, 1.0, None, 2, C.byref(out), C.byref(estimated)) != 0
-    assert L.apd_fusion_last_error().startswith(b"apd_points_with_estimated_normals: ")
+    assert L.apd_fusion_last_error().startswith(b"apd_points_with_estimated_normals: hipSetDevice(")
     assert out.value == 1234 and estimated.value == -7
-    with pytest.raises(pkg.ApdError, match="apd_points_estimate_normals: "):
+    with pytest.raises(pkg.ApdError, match=r"apd_points_estimate_normals: hipSetDevice\("):
         pts.estimate_normals(1.0, 2)
     pts.close()
 
@@ -538,25 +538,6 @@ def test_real_cloud_choice_is_not_vacuous(ob, vis, radius_checker, checker):
 def test_the_normals_kernel_uses_no_scratch_memory(tmp_path):
     """k_point_normals keeps its ten sums, the matrix and the vectors in registers: the compiler reports 0 bytes of scratch per lane,
     no spilled register and no LDS for it, and no scratch for any kernel of the file."""
-    from importlib import util
-    spec = util.spec_from_file_location("apd_build_for_flags", os.path.join(ROOT, "apd-mvs_amd", "build.py"))
-    builder = util.module_from_spec(spec)
-    spec.loader.exec_module(builder)
-    flags = [f for f in builder.FLAGS if not f.startswith("-W")]
-    r = subprocess.run([builder.HIPCC] + flags + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                                                  os.path.join(builder.CSRC, "apd_points_normals.hip"), "-o", str(tmp_path / "normals.o")],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    found, name = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"remark:.*?\s(Function Name|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
-        if m and m.group(1) == "Function Name":
-            name = m.group(2)
-        elif m and name is not None:
-            found.setdefault(name, {})[m.group(1)] = m.group(2)
-    mine = [v for k, v in found.items() if "k_point_normals" in k]
-    assert len(mine) == 1, sorted(found)
-    assert mine[0]["ScratchSize [bytes/lane]"] == "0" and mine[0]["VGPRs Spill"] == "0" and mine[0]["SGPRs Spill"] == "0", mine[0]
-    assert mine[0]["LDS Size [bytes/block]"] == "0"
+    found = walk_kernel_resources("k_point_normals", tmp_path)
     for name, v in found.items():
         assert v["ScratchSize [bytes/lane]"] == "0", name

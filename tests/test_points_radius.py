@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import fusion_cases
+from common import walk_kernel_resources
 import points_radius_checker as PR
 import points_voxel_checker as PV
 import vis_checker as VC
@@ -373,16 +374,24 @@ def test_no_gpu_means_the_counts_fail_loudly(pkg):
     pts = from_cloud(pkg, cloud([[0.5, 0, 0], [0.6, 0, 0]]), [4], [5], [[]])
     out, removed = C.c_void_p(1234), C.c_longlong(-7)
     assert L.apd_points_remove_sparse(pts._p, 1.0, None, 1, C.byref(out), C.byref(removed)) != 0
-    assert L.apd_fusion_last_error().startswith(b"apd_points_remove_sparse: ")
+    assert L.apd_fusion_last_error().startswith(b"apd_points_remove_sparse: hipSetDevice(")
     assert out.value == 1234 and removed.value == -7
-    with pytest.raises(pkg.ApdError, match="apd_points_neighbour_counts: "):
+    with pytest.raises(pkg.ApdError, match=r"apd_points_neighbour_counts: hipSetDevice\("):
         pts.neighbour_counts(1.0)
     pts.close()
 
 
 # --------------------------------------------------------------------------------------------------------------------
-# the real clouds of the device tests
+# the real clouds of the device tests; the kernel's resources
 # --------------------------------------------------------------------------------------------------------------------
+
+def test_the_count_kernel_uses_no_scratch_memory(tmp_path):
+    """k_neighbour_count, the walk with the least around it: the compiler reports 0 bytes of scratch per lane, no spilled register,
+    no LDS and 8 waves per SIMD for it, and no scratch for any kernel of the file."""
+    found = walk_kernel_resources("k_neighbour_count", tmp_path)
+    for name, v in found.items():
+        assert v["ScratchSize [bytes/lane]"] == "0", name
+
 
 @pytest.mark.parametrize("name,variant", [(n, v) for n, v, _ in REAL_CLOUDS])
 def test_real_cloud_radius_removes_some_points_and_not_all(ob, vis, checker, name, variant):
