@@ -197,6 +197,9 @@ def lib():
     L.apd_points_estimate_normals.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p, C.c_void_p]
     L.apd_points_with_estimated_normals.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.POINTER(C.c_void_p),
                                                     C.POINTER(C.c_longlong)]
+    L.apd_points_smoothed_positions.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p, C.c_void_p]
+    L.apd_points_with_smoothed_positions.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_uint, C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_longlong)]
     L.apd_points_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_void_p, C.c_void_p]
     L.apd_points_rendered_visibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
     L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
@@ -259,7 +262,10 @@ class Points:
     a radius of each other (apd_points_components) and remove_small_components() gives the points of the components that are large
     enough (apd_points_remove_small_components), likewise.  estimate_normals() gives every point's normal and surface variation
     from its neighbourhood within a radius (apd_points_estimate_normals) and with_estimated_normals() these points with those
-    normals in place of the stored ones (apd_points_with_estimated_normals), likewise.  render() draws the points into a camera
+    normals in place of the stored ones (apd_points_with_estimated_normals), likewise.  smoothed_positions() gives every point's
+    position projected on the weighted least-squares plane of its neighbourhood within a radius and the signed distance it moved
+    (apd_points_smoothed_positions) and with_smoothed_positions() these points with those positions, iterated, in place of the
+    stored ones (apd_points_with_smoothed_positions), likewise: the one step that moves a point.  render() draws the points into a camera
     with a z-buffer: the depth and the index of the nearest point per pixel (apd_points_render); with_rendered_visibility() gives
     these points as a merged object whose lists name the cameras that see each point, occlusion included
     (apd_points_rendered_visibility)."""
@@ -511,6 +517,55 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Points(out, self.device), int(estimated.value)
+
+    def smoothed_positions(self, radius, min_neighbours, origin=None):
+        """apd_points_smoothed_positions: (xyz float32 [N, 3], offset float32 [N]) -- for a point with at least `min_neighbours`
+        (2 .. 2^31 - 1) other points within `radius` (the relation of neighbour_counts) its position projected on the weighted
+        least-squares plane of the point and those neighbours (contract C16: the weight (1 - d^2 / radius^2)^2, binary64 sums in cell
+        order, the eigen-solve of estimate_normals) and the signed distance it moved along that plane's normal, which is signed
+        like the stored one; for any other point, one outside the grid among them, its position and +inf.  One iteration.  numpy
+        arrays for host points, torch tensors on their device for device points.  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.smoothed_positions: the points are closed")
+        if not 0 <= int(min_neighbours) <= 0xFFFFFFFF:
+            raise ValueError("Points.smoothed_positions: a minimum of %r neighbours, not in 0 .. 2^32 - 1" % (min_neighbours,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        nothing = (C.c_float * 3)()   # where an object without points gets its no results: the library refuses NULL for both
+        if self.on_device:
+            import torch
+            xyz = torch.empty((self.count, 3), dtype=torch.float32, device=torch.device("cuda", self.device))
+            offset = torch.empty((self.count,), dtype=torch.float32, device=torch.device("cuda", self.device))
+            torch.cuda.synchronize(xyz.device)
+            addresses = [a.data_ptr() if self.count else C.addressof(nothing) for a in (xyz, offset)]
+        else:
+            xyz, offset = np.zeros((self.count, 3), np.float32), np.zeros(self.count, np.float32)
+            addresses = [a.ctypes.data if self.count else C.addressof(nothing) for a in (xyz, offset)]
+        rc = L.apd_points_smoothed_positions(self._p, float(radius), org, int(min_neighbours), C.c_void_p(addresses[0]), C.c_void_p(addresses[1]))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return xyz, offset
+
+    def with_smoothed_positions(self, radius, min_neighbours, iterations=1, origin=None):
+        """apd_points_with_smoothed_positions: (Points, moved) -- these points in their order with `xyz` replaced by the positions
+        of smoothed_positions(radius, min_neighbours) applied `iterations` (1 .. 16) times, each iteration to every point at once
+        on the grid of the positions before it, and every other array and the lists as they are; `moved` is the number of points
+        that had an estimate in at least one iteration, the others keep their position.  A merged object gives a merged object.
+        A curved surface shrinks towards its centre of curvature by up to radius^2 / (2 R) per iteration.  Computed on these
+        points' device; the result lives where they live."""
+        if not self._p:
+            raise ApdError("Points.with_smoothed_positions: the points are closed")
+        if not 0 <= int(min_neighbours) <= 0xFFFFFFFF:
+            raise ValueError("Points.with_smoothed_positions: a minimum of %r neighbours, not in 0 .. 2^32 - 1" % (min_neighbours,))
+        if not 0 <= int(iterations) <= 0xFFFFFFFF:
+            raise ValueError("Points.with_smoothed_positions: %r iterations, not in 0 .. 2^32 - 1" % (iterations,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        out, moved = C.c_void_p(), C.c_longlong(0)
+        rc = L.apd_points_with_smoothed_positions(self._p, float(radius), org, int(min_neighbours), int(iterations), C.byref(out), C.byref(moved))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device), int(moved.value)
 
     def render(self, camera, splat=0):
         """apd_points_render: (depth float32 [height, width], index uint32 [height, width]) -- these points drawn into `camera` (a

@@ -182,6 +182,10 @@ void SetFusionPlyRadiusFilter(float radius, unsigned min_neighbours);
 // that radius of each other -- has at least min_size points (apd_points_remove_small_components, after everything above that is
 // asked for too); an APD.ply.vis is then that of the points kept.  0: off
 void SetFusionPlyComponentFilter(float radius, unsigned min_size);
+// additive: radius > 0: the points of <dense>/APD/APD.ply stand where `iterations` projections on the weighted plane of each point's
+// neighbourhood within that radius put them, a point moving where it has at least min_neighbours other points there
+// (apd_points_with_smoothed_positions, after everything above that is asked for too); an APD.ply.vis keeps its lists.  0: off
+void SetFusionPlySmooth(float radius, unsigned min_neighbours, unsigned iterations);
 // additive: radius > 0: the points of <dense>/APD/APD.ply carry normals estimated from the neighbourhood of each within that radius,
 // where it has at least min_neighbours other points (apd_points_with_estimated_normals, after everything above that is asked for
 // too); the file shows them with normals in it, and without them keeps its bytes.  0: off

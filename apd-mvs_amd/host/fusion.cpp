@@ -38,17 +38,20 @@ float g_fusion_ply_radius = 0.0f;       // SetFusionPlyRadiusFilter; 0: off
 unsigned g_fusion_ply_radius_min = 0;
 float g_fusion_ply_component_radius = 0.0f;  // SetFusionPlyComponentFilter; 0: off
 unsigned g_fusion_ply_component_min = 0;
+float g_fusion_ply_smooth_radius = 0.0f;  // SetFusionPlySmooth; 0: off
+unsigned g_fusion_ply_smooth_min = 0;
+unsigned g_fusion_ply_smooth_iterations = 1;
 float g_fusion_ply_normals_radius = 0.0f;  // SetFusionPlyEstimateNormals; 0: off
 unsigned g_fusion_ply_normals_min = 0;
 int g_fusion_ply_render_splat = -1;        // SetFusionPlyRenderVis; -1: off
 float g_fusion_ply_render_tolerance = 0.0f;
 
-// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-estimate-normals or --ply-render-vis:
-// APD.ply is written from the points after the fusion, not by it
+// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-smooth, --ply-estimate-normals or
+// --ply-render-vis: APD.ply is written from the points after the fusion, not by it
 bool ply_from_points()
 {
     return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f ||
-           g_fusion_ply_component_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f || g_fusion_ply_render_splat >= 0;
+           g_fusion_ply_component_radius > 0.0f || g_fusion_ply_smooth_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f || g_fusion_ply_render_splat >= 0;
 }
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
@@ -160,6 +163,13 @@ void SetFusionPlyComponentFilter(float radius, unsigned min_size)
     g_fusion_ply_component_min = min_size;
 }
 
+void SetFusionPlySmooth(float radius, unsigned min_neighbours, unsigned iterations)
+{
+    g_fusion_ply_smooth_radius = radius;
+    g_fusion_ply_smooth_min = min_neighbours;
+    g_fusion_ply_smooth_iterations = iterations;
+}
+
 void SetFusionPlyEstimateNormals(float radius, unsigned min_neighbours)
 {
     g_fusion_ply_normals_radius = radius;
@@ -180,6 +190,8 @@ namespace {
 // is no outlier (apd_points_remove_statistical) and prints how many went and the threshold; --ply-radius-filter: replaces what these left by the points with enough neighbours
 // (apd_points_remove_sparse) and prints how many went; --ply-component-filter: replaces what these left by the points of the connected
 // components that are large enough (apd_points_remove_small_components) and prints the components and how many points went;
+// --ply-smooth: replaces the positions of what these left by their projections on each neighbourhood's weighted plane
+// (apd_points_with_smoothed_positions) and prints how many points moved;
 // --ply-estimate-normals: replaces the normals of what these left by those of each point's neighbourhood
 // (apd_points_with_estimated_normals) and prints how many points got one; --ply-render-vis: replaces the lists of what these left by
 // the views that see each point when the cloud is drawn into full_cameras, the views' cameras at the size of their images
@@ -241,6 +253,18 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
         if (st == APD_OK) {
             std::cout << "Removed " << removed << " of " << apd_points_count(points) << " points in connected components of fewer than "
                       << g_fusion_ply_component_min << " points, of " << components << " components within " << g_fusion_ply_component_radius << std::endl;
+            apd_points_destroy(points);
+            points = kept;
+        }
+    }
+    if (st == APD_OK && g_fusion_ply_smooth_radius > 0.0f) {
+        apd_points_t kept = nullptr;
+        long long moved = 0;
+        st = apd_points_with_smoothed_positions(points, g_fusion_ply_smooth_radius, nullptr, g_fusion_ply_smooth_min, g_fusion_ply_smooth_iterations, &kept,
+                                                &moved);
+        if (st == APD_OK) {
+            std::cout << "Smoothed the positions of " << moved << " of " << apd_points_count(points) << " points with at least " << g_fusion_ply_smooth_min
+                      << " neighbours within " << g_fusion_ply_smooth_radius << " in " << g_fusion_ply_smooth_iterations << " iteration(s)" << std::endl;
             apd_points_destroy(points);
             points = kept;
         }

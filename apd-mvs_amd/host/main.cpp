@@ -4,7 +4,8 @@
 //       [--fusion eth|tat-intermediate|tat-advanced] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]]
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
 //       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN]
-//       [--ply-component-filter RADIUS,MIN] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--filtered-maps]
+//       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
+//       [--ply-render-vis SPLAT,TOL] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -36,10 +37,17 @@
 // RADIUS at the origin; a detached clump goes whole, however dense it is) and, with --ply-vis, APD.ply.vis their lists; applied
 // last, after --ply-radius-filter.  With every --fusion; the number of components and of removed points is printed.  RADIUS,MIN
 // as for --ply-radius-filter, or the usage line is all that happens.
+// --ply-smooth RADIUS,MIN[,ITERATIONS]: the points of APD.ply stand, where a point has at least MIN other points within RADIUS,
+// on the weighted least-squares plane of that neighbourhood -- the weight of a neighbour at distance d is (1 - d^2 / RADIUS^2)^2 --
+// ITERATIONS times (1 .. 16, 1 when left out), every point at once in each (apd_points_with_smoothed_positions, on the grid of
+// cell size RADIUS at the origin): the depth noise along the viewing ray goes, a curved surface shrinks by up to RADIUS^2 / (2 R)
+// per iteration.  Applied after --ply-component-filter and before --ply-estimate-normals and --ply-render-vis, which then act on
+// the smoothed cloud.  With every --fusion; the number of points moved is printed; APD.ply.vis keeps its lists.  RADIUS,MIN as
+// for --ply-estimate-normals, or the usage line is all that happens.
 // --ply-estimate-normals RADIUS,MIN: the points of APD.ply carry, where a point has at least MIN other points within RADIUS, the
 // normal of that neighbourhood -- its direction of least variance, signed like the point's own normal
 // (apd_points_with_estimated_normals, on the grid of cell size RADIUS at the origin) -- instead of the reference pixel's or the mean
-// one; applied after --ply-component-filter.  With every --fusion; the number of points estimated is printed.  The flag
+// one; applied after --ply-component-filter and --ply-smooth.  With every --fusion; the number of points estimated is printed.  The flag
 // implies nothing else: the normals are in the file with --ply-normals, and without it APD.ply keeps its bytes.  RADIUS as for
 // --ply-radius-filter, MIN a count of 2 or more, or the usage line is all that happens.
 // --ply-render-vis SPLAT,TOL: APD.ply.vis (the flag implies --ply-vis) lists per point the views that see it, occlusion included:
@@ -206,6 +214,25 @@ bool ParseOptions(int argc, char **argv, Options &o)
             }
             o.ply_component_radius = r;
             o.ply_component_min = (unsigned)k;
+        } else if (a == "--ply-smooth") {
+            const std::string all = i + 1 < argc ? argv[++i] : "";
+            const size_t c1 = all.find(','), c2 = c1 == std::string::npos ? c1 : all.find(',', c1 + 1);
+            const std::string count = c1 == std::string::npos ? "" : all.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+            const std::string times = c2 == std::string::npos ? "1" : all.substr(c2 + 1);
+            char *end = nullptr;
+            const unsigned long long k = strtoull(count.c_str(), &end, 10);
+            const bool digits = !count.empty() && count.find_first_not_of("0123456789") == std::string::npos && *end == '\0' && k >= 2 && k <= 0x7fffffffull;
+            const unsigned long long n = strtoull(times.c_str(), &end, 10);
+            const bool iterations = !times.empty() && times.size() <= 2 && times.find_first_not_of("0123456789") == std::string::npos && n >= 1 && n <= 16;
+            float r = 0.0f;
+            if (!digits || !iterations || !real(all.substr(0, c1).c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
+                fprintf(stderr, "bad value '%s' of %s: RADIUS,MIN[,ITERATIONS], a positive number, a count of 2 or more and a count of 1 .. 16\n", all.c_str(),
+                        a.c_str());
+                return false;
+            }
+            o.ply_smooth_radius = r;
+            o.ply_smooth_min = (unsigned)k;
+            o.ply_smooth_iterations = (unsigned)n;
         } else if (a == "--ply-estimate-normals") {
             const std::string both = i + 1 < argc ? argv[++i] : "";
             const size_t comma = both.find(',');
@@ -444,13 +471,14 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
                         "  --ply-stat-filter RADIUS,K,RATIO: APD.ply (and APD.ply.vis) without the points whose mean distance to their K nearest neighbours within RADIUS is above mean + RATIO * deviation of the cloud's, after --ply-mean and --ply-voxel, before --ply-radius-filter.\n"
                         "  --ply-radius-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points that have fewer than MIN other points within RADIUS, after --ply-mean and --ply-voxel.\n"
                         "  --ply-component-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points of connected components of fewer than MIN points, two points being joined when they are within RADIUS of each other, after --ply-radius-filter.\n"
+                        "  --ply-smooth RADIUS,MIN[,ITERATIONS]: the points of APD.ply (and of what --ply-estimate-normals and --ply-render-vis then see) each projected on the weighted plane of the other points within RADIUS of it, where there are at least MIN (2 or more) of them, ITERATIONS (1 .. 16, default 1) times, after --ply-component-filter.\n"
                         "  --ply-estimate-normals RADIUS,MIN: the normals of the points of APD.ply (shown with --ply-normals) estimated from the other points within RADIUS of each, where there are at least MIN (2 or more) of them, after every other --ply-* flag but --ply-render-vis.\n"
                         "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag.\n");
         return EXIT_FAILURE;
@@ -473,6 +501,7 @@ int main(int argc, char **argv)
     SetFusionPlyStatFilter(opt.ply_stat_radius, opt.ply_stat_k, opt.ply_stat_ratio);
     SetFusionPlyRadiusFilter(opt.ply_radius, opt.ply_radius_min);
     SetFusionPlyComponentFilter(opt.ply_component_radius, opt.ply_component_min);
+    SetFusionPlySmooth(opt.ply_smooth_radius, opt.ply_smooth_min, opt.ply_smooth_iterations);
     SetFusionPlyEstimateNormals(opt.ply_normals_radius, opt.ply_normals_min);
     SetFusionPlyRenderVis(opt.ply_render_splat, opt.ply_render_tolerance);
 

@@ -45,6 +45,9 @@ struct Options {
     unsigned ply_radius_min = 0;          // RADIUS (apd_points_remove_sparse), after --ply-mean and --ply-voxel; radius 0: off
     float ply_component_radius = 0.0f;    // --ply-component-filter RADIUS,MIN: APD.ply (and APD.ply.vis) of the points whose connected component within
     unsigned ply_component_min = 0;       // RADIUS has at least MIN points (apd_points_remove_small_components), after --ply-radius-filter; radius 0: off
+    float ply_smooth_radius = 0.0f;       // --ply-smooth RADIUS,MIN[,ITERATIONS]: the points of APD.ply with each position projected on the weighted plane of
+    unsigned ply_smooth_min = 0;          // its neighbourhood within RADIUS where it has at least MIN others there, ITERATIONS (1 .. 16, default 1) times
+    unsigned ply_smooth_iterations = 1;   // (apd_points_with_smoothed_positions), after --ply-component-filter, before --ply-estimate-normals; radius 0: off
     float ply_normals_radius = 0.0f;      // --ply-estimate-normals RADIUS,MIN: the points of APD.ply with normals estimated from the neighbourhood within
     unsigned ply_normals_min = 0;         // RADIUS of each point that has at least MIN others there (apd_points_with_estimated_normals), last; radius 0: off
     int ply_render_splat = -1;            // --ply-render-vis SPLAT,TOL: APD.ply.vis (the flag implies --ply-vis) lists per point the views that see it when the

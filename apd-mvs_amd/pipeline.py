@@ -552,7 +552,7 @@ def average_points(scene, results, points, device=0):
 
 def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False,
          vis_path=None, average=False, voxel=None, voxel_origin=None, radius_filter=None, stat_filter=None, component_filter=None,
-         estimate_normals=None, render_visibility=None):
+         estimate_normals=None, render_visibility=None, smooth=None):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -581,8 +581,12 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     component_filter: (radius, min_size) -- applied last, after `average`, `voxel`, `stat_filter` and `radius_filter`: the file, the
     returned points and the .vis file are those of Points.remove_small_components(radius, min_size), the points whose connected
     component within the radius has at least that many points; the count returned is that of the points kept.
-    estimate_normals: (radius, min_neighbours) -- applied after `average`, `voxel`, `stat_filter`, `radius_filter` and
-    `component_filter`, since normals belong to the cloud that is kept: the file, the returned points and the .vis file are those of
+    smooth: (radius, min_neighbours, iterations) -- applied after `component_filter` and before `estimate_normals`: the file, the
+    returned points and the .vis file are those of Points.with_smoothed_positions(radius, min_neighbours, iterations), the same
+    points with each position projected on the weighted plane of its neighbourhood, `iterations` times; normals estimated and
+    visibility rendered afterwards belong to the smoothed cloud.
+    estimate_normals: (radius, min_neighbours) -- applied after `average`, `voxel`, `stat_filter`, `radius_filter`,
+    `component_filter` and `smooth`, since normals belong to the cloud that is kept: the file, the returned points and the .vis file are those of
     Points.with_estimated_normals(radius, min_neighbours), the same points with their normals re-estimated from the cloud's own
     geometry.  Without ply_normals in the options the step changes no byte of the file; it still acts on the returned points.
     render_visibility: (splat, rel_tolerance) -- applied last, after `estimate_normals`: the file, the returned points and the .vis
@@ -599,7 +603,7 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
         splat, rel_tolerance = render_visibility
         _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
                         voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                        component_filter=component_filter, estimate_normals=estimate_normals)
+                        component_filter=component_filter, estimate_normals=estimate_normals, smooth=smooth)
         kept, _ = whole.with_rendered_visibility([scene.cameras[v] for v in range(scene.num_views)], splat, rel_tolerance)
         whole.close()
         if ply_path is not None:
@@ -615,8 +619,24 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
         radius, min_neighbours = estimate_normals
         _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
                         voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                        component_filter=component_filter)
+                        component_filter=component_filter, smooth=smooth)
         kept, _ = whole.with_estimated_normals(radius, min_neighbours)
+        whole.close()
+        if ply_path is not None:
+            kept.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
+        if vis_path is not None:
+            kept.write_vis(vis_path)
+        if return_points:
+            return kept.count, kept
+        n = kept.count
+        kept.close()
+        return n
+    if smooth is not None:
+        radius, min_neighbours, iterations = smooth
+        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
+                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
+                        component_filter=component_filter)
+        kept, _ = whole.with_smoothed_positions(radius, min_neighbours, iterations)
         whole.close()
         if ply_path is not None:
             kept.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))

@@ -618,6 +618,40 @@ int apd_points_estimate_normals(apd_points_t p, float radius, const float *origi
                                 float *variation);
 int apd_points_with_estimated_normals(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, apd_points_t *out,
                                       long long *estimated);
+/* Smoothed positions: every point projected on the weighted least-squares plane of its neighbourhood, the step that takes the
+ * depth noise along the viewing ray out of a cloud before a Poisson or Delaunay mesher (PCL's MovingLeastSquares, CloudCompare,
+ * MeshLab), here on the points object, so that sources, support, view / pixel and the visibility lists survive it.  The only step
+ * that moves a point.  IEEE operations in the order given (contract C16; csrc/apd_smooth_math.h).
+ *   Neighbours.  Those of apd_points_neighbour_counts, on the grid of cell size `radius` at origin3 (NULL: 0, 0, 0).
+ *   Estimate.  A point at P with at least min_neighbours neighbours (itself not counted; min_neighbours is 2 .. 2^31 - 1): over
+ *   the point and its neighbours in ascending (cell, index) order, a term at Q has the weight w = t * t with t = 1 - d2 / r2 in
+ *   binary64, d2 the binary32 squared distance and r2 = radius * radius in binary32 -- 1 for the point itself, 0 at exactly the
+ *   radius -- and, with d = Q - P in binary32, the binary64 sums W of w, s of w * d and S of the six (w * d_a) * d_b.  The plane's
+ *   normal is that of apd_points_estimate_normals on these sums with n = W (the same solve, the same cap of 5 sweeps, signed like
+ *   the stored normal), as binary32.  With m = s / W and that normal n: h = (m_0 n_0 + m_1 n_1) + m_2 n_2; the new position is
+ *   (float)(P_a + h * n_a) and the offset (float)h, the signed distance moved along the returned normal.  |h| <= radius.
+ *   No estimate.  A point with fewer neighbours and a point outside the grid: its position is copied bit for bit and its offset
+ *   is +inf.
+ *   Iterations.  Simultaneous: iteration k takes every position from iteration k - 1, with the grid and the cell order rebuilt
+ *   from them; the stored normal stays p's own.  A point that moves out of the grid stays where it then is.
+ * apd_points_smoothed_positions: one iteration.  xyz3 takes 3 * apd_points_count(p) floats and offset apd_points_count(p), host
+ * memory for host-resident points, device memory on p's device for device-resident ones; either may be NULL, not both.
+ * apd_points_with_smoothed_positions: `iterations` is 1 .. 16.  *out is a new object with p's points in p's order, every array
+ * copied and `xyz` replaced by the positions after the last iteration; it lives where p lives, is merged when p is and then
+ * carries p's lists; *moved (may be NULL) is the number of points that had an estimate in at least one iteration.  p is left as
+ * it is.  Host-resident points go up once and the result comes down once.
+ * Both are computed on p's device, on its null stream, whatever memory p is in; there is no host implementation.  An object
+ * without points gives no results, or an object without points and *moved = 0, with no device touched.  The work per iteration
+ * is that of apd_points_estimate_normals at the same radius, with one binary64 division and a few multiplications more per
+ * neighbour.  Plane projection shrinks a curved surface towards its centre of curvature by about the sagitta of the
+ * neighbourhood, radius^2 / (2 R) and less, per iteration: choose the radius and the iterations with that in mind.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_smoothed_positions: ..." or
+ * "apd_points_with_smoothed_positions: ..." (apd_fusion_last_error): what apd_points_neighbour_counts refuses, both of xyz3 and
+ * offset NULL, a min_neighbours outside 2 .. 2^31 - 1, iterations outside 1 .. 16; APD_ERR_UNSUPPORTED for 2^31 or more points.
+ * *out and *moved are untouched when the call fails. */
+int apd_points_smoothed_positions(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, float *xyz3, float *offset);
+int apd_points_with_smoothed_positions(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, unsigned iterations,
+                                       apd_points_t *out, long long *moved);
 /* The cloud drawn into a camera with a z-buffer, and from such maps the views that see each point, occlusion included: what the
  * cleaned cloud looks like from a camera (a depth map and a point-index map, to inspect holes, to derive a mask, to compare with a
  * view's own depth map), and the visibility lists COLMAP's Delaunay mesher and Poisson trimming read, rebuilt for the cloud as it
