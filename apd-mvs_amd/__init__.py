@@ -7,6 +7,7 @@ library is missing or a GPU call fails, this module raises.
 The directory is called `apd-mvs_amd` (not importable by name); `__graft_entry__.load_package()`
 registers it as the module `apd_mvs_amd`.
 """
+import collections
 import ctypes as C
 import os
 
@@ -200,6 +201,9 @@ def lib():
     L.apd_points_smoothed_positions.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p, C.c_void_p]
     L.apd_points_with_smoothed_positions.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_uint, C.POINTER(C.c_void_p),
                                                      C.POINTER(C.c_longlong)]
+    L.apd_points_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    L.apd_points_score.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsScore)]
+    L.apd_points_read_ply.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.apd_points_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_void_p, C.c_void_p]
     L.apd_points_rendered_visibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
     L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
@@ -234,6 +238,16 @@ def default_fusion_options(**kw):
     return o
 
 
+class PointsScore(C.Structure):
+    """apd_points_score_t."""
+    _fields_ = [(n, C.c_longlong) for n in ("n_p", "n_q", "p_within", "q_within")] + \
+               [(n, C.c_double) for n in ("precision", "recall", "fscore", "mean_p", "mean_q")]
+
+
+# What Points.score returns: the nine fields of apd_points_score_t
+Score = collections.namedtuple("Score", [n for n, _ in PointsScore._fields_])
+
+
 class _Borrowed:
     """Memory of a Points object as an array interface; keeps its owner alive."""
 
@@ -265,7 +279,10 @@ class Points:
     normals in place of the stored ones (apd_points_with_estimated_normals), likewise.  smoothed_positions() gives every point's
     position projected on the weighted least-squares plane of its neighbourhood within a radius and the signed distance it moved
     (apd_points_smoothed_positions) and with_smoothed_positions() these points with those positions, iterated, in place of the
-    stored ones (apd_points_with_smoothed_positions), likewise: the one step that moves a point.  render() draws the points into a camera
+    stored ones (apd_points_with_smoothed_positions), likewise: the one step that moves a point.  nearest() gives for every point
+    the nearest point of another Points within a radius (apd_points_nearest), score() the precision, recall and F-score of these
+    points against another Points at a threshold (apd_points_score), and read_ply() makes a Points of a PLY file, a ground truth
+    for instance (apd_points_read_ply).  render() draws the points into a camera
     with a z-buffer: the depth and the index of the nearest point per pixel (apd_points_render); with_rendered_visibility() gives
     these points as a merged object whose lists name the cameras that see each point, occlusion included
     (apd_points_rendered_visibility)."""
@@ -566,6 +583,66 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Points(out, self.device), int(moved.value)
+
+    def nearest(self, other, radius, origin=None):
+        """apd_points_nearest: (distance float32 [N], index int32 [N]) -- per point the distance to the nearest point of `other` (a
+        Points, which may be this one) within `radius` and that point's index in `other` (contract C17: both clouds on the grid of
+        cell size `radius` with a corner at `origin`, 0, 0, 0 by default; the candidates are the points of `other` in the 27 cells
+        around the point's; among equally near ones the smallest index), +inf and -1 where there is none.  numpy arrays for host
+        points, torch tensors on their device for device points.  Computed on these points' device: host-resident `other` goes up
+        for the call, device-resident `other` must live on that device."""
+        if not self._p:
+            raise ApdError("Points.nearest: the points are closed")
+        if not isinstance(other, Points) or not other._p:
+            raise ApdError("Points.nearest: the other points are closed or not a Points")
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        nothing = (C.c_float * 1)()   # where an object without points gets its no results: the library refuses NULL for both
+        if self.on_device:
+            import torch
+            distance = torch.empty((self.count,), dtype=torch.float32, device=torch.device("cuda", self.device))
+            index = torch.empty((self.count,), dtype=torch.int32, device=torch.device("cuda", self.device))
+            torch.cuda.synchronize(distance.device)
+            addresses = [a.data_ptr() if self.count else C.addressof(nothing) for a in (distance, index)]
+        else:
+            distance, index = np.zeros(self.count, np.float32), np.zeros(self.count, np.int32)
+            addresses = [a.ctypes.data if self.count else C.addressof(nothing) for a in (distance, index)]
+        rc = L.apd_points_nearest(self._p, other._p, float(radius), org, C.c_void_p(addresses[0]), C.c_void_p(addresses[1]))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return distance, index
+
+    def score(self, truth, threshold, origin=None):
+        """apd_points_score: Score(n_p, n_q, p_within, q_within, precision, recall, fscore, mean_p, mean_q) of these points against
+        `truth` (a Points) at `threshold`: precision is the share of these points that have a point of `truth` within the threshold
+        (p_within of n_p), recall the share of `truth` that has one of these within it (q_within of n_q), fscore their harmonic
+        mean, mean_p and mean_q the mean distances of those that have one (contract C17; nearest() with radius = threshold in
+        both directions).  Nearest-neighbour precision and recall at one threshold, with no registration, cropping or occlusion
+        reasoning: scores compare with each other.  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.score: the points are closed")
+        if not isinstance(truth, Points) or not truth._p:
+            raise ApdError("Points.score: the other points are closed or not a Points")
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        out = PointsScore()
+        rc = L.apd_points_score(self._p, truth._p, float(threshold), org, C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Score(*[getattr(out, n) for n in Score._fields])
+
+    @classmethod
+    def read_ply(cls, path, device=0, on_device=False):
+        """apd_points_read_ply: a Points of the vertices of a binary little-endian PLY file -- what write_ply() writes and what ETH3D
+        and Tanks and Temples ship as ground truth: float x y z, float nx ny nz and uchar red green blue (or diffuse_*) when the
+        file has them (zeros otherwise), any other scalar property skipped, the faces of a mesh ignored.  The points name one view of
+        1 x 1 without sources.  on_device: they live on GPU `device`; otherwise in host memory and no device is touched."""
+        L = lib()
+        out = C.c_void_p()
+        rc = L.apd_points_read_ply(os.fspath(path).encode(), int(device), int(bool(on_device)), C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return cls(out, device)
 
     def render(self, camera, splat=0):
         """apd_points_render: (depth float32 [height, width], index uint32 [height, width]) -- these points drawn into `camera` (a

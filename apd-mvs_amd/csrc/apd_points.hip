@@ -1,6 +1,6 @@
 // apd_points.hip -- the life and the files of a points object (apd_points_t of include/apd_mi355x.h, struct apd_points of
 // apd_points_host.h): the operations on the table of its arrays, the one function that makes a new object, the accessors,
-// apd_points_create, apd_points_destroy, apd_points_write_ply and apd_points_write_vis, and compact_points: an object without some
+// apd_points_create, apd_points_destroy, apd_points_write_ply, apd_points_write_vis and apd_points_read_ply, and compact_points: an object without some
 // of its points.  Who fills one: the fusions (apd_fusion_call.hip), apd_points_average.hip, apd_points_merge.hip,
 // apd_points_radius.hip (through compact_points); its visibility lists: apd_points_vis.hip.
 //
@@ -10,6 +10,9 @@
 // apd_points_write_ply: ExportPointCloud's file (APD.cpp:214-254) of any points object, the fusion's own or an averaged one: the
 // header, then the 15-byte or 27-byte records k_fusion_compact packs (apd_fusion_call.hip), packed here on the host from the
 // arrays (device-resident points come down in chunks).
+//
+// apd_points_read_ply: the way back, and the way in of a cloud made elsewhere (a ground truth): the header parsed line by line into
+// the offsets of the fields kept within a vertex record, the records read in chunks on the host, then apd_points_create.
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
@@ -396,6 +399,224 @@ extern "C" int apd_points_write_vis(apd_points_t p, const char *path)
         return APD_ERR_IO;
     }
     return APD_OK;
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// apd_points_read_ply
+// --------------------------------------------------------------------------------------------------------------------
+
+namespace {
+
+// A scalar type of a PLY header: its size in bytes, 0: not one; *real32 / *byte8: it is `float` / `uchar`
+size_t ply_scalar(const std::string &type, bool *real32, bool *byte8)
+{
+    static const struct {
+        const char *name;
+        size_t size;
+    } kinds[] = {{"char", 1}, {"uchar", 1}, {"int8", 1}, {"uint8", 1}, {"short", 2}, {"ushort", 2}, {"int16", 2}, {"uint16", 2},
+                 {"int", 4},  {"uint", 4},  {"int32", 4}, {"uint32", 4}, {"float", 4}, {"float32", 4}, {"double", 8}, {"float64", 8}};
+    *real32 = type == "float" || type == "float32";
+    *byte8 = type == "uchar" || type == "uint8";
+    for (const auto &k : kinds) {
+        if (type == k.name) {
+            return k.size;
+        }
+    }
+    return 0;
+}
+
+std::vector<std::string> words_of(const std::string &line)
+{
+    std::vector<std::string> words;
+    size_t at = 0;
+    while (at < line.size()) {
+        const size_t from = line.find_first_not_of(" \t\r", at);
+        if (from == std::string::npos) {
+            break;
+        }
+        const size_t to = line.find_first_of(" \t\r", from);
+        words.push_back(line.substr(from, to == std::string::npos ? to : to - from));
+        at = to == std::string::npos ? line.size() : to;
+    }
+    return words;
+}
+
+// Where the fields apd_points_read_ply keeps stand in a vertex record; -1: not in the file
+struct PlyLayout {
+    long long count = -1;  // of `element vertex`; -1: none seen
+    size_t record = 0;
+    int xyz[3] = {-1, -1, -1}, normal[3] = {-1, -1, -1}, bgr[3] = {-1, -1, -1};
+};
+
+int refuse_ply(int code, const char *path, const std::string &why)
+{
+    err() = std::string("apd_points_read_ply: ") + path + ": " + why;  // no length limit: not through set_error
+    return code;
+}
+
+// The header of the file at f, up to and including end_header
+int read_ply_header(FILE *f, const char *path, PlyLayout &layout)
+{
+    std::string line;
+    bool first = true, format = false, in_vertex = false, after_vertex = false;
+    for (;;) {
+        line.clear();
+        int c = 0;
+        while ((c = fgetc(f)) != EOF && c != '\n') {
+            line.push_back((char)c);
+            if (line.size() > 4096) {
+                return refuse_ply(APD_ERR_INVALID, path, "a header line of more than 4096 bytes");
+            }
+        }
+        if (c == EOF) {
+            return first && line != "ply" ? refuse_ply(APD_ERR_INVALID, path, "not a PLY file") : refuse_ply(APD_ERR_IO, path, "the file ends inside the header");
+        }
+        const std::vector<std::string> w = words_of(line);
+        if (first) {
+            if (w.size() != 1 || w[0] != "ply") {
+                return refuse_ply(APD_ERR_INVALID, path, "not a PLY file");
+            }
+            first = false;
+            continue;
+        }
+        if (w.empty() || w[0] == "comment" || w[0] == "obj_info") {
+            continue;
+        }
+        if (w[0] == "end_header") {
+            break;
+        }
+        if (w[0] == "format") {
+            if (w.size() != 3 || w[1] != "binary_little_endian" || w[2] != "1.0") {
+                return refuse_ply(APD_ERR_INVALID, path, "format " + (w.size() > 1 ? w[1] : std::string("?")) + ", not binary_little_endian 1.0");
+            }
+            format = true;
+        } else if (w[0] == "element") {
+            if (w.size() != 3) {
+                return refuse_ply(APD_ERR_INVALID, path, "a malformed element line");
+            }
+            in_vertex = w[1] == "vertex";
+            if (in_vertex) {
+                char *end = nullptr;
+                const long long n = strtoll(w[2].c_str(), &end, 10);
+                if (layout.count >= 0 || w[2].find_first_not_of("0123456789") != std::string::npos || *end != '\0' || w[2].size() > 18) {
+                    return refuse_ply(APD_ERR_INVALID, path, "element vertex " + w[2] + ", not one count of vertices");
+                }
+                layout.count = n;
+            } else if (layout.count < 0) {
+                return refuse_ply(APD_ERR_INVALID, path, "element " + w[1] + " before element vertex");
+            } else {
+                after_vertex = true;
+            }
+        } else if (w[0] == "property") {
+            if (after_vertex) {
+                continue;  // of an element that is not read
+            }
+            if (!in_vertex) {
+                return refuse_ply(APD_ERR_INVALID, path, "a property before any element");
+            }
+            if (w.size() >= 2 && w[1] == "list") {
+                return refuse_ply(APD_ERR_INVALID, path, "a list property in element vertex");
+            }
+            bool real32 = false, byte8 = false;
+            const size_t size = w.size() == 3 ? ply_scalar(w[1], &real32, &byte8) : 0;
+            if (size == 0) {
+                return refuse_ply(APD_ERR_INVALID, path, "a malformed property line: " + line);
+            }
+            static const char *const coordinate[3] = {"x", "y", "z"}, *const normal[3] = {"nx", "ny", "nz"}, *const colour[3] = {"blue", "green", "red"};
+            for (int a = 0; a < 3; ++a) {
+                if (w[2] == coordinate[a]) {
+                    if (!real32) {
+                        return refuse_ply(APD_ERR_INVALID, path, "coordinate " + w[2] + " is " + w[1] + ", not float");
+                    }
+                    layout.xyz[a] = (int)layout.record;
+                } else if (w[2] == normal[a] && real32) {
+                    layout.normal[a] = (int)layout.record;
+                } else if ((w[2] == colour[a] || w[2] == std::string("diffuse_") + colour[a]) && byte8) {
+                    layout.bgr[a] = (int)layout.record;
+                }
+            }
+            layout.record += size;
+            if (layout.record > 65536) {
+                return refuse_ply(APD_ERR_INVALID, path, "a vertex record of more than 65536 bytes");
+            }
+        } else {
+            return refuse_ply(APD_ERR_INVALID, path, "an unknown header line: " + line);
+        }
+    }
+    if (!format) {
+        return refuse_ply(APD_ERR_INVALID, path, "no format line");
+    }
+    if (layout.count < 0) {
+        return refuse_ply(APD_ERR_INVALID, path, "no element vertex");
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (layout.xyz[a] < 0) {
+            return refuse_ply(APD_ERR_INVALID, path, std::string("no float coordinate ") + "xyz"[a] + " in element vertex");
+        }
+    }
+    return APD_OK;
+}
+
+}  // namespace
+
+extern "C" int apd_points_read_ply(const char *path, int device, int on_device, apd_points_t *out)
+{
+    err().clear();
+    if (!path || !out) {
+        return apd::set_error(err(), APD_ERR_INVALID, "apd_points_read_ply: null argument");
+    }
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        return refuse_ply(APD_ERR_IO, path, "cannot read the file");
+    }
+    PlyLayout layout;
+    if (const int rc = read_ply_header(f, path, layout); rc != APD_OK) {
+        fclose(f);
+        return rc;
+    }
+    const size_t n = (size_t)layout.count;
+    const bool normals = layout.normal[0] >= 0 && layout.normal[1] >= 0 && layout.normal[2] >= 0;
+    const bool colours = layout.bgr[0] >= 0 && layout.bgr[1] >= 0 && layout.bgr[2] >= 0;
+    std::vector<float> xyz, normal;
+    std::vector<uint8_t> bgr, records;
+    const size_t kChunk = std::max<size_t>(((size_t)1 << 24) / layout.record, 1);  // records per fread: 16 MiB of them
+    bool ok = true;
+    for (size_t k0 = 0; k0 < n && ok; k0 += kChunk) {
+        const size_t m = std::min(n - k0, kChunk);
+        records.resize(m * layout.record);
+        ok = fread(records.data(), 1, records.size(), f) == records.size();
+        xyz.resize(3 * (k0 + (ok ? m : 0)));  // grows with what the file holds, not with what its header says
+        normal.resize(xyz.size(), 0.0f);
+        bgr.resize(xyz.size(), 0);
+        for (size_t k = 0; k < m && ok; ++k) {  // little endian floats, as the host's memcpy reads them
+            const uint8_t *rec = records.data() + k * layout.record;
+            for (int a = 0; a < 3; ++a) {
+                memcpy(&xyz[3 * (k0 + k) + a], rec + layout.xyz[a], 4);
+                if (normals) {
+                    memcpy(&normal[3 * (k0 + k) + a], rec + layout.normal[a], 4);
+                }
+                if (colours) {
+                    bgr[3 * (k0 + k) + a] = rec[layout.bgr[a]];
+                }
+            }
+        }
+    }
+    fclose(f);
+    if (!ok) {
+        return refuse_ply(APD_ERR_IO, path, "the file ends before its " + std::to_string(layout.count) + " vertices of " + std::to_string(layout.record) +
+                                                " bytes do");
+    }
+    // one view of 1 x 1 without sources: every point is its pixel 0 and has no support
+    const std::vector<uint8_t> support(n, 0);
+    const std::vector<int32_t> zeros(n, 0);
+    const std::vector<uint32_t> sources(n, 0);
+    const int rows[1] = {1}, cols[1] = {1}, pair_offsets[2] = {0, 0};
+    const int rc = apd_points_create(device, on_device, layout.count, xyz.data(), normal.data(), bgr.data(), support.data(), zeros.data(), zeros.data(),
+                                     sources.data(), 1, rows, cols, pair_offsets, nullptr, out);
+    if (rc != APD_OK) {
+        err() = std::string("apd_points_read_ply: ") + path + ": " + err();
+    }
+    return rc;
 }
 
 // --------------------------------------------------------------------------------------------------------------------

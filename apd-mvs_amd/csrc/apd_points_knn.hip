@@ -9,7 +9,7 @@
 //   2. the points inside the grid in cell order.
 //   3. k_knn_mean: one lane per point in sorted order, the walk over the 27 cells (for_each_candidate), and for each of its
 //      candidates the selection of the k smallest d2 the lane has seen.
-//   4. removal: k_chunk_sums (one lane per chunk of 256 input indices, binary64, sequential: the order is the contract), the
+//   4. removal: k_chunk_sums (apd_points_search.h: one lane per chunk of 256 input indices, binary64, sequential: the order is the contract), the
 //      chunk sums -- n / 256 triples, never the n scores -- come down and the host adds them in order and forms T;
 //      k_keep_flags; compact_points (apd_points.hip).
 // There is no host path: host-resident points go up, the result comes down.
@@ -120,25 +120,6 @@ __global__ __launch_bounds__(kLanes) void k_knn_mean(const uint64_t *__restrict_
     mean[member[i]] = apd_fusion::knn_score([mine](unsigned s) { return mine[kLanes * s]; }, k);
 }
 
-// Chunk c < chunks of kKnnChunk consecutive input indices: its sums by contract C12.  One lane per chunk: the order of a
-// binary64 sum is the contract
-__global__ __launch_bounds__(64) void k_chunk_sums(const float *__restrict__ mean, size_t n, size_t chunks, double *__restrict__ s1,
-                                                    double *__restrict__ s2, uint32_t *__restrict__ full)
-{
-    const size_t c = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (c >= chunks) {
-        return;
-    }
-    const size_t first = c * apd_fusion::kKnnChunk;
-    const size_t count = n - first < (size_t)apd_fusion::kKnnChunk ? n - first : (size_t)apd_fusion::kKnnChunk;
-    double a = 0.0, b = 0.0;
-    unsigned f = 0;
-    apd_fusion::knn_chunk_sums(mean + first, count, a, b, f);
-    s1[c] = a;
-    s2[c] = b;
-    full[c] = f;
-}
-
 // keep[k] = 1 where the score is finite and at most T
 __global__ __launch_bounds__(256) void k_keep_flags(const float *__restrict__ mean, size_t n, double T, uint32_t *__restrict__ keep)
 {
@@ -195,26 +176,10 @@ struct Call : Search {
     // T of the n scores at `mean` (device memory): the chunk sums on the device, their totals and the threshold on the host
     int threshold_of(const float *mean, size_t n, float std_ratio, double *T) const
     {
-        const size_t chunks = (n + apd_fusion::kKnnChunk - 1) / apd_fusion::kKnnChunk;
-        Scratch scratch;
-        double *s1 = nullptr, *s2 = nullptr;
-        uint32_t *full = nullptr;
-        HIP_TRY(scratch.alloc(chunks * 8, &s1));
-        HIP_TRY(scratch.alloc(chunks * 8, &s2));
-        HIP_TRY(scratch.alloc(chunks * 4, &full));
-        hipLaunchKernelGGL(k_chunk_sums, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, 0, mean, n, chunks, s1, s2, full);
-        HIP_TRY(hipGetLastError());
-        std::vector<double> h1(chunks), h2(chunks);
-        std::vector<uint32_t> hf(chunks);
-        HIP_TRY(hipMemcpy(h1.data(), s1, chunks * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h2.data(), s2, chunks * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hf.data(), full, chunks * 4, hipMemcpyDeviceToHost));
         double S1 = 0.0, S2 = 0.0;
         unsigned long long n_f = 0;
-        for (size_t c = 0; c < chunks; ++c) {
-            S1 = S1 + h1[c];
-            S2 = S2 + h2[c];
-            n_f += hf[c];
+        if (const int rc = chunk_totals(mean, n, &S1, &S2, &n_f); rc != APD_OK) {
+            return rc;
         }
         *T = apd_fusion::knn_threshold(n_f, S1, S2, std_ratio);
         return APD_OK;

@@ -1,13 +1,15 @@
 // apd_points_search.h -- what every search of the 27 cells around a point shares (apd_points_radius.hip: contract C11,
-// apd_points_knn.hip: C12, apd_points_clusters.hip: C13, apd_points_normals.hip: C14).
+// apd_points_knn.hip: C12, apd_points_clusters.hip: C13, apd_points_normals.hip: C14, apd_points_smooth.hip: C16,
+// apd_points_nearest.hip: C17).
 // Device: the positions gathered into cell order (k_gather_xyz), the binary search for a (dz, dy) row's run (lower_bound), THE walk
-// over the 27 cells (for_each_candidate: the one place where a key is decoded, the x range clamped, a row outside the grid skipped),
-// a typed fill and the flags "v[k] >= bound" of the removals.
+// over the 27 cells (for_each_candidate_around: the one place where the x range is clamped and a row outside the grid skipped, around
+// a cell given as integers; for_each_candidate: around the cell of a member, the one place where a key is decoded), a typed fill, the
+// flags "v[k] >= bound" of the removals and the binary64 chunk sums of contract C12 (k_chunk_sums).
 // Host, as methods of Search, one call of an entry point: what such a call refuses before any device is touched (check); the points
 // inside the grid of cell size `radius` brought into cell order -- keys, scan, compaction (apd_points_grid.h), the stable sort of
 // (key, input index), the gather -- ready for a kernel with one lane per point in sorted order (sort_into_cells); where a query
 // reads the points and writes its answer when they are host-resident (positions, readable, stage, download); the seven arrays a
-// removal compacts (device_arrays); and the tail of an entry point that hands a new object back (into_new_points).  Device code: hipcc only.
+// removal compacts (device_arrays); the totals of the chunk sums (chunk_totals); and the tail of an entry point that hands a new object back (into_new_points).  Device code: hipcc only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,9 +17,11 @@
 #include <math.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_device.h"
+#include "apd_knn_math.h"
 #include "apd_points_grid.h"
 #include "apd_points_host.h"
 #include "apd_radius_math.h"
@@ -61,6 +65,25 @@ __global__ __launch_bounds__(256) void k_gather_xyz(const float *__restrict__ xy
     }
 }
 
+// Chunk c < chunks of kKnnChunk consecutive input indices: its sums by contract C12.  One lane per chunk: the order of a
+// binary64 sum is the contract
+__global__ __launch_bounds__(64) void k_chunk_sums(const float *__restrict__ mean, size_t n, size_t chunks, double *__restrict__ s1,
+                                                    double *__restrict__ s2, uint32_t *__restrict__ full)
+{
+    const size_t c = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (c >= chunks) {
+        return;
+    }
+    const size_t first = c * apd_fusion::kKnnChunk;
+    const size_t count = n - first < (size_t)apd_fusion::kKnnChunk ? n - first : (size_t)apd_fusion::kKnnChunk;
+    double a = 0.0, b = 0.0;
+    unsigned f = 0;
+    apd_fusion::knn_chunk_sums(mean + first, count, a, b, f);
+    s1[c] = a;
+    s2[c] = b;
+    full[c] = f;
+}
+
 // the first position in [from, m) whose key is not below `want`
 __device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ keys, uint32_t from, uint32_t m, uint64_t want)
 {
@@ -85,11 +108,14 @@ __device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ key
 // borrows into the next field of the key.  Every candidate lies in a cell adjacent to i's by construction; what is left of the
 // relation of apd_radius_math.h is the index and the distance, which are f's.  No read of keys or xyz reaches position `end` but
 // that of keys[i]: end = m walks all 27 cells, end = i the part of them below i.
+//
+// for_each_candidate_around is that walk around a cell given as three integers (each in [-2^20, 2^20)), which need not hold a
+// member of the cloud walked: keys / xyz may be another cloud's than the one the cell was taken from (apd_points_nearest.hip,
+// contract C17), and then no read reaches position `end` at all.  for_each_candidate is the walk around the cell of member i.
 template <typename F>
-__device__ __forceinline__ void for_each_candidate(const uint64_t *__restrict__ keys, const float *__restrict__ xyz, uint32_t i, uint32_t end, F &&f)
+__device__ __forceinline__ void for_each_candidate_around(const uint64_t *__restrict__ keys, const float *__restrict__ xyz, const int cell[3], uint32_t end,
+                                                          F &&f)
 {
-    int cell[3];
-    apd_fusion::radius_cells_of_key(keys[i], cell);
     const int lo = -apd_fusion::kVoxelHalf, hi = apd_fusion::kVoxelHalf - 1;
     const int x0 = cell[0] > lo ? cell[0] - 1 : lo, x1 = cell[0] < hi ? cell[0] + 1 : hi;
     uint32_t at = 0;
@@ -113,6 +139,14 @@ __device__ __forceinline__ void for_each_candidate(const uint64_t *__restrict__ 
             }
         }
     }
+}
+
+template <typename F>
+__device__ __forceinline__ void for_each_candidate(const uint64_t *__restrict__ keys, const float *__restrict__ xyz, uint32_t i, uint32_t end, F &&f)
+{
+    int cell[3];
+    apd_fusion::radius_cells_of_key(keys[i], cell);
+    for_each_candidate_around(keys, xyz, cell, end, static_cast<F &&>(f));
 }
 
 std::string &err() { return apd_fusion::g_fusion_error; }
@@ -257,6 +291,39 @@ struct Search {
         if (s.host) {
             HIP_TRY(hipMemcpy(s.host, s.device, s.bytes, hipMemcpyDeviceToHost));
         }
+        return APD_OK;
+    }
+
+    // The totals of contract C12 over the n > 0 values at v (device memory on the current device): k_chunk_sums, the chunk sums --
+    // n / 256 triples, never the n values -- come down and the host adds them in ascending order.  *S2 may be null
+    int chunk_totals(const float *v, size_t n, double *S1, double *S2, unsigned long long *n_f) const
+    {
+        const size_t chunks = (n + apd_fusion::kKnnChunk - 1) / apd_fusion::kKnnChunk;
+        Scratch scratch;
+        double *s1 = nullptr, *s2 = nullptr;
+        uint32_t *full = nullptr;
+        HIP_TRY(scratch.alloc(chunks * 8, &s1));
+        HIP_TRY(scratch.alloc(chunks * 8, &s2));
+        HIP_TRY(scratch.alloc(chunks * 4, &full));
+        hipLaunchKernelGGL(k_chunk_sums, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, 0, v, n, chunks, s1, s2, full);
+        HIP_TRY(hipGetLastError());
+        std::vector<double> h1(chunks), h2(chunks);
+        std::vector<uint32_t> hf(chunks);
+        HIP_TRY(hipMemcpy(h1.data(), s1, chunks * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h2.data(), s2, chunks * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hf.data(), full, chunks * 4, hipMemcpyDeviceToHost));
+        double t1 = 0.0, t2 = 0.0;
+        unsigned long long count = 0;
+        for (size_t c = 0; c < chunks; ++c) {
+            t1 = t1 + h1[c];
+            t2 = t2 + h2[c];
+            count += hf[c];
+        }
+        *S1 = t1;
+        if (S2) {
+            *S2 = t2;
+        }
+        *n_f = count;
         return APD_OK;
     }
 

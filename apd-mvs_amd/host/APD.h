@@ -195,6 +195,10 @@ void SetFusionPlyEstimateNormals(float radius, unsigned min_neighbours);
 // depth at the point's pixel (apd_points_rendered_visibility, after everything above that is asked for too); APD.ply keeps its
 // bytes.  -1: off
 void SetFusionPlyRenderVis(int splat, float rel_tolerance);
+// additive: a path: the points <dense>/APD/APD.ply is written from are scored against the cloud of that binary PLY file at
+// `threshold` (apd_points_read_ply, apd_points_score, after everything above): the precision, recall and F-score are printed and
+// written to <dense>/APD/APD.ply.score as `key value` lines; APD.ply and APD.ply.vis keep their bytes.  empty: off
+void SetFusionPlyScore(const std::string &truth_ply, float threshold);
 
 class APD {
 public:

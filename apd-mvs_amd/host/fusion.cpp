@@ -45,13 +45,16 @@ float g_fusion_ply_normals_radius = 0.0f;  // SetFusionPlyEstimateNormals; 0: of
 unsigned g_fusion_ply_normals_min = 0;
 int g_fusion_ply_render_splat = -1;        // SetFusionPlyRenderVis; -1: off
 float g_fusion_ply_render_tolerance = 0.0f;
+std::string g_fusion_ply_score_truth;      // SetFusionPlyScore; empty: off
+float g_fusion_ply_score_threshold = 0.0f;
 
-// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-smooth, --ply-estimate-normals or
-// --ply-render-vis: APD.ply is written from the points after the fusion, not by it
+// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-smooth, --ply-estimate-normals,
+// --ply-render-vis or --ply-score: APD.ply is written from the points after the fusion, not by it
 bool ply_from_points()
 {
     return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f ||
-           g_fusion_ply_component_radius > 0.0f || g_fusion_ply_smooth_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f || g_fusion_ply_render_splat >= 0;
+           g_fusion_ply_component_radius > 0.0f || g_fusion_ply_smooth_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f || g_fusion_ply_render_splat >= 0 ||
+           !g_fusion_ply_score_truth.empty();
 }
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
@@ -182,7 +185,50 @@ void SetFusionPlyRenderVis(int splat, float rel_tolerance)
     g_fusion_ply_render_tolerance = rel_tolerance;
 }
 
+void SetFusionPlyScore(const std::string &truth_ply, float threshold)
+{
+    g_fusion_ply_score_truth = truth_ply;
+    g_fusion_ply_score_threshold = threshold;
+}
+
 namespace {
+
+// --ply-score: the points ply_path was written from against the cloud of the truth file (apd_points_read_ply into host memory,
+// apd_points_score on the fusion's device): one line with the nine fields, and the same as `key value` lines in <ply_path>.score
+int score_beside(apd_points_t points, const path &ply_path)
+{
+    apd_points_t truth = nullptr;
+    int st = apd_points_read_ply(g_fusion_ply_score_truth.c_str(), g_fusion_device, 0, &truth);
+    apd_points_score_t s;
+    st = st != APD_OK ? st : apd_points_score(points, truth, g_fusion_ply_score_threshold, nullptr, &s);
+    apd_points_destroy(truth);  // leaves the message of a failed call as it is
+    if (st != APD_OK) {
+        return st;
+    }
+    const char *const names[9] = {"n_p", "n_q", "p_within", "q_within", "precision", "recall", "fscore", "mean_p", "mean_q"};
+    const long long integers[4] = {s.n_p, s.n_q, s.p_within, s.q_within};
+    const double reals[5] = {s.precision, s.recall, s.fscore, s.mean_p, s.mean_q};
+    std::string line, lines;
+    char text[64];
+    for (int k = 0; k < 9; ++k) {
+        if (k < 4) {
+            snprintf(text, sizeof(text), "%lld", integers[k]);
+        } else {
+            snprintf(text, sizeof(text), "%.17g", reals[k - 4]);  // the double, back to the bit
+        }
+        line += std::string(" ") + names[k] + " " + text;
+        lines += std::string(names[k]) + " " + text + "\n";
+    }
+    std::cout << "Score against " << g_fusion_ply_score_truth << " at " << g_fusion_ply_score_threshold << ":" << line << std::endl;
+    const std::string score_path = ply_path.string() + ".score";
+    FILE *f = fopen(score_path.c_str(), "wb");
+    const bool ok = f && fwrite(lines.data(), 1, lines.size(), f) == lines.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        std::cerr << "cannot write " << score_path << std::endl;
+        exit(EXIT_FAILURE);
+    }
+    return APD_OK;
+}
 
 // --ply-mean: replaces the points of a fusion by their means over the agreeing views (apd_points_average with the fusion's own
 // cameras and maps); --ply-voxel: replaces them -- the means, with both -- by one point per cell (apd_points_merge_voxels) and
@@ -195,7 +241,8 @@ namespace {
 // --ply-estimate-normals: replaces the normals of what these left by those of each point's neighbourhood
 // (apd_points_with_estimated_normals) and prints how many points got one; --ply-render-vis: replaces the lists of what these left by
 // the views that see each point when the cloud is drawn into full_cameras, the views' cameras at the size of their images
-// (apd_points_rendered_visibility), and prints how many points no view sees.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file
+// (apd_points_rendered_visibility), and prints how many points no view sees.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file;
+// --ply-score: scores the points the file was written from (score_beside), which changes none of them
 void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const apd_camera *full_cameras, const float *const *depths,
                       const float *const *normals, const int *rows, const int *cols, int maps_on_device, const path &ply_path)
 {
@@ -293,8 +340,11 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
         }
     }
     st = st != APD_OK ? st : apd_points_write_ply(points, ply_path.string().c_str(), fusion_options().ply_normals);
+    std::string err = st != APD_OK ? apd_fusion_last_error() : "";
+    if (st == APD_OK && !g_fusion_ply_score_truth.empty() && (st = score_beside(points, ply_path)) != APD_OK) {
+        err = apd_fusion_last_error();
+    }
     if (st != APD_OK) {
-        const std::string err = apd_fusion_last_error();
         apd_points_destroy(points);
         std::cerr << err << std::endl;
         exit(EXIT_FAILURE);

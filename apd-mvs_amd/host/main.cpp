@@ -5,7 +5,7 @@
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
 //       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN]
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
-//       [--ply-render-vis SPLAT,TOL] [--filtered-maps]
+//       [--ply-render-vis SPLAT,TOL] [--ply-score TRUTH.ply,TAU] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -56,6 +56,14 @@
 // its pixel (apd_points_rendered_visibility); applied last, after --ply-estimate-normals.  With every --fusion; APD.ply keeps the
 // bytes it has without the flag, and the number of points no view sees is printed.  SPLAT must be a count of 0 .. 8 and TOL a
 // non-negative finite number, or the usage line is all that happens.
+// --ply-score TRUTH.ply,TAU: the points that APD.ply holds are scored against the vertices of the binary little-endian PLY file
+// TRUTH.ply at the threshold TAU (apd_points_read_ply, apd_points_score, on the grid of cell size TAU at the origin): precision is
+// the share of the points that have a vertex of TRUTH.ply within TAU, recall the share of those vertices that have a point within
+// TAU, fscore their harmonic mean -- nearest-neighbour precision and recall at one threshold, with no registration, cropping
+// or occlusion reasoning: to compare runs with each other.  Applied after every other --ply-* flag; APD.ply and APD.ply.vis
+// keep the bytes they have without the flag.  One line with the nine fields of apd_points_score_t is printed, and APD.ply.score
+// holds them as `key value` lines, the reals with 17 significant digits.  With every --fusion.  The value is split at its last
+// comma; TAU as RADIUS of --ply-radius-filter, or the usage line is all that happens.  A file that cannot be read ends the run.
 // --ply-radius-filter RADIUS,MIN: APD.ply holds the points that have at least MIN other points within RADIUS
 // (apd_points_remove_sparse: the radius outlier filter, on the grid of cell size RADIUS at the origin) and, with --ply-vis,
 // APD.ply.vis their lists; applied after --ply-mean, --ply-voxel and --ply-stat-filter.  With every --fusion; the number removed is printed.
@@ -260,6 +268,16 @@ bool ParseOptions(int argc, char **argv, Options &o)
             o.ply_render_splat = count[0] - '0';
             o.ply_render_tolerance = t;
             o.ply_vis = true;
+        } else if (a == "--ply-score") {
+            const std::string both = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = both.rfind(',');
+            float t = 0.0f;
+            if (comma == std::string::npos || comma == 0 || !real(both.substr(comma + 1).c_str(), t) || !(t * t > 0.0f) || t * t > 3.402823466e+38f) {
+                fprintf(stderr, "bad value '%s' of %s: TRUTH.ply,TAU, a file and a positive number\n", both.c_str(), a.c_str());
+                return false;
+            }
+            o.ply_score_truth = both.substr(0, comma);
+            o.ply_score_threshold = t;
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
         } else if (a == "--seed") {
@@ -471,7 +489,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
@@ -480,7 +498,8 @@ int main(int argc, char **argv)
                         "  --ply-component-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points of connected components of fewer than MIN points, two points being joined when they are within RADIUS of each other, after --ply-radius-filter.\n"
                         "  --ply-smooth RADIUS,MIN[,ITERATIONS]: the points of APD.ply (and of what --ply-estimate-normals and --ply-render-vis then see) each projected on the weighted plane of the other points within RADIUS of it, where there are at least MIN (2 or more) of them, ITERATIONS (1 .. 16, default 1) times, after --ply-component-filter.\n"
                         "  --ply-estimate-normals RADIUS,MIN: the normals of the points of APD.ply (shown with --ply-normals) estimated from the other points within RADIUS of each, where there are at least MIN (2 or more) of them, after every other --ply-* flag but --ply-render-vis.\n"
-                        "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag.\n");
+                        "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag but --ply-score.\n"
+                        "  --ply-score TRUTH.ply,TAU: prints, and writes to APD.ply.score, the precision, recall and F-score of the points of APD.ply against the vertices of the binary PLY file TRUTH.ply at the threshold TAU: the share of each cloud that has a point of the other within TAU; after every other --ply-* flag, APD.ply keeps its bytes.\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -504,6 +523,7 @@ int main(int argc, char **argv)
     SetFusionPlySmooth(opt.ply_smooth_radius, opt.ply_smooth_min, opt.ply_smooth_iterations);
     SetFusionPlyEstimateNormals(opt.ply_normals_radius, opt.ply_normals_min);
     SetFusionPlyRenderVis(opt.ply_render_splat, opt.ply_render_tolerance);
+    SetFusionPlyScore(opt.ply_score_truth, opt.ply_score_threshold);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

@@ -52,6 +52,8 @@ struct Options {
     unsigned ply_normals_min = 0;         // RADIUS of each point that has at least MIN others there (apd_points_with_estimated_normals), last; radius 0: off
     int ply_render_splat = -1;            // --ply-render-vis SPLAT,TOL: APD.ply.vis (the flag implies --ply-vis) lists per point the views that see it when the
     float ply_render_tolerance = 0.0f;    // cloud is drawn into them with footprints of SPLAT (apd_points_rendered_visibility), last; splat -1: off
+    std::string ply_score_truth;          // --ply-score TRUTH.ply,TAU: the points of APD.ply scored against the cloud of TRUTH.ply at threshold TAU
+    float ply_score_threshold = 0.0f;     // (apd_points_score), after every other --ply-* flag: one printed line and APD.ply.score; empty: off
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)

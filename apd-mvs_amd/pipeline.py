@@ -552,7 +552,7 @@ def average_points(scene, results, points, device=0):
 
 def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False,
          vis_path=None, average=False, voxel=None, voxel_origin=None, radius_filter=None, stat_filter=None, component_filter=None,
-         estimate_normals=None, render_visibility=None, smooth=None):
+         estimate_normals=None, render_visibility=None, smooth=None, score=None):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -592,13 +592,27 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     render_visibility: (splat, rel_tolerance) -- applied last, after `estimate_normals`: the file, the returned points and the .vis
     file are those of Points.with_rendered_visibility(scene.cameras, splat, rel_tolerance), the same points as a merged object whose
     lists name the views that see each point of the cloud as it is then, occlusion included: the cloud is drawn into the scene's
-    full-resolution cameras, in view order.  The step changes no byte of the PLY file."""
+    full-resolution cameras, in view order.  The step changes no byte of the PLY file.
+    score: (truth, threshold) -- applied last, to the points every other option has produced, and changes none of them nor a byte of
+    a file: Points.score(truth, threshold) of those points against `truth` (a Points: Points.read_ply of a ground truth, or another
+    fusion's), the precision, recall and F-score at the threshold, returned as one more value after the others: (count, Score), or
+    (count, Points, Score) with return_points."""
     import ctypes as C
     from . import Points, default_fusion_options
     if variant not in FUSION_VARIANTS:
         raise ValueError("unknown fusion variant %r: one of %s" % (variant, ", ".join(sorted(FUSION_VARIANTS))))
     if ply_path is None and not return_points and vis_path is None:
         raise ValueError("fuse: neither a PLY file nor the points nor the visibility file are asked for")
+    if score is not None:
+        truth, threshold = score
+        n, whole = fuse(scene, results, ply_path, device, colour_images, block_masks, variant, options, return_points=True, vis_path=vis_path,
+                        average=average, voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
+                        component_filter=component_filter, estimate_normals=estimate_normals, render_visibility=render_visibility, smooth=smooth)
+        result = whole.score(truth, threshold)
+        if return_points:
+            return n, whole, result
+        whole.close()
+        return n, result
     if render_visibility is not None:
         splat, rel_tolerance = render_visibility
         _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,

@@ -452,6 +452,21 @@ int apd_points_average(apd_points_t p, int num_views, const apd_camera *cameras,
  * points.  `element vertex` is printed from the 64-bit count.  NULL p or path: APD_ERR_INVALID; a file that cannot be written:
  * APD_ERR_IO. */
 int apd_points_write_ply(apd_points_t p, const char *path, int with_normals);
+/* A points object from a PLY file: the way back from apd_points_write_ply, and the way in of a cloud made elsewhere -- the ground
+ * truth ETH3D and Tanks and Temples ship -- so that it can be searched, filtered and scored like one that was fused here.  Host
+ * code.  Read: a `format binary_little_endian 1.0` file whose `element vertex` has float (float32) properties x, y and z; float nx,
+ * ny, nz when all three are there (otherwise every normal is 0, 0, 0); uchar (uint8) red, green, blue or diffuse_red,
+ * diffuse_green, diffuse_blue when all three are there (otherwise every colour is 0, 0, 0).  Any other scalar property of a
+ * vertex is skipped by the size of its type, the properties may stand in any order, `comment` and `obj_info` lines and every
+ * element after `vertex` (the faces of a mesh) are ignored.  The object names one view of 1 x 1 pixels without sources: support,
+ * view, pixel and sources are 0 for every point, which are apd_points_create's rules.  on_device != 0: device memory on `device`;
+ * otherwise host memory, no device is touched and the call works on a machine without a GPU.
+ * Refused with a message "apd_points_read_ply: <path>: <reason>" (apd_fusion_last_error).  APD_ERR_INVALID: a NULL argument (no
+ * path in the message), a file that does not start with `ply`, a format other than binary_little_endian 1.0 (ascii, big endian), a
+ * list property in `element vertex`, a missing or non-float coordinate, an element before `vertex`, no `element vertex`, an unknown
+ * header line or type.  APD_ERR_IO: a file that cannot be read, that ends inside its header or before its vertices do.  *out is
+ * untouched when the call fails. */
+int apd_points_read_ply(const char *path, int device, int on_device, apd_points_t *out);
 /* A points object from caller arrays: a cloud that was not fused in this call, to be merged, listed or written like one that
  * was.  The arrays are HOST pointers with the layout of the accessors above (xyz and normal 3 floats, bgr 3 bytes per point) and
  * are copied; rows, cols, pair_offsets (num_views + 1 entries) and pair_indices are those of a fusion call and say what view,
@@ -652,6 +667,45 @@ int apd_points_with_estimated_normals(apd_points_t p, float radius, const float 
 int apd_points_smoothed_positions(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, float *xyz3, float *offset);
 int apd_points_with_smoothed_positions(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, unsigned iterations,
                                        apd_points_t *out, long long *moved);
+/* The nearest point of another cloud, and from it precision, recall and F-score: the first query that relates two points objects.
+ * How close a fused cloud is to a ground truth and how much of the ground truth it covers is what accuracy, completeness and
+ * F-score of Tanks and Temples measure, and what the radii and thresholds of every filter above can be chosen by.  IEEE operations
+ * in the order given (contract C17; csrc/apd_nearest_math.h).
+ *   Grid.  That of apd_points_neighbour_counts, cell size `radius` at origin3 (NULL: 0, 0, 0), for both clouds.  A point outside it
+ *   (a non-finite coordinate, a cell beyond +-2^20) has no nearest point and is nobody's nearest point.
+ *   Candidates.  Those of point i of p are the points j of q inside the grid whose cell differs from i's by at most 1 on every axis
+ *   and whose binary32 squared distance d2 = (dx * dx + dy * dy) + dz * dz is <= radius * radius.  As for the neighbour counts the
+ *   cell condition is part of the definition.  p and q may be the same object: a point is then its own candidate.
+ *   Nearest.  The candidate with the least d2, among equal d2 the smallest index j.  distance[i] = sqrtf(d2), index[i] = j; without
+ *   a candidate +inf and -1.  A distance is finite exactly when some point of q is within the radius.
+ * apd_points_nearest: distance and index take apd_points_count(p) entries each, host memory for a host-resident p, device memory
+ * on p's device for a device-resident one; either may be NULL, not both.  Computed on p's device, on its null stream, whatever
+ * memory p is in; there is no host implementation.  A host-resident q goes up for the call; a device-resident q must live on
+ * that device (APD_ERR_UNSUPPORTED otherwise, before any device is touched).  A p without points gives no results with no device
+ * touched; a q without points, or without a point inside the grid, gives +inf and -1 throughout.  The work is the number of
+ * (point of p, point of q in the 27 cells around it) pairs, plus one sort of each cloud.
+ * apd_points_score: p against `truth` at radius = threshold, so that "finite" is "within the threshold".  With a the number of
+ * finite distances from p to truth and b that from truth to p, both searches from one pair of sorts:
+ *   n_p, n_q       the points of p and of truth, those outside the grid too
+ *   p_within, q_within   a and b
+ *   precision      (double)a / (double)n_p, 0 when n_p is 0: the share of p that has truth within the threshold (accuracy)
+ *   recall         (double)b / (double)n_q, 0 when n_q is 0: the share of truth that has p within the threshold (completeness)
+ *   fscore         2 * precision * recall / (precision + recall), 0 when the sum is 0
+ *   mean_p, mean_q the mean finite distance from p to truth and from truth to p: binary64 sums over chunks of 256 consecutive
+ *                  indices as in apd_points_remove_statistical, divided by a and by b; 0 when there is none
+ * Of the distances only the chunk sums leave the device.  When either object has no points the counts are set, the rest is 0 and
+ * no device is touched.  This is nearest-neighbour precision / recall at one threshold as Tanks and Temples defines them, without
+ * its registration and cropping and without ETH3D's occlusion-aware evaluation: scores of two runs compare with each other.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_nearest: ..." or "apd_points_score: ..."
+ * (apd_fusion_last_error): what apd_points_neighbour_counts refuses, for either object (the threshold is the radius), a NULL q or
+ * truth, both of distance and index NULL, a NULL out; APD_ERR_UNSUPPORTED for 2^31 or more points in either.  *out is untouched
+ * when the call fails. */
+typedef struct {
+    long long n_p, n_q, p_within, q_within;
+    double precision, recall, fscore, mean_p, mean_q;
+} apd_points_score_t;
+int apd_points_nearest(apd_points_t p, apd_points_t q, float radius, const float *origin3, float *distance, int32_t *index);
+int apd_points_score(apd_points_t p, apd_points_t truth, float threshold, const float *origin3, apd_points_score_t *out);
 /* The cloud drawn into a camera with a z-buffer, and from such maps the views that see each point, occlusion included: what the
  * cleaned cloud looks like from a camera (a depth map and a point-index map, to inspect holes, to derive a mask, to compare with a
  * view's own depth map), and the visibility lists COLMAP's Delaunay mesher and Poisson trimming read, rebuilt for the cloud as it
