@@ -203,6 +203,8 @@ def lib():
                                                      C.POINTER(C.c_longlong)]
     L.apd_points_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     L.apd_points_score.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsScore)]
+    L.apd_points_align.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsAlignOptions), C.POINTER(PointsAlignment)]
+    L.apd_points_transformed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_void_p)]
     L.apd_points_read_ply.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.apd_points_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_void_p, C.c_void_p]
     L.apd_points_rendered_visibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
@@ -248,6 +250,23 @@ class PointsScore(C.Structure):
 Score = collections.namedtuple("Score", [n for n, _ in PointsScore._fields_])
 
 
+class PointsAlignOptions(C.Structure):
+    """apd_points_align_options."""
+    _fields_ = [("iterations", C.c_uint), ("tolerance", C.c_double), ("with_scale", C.c_int)]
+
+
+class PointsAlignment(C.Structure):
+    """apd_points_alignment_t."""
+    _fields_ = [("scale", C.c_double), ("rotation", C.c_double * 9), ("translation", C.c_double * 3), ("matched_before", C.c_longlong),
+                ("matched_after", C.c_longlong), ("rms_before", C.c_double), ("rms_after", C.c_double), ("steps", C.c_int), ("stopped", C.c_int)]
+
+
+# What Points.align returns: the fields of apd_points_alignment_t, rotation as a float64 [3, 3] array and translation as a float64
+# [3] array; `stopped` is one of these
+Alignment = collections.namedtuple("Alignment", [n for n, _ in PointsAlignment._fields_])
+ALIGN_ITERATIONS, ALIGN_CONVERGED, ALIGN_TOO_FEW = 0, 1, 2
+
+
 class _Borrowed:
     """Memory of a Points object as an array interface; keeps its owner alive."""
 
@@ -281,11 +300,12 @@ class Points:
     (apd_points_smoothed_positions) and with_smoothed_positions() these points with those positions, iterated, in place of the
     stored ones (apd_points_with_smoothed_positions), likewise: the one step that moves a point.  nearest() gives for every point
     the nearest point of another Points within a radius (apd_points_nearest), score() the precision, recall and F-score of these
-    points against another Points at a threshold (apd_points_score), and read_ply() makes a Points of a PLY file, a ground truth
-    for instance (apd_points_read_ply).  render() draws the points into a camera
-    with a z-buffer: the depth and the index of the nearest point per pixel (apd_points_render); with_rendered_visibility() gives
-    these points as a merged object whose lists name the cameras that see each point, occlusion included
-    (apd_points_rendered_visibility)."""
+    points against another Points at a threshold (apd_points_score), align() the rigid or similarity transform that brings these
+    points onto another Points by ICP within a radius (apd_points_align), transformed() these points moved by such a transform
+    (apd_points_transformed), and read_ply() makes a Points of a PLY file, a ground truth for instance (apd_points_read_ply).
+    render() draws the points into a camera with a z-buffer: the depth and the index of the nearest point per pixel
+    (apd_points_render); with_rendered_visibility() gives these points as a merged object whose lists name the cameras that see
+    each point, occlusion included (apd_points_rendered_visibility)."""
 
     _FIELDS = (("xyz", 3, "<f4", 4), ("normal", 3, "<f4", 4), ("bgr", 3, "|u1", 1), ("support", 1, "|u1", 1), ("view", 1, "<i4", 4),
                ("pixel", 1, "<i4", 4), ("sources", 1, "<u4", 4))
@@ -617,8 +637,9 @@ class Points:
         `truth` (a Points) at `threshold`: precision is the share of these points that have a point of `truth` within the threshold
         (p_within of n_p), recall the share of `truth` that has one of these within it (q_within of n_q), fscore their harmonic
         mean, mean_p and mean_q the mean distances of those that have one (contract C17; nearest() with radius = threshold in
-        both directions).  Nearest-neighbour precision and recall at one threshold, with no registration, cropping or occlusion
-        reasoning: scores compare with each other.  Computed on these points' device."""
+        both directions).  Nearest-neighbour precision and recall at one threshold: align() and transformed() refine a registration
+        first, but there is no initial global registration (ICP within a radius needs a start within about that radius), no
+        cropping volume and no occlusion-aware evaluation: scores compare with each other.  Computed on these points' device."""
         if not self._p:
             raise ApdError("Points.score: the points are closed")
         if not isinstance(truth, Points) or not truth._p:
@@ -630,6 +651,56 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Score(*[getattr(out, n) for n in Score._fields])
+
+    def align(self, other, radius, origin=None, iterations=16, tolerance=1e-6, with_scale=False):
+        """apd_points_align: Alignment(scale, rotation, translation, matched_before, matched_after, rms_before, rms_after, steps,
+        stopped) -- the transform x' = scale * rotation @ x + translation that brings these points onto `other` (a Points) by
+        point-to-point ICP (contract C18): per step every point is matched to its nearest point of `other` within `radius`
+        (nearest(), on the grid at `origin`), the matched pairs give the rigid transform -- with_scale: the similarity -- that
+        brings them closest in the least-squares sense (Horn's closed form), and the total moves these points' own positions for
+        the next step.  It ends after `iterations` (1 .. 64) steps (stopped == ALIGN_ITERATIONS), when the rms distance of the
+        matched pairs changes by no more than `tolerance` times itself (ALIGN_CONVERGED), or when fewer than 3 points are matched
+        or all matched points coincide (ALIGN_TOO_FEW).  matched_ and rms_before describe the points as they are, _after under
+        the returned transform.  Nothing is moved: transformed() does that.  The start must be within about a radius of the answer;
+        there is no global registration.  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.align: the points are closed")
+        if not isinstance(other, Points) or not other._p:
+            raise ApdError("Points.align: the other points are closed or not a Points")
+        if not 0 <= int(iterations) <= 0xFFFFFFFF:
+            raise ValueError("Points.align: %r iterations, not in 0 .. 2^32 - 1" % (iterations,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        options, out = PointsAlignOptions(int(iterations), float(tolerance), int(bool(with_scale))), PointsAlignment()
+        rc = L.apd_points_align(self._p, other._p, float(radius), org, C.byref(options), C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Alignment(out.scale, np.array(out.rotation, np.float64).reshape(3, 3), np.array(out.translation, np.float64), out.matched_before,
+                         out.matched_after, out.rms_before, out.rms_after, out.steps, out.stopped)
+
+    def transformed(self, scale, rotation=None, translation=None):
+        """apd_points_transformed: these points in their order with xyz replaced by scale * rotation @ x + translation and normal by
+        rotation @ n (not scaled, not renormalised), each component as (float)(((m0 x + m1 y) + m2 z) + t) in binary64, and every
+        other array and the lists as they are: transformed(alignment) with what align() returned, or transformed(scale, rotation,
+        translation) with a positive scale, a rotation (3 x 3, row-major, orthonormal to 1e-6) and a translation.  A merged object
+        gives a merged object.  Computed on these points' device; the result lives where they live."""
+        if not self._p:
+            raise ApdError("Points.transformed: the points are closed")
+        if isinstance(scale, Alignment):
+            if rotation is not None or translation is not None:
+                raise TypeError("Points.transformed: an Alignment, or scale, rotation and translation")
+            scale, rotation, translation = scale.scale, scale.rotation, scale.translation
+        if rotation is None or translation is None:
+            raise TypeError("Points.transformed: an Alignment, or scale, rotation and translation")
+        R, t = np.ascontiguousarray(rotation, np.float64), np.ascontiguousarray(translation, np.float64)
+        if R.size != 9 or t.size != 3:
+            raise ValueError("Points.transformed: a rotation of %d and a translation of %d numbers, not 9 and 3" % (R.size, t.size))
+        L = lib()
+        out = C.c_void_p()
+        rc = L.apd_points_transformed(self._p, float(scale), R.ctypes.data_as(C.POINTER(C.c_double)), t.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Points(out, self.device)
 
     @classmethod
     def read_ply(cls, path, device=0, on_device=False):

@@ -199,6 +199,7 @@ void SetFusionPlyRenderVis(int splat, float rel_tolerance);
 // `threshold` (apd_points_read_ply, apd_points_score, after everything above): the precision, recall and F-score are printed and
 // written to <dense>/APD/APD.ply.score as `key value` lines; APD.ply and APD.ply.vis keep their bytes.  empty: off
 void SetFusionPlyScore(const std::string &truth_ply, float threshold);
+void SetFusionPlyAlign(const std::string &truth_ply, float radius, unsigned iterations, bool with_scale);
 
 class APD {
 public:

@@ -47,14 +47,18 @@ int g_fusion_ply_render_splat = -1;        // SetFusionPlyRenderVis; -1: off
 float g_fusion_ply_render_tolerance = 0.0f;
 std::string g_fusion_ply_score_truth;      // SetFusionPlyScore; empty: off
 float g_fusion_ply_score_threshold = 0.0f;
+std::string g_fusion_ply_align_truth;      // SetFusionPlyAlign; empty: off
+float g_fusion_ply_align_radius = 0.0f;
+unsigned g_fusion_ply_align_iterations = 16;
+bool g_fusion_ply_align_scale = false;
 
 // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-smooth, --ply-estimate-normals,
-// --ply-render-vis or --ply-score: APD.ply is written from the points after the fusion, not by it
+// --ply-render-vis, --ply-align or --ply-score: APD.ply is written from the points after the fusion, not by it
 bool ply_from_points()
 {
     return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f ||
            g_fusion_ply_component_radius > 0.0f || g_fusion_ply_smooth_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f || g_fusion_ply_render_splat >= 0 ||
-           !g_fusion_ply_score_truth.empty();
+           !g_fusion_ply_align_truth.empty() || !g_fusion_ply_score_truth.empty();
 }
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
@@ -191,17 +195,98 @@ void SetFusionPlyScore(const std::string &truth_ply, float threshold)
     g_fusion_ply_score_threshold = threshold;
 }
 
+void SetFusionPlyAlign(const std::string &truth_ply, float radius, unsigned iterations, bool with_scale)
+{
+    g_fusion_ply_align_truth = truth_ply;
+    g_fusion_ply_align_radius = radius;
+    g_fusion_ply_align_iterations = iterations;
+    g_fusion_ply_align_scale = with_scale;
+}
+
 namespace {
 
-// --ply-score: the points ply_path was written from against the cloud of the truth file (apd_points_read_ply into host memory,
-// apd_points_score on the fusion's device): one line with the nine fields, and the same as `key value` lines in <ply_path>.score
-int score_beside(apd_points_t points, const path &ply_path)
+// The cloud of a truth file of --ply-align and --ply-score (apd_points_read_ply into host memory): read once when both name
+// the same file
+struct Truth {
+    apd_points_t points = nullptr;
+    std::string file;
+    ~Truth() { apd_points_destroy(points); }  // leaves the message of a failed call as it is
+    int read(const std::string &from)
+    {
+        if (points && file == from) {
+            return APD_OK;
+        }
+        apd_points_destroy(points);
+        points = nullptr;
+        file = from;
+        return apd_points_read_ply(from.c_str(), g_fusion_device, 0, &points);
+    }
+};
+
+void write_lines_or_exit(const std::string &to, const std::string &lines)
 {
-    apd_points_t truth = nullptr;
-    int st = apd_points_read_ply(g_fusion_ply_score_truth.c_str(), g_fusion_device, 0, &truth);
+    FILE *f = fopen(to.c_str(), "wb");
+    const bool ok = f && fwrite(lines.data(), 1, lines.size(), f) == lines.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        std::cerr << "cannot write " << to << std::endl;
+        exit(EXIT_FAILURE);
+    }
+}
+
+// --ply-align: replaces the points by themselves moved onto the cloud of the truth file (apd_points_align on the fusion's device,
+// apd_points_transformed by its answer): one line with every field, and the same as `name value` lines in <ply_path>.align
+int align_beside(apd_points_t &points, Truth &truth, const path &ply_path)
+{
+    int st = truth.read(g_fusion_ply_align_truth);
+    const apd_points_align_options options = {g_fusion_ply_align_iterations, 1e-6, g_fusion_ply_align_scale ? 1 : 0};
+    apd_points_alignment_t a;
+    st = st != APD_OK ? st : apd_points_align(points, truth.points, g_fusion_ply_align_radius, nullptr, &options, &a);
+    apd_points_t moved = nullptr;
+    st = st != APD_OK ? st : apd_points_transformed(points, a.scale, a.rotation, a.translation, &moved);
+    if (st != APD_OK) {
+        return st;
+    }
+    apd_points_destroy(points);
+    points = moved;
+    std::string line, lines;
+    char text[64];
+    const auto add = [&](const std::string &name, const char *value) {
+        line += " " + name + " " + value;
+        lines += name + " " + value + "\n";
+    };
+    const auto real = [&](const std::string &name, double v) {
+        snprintf(text, sizeof(text), "%.17g", v);  // the double, back to the bit
+        add(name, text);
+    };
+    const auto integer = [&](const std::string &name, long long v) {
+        snprintf(text, sizeof(text), "%lld", v);
+        add(name, text);
+    };
+    real("scale", a.scale);
+    for (int e = 0; e < 9; ++e) {
+        real("rotation" + std::to_string(e), a.rotation[e]);
+    }
+    for (int e = 0; e < 3; ++e) {
+        real("translation" + std::to_string(e), a.translation[e]);
+    }
+    integer("matched_before", a.matched_before);
+    integer("matched_after", a.matched_after);
+    real("rms_before", a.rms_before);
+    real("rms_after", a.rms_after);
+    integer("steps", a.steps);
+    integer("stopped", a.stopped);
+    std::cout << "Aligned to " << g_fusion_ply_align_truth << " within " << g_fusion_ply_align_radius << ":" << line << std::endl;
+    write_lines_or_exit(ply_path.string() + ".align", lines);
+    return APD_OK;
+}
+
+// --ply-score: the points ply_path was written from against the cloud of the truth file (apd_points_score on the fusion's
+// device): one line with the nine fields, and the same as `key value` lines in <ply_path>.score
+int score_beside(apd_points_t points, Truth &truth, const path &ply_path)
+{
+    int st = truth.read(g_fusion_ply_score_truth);
     apd_points_score_t s;
-    st = st != APD_OK ? st : apd_points_score(points, truth, g_fusion_ply_score_threshold, nullptr, &s);
-    apd_points_destroy(truth);  // leaves the message of a failed call as it is
+    st = st != APD_OK ? st : apd_points_score(points, truth.points, g_fusion_ply_score_threshold, nullptr, &s);
     if (st != APD_OK) {
         return st;
     }
@@ -220,13 +305,7 @@ int score_beside(apd_points_t points, const path &ply_path)
         lines += std::string(names[k]) + " " + text + "\n";
     }
     std::cout << "Score against " << g_fusion_ply_score_truth << " at " << g_fusion_ply_score_threshold << ":" << line << std::endl;
-    const std::string score_path = ply_path.string() + ".score";
-    FILE *f = fopen(score_path.c_str(), "wb");
-    const bool ok = f && fwrite(lines.data(), 1, lines.size(), f) == lines.size();
-    if ((f && fclose(f) != 0) || !ok) {
-        std::cerr << "cannot write " << score_path << std::endl;
-        exit(EXIT_FAILURE);
-    }
+    write_lines_or_exit(ply_path.string() + ".score", lines);
     return APD_OK;
 }
 
@@ -241,8 +320,9 @@ int score_beside(apd_points_t points, const path &ply_path)
 // --ply-estimate-normals: replaces the normals of what these left by those of each point's neighbourhood
 // (apd_points_with_estimated_normals) and prints how many points got one; --ply-render-vis: replaces the lists of what these left by
 // the views that see each point when the cloud is drawn into full_cameras, the views' cameras at the size of their images
-// (apd_points_rendered_visibility), and prints how many points no view sees.  Then writes ply_path from them (apd_points_write_ply); the fusion itself wrote no file;
-// --ply-score: scores the points the file was written from (score_beside), which changes none of them
+// (apd_points_rendered_visibility), and prints how many points no view sees; --ply-align: replaces what these left by the same points
+// moved onto the cloud of a truth file (align_beside).  Then writes ply_path from them (apd_points_write_ply); the fusion itself
+// wrote no file; --ply-score: scores the points the file was written from (score_beside), which changes none of them
 void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const apd_camera *full_cameras, const float *const *depths,
                       const float *const *normals, const int *rows, const int *cols, int maps_on_device, const path &ply_path)
 {
@@ -339,9 +419,13 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
             points = kept;
         }
     }
+    Truth truth;
+    if (st == APD_OK && !g_fusion_ply_align_truth.empty()) {
+        st = align_beside(points, truth, ply_path);
+    }
     st = st != APD_OK ? st : apd_points_write_ply(points, ply_path.string().c_str(), fusion_options().ply_normals);
     std::string err = st != APD_OK ? apd_fusion_last_error() : "";
-    if (st == APD_OK && !g_fusion_ply_score_truth.empty() && (st = score_beside(points, ply_path)) != APD_OK) {
+    if (st == APD_OK && !g_fusion_ply_score_truth.empty() && (st = score_beside(points, truth, ply_path)) != APD_OK) {
         err = apd_fusion_last_error();
     }
     if (st != APD_OK) {

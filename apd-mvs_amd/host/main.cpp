@@ -5,7 +5,7 @@
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
 //       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN]
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
-//       [--ply-render-vis SPLAT,TOL] [--ply-score TRUTH.ply,TAU] [--filtered-maps]
+//       [--ply-render-vis SPLAT,TOL] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-score TRUTH.ply,TAU] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -56,11 +56,20 @@
 // its pixel (apd_points_rendered_visibility); applied last, after --ply-estimate-normals.  With every --fusion; APD.ply keeps the
 // bytes it has without the flag, and the number of points no view sees is printed.  SPLAT must be a count of 0 .. 8 and TOL a
 // non-negative finite number, or the usage line is all that happens.
+// --ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]: the points that APD.ply holds are moved onto the vertices of the binary
+// little-endian PLY file TRUTH.ply by point-to-point ICP within RADIUS (apd_points_read_ply, apd_points_align with ITERATIONS steps
+// at most -- 1 .. 64, 16 without -- and the tolerance 1e-6, rigid, or a similarity with `scale`; apd_points_transformed by its
+// answer).  Applied after every other --ply-* flag but --ply-score, which then scores the moved points; the file is read once
+// when both name it.  APD.ply holds the moved positions and normals; APD.ply.vis keeps its bytes, since moving changes no list.
+// One line "Aligned to ..." with every field of apd_points_alignment_t is printed -- rotation0 .. rotation8 row-major and
+// translation0 .. translation2 -- and APD.ply.align holds the same as one `name value` line per number, the doubles as %.17g.
+// The value is read from its end, since a file's name may hold commas; a bad one leaves the usage line as all that happens.
 // --ply-score TRUTH.ply,TAU: the points that APD.ply holds are scored against the vertices of the binary little-endian PLY file
 // TRUTH.ply at the threshold TAU (apd_points_read_ply, apd_points_score, on the grid of cell size TAU at the origin): precision is
 // the share of the points that have a vertex of TRUTH.ply within TAU, recall the share of those vertices that have a point within
-// TAU, fscore their harmonic mean -- nearest-neighbour precision and recall at one threshold, with no registration, cropping
-// or occlusion reasoning: to compare runs with each other.  Applied after every other --ply-* flag; APD.ply and APD.ply.vis
+// TAU, fscore their harmonic mean -- nearest-neighbour precision and recall at one threshold; --ply-align refines a registration
+// first, but there is no initial global registration, no cropping volume and no occlusion-aware evaluation: to compare runs
+// with each other.  Applied after every other --ply-* flag; APD.ply and APD.ply.vis
 // keep the bytes they have without the flag.  One line with the nine fields of apd_points_score_t is printed, and APD.ply.score
 // holds them as `key value` lines, the reals with 17 significant digits.  With every --fusion.  The value is split at its last
 // comma; TAU as RADIUS of --ply-radius-filter, or the usage line is all that happens.  A file that cannot be read ends the run.
@@ -278,6 +287,36 @@ bool ParseOptions(int argc, char **argv, Options &o)
             }
             o.ply_score_truth = both.substr(0, comma);
             o.ply_score_threshold = t;
+        } else if (a == "--ply-align") {
+            // read from the right, since the file's name may hold commas: [,scale], then [,ITERATIONS] when what stands before it is a
+            // radius too, then ,RADIUS
+            const std::string all = i + 1 < argc ? argv[++i] : "";
+            std::string rest = all;
+            const bool scale = rest.size() > 6 && rest.compare(rest.size() - 6, 6, ",scale") == 0;
+            rest = scale ? rest.substr(0, rest.size() - 6) : rest;
+            size_t comma = rest.rfind(',');
+            std::string last = comma == std::string::npos ? "" : rest.substr(comma + 1);
+            const size_t before = comma == std::string::npos || comma == 0 ? std::string::npos : rest.rfind(',', comma - 1);
+            char *end = nullptr;
+            const unsigned long long n = strtoull(last.c_str(), &end, 10);
+            float r = 0.0f;
+            unsigned long long iterations = 16;
+            if (before != std::string::npos && before > 0 && !last.empty() && last.find_first_not_of("0123456789") == std::string::npos && *end == '\0' &&
+                n >= 1 && n <= 64 && real(rest.substr(before + 1, comma - before - 1).c_str(), r) && r * r > 0.0f && r * r <= 3.402823466e+38f) {
+                iterations = n;
+                rest = rest.substr(0, comma);
+                comma = before;
+                last = rest.substr(comma + 1);
+            }
+            if (comma == std::string::npos || comma == 0 || !real(last.c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
+                fprintf(stderr, "bad value '%s' of %s: TRUTH.ply,RADIUS[,ITERATIONS[,scale]], a file, a positive number and a count of 1 .. 64\n", all.c_str(),
+                        a.c_str());
+                return false;
+            }
+            o.ply_align_truth = rest.substr(0, comma);
+            o.ply_align_radius = r;
+            o.ply_align_iterations = (unsigned)iterations;
+            o.ply_align_scale = scale;
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
         } else if (a == "--seed") {
@@ -489,7 +528,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
@@ -498,8 +537,9 @@ int main(int argc, char **argv)
                         "  --ply-component-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points of connected components of fewer than MIN points, two points being joined when they are within RADIUS of each other, after --ply-radius-filter.\n"
                         "  --ply-smooth RADIUS,MIN[,ITERATIONS]: the points of APD.ply (and of what --ply-estimate-normals and --ply-render-vis then see) each projected on the weighted plane of the other points within RADIUS of it, where there are at least MIN (2 or more) of them, ITERATIONS (1 .. 16, default 1) times, after --ply-component-filter.\n"
                         "  --ply-estimate-normals RADIUS,MIN: the normals of the points of APD.ply (shown with --ply-normals) estimated from the other points within RADIUS of each, where there are at least MIN (2 or more) of them, after every other --ply-* flag but --ply-render-vis.\n"
-                        "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag but --ply-score.\n"
-                        "  --ply-score TRUTH.ply,TAU: prints, and writes to APD.ply.score, the precision, recall and F-score of the points of APD.ply against the vertices of the binary PLY file TRUTH.ply at the threshold TAU: the share of each cloud that has a point of the other within TAU; after every other --ply-* flag, APD.ply keeps its bytes.\n");
+                        "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag but --ply-align and --ply-score.\n"
+                        "  --ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]: the points of APD.ply are moved onto the vertices of the binary PLY file TRUTH.ply by point-to-point ICP within RADIUS, at most ITERATIONS (1 .. 64, default 16) steps, rigid or with `scale` a similarity; prints the transform and writes it to APD.ply.align; after every other --ply-* flag but --ply-score, APD.ply.vis is unchanged.\n"
+                        "  --ply-score TRUTH.ply,TAU: prints, and writes to APD.ply.score, the precision, recall and F-score of the points of APD.ply against the vertices of the binary PLY file TRUTH.ply at the threshold TAU: the share of each cloud that has a point of the other within TAU; after every other --ply-* flag, --ply-align included (it then scores the aligned points, and TRUTH.ply is read once when both name it), APD.ply keeps its bytes.\n");
         return EXIT_FAILURE;
     }
     if (opt.devices.empty()) {
@@ -524,6 +564,7 @@ int main(int argc, char **argv)
     SetFusionPlyEstimateNormals(opt.ply_normals_radius, opt.ply_normals_min);
     SetFusionPlyRenderVis(opt.ply_render_splat, opt.ply_render_tolerance);
     SetFusionPlyScore(opt.ply_score_truth, opt.ply_score_threshold);
+    SetFusionPlyAlign(opt.ply_align_truth, opt.ply_align_radius, opt.ply_align_iterations, opt.ply_align_scale);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

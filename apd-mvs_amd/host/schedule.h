@@ -54,6 +54,10 @@ struct Options {
     float ply_render_tolerance = 0.0f;    // cloud is drawn into them with footprints of SPLAT (apd_points_rendered_visibility), last; splat -1: off
     std::string ply_score_truth;          // --ply-score TRUTH.ply,TAU: the points of APD.ply scored against the cloud of TRUTH.ply at threshold TAU
     float ply_score_threshold = 0.0f;     // (apd_points_score), after every other --ply-* flag: one printed line and APD.ply.score; empty: off
+    std::string ply_align_truth;          // --ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]: the points of APD.ply moved onto the cloud of TRUTH.ply by ICP
+    float ply_align_radius = 0.0f;        // within RADIUS (apd_points_align, apd_points_transformed), after every other --ply-* flag but --ply-score: one
+    unsigned ply_align_iterations = 16;   // printed line and APD.ply.align; empty: off
+    bool ply_align_scale = false;
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)

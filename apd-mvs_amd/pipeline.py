@@ -552,7 +552,7 @@ def average_points(scene, results, points, device=0):
 
 def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False,
          vis_path=None, average=False, voxel=None, voxel_origin=None, radius_filter=None, stat_filter=None, component_filter=None,
-         estimate_normals=None, render_visibility=None, smooth=None, score=None):
+         estimate_normals=None, render_visibility=None, smooth=None, score=None, align=None):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -593,10 +593,16 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     file are those of Points.with_rendered_visibility(scene.cameras, splat, rel_tolerance), the same points as a merged object whose
     lists name the views that see each point of the cloud as it is then, occlusion included: the cloud is drawn into the scene's
     full-resolution cameras, in view order.  The step changes no byte of the PLY file.
+    align: (truth, radius[, iterations[, with_scale]]) -- applied after every other option but `score`: Points.align(truth, radius,
+    iterations=iterations, with_scale=with_scale) of the points the other options have produced (16 iterations, rigid, unless given)
+    and Points.transformed of them by its answer: the file and the returned points are the moved ones -- positions and normals;
+    the .vis file is what it is without the option, since moving changes no list -- and the Alignment is returned as one more
+    value after the count and the points and before the score: (count, Alignment), (count, Points, Alignment), (count, Points,
+    Alignment, Score).
     score: (truth, threshold) -- applied last, to the points every other option has produced, and changes none of them nor a byte of
     a file: Points.score(truth, threshold) of those points against `truth` (a Points: Points.read_ply of a ground truth, or another
     fusion's), the precision, recall and F-score at the threshold, returned as one more value after the others: (count, Score), or
-    (count, Points, Score) with return_points."""
+    (count, Points, Score) with return_points.  With `align` the points scored are the moved ones."""
     import ctypes as C
     from . import Points, default_fusion_options
     if variant not in FUSION_VARIANTS:
@@ -605,14 +611,35 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
         raise ValueError("fuse: neither a PLY file nor the points nor the visibility file are asked for")
     if score is not None:
         truth, threshold = score
-        n, whole = fuse(scene, results, ply_path, device, colour_images, block_masks, variant, options, return_points=True, vis_path=vis_path,
-                        average=average, voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                        component_filter=component_filter, estimate_normals=estimate_normals, render_visibility=render_visibility, smooth=smooth)
+        n, whole, *alignment = fuse(scene, results, ply_path, device, colour_images, block_masks, variant, options, return_points=True,
+                                    vis_path=vis_path, average=average, voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter,
+                                    stat_filter=stat_filter, component_filter=component_filter, estimate_normals=estimate_normals,
+                                    render_visibility=render_visibility, smooth=smooth, align=align)
         result = whole.score(truth, threshold)
         if return_points:
-            return n, whole, result
+            return (n, whole, *alignment, result)
         whole.close()
-        return n, result
+        return (n, *alignment, result)
+    if align is not None:
+        truth, radius, *rest = align
+        if len(rest) > 2:
+            raise ValueError("fuse: align=(truth, radius[, iterations[, with_scale]]), not %d values" % len(align))
+        iterations, with_scale = (rest + [16, False][len(rest):])
+        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
+                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
+                        component_filter=component_filter, estimate_normals=estimate_normals, render_visibility=render_visibility, smooth=smooth)
+        alignment = whole.align(truth, radius, iterations=iterations, with_scale=with_scale)
+        moved = whole.transformed(alignment)
+        whole.close()
+        if ply_path is not None:
+            moved.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
+        if vis_path is not None:
+            moved.write_vis(vis_path)
+        if return_points:
+            return moved.count, moved, alignment
+        n = moved.count
+        moved.close()
+        return n, alignment
     if render_visibility is not None:
         splat, rel_tolerance = render_visibility
         _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,

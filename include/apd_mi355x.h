@@ -706,6 +706,57 @@ typedef struct {
 } apd_points_score_t;
 int apd_points_nearest(apd_points_t p, apd_points_t q, float radius, const float *origin3, float *distance, int32_t *index);
 int apd_points_score(apd_points_t p, apd_points_t truth, float threshold, const float *origin3, apd_points_score_t *out);
+/* Alignment to another cloud, and the points moved by a transform.  A reconstruction stands in the arbitrary frame and scale of
+ * its structure-from-motion model and a ground truth in its scanner's; the Tanks and Temples protocol registers the two, refines
+ * with ICP and then computes the precision / recall of apd_points_score.  apd_points_align is that refinement: point-to-point ICP,
+ * rigid or with a scale, bounded by a radius; apd_points_transformed applies its answer, or any similarity transform, to the
+ * points object, so that sources, support, view / pixel and the visibility lists survive.  IEEE operations in the order given
+ * (contract C18; csrc/apd_align_math.h), binary64 with + - * / and sqrt alone.
+ *   Step k = 0, 1, .. on the positions X_k of p; X_0 is p's own.
+ *   Matches.  apd_points_nearest of X_k in q at `radius` and origin3, as it stands: a point without a candidate has no match.
+ *   Sums.  Over the matched points, p a point of X_k and q its match, coordinates converted to binary64: their number m, the sums
+ *   of p and of q, and of |p - q|^2; then, about the means pm and qm, the nine sums of (p - pm)_a (q - qm)_b and that of |p - pm|^2.
+ *   Each is taken per chunk of 256 consecutive indices of p by a fixed pairwise tree (csrc/apd_align_math.h) and the chunk sums are
+ *   added in ascending order.  rms_k = sqrt(sum |p - q|^2 / m).
+ *   Solve.  Horn's closed form: the 4 x 4 symmetric matrix of the nine sums, diagonalised by cyclic Jacobi (at most 16 sweeps); the
+ *   eigenvector of the largest eigenvalue is the rotation's quaternion, taken with w >= 0 and normalised: always a proper
+ *   rotation.  The step's scale is 1, or with_scale sum (q - qm) . R (p - pm) / sum |p - pm|^2; its translation qm - scale R pm.
+ *   Total.  The step is applied after the total of the steps before it, in binary64 on the host; X_{k+1} is X_0 moved by the
+ *   total, x' = (float)(((m_0 x + m_1 y) + m_2 z) + t) per component with m = scale * R, so that no rounding accumulates.
+ *   Stop.  After opt->iterations steps (1 .. 64; APD_ALIGN_ITERATIONS), or before step k when m < 3 or sum |p - pm|^2 == 0
+ *   (APD_ALIGN_TOO_FEW), or when k > 0 and |rms_k - rms_(k-1)| <= opt->tolerance * rms_(k-1) (APD_ALIGN_CONVERGED).
+ * apd_points_align: *out is the total (x' = scale * rotation x + translation, rotation row-major, takes p onto q), the number of
+ * matched points and their rms distance before any step and under the returned transform, the steps taken and why they ended.
+ * It moves nothing.  opt NULL: 16 iterations, tolerance 1e-6, no scale.  K steps take K + 1 searches, each with one sort of p's
+ * positions; q is sorted once.  Computed on p's device, on its null stream, whatever memory p is in; a host-resident q goes up
+ * for the call, a device-resident q must live on that device.  Of the points only chunk sums leave the device.  p and q may be the
+ * same object: the identity and rms 0.  When either has no points the answer is the identity, APD_ALIGN_TOO_FEW and 0 steps and
+ * no device is touched.  ICP within a radius needs a start within about that radius of the answer: there is no global
+ * registration here.
+ * apd_points_transformed: *out is a new object with p's points in p's order, xyz replaced by scale * R x + t (the expression
+ * above) and normal by R n, unscaled, in the same expression with t = +0.0, not renormalised; every other array is copied; it
+ * lives where p lives, is merged when p is and then carries p's lists.  p is left as it is.  An object without points gives an
+ * object without points with no device touched.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_align: ..." or "apd_points_transformed: ..."
+ * (apd_fusion_last_error): what apd_points_nearest refuses; iterations outside 1 .. 64, a tolerance that is negative or not
+ * finite; a NULL p, rotation9, translation3 or out, a number that is not finite, a scale <= 0, a rotation9 for which an entry of
+ * R^T R, in binary64, differs from the identity's by more than 1e-6; APD_ERR_UNSUPPORTED for 2^31 or more points.  *out is
+ * untouched when a call fails. */
+enum { APD_ALIGN_ITERATIONS = 0, APD_ALIGN_CONVERGED = 1, APD_ALIGN_TOO_FEW = 2 };
+typedef struct {
+    unsigned iterations;
+    double tolerance;
+    int with_scale;
+} apd_points_align_options;
+typedef struct {
+    double scale, rotation[9], translation[3];
+    long long matched_before, matched_after;
+    double rms_before, rms_after;
+    int steps, stopped;
+} apd_points_alignment_t;
+int apd_points_align(apd_points_t p, apd_points_t q, float radius, const float *origin3, const apd_points_align_options *opt,
+                     apd_points_alignment_t *out);
+int apd_points_transformed(apd_points_t p, double scale, const double *rotation9, const double *translation3, apd_points_t *out);
 /* The cloud drawn into a camera with a z-buffer, and from such maps the views that see each point, occlusion included: what the
  * cleaned cloud looks like from a camera (a depth map and a point-index map, to inspect holes, to derive a mask, to compare with a
  * view's own depth map), and the visibility lists COLMAP's Delaunay mesher and Poisson trimming read, rebuilt for the cloud as it
