@@ -205,6 +205,12 @@ def lib():
     L.apd_points_score.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsScore)]
     L.apd_points_align.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsAlignOptions), C.POINTER(PointsAlignment)]
     L.apd_points_transformed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_void_p)]
+    L.apd_points_features.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p, C.c_void_p]
+    L.apd_points_match_features.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
+    L.apd_points_match_features_bounded.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_int, C.c_ulonglong,
+                                                    C.c_void_p, C.c_void_p]
+    L.apd_points_register.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsRegisterOptions),
+                                      C.POINTER(PointsRegistration)]
     L.apd_points_read_ply.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.apd_points_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_void_p, C.c_void_p]
     L.apd_points_rendered_visibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
@@ -267,6 +273,26 @@ Alignment = collections.namedtuple("Alignment", [n for n, _ in PointsAlignment._
 ALIGN_ITERATIONS, ALIGN_CONVERGED, ALIGN_TOO_FEW = 0, 1, 2
 
 
+class PointsRegisterOptions(C.Structure):
+    """apd_points_register_options."""
+    _fields_ = [("trials", C.c_uint), ("seed", C.c_ulonglong), ("inlier_distance", C.c_float), ("edge_ratio", C.c_float), ("min_neighbours", C.c_uint),
+                ("mutual", C.c_int), ("with_scale", C.c_int)]
+
+
+class PointsRegistration(C.Structure):
+    """apd_points_registration_t."""
+    _fields_ = [("scale", C.c_double), ("rotation", C.c_double * 9), ("translation", C.c_double * 3)] + \
+               [(n, C.c_longlong) for n in ("features_p", "features_q", "matches", "trials_admitted", "best_trial", "inliers", "inliers_after")] + \
+               [("rms_after", C.c_double), ("stopped", C.c_int)]
+
+
+# What Points.register returns: the fields of apd_points_registration_t, rotation as a float64 [3, 3] array and translation as a
+# float64 [3] array; `stopped` is one of these
+Registration = collections.namedtuple("Registration", [n for n, _ in PointsRegistration._fields_])
+REGISTER_OK, REGISTER_TOO_FEW_MATCHES, REGISTER_NO_TRIAL = 0, 1, 2
+FEATURE_WIDTH = 33
+
+
 class _Borrowed:
     """Memory of a Points object as an array interface; keeps its owner alive."""
 
@@ -302,7 +328,9 @@ class Points:
     the nearest point of another Points within a radius (apd_points_nearest), score() the precision, recall and F-score of these
     points against another Points at a threshold (apd_points_score), align() the rigid or similarity transform that brings these
     points onto another Points by ICP within a radius (apd_points_align), transformed() these points moved by such a transform
-    (apd_points_transformed), and read_ply() makes a Points of a PLY file, a ground truth for instance (apd_points_read_ply).
+    (apd_points_transformed), features() every point's FPFH descriptor from the stored normals (apd_points_features),
+    match_features() the point of another Points with the nearest descriptor (apd_points_match_features), register() the transform
+    that brings these points onto another Points from any start, by RANSAC over those matches (apd_points_register), and read_ply() makes a Points of a PLY file, a ground truth for instance (apd_points_read_ply).
     render() draws the points into a camera with a z-buffer: the depth and the index of the nearest point per pixel
     (apd_points_render); with_rendered_visibility() gives these points as a merged object whose lists name the cameras that see
     each point, occlusion included (apd_points_rendered_visibility)."""
@@ -637,9 +665,9 @@ class Points:
         `truth` (a Points) at `threshold`: precision is the share of these points that have a point of `truth` within the threshold
         (p_within of n_p), recall the share of `truth` that has one of these within it (q_within of n_q), fscore their harmonic
         mean, mean_p and mean_q the mean distances of those that have one (contract C17; nearest() with radius = threshold in
-        both directions).  Nearest-neighbour precision and recall at one threshold: align() and transformed() refine a registration
-        first, but there is no initial global registration (ICP within a radius needs a start within about that radius), no
-        cropping volume and no occlusion-aware evaluation: scores compare with each other.  Computed on these points' device."""
+        both directions).  Nearest-neighbour precision and recall at one threshold: register() gives a registration from any start
+        and align() and transformed() refine it first, but there is no cropping volume, no point-to-plane refinement and no
+        occlusion-aware evaluation as ETH3D's: scores compare with each other.  Computed on these points' device."""
         if not self._p:
             raise ApdError("Points.score: the points are closed")
         if not isinstance(truth, Points) or not truth._p:
@@ -661,8 +689,8 @@ class Points:
         the next step.  It ends after `iterations` (1 .. 64) steps (stopped == ALIGN_ITERATIONS), when the rms distance of the
         matched pairs changes by no more than `tolerance` times itself (ALIGN_CONVERGED), or when fewer than 3 points are matched
         or all matched points coincide (ALIGN_TOO_FEW).  matched_ and rms_before describe the points as they are, _after under
-        the returned transform.  Nothing is moved: transformed() does that.  The start must be within about a radius of the answer;
-        there is no global registration.  Computed on these points' device."""
+        the returned transform.  Nothing is moved: transformed() does that.  The start must be within about a radius of the answer:
+        register() gives such a start from anywhere.  Computed on these points' device."""
         if not self._p:
             raise ApdError("Points.align: the points are closed")
         if not isinstance(other, Points) or not other._p:
@@ -681,17 +709,17 @@ class Points:
     def transformed(self, scale, rotation=None, translation=None):
         """apd_points_transformed: these points in their order with xyz replaced by scale * rotation @ x + translation and normal by
         rotation @ n (not scaled, not renormalised), each component as (float)(((m0 x + m1 y) + m2 z) + t) in binary64, and every
-        other array and the lists as they are: transformed(alignment) with what align() returned, or transformed(scale, rotation,
+        other array and the lists as they are: transformed(alignment) with what align() or register() returned, or transformed(scale, rotation,
         translation) with a positive scale, a rotation (3 x 3, row-major, orthonormal to 1e-6) and a translation.  A merged object
         gives a merged object.  Computed on these points' device; the result lives where they live."""
         if not self._p:
             raise ApdError("Points.transformed: the points are closed")
-        if isinstance(scale, Alignment):
+        if isinstance(scale, (Alignment, Registration)):
             if rotation is not None or translation is not None:
-                raise TypeError("Points.transformed: an Alignment, or scale, rotation and translation")
+                raise TypeError("Points.transformed: an Alignment or a Registration, or scale, rotation and translation")
             scale, rotation, translation = scale.scale, scale.rotation, scale.translation
         if rotation is None or translation is None:
-            raise TypeError("Points.transformed: an Alignment, or scale, rotation and translation")
+            raise TypeError("Points.transformed: an Alignment or a Registration, or scale, rotation and translation")
         R, t = np.ascontiguousarray(rotation, np.float64), np.ascontiguousarray(translation, np.float64)
         if R.size != 9 or t.size != 3:
             raise ValueError("Points.transformed: a rotation of %d and a translation of %d numbers, not 9 and 3" % (R.size, t.size))
@@ -701,6 +729,93 @@ class Points:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Points(out, self.device)
+
+    def _outputs(self, specs):
+        """Arrays for a query's results, [(shape after the point count, numpy dtype)]: (arrays, addresses) -- numpy for host points,
+        torch tensors on their device for device points; an object without points gets the address of a dummy, which the library wants and
+        which lives as long as `addresses` does."""
+        nothing = (C.c_float * 1)()
+        if self.on_device:
+            import torch
+            device = torch.device("cuda", self.device)
+            arrays = [torch.empty((self.count,) + shape, dtype=getattr(torch, np.dtype(dt).name), device=device) for shape, dt in specs]
+            torch.cuda.synchronize(device)
+            addresses = [C.c_void_p(a.data_ptr()) if self.count else C.cast(nothing, C.c_void_p) for a in arrays]
+        else:
+            arrays = [np.zeros((self.count,) + shape, dt) for shape, dt in specs]
+            addresses = [C.c_void_p(a.ctypes.data) if self.count else C.cast(nothing, C.c_void_p) for a in arrays]
+        return arrays, (addresses, nothing)
+
+    def features(self, radius, min_neighbours=5, origin=None):
+        """apd_points_features: (features float32 [N, 33], has uint8 [N]) -- every point's FPFH descriptor from the STORED normals
+        and its neighbours within `radius` (contract C19: three histograms of 11 bins over the pair features of PCL's
+        computePairFeatures, each block summing to 1), zeros and has = 0 for a point with fewer than `min_neighbours` (>= 3)
+        admitted neighbours, a normal of length 0 or not finite, or a position outside the grid.  with_estimated_normals() first
+        for points that carry no normals.  numpy arrays for host points, torch tensors on their device for device points."""
+        if not self._p:
+            raise ApdError("Points.features: the points are closed")
+        if not 0 <= int(min_neighbours) <= 0xFFFFFFFF:
+            raise ValueError("Points.features: a minimum of %r neighbours, not in 0 .. 2^32 - 1" % (min_neighbours,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        (features, has), (addresses, _keep) = self._outputs([((FEATURE_WIDTH,), np.float32), ((), np.uint8)])
+        rc = L.apd_points_features(self._p, float(radius), org, int(min_neighbours), addresses[0], addresses[1])
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return features, has
+
+    def match_features(self, other, radius, min_neighbours=5, mutual=True, origin=None, _pair_bound=None):
+        """apd_points_match_features: (index int32 [N], distance float32 [N]) -- per point with a descriptor (features()) the index
+        in `other` (a Points, which may be this one) of the point whose descriptor is nearest in the 33 dimensions and that
+        distance, the smallest index among equals; `mutual`: only where the match's own match is the point; -1 and +inf where
+        there is none.  The cost is the product of the two numbers of descriptors: at most 262144 points on either side
+        (merge_voxels() thins a cloud).  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.match_features: the points are closed")
+        if not isinstance(other, Points) or not other._p:
+            raise ApdError("Points.match_features: the other points are closed or not a Points")
+        if not 0 <= int(min_neighbours) <= 0xFFFFFFFF:
+            raise ValueError("Points.match_features: a minimum of %r neighbours, not in 0 .. 2^32 - 1" % (min_neighbours,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        (index, distance), (addresses, _keep) = self._outputs([((), np.int32), ((), np.float32)])
+        if _pair_bound is None:
+            rc = L.apd_points_match_features(self._p, other._p, float(radius), org, int(min_neighbours), int(bool(mutual)), addresses[0], addresses[1])
+        else:
+            rc = L.apd_points_match_features_bounded(self._p, other._p, float(radius), org, int(min_neighbours), int(bool(mutual)), int(_pair_bound),
+                                                     addresses[0], addresses[1])
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return index, distance
+
+    def register(self, other, radius, inlier_distance=None, origin=None, trials=4096, seed=0, edge_ratio=0.9, min_neighbours=5, mutual=True,
+                 with_scale=False):
+        """apd_points_register: Registration(scale, rotation, translation, features_p, features_q, matches, trials_admitted,
+        best_trial, inliers, inliers_after, rms_after, stopped) -- the transform x' = scale * rotation @ x + translation that
+        brings these points onto `other` (a Points) from ANY start, for clouds whose scale is already about right (contract C19):
+        the matches of match_features() at `radius`; `trials` (1 .. 65536) RANSAC trials, each on three matches drawn by a
+        counter-based generator keyed by (seed, trial), admitted when the two triangles' edges agree within `edge_ratio`; the
+        trial with the most matches within `inlier_distance` (radius / 2 by default) after its rigid transform; and that transform
+        refitted on its inliers by align()'s solve -- with_scale: with a scale, which is only refined.  stopped is REGISTER_OK,
+        REGISTER_TOO_FEW_MATCHES (fewer than 3 matches) or REGISTER_NO_TRIAL (no admitted trial, or fewer than 3 inliers); the
+        failures give the identity.  The descriptors use the stored normals.  Nothing is moved: transformed(registration) does
+        that, and align() then refines it.  The same call gives the same bits.  Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.register: the points are closed")
+        if not isinstance(other, Points) or not other._p:
+            raise ApdError("Points.register: the other points are closed or not a Points")
+        if not (0 <= int(trials) <= 0xFFFFFFFF and 0 <= int(min_neighbours) <= 0xFFFFFFFF and 0 <= int(seed) < 2 ** 64):
+            raise ValueError("Points.register: trials %r, min_neighbours %r or seed %r outside their unsigned types" % (trials, min_neighbours, seed))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        distance = float(np.float32(radius) * np.float32(0.5)) if inlier_distance is None else float(inlier_distance)
+        options = PointsRegisterOptions(int(trials), int(seed), distance, float(edge_ratio), int(min_neighbours), int(bool(mutual)), int(bool(with_scale)))
+        out = PointsRegistration()
+        rc = L.apd_points_register(self._p, other._p, float(radius), org, C.byref(options), C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Registration(out.scale, np.array(out.rotation, np.float64).reshape(3, 3), np.array(out.translation, np.float64),
+                            *[getattr(out, n) for n in Registration._fields[3:]])
 
     @classmethod
     def read_ply(cls, path, device=0, on_device=False):

@@ -200,6 +200,7 @@ void SetFusionPlyRenderVis(int splat, float rel_tolerance);
 // written to <dense>/APD/APD.ply.score as `key value` lines; APD.ply and APD.ply.vis keep their bytes.  empty: off
 void SetFusionPlyScore(const std::string &truth_ply, float threshold);
 void SetFusionPlyAlign(const std::string &truth_ply, float radius, unsigned iterations, bool with_scale);
+void SetFusionPlyRegister(const std::string &truth_ply, float radius, float inlier_distance, unsigned trials, unsigned long long seed);
 
 class APD {
 public:

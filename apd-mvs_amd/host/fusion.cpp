@@ -51,14 +51,19 @@ std::string g_fusion_ply_align_truth;      // SetFusionPlyAlign; empty: off
 float g_fusion_ply_align_radius = 0.0f;
 unsigned g_fusion_ply_align_iterations = 16;
 bool g_fusion_ply_align_scale = false;
+std::string g_fusion_ply_register_truth;   // SetFusionPlyRegister; empty: off
+float g_fusion_ply_register_radius = 0.0f;
+float g_fusion_ply_register_distance = 0.0f;
+unsigned g_fusion_ply_register_trials = 4096;
+unsigned long long g_fusion_ply_register_seed = 0;
 
 // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-smooth, --ply-estimate-normals,
-// --ply-render-vis, --ply-align or --ply-score: APD.ply is written from the points after the fusion, not by it
+// --ply-render-vis, --ply-register, --ply-align or --ply-score: APD.ply is written from the points after the fusion, not by it
 bool ply_from_points()
 {
     return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f ||
            g_fusion_ply_component_radius > 0.0f || g_fusion_ply_smooth_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f || g_fusion_ply_render_splat >= 0 ||
-           !g_fusion_ply_align_truth.empty() || !g_fusion_ply_score_truth.empty();
+           !g_fusion_ply_register_truth.empty() || !g_fusion_ply_align_truth.empty() || !g_fusion_ply_score_truth.empty();
 }
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
@@ -203,10 +208,19 @@ void SetFusionPlyAlign(const std::string &truth_ply, float radius, unsigned iter
     g_fusion_ply_align_scale = with_scale;
 }
 
+void SetFusionPlyRegister(const std::string &truth_ply, float radius, float inlier_distance, unsigned trials, unsigned long long seed)
+{
+    g_fusion_ply_register_truth = truth_ply;
+    g_fusion_ply_register_radius = radius;
+    g_fusion_ply_register_distance = inlier_distance;
+    g_fusion_ply_register_trials = trials;
+    g_fusion_ply_register_seed = seed;
+}
+
 namespace {
 
-// The cloud of a truth file of --ply-align and --ply-score (apd_points_read_ply into host memory): read once when both name
-// the same file
+// The cloud of a truth file of --ply-register, --ply-align and --ply-score (apd_points_read_ply into host memory): read once when
+// several name the same file
 struct Truth {
     apd_points_t points = nullptr;
     std::string file;
@@ -231,6 +245,58 @@ void write_lines_or_exit(const std::string &to, const std::string &lines)
         std::cerr << "cannot write " << to << std::endl;
         exit(EXIT_FAILURE);
     }
+}
+
+// --ply-register: replaces the points by themselves moved onto the cloud of the truth file from any start (apd_points_register on
+// the fusion's device with the defaults of its other options, apd_points_transformed by its answer): one line with every field, and
+// the same as `name value` lines in <ply_path>.register
+int register_beside(apd_points_t &points, Truth &truth, const path &ply_path)
+{
+    int st = truth.read(g_fusion_ply_register_truth);
+    const apd_points_register_options options = {g_fusion_ply_register_trials, g_fusion_ply_register_seed, g_fusion_ply_register_distance, 0.9f, 5, 1, 0};
+    apd_points_registration_t r;
+    st = st != APD_OK ? st : apd_points_register(points, truth.points, g_fusion_ply_register_radius, nullptr, &options, &r);
+    apd_points_t moved = nullptr;
+    st = st != APD_OK ? st : apd_points_transformed(points, r.scale, r.rotation, r.translation, &moved);
+    if (st != APD_OK) {
+        return st;
+    }
+    apd_points_destroy(points);
+    points = moved;
+    std::string line, lines;
+    char text[64];
+    const auto add = [&](const std::string &name, const char *value) {
+        line += " " + name + " " + value;
+        lines += name + " " + value + "\n";
+    };
+    const auto real = [&](const std::string &name, double v) {
+        snprintf(text, sizeof(text), "%.17g", v);  // the double, back to the bit
+        add(name, text);
+    };
+    const auto integer = [&](const std::string &name, long long v) {
+        snprintf(text, sizeof(text), "%lld", v);
+        add(name, text);
+    };
+    real("scale", r.scale);
+    for (int e = 0; e < 9; ++e) {
+        real("rotation" + std::to_string(e), r.rotation[e]);
+    }
+    for (int e = 0; e < 3; ++e) {
+        real("translation" + std::to_string(e), r.translation[e]);
+    }
+    integer("features_p", r.features_p);
+    integer("features_q", r.features_q);
+    integer("matches", r.matches);
+    integer("trials_admitted", r.trials_admitted);
+    integer("best_trial", r.best_trial);
+    integer("inliers", r.inliers);
+    integer("inliers_after", r.inliers_after);
+    real("rms_after", r.rms_after);
+    integer("stopped", r.stopped);
+    std::cout << "Registered to " << g_fusion_ply_register_truth << " at " << g_fusion_ply_register_radius << " within " << g_fusion_ply_register_distance
+              << ":" << line << std::endl;
+    write_lines_or_exit(ply_path.string() + ".register", lines);
+    return APD_OK;
 }
 
 // --ply-align: replaces the points by themselves moved onto the cloud of the truth file (apd_points_align on the fusion's device,
@@ -320,7 +386,8 @@ int score_beside(apd_points_t points, Truth &truth, const path &ply_path)
 // --ply-estimate-normals: replaces the normals of what these left by those of each point's neighbourhood
 // (apd_points_with_estimated_normals) and prints how many points got one; --ply-render-vis: replaces the lists of what these left by
 // the views that see each point when the cloud is drawn into full_cameras, the views' cameras at the size of their images
-// (apd_points_rendered_visibility), and prints how many points no view sees; --ply-align: replaces what these left by the same points
+// (apd_points_rendered_visibility), and prints how many points no view sees; --ply-register: replaces what these left by the same
+// points moved onto the cloud of a truth file from any start (register_beside); --ply-align: replaces what these left by the same points
 // moved onto the cloud of a truth file (align_beside).  Then writes ply_path from them (apd_points_write_ply); the fusion itself
 // wrote no file; --ply-score: scores the points the file was written from (score_beside), which changes none of them
 void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const apd_camera *full_cameras, const float *const *depths,
@@ -420,6 +487,9 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
         }
     }
     Truth truth;
+    if (st == APD_OK && !g_fusion_ply_register_truth.empty()) {
+        st = register_beside(points, truth, ply_path);
+    }
     if (st == APD_OK && !g_fusion_ply_align_truth.empty()) {
         st = align_beside(points, truth, ply_path);
     }

@@ -5,7 +5,8 @@
 //       [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK]
 //       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN]
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
-//       [--ply-render-vis SPLAT,TOL] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-score TRUTH.ply,TAU] [--filtered-maps]
+//       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
+//       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-score TRUTH.ply,TAU] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -56,6 +57,13 @@
 // its pixel (apd_points_rendered_visibility); applied last, after --ply-estimate-normals.  With every --fusion; APD.ply keeps the
 // bytes it has without the flag, and the number of points no view sees is printed.  SPLAT must be a count of 0 .. 8 and TOL a
 // non-negative finite number, or the usage line is all that happens.
+// --ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]: the points that APD.ply holds are moved onto the vertices of the binary
+// little-endian PLY file TRUTH.ply from any start (apd_points_read_ply, apd_points_register: FPFH descriptors of the stored normals
+// at RADIUS, their mutual matches, TRIALS (1 .. 65536, default 4096) RANSAC trials keyed by SEED (default 0) with inliers within
+// DISTANCE, a refit; apd_points_transformed by its answer), after every other --ply-* flag but --ply-align and --ply-score, which
+// then work on the moved points; TRUTH.ply is read once when several flags name it.  One line "Registered to ..." with every field
+// of apd_points_registration_t is printed and APD.ply.register holds the same as one `name value` line per number, the doubles as
+// %.17g.  APD.ply.vis keeps its bytes.  The value is read from its end: the longest tail of two to four numbers that fits.
 // --ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]: the points that APD.ply holds are moved onto the vertices of the binary
 // little-endian PLY file TRUTH.ply by point-to-point ICP within RADIUS (apd_points_read_ply, apd_points_align with ITERATIONS steps
 // at most -- 1 .. 64, 16 without -- and the tolerance 1e-6, rigid, or a similarity with `scale`; apd_points_transformed by its
@@ -101,6 +109,7 @@
 // --in-memory) when the folder fits it -- the files of the last pass are written with --keep-maps.
 // Not built: the debug JPEGs of show_medium_result.
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -108,6 +117,7 @@
 #include <fstream>
 #include <iterator>
 #include <string>
+#include <vector>
 
 #include "APD.h"
 #include "schedule.h"
@@ -287,6 +297,49 @@ bool ParseOptions(int argc, char **argv, Options &o)
             }
             o.ply_score_truth = both.substr(0, comma);
             o.ply_score_threshold = t;
+        } else if (a == "--ply-register") {
+            // read from the right, since the file's name may hold commas: the longest tail of four, three or two tokens that is
+            // RADIUS,DISTANCE[,TRIALS[,SEED]]
+            const std::string all = i + 1 < argc ? argv[++i] : "";
+            std::vector<size_t> commas;  // from the right
+            for (size_t at = all.rfind(','); at != std::string::npos && at > 0 && commas.size() < 4; at = all.rfind(',', at - 1)) {
+                commas.push_back(at);
+            }
+            const auto count = [](const std::string &text, unsigned long long lo, unsigned long long hi, unsigned long long &dst) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long n = strtoull(text.c_str(), &end, 10);
+                if (text.empty() || text.find_first_not_of("0123456789") != std::string::npos || *end != '\0' || errno != 0 || n < lo || n > hi) {
+                    return false;
+                }
+                dst = n;
+                return true;
+            };
+            bool found = false;
+            for (size_t tokens = commas.size(); tokens >= 2 && !found; --tokens) {
+                std::vector<std::string> token;
+                for (size_t k = tokens; k >= 1; --k) {
+                    const size_t from = commas[k - 1] + 1, to = k >= 2 ? commas[k - 2] : all.size();
+                    token.push_back(all.substr(from, to - from));
+                }
+                float r = 0.0f, d = 0.0f;
+                unsigned long long trials = 4096, seed = 0;
+                if (real(token[0].c_str(), r) && r * r > 0.0f && r * r <= 3.402823466e+38f && real(token[1].c_str(), d) && d * d > 0.0f &&
+                    d * d <= 3.402823466e+38f && (tokens < 3 || count(token[2], 1, 65536, trials)) && (tokens < 4 || count(token[3], 0, ~0ull, seed))) {
+                    found = true;
+                    o.ply_register_truth = all.substr(0, commas[tokens - 1]);
+                    o.ply_register_radius = r;
+                    o.ply_register_distance = d;
+                    o.ply_register_trials = (unsigned)trials;
+                    o.ply_register_seed = seed;
+                }
+            }
+            if (!found) {
+                fprintf(stderr,
+                        "bad value '%s' of %s: TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]], a file, two positive numbers, a count of 1 .. 65536 and a seed\n",
+                        all.c_str(), a.c_str());
+                return false;
+            }
         } else if (a == "--ply-align") {
             // read from the right, since the file's name may hold commas: [,scale], then [,ITERATIONS] when what stands before it is a
             // radius too, then ,RADIUS
@@ -528,7 +581,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
@@ -537,7 +590,8 @@ int main(int argc, char **argv)
                         "  --ply-component-filter RADIUS,MIN: APD.ply (and APD.ply.vis) without the points of connected components of fewer than MIN points, two points being joined when they are within RADIUS of each other, after --ply-radius-filter.\n"
                         "  --ply-smooth RADIUS,MIN[,ITERATIONS]: the points of APD.ply (and of what --ply-estimate-normals and --ply-render-vis then see) each projected on the weighted plane of the other points within RADIUS of it, where there are at least MIN (2 or more) of them, ITERATIONS (1 .. 16, default 1) times, after --ply-component-filter.\n"
                         "  --ply-estimate-normals RADIUS,MIN: the normals of the points of APD.ply (shown with --ply-normals) estimated from the other points within RADIUS of each, where there are at least MIN (2 or more) of them, after every other --ply-* flag but --ply-render-vis.\n"
-                        "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag but --ply-align and --ply-score.\n"
+                        "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag but --ply-register, --ply-align and --ply-score.\n"
+                        "  --ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]: the points of APD.ply are moved onto the vertices of the binary PLY file TRUTH.ply from any start, at a scale that is about right: FPFH descriptors of the stored normals at RADIUS, their mutual matches, TRIALS (1 .. 65536, default 4096) RANSAC trials keyed by SEED (default 0) with inliers within DISTANCE, a refit; prints the transform and writes it to APD.ply.register; after every other --ply-* flag but --ply-align and --ply-score, which work on the moved points; APD.ply.vis is unchanged.\n"
                         "  --ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]: the points of APD.ply are moved onto the vertices of the binary PLY file TRUTH.ply by point-to-point ICP within RADIUS, at most ITERATIONS (1 .. 64, default 16) steps, rigid or with `scale` a similarity; prints the transform and writes it to APD.ply.align; after every other --ply-* flag but --ply-score, APD.ply.vis is unchanged.\n"
                         "  --ply-score TRUTH.ply,TAU: prints, and writes to APD.ply.score, the precision, recall and F-score of the points of APD.ply against the vertices of the binary PLY file TRUTH.ply at the threshold TAU: the share of each cloud that has a point of the other within TAU; after every other --ply-* flag, --ply-align included (it then scores the aligned points, and TRUTH.ply is read once when both name it), APD.ply keeps its bytes.\n");
         return EXIT_FAILURE;
@@ -564,6 +618,7 @@ int main(int argc, char **argv)
     SetFusionPlyEstimateNormals(opt.ply_normals_radius, opt.ply_normals_min);
     SetFusionPlyRenderVis(opt.ply_render_splat, opt.ply_render_tolerance);
     SetFusionPlyScore(opt.ply_score_truth, opt.ply_score_threshold);
+    SetFusionPlyRegister(opt.ply_register_truth, opt.ply_register_radius, opt.ply_register_distance, opt.ply_register_trials, opt.ply_register_seed);
     SetFusionPlyAlign(opt.ply_align_truth, opt.ply_align_radius, opt.ply_align_iterations, opt.ply_align_scale);
 
     std::vector<Problem> problems;

@@ -58,6 +58,11 @@ struct Options {
     float ply_align_radius = 0.0f;        // within RADIUS (apd_points_align, apd_points_transformed), after every other --ply-* flag but --ply-score: one
     unsigned ply_align_iterations = 16;   // printed line and APD.ply.align; empty: off
     bool ply_align_scale = false;
+    std::string ply_register_truth;       // --ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]: the points of APD.ply moved onto the cloud of TRUTH.ply from
+    float ply_register_radius = 0.0f;     // any start (apd_points_register with descriptors at RADIUS and inliers within DISTANCE, apd_points_transformed),
+    float ply_register_distance = 0.0f;   // after every other --ply-* flag but --ply-align and --ply-score: one printed line and APD.ply.register; empty: off
+    unsigned ply_register_trials = 4096;
+    unsigned long long ply_register_seed = 0;
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)

@@ -552,7 +552,7 @@ def average_points(scene, results, points, device=0):
 
 def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False,
          vis_path=None, average=False, voxel=None, voxel_origin=None, radius_filter=None, stat_filter=None, component_filter=None,
-         estimate_normals=None, render_visibility=None, smooth=None, score=None, align=None):
+         estimate_normals=None, render_visibility=None, smooth=None, score=None, align=None, register=None):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -593,6 +593,11 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     file are those of Points.with_rendered_visibility(scene.cameras, splat, rel_tolerance), the same points as a merged object whose
     lists name the views that see each point of the cloud as it is then, occlusion included: the cloud is drawn into the scene's
     full-resolution cameras, in view order.  The step changes no byte of the PLY file.
+    register: (truth, radius, inlier_distance[, trials[, seed]]) -- applied after every other option and before `align`:
+    Points.register(truth, radius, inlier_distance, trials=trials, seed=seed) of the points the other options have produced (4096
+    trials, seed 0, unless given) -- global registration from any start by FPFH descriptors of the STORED normals, their matches and
+    RANSAC -- and Points.transformed of them by its answer, as `align` moves them; the Registration is returned as one more value
+    before the Alignment: (count, Registration[, Alignment][, Score]), or (count, Points, Registration, ..) with return_points.
     align: (truth, radius[, iterations[, with_scale]]) -- applied after every other option but `score`: Points.align(truth, radius,
     iterations=iterations, with_scale=with_scale) of the points the other options have produced (16 iterations, rigid, unless given)
     and Points.transformed of them by its answer: the file and the returned points are the moved ones -- positions and normals;
@@ -614,7 +619,7 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
         n, whole, *alignment = fuse(scene, results, ply_path, device, colour_images, block_masks, variant, options, return_points=True,
                                     vis_path=vis_path, average=average, voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter,
                                     stat_filter=stat_filter, component_filter=component_filter, estimate_normals=estimate_normals,
-                                    render_visibility=render_visibility, smooth=smooth, align=align)
+                                    render_visibility=render_visibility, smooth=smooth, align=align, register=register)
         result = whole.score(truth, threshold)
         if return_points:
             return (n, whole, *alignment, result)
@@ -625,9 +630,10 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
         if len(rest) > 2:
             raise ValueError("fuse: align=(truth, radius[, iterations[, with_scale]]), not %d values" % len(align))
         iterations, with_scale = (rest + [16, False][len(rest):])
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                        component_filter=component_filter, estimate_normals=estimate_normals, render_visibility=render_visibility, smooth=smooth)
+        _, whole, *registration = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
+                                       voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
+                                       component_filter=component_filter, estimate_normals=estimate_normals, render_visibility=render_visibility,
+                                       smooth=smooth, register=register)
         alignment = whole.align(truth, radius, iterations=iterations, with_scale=with_scale)
         moved = whole.transformed(alignment)
         whole.close()
@@ -636,10 +642,30 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
         if vis_path is not None:
             moved.write_vis(vis_path)
         if return_points:
-            return moved.count, moved, alignment
+            return (moved.count, moved, *registration, alignment)
         n = moved.count
         moved.close()
-        return n, alignment
+        return (n, *registration, alignment)
+    if register is not None:
+        truth, radius, inlier_distance, *rest = register
+        if len(rest) > 2:
+            raise ValueError("fuse: register=(truth, radius, inlier_distance[, trials[, seed]]), not %d values" % len(register))
+        trials, seed = (rest + [4096, 0][len(rest):])
+        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
+                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
+                        component_filter=component_filter, estimate_normals=estimate_normals, render_visibility=render_visibility, smooth=smooth)
+        registration = whole.register(truth, radius, inlier_distance, trials=trials, seed=seed)
+        moved = whole.transformed(registration)
+        whole.close()
+        if ply_path is not None:
+            moved.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
+        if vis_path is not None:
+            moved.write_vis(vis_path)
+        if return_points:
+            return moved.count, moved, registration
+        n = moved.count
+        moved.close()
+        return n, registration
     if render_visibility is not None:
         splat, rel_tolerance = render_visibility
         _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,

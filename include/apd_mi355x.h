@@ -731,8 +731,8 @@ int apd_points_score(apd_points_t p, apd_points_t truth, float threshold, const 
  * positions; q is sorted once.  Computed on p's device, on its null stream, whatever memory p is in; a host-resident q goes up
  * for the call, a device-resident q must live on that device.  Of the points only chunk sums leave the device.  p and q may be the
  * same object: the identity and rms 0.  When either has no points the answer is the identity, APD_ALIGN_TOO_FEW and 0 steps and
- * no device is touched.  ICP within a radius needs a start within about that radius of the answer: there is no global
- * registration here.
+ * no device is touched.  ICP within a radius needs a start within about that radius of the answer: apd_points_register (below)
+ * gives one from any start.
  * apd_points_transformed: *out is a new object with p's points in p's order, xyz replaced by scale * R x + t (the expression
  * above) and normal by R n, unscaled, in the same expression with t = +0.0, not renormalised; every other array is copied; it
  * lives where p lives, is merged when p is and then carries p's lists.  p is left as it is.  An object without points gives an
@@ -757,6 +757,69 @@ typedef struct {
 int apd_points_align(apd_points_t p, apd_points_t q, float radius, const float *origin3, const apd_points_align_options *opt,
                      apd_points_alignment_t *out);
 int apd_points_transformed(apd_points_t p, double scale, const double *rotation9, const double *translation3, apd_points_t *out);
+/* Global registration to another cloud: the first step of "register, refine with ICP, score" for a cloud that stands in an
+ * arbitrary frame relative to the other, at a scale that is already about right.  FPFH descriptors from the STORED normals
+ * (apd_points_with_estimated_normals gives a cloud that has none its normals), the nearest descriptor of the other cloud for
+ * every point, RANSAC over those matches and a refit of the winning transform on its inliers by the solve of apd_points_align.
+ * IEEE operations in the order given (contract C19; csrc/apd_register_math.h): + - * / and sqrt alone, no trigonometric
+ * function anywhere.
+ *   Descriptors.  A point has a frame when its normal's length is finite and > 0 and it lies inside the grid (cell size `radius`,
+ *   origin3); its neighbours are those of apd_points_neighbour_counts at `radius` that have a frame.  Per (centre, neighbour) the
+ *   Darboux frame and the three features of PCL's computePairFeatures, in binary64; a neighbour at the same position, or with
+ *   the connecting line parallel to the source normal, is skipped.  Each feature falls into one of 11 bins: the two cosines
+ *   linearly over [-1, 1], the angle over [-pi, pi) by comparing its (sine, cosine) pair with the ten edge directions.  SPFH: the
+ *   three histograms over the k admitted neighbours divided by k; a point with k < min_neighbours (>= 3) has no descriptor.
+ *   FPFH = SPFH + (1 / k) sum SPFH(neighbour) / d^2 over the admitted neighbours that have an SPFH, in the search's ascending
+ *   order, each block of 11 divided by its own sum: 33 floats per point, 33 zeros and has = 0 for a point without a descriptor.
+ *   Matches.  For a point of p with a descriptor the point of q with a descriptor at the least squared distance in the 33
+ *   dimensions (binary32, ascending bins), the smallest index among equals; `mutual`: kept only when the match's match is the
+ *   point itself.  index is the match's index in q (-1: none), distance the distance in the 33 dimensions (+inf: none).
+ *   Trials.  Trial t = 0 .. trials - 1 draws three distinct matches from a counter-based generator keyed by (seed, t); it is
+ *   admitted when each edge of the triangle has squared lengths on the two sides within edge_ratio^2 of each other and neither
+ *   triangle is degenerate; its rigid transform is the solve of apd_points_align on the three pairs.  A match is an inlier of a
+ *   transform when p's point, moved, lies within inlier_distance of q's.  The best trial has the most inliers, the lowest t among
+ *   equals.
+ *   Refit.  One solve of apd_points_align over the best trial's inlier pairs, with_scale the caller's choice (the scale is only
+ *   refined: the trials are rigid); the inliers are counted once more under it, with their rms distance.
+ * apd_points_features: features (33 per point) and has (may be NULL) in host or device memory by p's residence.
+ * apd_points_match_features: index and distance (either may be NULL, not both), likewise.
+ * apd_points_register: *out is the transform (x' = scale * rotation x + translation, takes p onto q; apd_points_transformed
+ * applies it), the number of points with a descriptor on either side, of matches, of admitted trials, the best trial (-1: none)
+ * and its inliers, the inliers and their rms distance under the returned transform, and how it ended: APD_REGISTER_OK;
+ * APD_REGISTER_TOO_FEW_MATCHES with fewer than 3 matches; APD_REGISTER_NO_TRIAL when no trial is admitted or the best has fewer
+ * than 3 inliers; both failures return the identity.  opt NULL: 4096 trials, seed 0, inlier_distance radius / 2, edge_ratio 0.9,
+ * min_neighbours 5, mutual, no scale.  The same call gives the same bits.  Computed on p's device, on its null stream; a
+ * host-resident q goes up for the call, a device-resident q must live on that device.  The index array and the positions come to
+ * the host for the trials; of the trials only the admitted transforms go up and the counts come down.  When either object has no
+ * points the answer is the identity and APD_REGISTER_TOO_FEW_MATCHES and no device is touched.
+ * The cost of matching is the product of the two numbers of descriptors: registration is done on a thinned cloud
+ * (apd_points_merge_voxels).  Not here: a cropping volume, point-to-plane refinement, ETH3D's occlusion-aware evaluation.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_features: ...", "apd_points_match_features:
+ * ..." or "apd_points_register: ..." (apd_fusion_last_error): what apd_points_neighbour_counts refuses for either object, a
+ * min_neighbours < 3, trials outside 1 .. 65536, an inlier_distance that is not positive and finite with such a square, an
+ * edge_ratio outside (0, 1]; APD_ERR_UNSUPPORTED for more than 262144 points on either side of a match.  The outputs are
+ * untouched when a call fails. */
+enum { APD_REGISTER_OK = 0, APD_REGISTER_TOO_FEW_MATCHES = 1, APD_REGISTER_NO_TRIAL = 2 };
+int apd_points_features(apd_points_t p, float radius, const float *origin3, unsigned min_neighbours, float *features, unsigned char *has);
+int apd_points_match_features(apd_points_t p, apd_points_t q, float radius, const float *origin3, unsigned min_neighbours, int mutual,
+                              int32_t *index, float *distance);
+typedef struct {
+    unsigned trials;
+    unsigned long long seed;
+    float inlier_distance;
+    float edge_ratio;
+    unsigned min_neighbours;
+    int mutual;
+    int with_scale;
+} apd_points_register_options;
+typedef struct {
+    double scale, rotation[9], translation[3];
+    long long features_p, features_q, matches, trials_admitted, best_trial, inliers, inliers_after;
+    double rms_after;
+    int stopped;
+} apd_points_registration_t;
+int apd_points_register(apd_points_t p, apd_points_t q, float radius, const float *origin3, const apd_points_register_options *options,
+                        apd_points_registration_t *out);
 /* The cloud drawn into a camera with a z-buffer, and from such maps the views that see each point, occlusion included: what the
  * cleaned cloud looks like from a camera (a depth map and a point-index map, to inspect holes, to derive a mask, to compare with a
  * view's own depth map), and the visibility lists COLMAP's Delaunay mesher and Poisson trimming read, rebuilt for the cloud as it
