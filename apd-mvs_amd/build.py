@@ -133,7 +133,7 @@ def build_host(force=False, verbose=False):
     build_library()
     cxx = os.environ.get("CXX", "g++")
     srcs = [os.path.join(HOST_DIR, s) for s in HOST_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "apd_fusion_math.h"), os.path.join(HOST_DIR, "APD.h"), os.path.join(HOST_DIR, "schedule.h"), os.path.join(HOST_DIR, "wavefront.h"), os.path.join(HOST_DIR, "main.cpp"), os.path.join(HOST_DIR, "host_capi.cpp"),
+    deps = srcs + [os.path.join(CSRC, "apd_fusion_math.h"), os.path.join(HOST_DIR, "APD.h"), os.path.join(HOST_DIR, "schedule.h"), os.path.join(HOST_DIR, "wavefront.h"), os.path.join(HOST_DIR, "ply_options.h"), os.path.join(HOST_DIR, "main.cpp"), os.path.join(HOST_DIR, "host_capi.cpp"),
                    os.path.join(HERE, "..", "include", "apd_mi355x.h"), LIB_PATH]
     common = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-result"]  # contract C9: no FMA contraction in the fusion arithmetic
     link = ["-L" + OUT_DIR, "-lapd_mi355x", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + OUT_DIR, "-pthread"]

@@ -161,46 +161,11 @@ void SetFusionVariant(int variant);
 // additive: the options of the fusion (apd_fusion_options, include/apd_mi355x.h: the ETH loop's acceptance rule as values, normals
 // in the PLY file) that RunFusion, the in-memory paths and apdhost_fuse hand to apd_fuse_views_opt; its `variant` included
 void SetFusionOptions(const apd_fusion_options &options);
-// additive: RunFusion and the in-memory paths also write <dense>/APD/APD.ply.vis, COLMAP's fused.ply.vis (apd_points_write_vis):
-// per point the views that see it, as positions in pair.txt
-void SetFusionPlyVis(bool on);
-// additive: <dense>/APD/APD.ply holds the mean position (and, with normals in the file, the mean normal) of every point over the
-// views that agree on it (apd_points_average, apd_points_write_ply); an APD.ply.vis is then that of the averaged points
-void SetFusionPlyMean(bool on);
-// additive: size > 0: <dense>/APD/APD.ply holds one point per occupied cell of a cubic grid of that cell size (apd_points_merge_voxels,
-// after the averaging if that is asked for too); an APD.ply.vis is then that of the merged points.  0: off
-void SetFusionPlyVoxel(float size);
-// additive: radius > 0: <dense>/APD/APD.ply holds the points whose mean distance to their k nearest neighbours within that radius is
-// at most mean + std_ratio * deviation of the cloud's (apd_points_remove_statistical, after the averaging and the merge and before
-// the radius filter if those are asked for too); an APD.ply.vis is then that of the points kept.  0: off
-void SetFusionPlyStatFilter(float radius, unsigned k, float std_ratio);
-// additive: radius > 0: <dense>/APD/APD.ply holds the points that have at least min_neighbours other points within that radius
-// (apd_points_remove_sparse, after the averaging and the merge if those are asked for too); an APD.ply.vis is then that of the
-// points kept.  0: off
-void SetFusionPlyRadiusFilter(float radius, unsigned min_neighbours);
-// additive: radius > 0: <dense>/APD/APD.ply holds the points whose connected component -- two points are joined when they are within
-// that radius of each other -- has at least min_size points (apd_points_remove_small_components, after everything above that is
-// asked for too); an APD.ply.vis is then that of the points kept.  0: off
-void SetFusionPlyComponentFilter(float radius, unsigned min_size);
-// additive: radius > 0: the points of <dense>/APD/APD.ply stand where `iterations` projections on the weighted plane of each point's
-// neighbourhood within that radius put them, a point moving where it has at least min_neighbours other points there
-// (apd_points_with_smoothed_positions, after everything above that is asked for too); an APD.ply.vis keeps its lists.  0: off
-void SetFusionPlySmooth(float radius, unsigned min_neighbours, unsigned iterations);
-// additive: radius > 0: the points of <dense>/APD/APD.ply carry normals estimated from the neighbourhood of each within that radius,
-// where it has at least min_neighbours other points (apd_points_with_estimated_normals, after everything above that is asked for
-// too); the file shows them with normals in it, and without them keeps its bytes.  0: off
-void SetFusionPlyEstimateNormals(float radius, unsigned min_neighbours);
-// additive: splat >= 0: the lists of <dense>/APD/APD.ply.vis are the rendered ones: per point the views that see it when the cloud that
-// is written is drawn into every view's full-resolution camera with footprints of that splat, within rel_tolerance of the nearest
-// depth at the point's pixel (apd_points_rendered_visibility, after everything above that is asked for too); APD.ply keeps its
-// bytes.  -1: off
-void SetFusionPlyRenderVis(int splat, float rel_tolerance);
-// additive: a path: the points <dense>/APD/APD.ply is written from are scored against the cloud of that binary PLY file at
-// `threshold` (apd_points_read_ply, apd_points_score, after everything above): the precision, recall and F-score are printed and
-// written to <dense>/APD/APD.ply.score as `key value` lines; APD.ply and APD.ply.vis keep their bytes.  empty: off
-void SetFusionPlyScore(const std::string &truth_ply, float threshold);
-void SetFusionPlyAlign(const std::string &truth_ply, float radius, unsigned iterations, bool with_scale);
-void SetFusionPlyRegister(const std::string &truth_ply, float radius, float inlier_distance, unsigned trials, unsigned long long seed);
+// additive: what RunFusion and the in-memory paths do to the fused points before and besides writing <dense>/APD/APD.ply: the
+// --ply-* flags of host/ply_options.h, where every field says what it asks for, applied in the order of the fields.  APD.ply.vis,
+// if asked for, is that of the points the file holds; APD.ply.register, .align and .score hold the printed figures
+struct PlyOptions;
+void SetFusionPly(const PlyOptions &ply);
 
 class APD {
 public:

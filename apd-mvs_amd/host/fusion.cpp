@@ -13,6 +13,7 @@
 #include <chrono>
 #include <sstream>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,43 +29,7 @@ namespace {
 
 int g_fusion_device = 0;
 int g_fusion_variant = APD_FUSION_ETH;  // which of the reference's loops (APD_FUSION_*, include/apd_mi355x.h)
-bool g_fusion_ply_vis = false;          // SetFusionPlyVis
-bool g_fusion_ply_mean = false;         // SetFusionPlyMean
-float g_fusion_ply_voxel = 0.0f;        // SetFusionPlyVoxel; 0: off
-float g_fusion_ply_stat_radius = 0.0f;  // SetFusionPlyStatFilter; 0: off
-unsigned g_fusion_ply_stat_k = 0;
-float g_fusion_ply_stat_ratio = 0.0f;
-float g_fusion_ply_radius = 0.0f;       // SetFusionPlyRadiusFilter; 0: off
-unsigned g_fusion_ply_radius_min = 0;
-float g_fusion_ply_component_radius = 0.0f;  // SetFusionPlyComponentFilter; 0: off
-unsigned g_fusion_ply_component_min = 0;
-float g_fusion_ply_smooth_radius = 0.0f;  // SetFusionPlySmooth; 0: off
-unsigned g_fusion_ply_smooth_min = 0;
-unsigned g_fusion_ply_smooth_iterations = 1;
-float g_fusion_ply_normals_radius = 0.0f;  // SetFusionPlyEstimateNormals; 0: off
-unsigned g_fusion_ply_normals_min = 0;
-int g_fusion_ply_render_splat = -1;        // SetFusionPlyRenderVis; -1: off
-float g_fusion_ply_render_tolerance = 0.0f;
-std::string g_fusion_ply_score_truth;      // SetFusionPlyScore; empty: off
-float g_fusion_ply_score_threshold = 0.0f;
-std::string g_fusion_ply_align_truth;      // SetFusionPlyAlign; empty: off
-float g_fusion_ply_align_radius = 0.0f;
-unsigned g_fusion_ply_align_iterations = 16;
-bool g_fusion_ply_align_scale = false;
-std::string g_fusion_ply_register_truth;   // SetFusionPlyRegister; empty: off
-float g_fusion_ply_register_radius = 0.0f;
-float g_fusion_ply_register_distance = 0.0f;
-unsigned g_fusion_ply_register_trials = 4096;
-unsigned long long g_fusion_ply_register_seed = 0;
-
-// --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-smooth, --ply-estimate-normals,
-// --ply-render-vis, --ply-register, --ply-align or --ply-score: APD.ply is written from the points after the fusion, not by it
-bool ply_from_points()
-{
-    return g_fusion_ply_mean || g_fusion_ply_voxel > 0.0f || g_fusion_ply_stat_radius > 0.0f || g_fusion_ply_radius > 0.0f ||
-           g_fusion_ply_component_radius > 0.0f || g_fusion_ply_smooth_radius > 0.0f || g_fusion_ply_normals_radius > 0.0f || g_fusion_ply_render_splat >= 0 ||
-           !g_fusion_ply_register_truth.empty() || !g_fusion_ply_align_truth.empty() || !g_fusion_ply_score_truth.empty();
-}
+PlyOptions g_ply;                       // SetFusionPly: the --ply-* flags (host/ply_options.h)
 
 // SetFusionOptions; `variant` is g_fusion_variant's at the moment of the call
 apd_fusion_options &fusion_options()
@@ -98,8 +63,8 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
                       const float *const *normals, const int *rows, const int *cols, int maps_on_device, const path &ply_path);
 
 // Device fusion through the C ABI (host pointers).  options: nullptr = those of SetFusionOptions; ply_path may be null when
-// points is not.  mean_path (--ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter, --ply-estimate-normals; points must be given): the fusion writes no file, *points
-// become the averaged and / or merged and / or filtered points and their PLY goes to *mean_path.
+// points is not.  mean_path (PlyOptions::from_points; points must be given): the fusion writes no file, *points become the
+// reworked points and their PLY goes to *mean_path (rework_and_write).
 long long fuse_dispatch(std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const char *ply_path,
                         const apd_fusion_options *options = nullptr, apd_points_t *points = nullptr, const path *mean_path = nullptr)
 {
@@ -150,72 +115,7 @@ void SetFusionDevice(int device) { g_fusion_device = device; }
 
 void SetFusionVariant(int variant) { g_fusion_variant = variant; }
 
-void SetFusionPlyVis(bool on) { g_fusion_ply_vis = on; }
-
-void SetFusionPlyMean(bool on) { g_fusion_ply_mean = on; }
-
-void SetFusionPlyVoxel(float size) { g_fusion_ply_voxel = size; }
-
-void SetFusionPlyStatFilter(float radius, unsigned k, float std_ratio)
-{
-    g_fusion_ply_stat_radius = radius;
-    g_fusion_ply_stat_k = k;
-    g_fusion_ply_stat_ratio = std_ratio;
-}
-
-void SetFusionPlyRadiusFilter(float radius, unsigned min_neighbours)
-{
-    g_fusion_ply_radius = radius;
-    g_fusion_ply_radius_min = min_neighbours;
-}
-
-void SetFusionPlyComponentFilter(float radius, unsigned min_size)
-{
-    g_fusion_ply_component_radius = radius;
-    g_fusion_ply_component_min = min_size;
-}
-
-void SetFusionPlySmooth(float radius, unsigned min_neighbours, unsigned iterations)
-{
-    g_fusion_ply_smooth_radius = radius;
-    g_fusion_ply_smooth_min = min_neighbours;
-    g_fusion_ply_smooth_iterations = iterations;
-}
-
-void SetFusionPlyEstimateNormals(float radius, unsigned min_neighbours)
-{
-    g_fusion_ply_normals_radius = radius;
-    g_fusion_ply_normals_min = min_neighbours;
-}
-
-void SetFusionPlyRenderVis(int splat, float rel_tolerance)
-{
-    g_fusion_ply_render_splat = splat;
-    g_fusion_ply_render_tolerance = rel_tolerance;
-}
-
-void SetFusionPlyScore(const std::string &truth_ply, float threshold)
-{
-    g_fusion_ply_score_truth = truth_ply;
-    g_fusion_ply_score_threshold = threshold;
-}
-
-void SetFusionPlyAlign(const std::string &truth_ply, float radius, unsigned iterations, bool with_scale)
-{
-    g_fusion_ply_align_truth = truth_ply;
-    g_fusion_ply_align_radius = radius;
-    g_fusion_ply_align_iterations = iterations;
-    g_fusion_ply_align_scale = with_scale;
-}
-
-void SetFusionPlyRegister(const std::string &truth_ply, float radius, float inlier_distance, unsigned trials, unsigned long long seed)
-{
-    g_fusion_ply_register_truth = truth_ply;
-    g_fusion_ply_register_radius = radius;
-    g_fusion_ply_register_distance = inlier_distance;
-    g_fusion_ply_register_trials = trials;
-    g_fusion_ply_register_seed = seed;
-}
+void SetFusionPly(const PlyOptions &ply) { g_ply = ply; }
 
 namespace {
 
@@ -247,55 +147,82 @@ void write_lines_or_exit(const std::string &to, const std::string &lines)
     }
 }
 
+// What --ply-register, --ply-align and --ply-score report: every figure once in the printed line and once as a `name value` line of
+// the file beside APD.ply
+struct Report {
+    std::string line, lines;
+    void add(const std::string &name, const char *format, ...)
+    {
+        char text[64];
+        va_list value;
+        va_start(value, format);
+        vsnprintf(text, sizeof(text), format, value);
+        va_end(value);
+        line += " " + name + " " + text;
+        lines += name + " " + text + "\n";
+    }
+    void real(const std::string &name, double v) { add(name, "%.17g", v); }  // the double, back to the bit
+    void integer(const std::string &name, long long v) { add(name, "%lld", v); }
+    // what apd_points_registration_t and apd_points_alignment_t begin with; the rotation row-major
+    void transform(double scale, const double *rotation, const double *translation)
+    {
+        real("scale", scale);
+        for (int e = 0; e < 9; ++e) {
+            real("rotation" + std::to_string(e), rotation[e]);
+        }
+        for (int e = 0; e < 3; ++e) {
+            real("translation" + std::to_string(e), translation[e]);
+        }
+    }
+    void write(const std::string &to)   // ends the line whose lead-in the caller has printed
+    {
+        std::cout << ":" << line << std::endl;
+        write_lines_or_exit(to, lines);
+    }
+};
+
+// The end of a reworking step: with APD_OK the new points take the place of the old ones, which are released, and the step's line
+// is due.  *was: how many the old ones were
+bool took(int st, apd_points_t &points, apd_points_t fresh, long long *was = nullptr)
+{
+    if (st != APD_OK) {
+        return false;
+    }
+    if (was) {
+        *was = apd_points_count(points);
+    }
+    apd_points_destroy(points);
+    points = fresh;
+    return true;
+}
+
 // --ply-register: replaces the points by themselves moved onto the cloud of the truth file from any start (apd_points_register on
 // the fusion's device with the defaults of its other options, apd_points_transformed by its answer): one line with every field, and
 // the same as `name value` lines in <ply_path>.register
 int register_beside(apd_points_t &points, Truth &truth, const path &ply_path)
 {
-    int st = truth.read(g_fusion_ply_register_truth);
-    const apd_points_register_options options = {g_fusion_ply_register_trials, g_fusion_ply_register_seed, g_fusion_ply_register_distance, 0.9f, 5, 1, 0};
+    int st = truth.read(g_ply.register_truth);
+    const apd_points_register_options options = {g_ply.register_trials, g_ply.register_seed, g_ply.register_distance, 0.9f, 5, 1, 0};
     apd_points_registration_t r;
-    st = st != APD_OK ? st : apd_points_register(points, truth.points, g_fusion_ply_register_radius, nullptr, &options, &r);
+    st = st != APD_OK ? st : apd_points_register(points, truth.points, g_ply.register_radius, nullptr, &options, &r);
     apd_points_t moved = nullptr;
     st = st != APD_OK ? st : apd_points_transformed(points, r.scale, r.rotation, r.translation, &moved);
-    if (st != APD_OK) {
+    if (!took(st, points, moved)) {
         return st;
     }
-    apd_points_destroy(points);
-    points = moved;
-    std::string line, lines;
-    char text[64];
-    const auto add = [&](const std::string &name, const char *value) {
-        line += " " + name + " " + value;
-        lines += name + " " + value + "\n";
-    };
-    const auto real = [&](const std::string &name, double v) {
-        snprintf(text, sizeof(text), "%.17g", v);  // the double, back to the bit
-        add(name, text);
-    };
-    const auto integer = [&](const std::string &name, long long v) {
-        snprintf(text, sizeof(text), "%lld", v);
-        add(name, text);
-    };
-    real("scale", r.scale);
-    for (int e = 0; e < 9; ++e) {
-        real("rotation" + std::to_string(e), r.rotation[e]);
-    }
-    for (int e = 0; e < 3; ++e) {
-        real("translation" + std::to_string(e), r.translation[e]);
-    }
-    integer("features_p", r.features_p);
-    integer("features_q", r.features_q);
-    integer("matches", r.matches);
-    integer("trials_admitted", r.trials_admitted);
-    integer("best_trial", r.best_trial);
-    integer("inliers", r.inliers);
-    integer("inliers_after", r.inliers_after);
-    real("rms_after", r.rms_after);
-    integer("stopped", r.stopped);
-    std::cout << "Registered to " << g_fusion_ply_register_truth << " at " << g_fusion_ply_register_radius << " within " << g_fusion_ply_register_distance
-              << ":" << line << std::endl;
-    write_lines_or_exit(ply_path.string() + ".register", lines);
+    Report report;
+    report.transform(r.scale, r.rotation, r.translation);
+    report.integer("features_p", r.features_p);
+    report.integer("features_q", r.features_q);
+    report.integer("matches", r.matches);
+    report.integer("trials_admitted", r.trials_admitted);
+    report.integer("best_trial", r.best_trial);
+    report.integer("inliers", r.inliers);
+    report.integer("inliers_after", r.inliers_after);
+    report.real("rms_after", r.rms_after);
+    report.integer("stopped", r.stopped);
+    std::cout << "Registered to " << g_ply.register_truth << " at " << g_ply.register_radius << " within " << g_ply.register_distance;
+    report.write(ply_path.string() + ".register");
     return APD_OK;
 }
 
@@ -303,46 +230,25 @@ int register_beside(apd_points_t &points, Truth &truth, const path &ply_path)
 // apd_points_transformed by its answer): one line with every field, and the same as `name value` lines in <ply_path>.align
 int align_beside(apd_points_t &points, Truth &truth, const path &ply_path)
 {
-    int st = truth.read(g_fusion_ply_align_truth);
-    const apd_points_align_options options = {g_fusion_ply_align_iterations, 1e-6, g_fusion_ply_align_scale ? 1 : 0};
+    int st = truth.read(g_ply.align_truth);
+    const apd_points_align_options options = {g_ply.align_iterations, 1e-6, g_ply.align_scale ? 1 : 0};
     apd_points_alignment_t a;
-    st = st != APD_OK ? st : apd_points_align(points, truth.points, g_fusion_ply_align_radius, nullptr, &options, &a);
+    st = st != APD_OK ? st : apd_points_align(points, truth.points, g_ply.align_radius, nullptr, &options, &a);
     apd_points_t moved = nullptr;
     st = st != APD_OK ? st : apd_points_transformed(points, a.scale, a.rotation, a.translation, &moved);
-    if (st != APD_OK) {
+    if (!took(st, points, moved)) {
         return st;
     }
-    apd_points_destroy(points);
-    points = moved;
-    std::string line, lines;
-    char text[64];
-    const auto add = [&](const std::string &name, const char *value) {
-        line += " " + name + " " + value;
-        lines += name + " " + value + "\n";
-    };
-    const auto real = [&](const std::string &name, double v) {
-        snprintf(text, sizeof(text), "%.17g", v);  // the double, back to the bit
-        add(name, text);
-    };
-    const auto integer = [&](const std::string &name, long long v) {
-        snprintf(text, sizeof(text), "%lld", v);
-        add(name, text);
-    };
-    real("scale", a.scale);
-    for (int e = 0; e < 9; ++e) {
-        real("rotation" + std::to_string(e), a.rotation[e]);
-    }
-    for (int e = 0; e < 3; ++e) {
-        real("translation" + std::to_string(e), a.translation[e]);
-    }
-    integer("matched_before", a.matched_before);
-    integer("matched_after", a.matched_after);
-    real("rms_before", a.rms_before);
-    real("rms_after", a.rms_after);
-    integer("steps", a.steps);
-    integer("stopped", a.stopped);
-    std::cout << "Aligned to " << g_fusion_ply_align_truth << " within " << g_fusion_ply_align_radius << ":" << line << std::endl;
-    write_lines_or_exit(ply_path.string() + ".align", lines);
+    Report report;
+    report.transform(a.scale, a.rotation, a.translation);
+    report.integer("matched_before", a.matched_before);
+    report.integer("matched_after", a.matched_after);
+    report.real("rms_before", a.rms_before);
+    report.real("rms_after", a.rms_after);
+    report.integer("steps", a.steps);
+    report.integer("stopped", a.stopped);
+    std::cout << "Aligned to " << g_ply.align_truth << " within " << g_ply.align_radius;
+    report.write(ply_path.string() + ".align");
     return APD_OK;
 }
 
@@ -350,152 +256,104 @@ int align_beside(apd_points_t &points, Truth &truth, const path &ply_path)
 // device): one line with the nine fields, and the same as `key value` lines in <ply_path>.score
 int score_beside(apd_points_t points, Truth &truth, const path &ply_path)
 {
-    int st = truth.read(g_fusion_ply_score_truth);
+    int st = truth.read(g_ply.score_truth);
     apd_points_score_t s;
-    st = st != APD_OK ? st : apd_points_score(points, truth.points, g_fusion_ply_score_threshold, nullptr, &s);
+    st = st != APD_OK ? st : apd_points_score(points, truth.points, g_ply.score_threshold, nullptr, &s);
     if (st != APD_OK) {
         return st;
     }
-    const char *const names[9] = {"n_p", "n_q", "p_within", "q_within", "precision", "recall", "fscore", "mean_p", "mean_q"};
-    const long long integers[4] = {s.n_p, s.n_q, s.p_within, s.q_within};
-    const double reals[5] = {s.precision, s.recall, s.fscore, s.mean_p, s.mean_q};
-    std::string line, lines;
-    char text[64];
-    for (int k = 0; k < 9; ++k) {
-        if (k < 4) {
-            snprintf(text, sizeof(text), "%lld", integers[k]);
-        } else {
-            snprintf(text, sizeof(text), "%.17g", reals[k - 4]);  // the double, back to the bit
-        }
-        line += std::string(" ") + names[k] + " " + text;
-        lines += std::string(names[k]) + " " + text + "\n";
-    }
-    std::cout << "Score against " << g_fusion_ply_score_truth << " at " << g_fusion_ply_score_threshold << ":" << line << std::endl;
-    write_lines_or_exit(ply_path.string() + ".score", lines);
+    Report report;
+    report.integer("n_p", s.n_p);
+    report.integer("n_q", s.n_q);
+    report.integer("p_within", s.p_within);
+    report.integer("q_within", s.q_within);
+    report.real("precision", s.precision);
+    report.real("recall", s.recall);
+    report.real("fscore", s.fscore);
+    report.real("mean_p", s.mean_p);
+    report.real("mean_q", s.mean_q);
+    std::cout << "Score against " << g_ply.score_truth << " at " << g_ply.score_threshold;
+    report.write(ply_path.string() + ".score");
     return APD_OK;
 }
 
-// --ply-mean: replaces the points of a fusion by their means over the agreeing views (apd_points_average with the fusion's own
-// cameras and maps); --ply-voxel: replaces them -- the means, with both -- by one point per cell (apd_points_merge_voxels) and
-// prints the cells and the dropped points; --ply-stat-filter: replaces what these left by the points whose k-nearest mean distance
-// is no outlier (apd_points_remove_statistical) and prints how many went and the threshold; --ply-radius-filter: replaces what these left by the points with enough neighbours
-// (apd_points_remove_sparse) and prints how many went; --ply-component-filter: replaces what these left by the points of the connected
-// components that are large enough (apd_points_remove_small_components) and prints the components and how many points went;
-// --ply-smooth: replaces the positions of what these left by their projections on each neighbourhood's weighted plane
-// (apd_points_with_smoothed_positions) and prints how many points moved;
-// --ply-estimate-normals: replaces the normals of what these left by those of each point's neighbourhood
-// (apd_points_with_estimated_normals) and prints how many points got one; --ply-render-vis: replaces the lists of what these left by
-// the views that see each point when the cloud is drawn into full_cameras, the views' cameras at the size of their images
-// (apd_points_rendered_visibility), and prints how many points no view sees; --ply-register: replaces what these left by the same
-// points moved onto the cloud of a truth file from any start (register_beside); --ply-align: replaces what these left by the same points
-// moved onto the cloud of a truth file (align_beside).  Then writes ply_path from them (apd_points_write_ply); the fusion itself
-// wrote no file; --ply-score: scores the points the file was written from (score_beside), which changes none of them
+// The --ply-* steps that are asked for (host/ply_options.h), in the order of their fields: each replaces the points of a fusion,
+// which wrote no file, by what it makes of them and prints its figures -- the mean over the fusion's own cameras and maps, the
+// rendering into full_cameras, the views' cameras at the size of their images.  Then writes ply_path from them
+// (apd_points_write_ply) and, with --ply-score, scores the points the file was written from, which changes none of them.
 void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cameras, const apd_camera *full_cameras, const float *const *depths,
                       const float *const *normals, const int *rows, const int *cols, int maps_on_device, const path &ply_path)
 {
+    const PlyOptions &o = g_ply;
     int st = APD_OK;
-    if (g_fusion_ply_mean) {
-        apd_points_t mean = nullptr;
-        st = apd_points_average(points, num_views, cameras, depths, normals, rows, cols, maps_on_device, &mean);
-        if (st == APD_OK) {
-            apd_points_destroy(points);
-            points = mean;
+    apd_points_t fresh = nullptr;
+    long long was = 0, gone = 0;   // the points a step was given, and those it removed or changed
+    if (o.mean) {
+        st = apd_points_average(points, num_views, cameras, depths, normals, rows, cols, maps_on_device, &fresh);
+        took(st, points, fresh);
+    }
+    if (st == APD_OK && o.voxel > 0.0f) {
+        st = apd_points_merge_voxels(points, o.voxel, nullptr, &fresh, &gone);
+        double ms_setup = 0, ms_kernels = 0;
+        apd_fusion_last_timing(&ms_setup, &ms_kernels, nullptr);
+        if (took(st, points, fresh, &was)) {
+            std::cout << "Merged " << was << " points into " << apd_points_count(points) << " cells of size " << o.voxel << ", dropped " << gone << ": "
+                      << (long long)(ms_setup + ms_kernels) << " ms (set-up " << (long long)ms_setup << ", kernels " << (long long)ms_kernels << ")" << std::endl;
         }
     }
-    if (st == APD_OK && g_fusion_ply_voxel > 0.0f) {
-        apd_points_t merged = nullptr;
-        long long dropped = 0;
-        st = apd_points_merge_voxels(points, g_fusion_ply_voxel, nullptr, &merged, &dropped);
-        if (st == APD_OK) {
-            double ms_setup = 0, ms_kernels = 0;
-            apd_fusion_last_timing(&ms_setup, &ms_kernels, nullptr);
-            std::cout << "Merged " << apd_points_count(points) << " points into " << apd_points_count(merged) << " cells of size " << g_fusion_ply_voxel
-                      << ", dropped " << dropped << ": " << (long long)(ms_setup + ms_kernels) << " ms (set-up " << (long long)ms_setup << ", kernels "
-                      << (long long)ms_kernels << ")" << std::endl;
-            apd_points_destroy(points);
-            points = merged;
-        }
-    }
-    if (st == APD_OK && g_fusion_ply_stat_radius > 0.0f) {
-        apd_points_t kept = nullptr;
-        long long removed = 0;
+    if (st == APD_OK && o.stat_radius > 0.0f) {
         double threshold = 0.0;
-        st = apd_points_remove_statistical(points, g_fusion_ply_stat_radius, nullptr, g_fusion_ply_stat_k, g_fusion_ply_stat_ratio, &kept, &removed,
-                                           &threshold);
-        if (st == APD_OK) {
-            std::cout << "Removed " << removed << " of " << apd_points_count(points) << " points whose mean distance to their " << g_fusion_ply_stat_k
-                      << " nearest neighbours within " << g_fusion_ply_stat_radius << " is above " << threshold << std::endl;
-            apd_points_destroy(points);
-            points = kept;
+        st = apd_points_remove_statistical(points, o.stat_radius, nullptr, o.stat_k, o.stat_ratio, &fresh, &gone, &threshold);
+        if (took(st, points, fresh, &was)) {
+            std::cout << "Removed " << gone << " of " << was << " points whose mean distance to their " << o.stat_k << " nearest neighbours within "
+                      << o.stat_radius << " is above " << threshold << std::endl;
         }
     }
-    if (st == APD_OK && g_fusion_ply_radius > 0.0f) {
-        apd_points_t kept = nullptr;
-        long long removed = 0;
-        st = apd_points_remove_sparse(points, g_fusion_ply_radius, nullptr, g_fusion_ply_radius_min, &kept, &removed);
-        if (st == APD_OK) {
-            std::cout << "Removed " << removed << " of " << apd_points_count(points) << " points with fewer than " << g_fusion_ply_radius_min
-                      << " neighbours within " << g_fusion_ply_radius << std::endl;
-            apd_points_destroy(points);
-            points = kept;
+    if (st == APD_OK && o.radius > 0.0f) {
+        st = apd_points_remove_sparse(points, o.radius, nullptr, o.radius_min, &fresh, &gone);
+        if (took(st, points, fresh, &was)) {
+            std::cout << "Removed " << gone << " of " << was << " points with fewer than " << o.radius_min << " neighbours within " << o.radius << std::endl;
         }
     }
-    if (st == APD_OK && g_fusion_ply_component_radius > 0.0f) {
-        apd_points_t kept = nullptr;
-        long long removed = 0, components = 0;
-        st = apd_points_remove_small_components(points, g_fusion_ply_component_radius, nullptr, g_fusion_ply_component_min, &kept, &removed, &components);
-        if (st == APD_OK) {
-            std::cout << "Removed " << removed << " of " << apd_points_count(points) << " points in connected components of fewer than "
-                      << g_fusion_ply_component_min << " points, of " << components << " components within " << g_fusion_ply_component_radius << std::endl;
-            apd_points_destroy(points);
-            points = kept;
+    if (st == APD_OK && o.component_radius > 0.0f) {
+        long long components = 0;
+        st = apd_points_remove_small_components(points, o.component_radius, nullptr, o.component_min, &fresh, &gone, &components);
+        if (took(st, points, fresh, &was)) {
+            std::cout << "Removed " << gone << " of " << was << " points in connected components of fewer than " << o.component_min << " points, of "
+                      << components << " components within " << o.component_radius << std::endl;
         }
     }
-    if (st == APD_OK && g_fusion_ply_smooth_radius > 0.0f) {
-        apd_points_t kept = nullptr;
-        long long moved = 0;
-        st = apd_points_with_smoothed_positions(points, g_fusion_ply_smooth_radius, nullptr, g_fusion_ply_smooth_min, g_fusion_ply_smooth_iterations, &kept,
-                                                &moved);
-        if (st == APD_OK) {
-            std::cout << "Smoothed the positions of " << moved << " of " << apd_points_count(points) << " points with at least " << g_fusion_ply_smooth_min
-                      << " neighbours within " << g_fusion_ply_smooth_radius << " in " << g_fusion_ply_smooth_iterations << " iteration(s)" << std::endl;
-            apd_points_destroy(points);
-            points = kept;
+    if (st == APD_OK && o.smooth_radius > 0.0f) {
+        st = apd_points_with_smoothed_positions(points, o.smooth_radius, nullptr, o.smooth_min, o.smooth_iterations, &fresh, &gone);
+        if (took(st, points, fresh, &was)) {
+            std::cout << "Smoothed the positions of " << gone << " of " << was << " points with at least " << o.smooth_min << " neighbours within "
+                      << o.smooth_radius << " in " << o.smooth_iterations << " iteration(s)" << std::endl;
         }
     }
-    if (st == APD_OK && g_fusion_ply_normals_radius > 0.0f) {
-        apd_points_t kept = nullptr;
-        long long estimated = 0;
-        st = apd_points_with_estimated_normals(points, g_fusion_ply_normals_radius, nullptr, g_fusion_ply_normals_min, &kept, &estimated);
-        if (st == APD_OK) {
-            std::cout << "Estimated the normals of " << estimated << " of " << apd_points_count(points) << " points from at least "
-                      << g_fusion_ply_normals_min << " neighbours within " << g_fusion_ply_normals_radius << std::endl;
-            apd_points_destroy(points);
-            points = kept;
+    if (st == APD_OK && o.normals_radius > 0.0f) {
+        st = apd_points_with_estimated_normals(points, o.normals_radius, nullptr, o.normals_min, &fresh, &gone);
+        if (took(st, points, fresh, &was)) {
+            std::cout << "Estimated the normals of " << gone << " of " << was << " points from at least " << o.normals_min << " neighbours within "
+                      << o.normals_radius << std::endl;
         }
     }
-    if (st == APD_OK && g_fusion_ply_render_splat >= 0) {
-        apd_points_t kept = nullptr;
-        long long unseen = 0;
-        st = apd_points_rendered_visibility(points, num_views, full_cameras, g_fusion_ply_render_splat, g_fusion_ply_render_tolerance, &kept, &unseen);
-        if (st == APD_OK) {
-            std::cout << "Rendered the visibility of " << apd_points_count(points) << " points in " << num_views << " views with a splat of "
-                      << g_fusion_ply_render_splat << " and a tolerance of " << g_fusion_ply_render_tolerance << ": " << unseen << " points are seen by no view"
-                      << std::endl;
-            apd_points_destroy(points);
-            points = kept;
+    if (st == APD_OK && o.render_splat >= 0) {
+        st = apd_points_rendered_visibility(points, num_views, full_cameras, o.render_splat, o.render_tolerance, &fresh, &gone);
+        if (took(st, points, fresh, &was)) {
+            std::cout << "Rendered the visibility of " << was << " points in " << num_views << " views with a splat of " << o.render_splat
+                      << " and a tolerance of " << o.render_tolerance << ": " << gone << " points are seen by no view" << std::endl;
         }
     }
     Truth truth;
-    if (st == APD_OK && !g_fusion_ply_register_truth.empty()) {
+    if (st == APD_OK && !o.register_truth.empty()) {
         st = register_beside(points, truth, ply_path);
     }
-    if (st == APD_OK && !g_fusion_ply_align_truth.empty()) {
+    if (st == APD_OK && !o.align_truth.empty()) {
         st = align_beside(points, truth, ply_path);
     }
     st = st != APD_OK ? st : apd_points_write_ply(points, ply_path.string().c_str(), fusion_options().ply_normals);
     std::string err = st != APD_OK ? apd_fusion_last_error() : "";
-    if (st == APD_OK && !g_fusion_ply_score_truth.empty() && (st = score_beside(points, truth, ply_path)) != APD_OK) {
+    if (st == APD_OK && !o.score_truth.empty() && (st = score_beside(points, truth, ply_path)) != APD_OK) {
         err = apd_fusion_last_error();
     }
     if (st != APD_OK) {
@@ -505,10 +363,15 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
     }
 }
 
-// --ply-vis: <ply_path>.vis from the points of the fusion that wrote ply_path; releases them
+// The end of both fusions: releases the points ply_path was written from (null: none were kept), after <ply_path>.vis has been written
+// from them with --ply-vis
 void write_vis_beside(const path &ply_path, apd_points_t points)
 {
     const std::string vis_path = ply_path.string() + ".vis";
+    if (!g_ply.vis) {
+        apd_points_destroy(points);
+        return;
+    }
     const int st = apd_points_write_vis(points, vis_path.c_str());
     const std::string err = st != APD_OK ? apd_fusion_last_error() : "";
     apd_points_destroy(points);
@@ -666,18 +529,14 @@ void RunFusionWithMaps(const path &dense_folder, const std::vector<Problem> &pro
     const auto t_fuse = std::chrono::steady_clock::now();
     std::cout << "Fusion inputs ready: " << std::chrono::duration_cast<std::chrono::milliseconds>(t_fuse - t_inputs).count() << " ms" << std::endl;
     apd_points_t points = nullptr;
-    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str(), nullptr, g_fusion_ply_vis || ply_from_points() ? &points : nullptr,
-                                      ply_from_points() ? &ply_path : nullptr);
+    const long long n = fuse_dispatch(views, sources, ply_path.string().c_str(), nullptr, g_ply.vis || g_ply.from_points() ? &points : nullptr,
+                                      g_ply.from_points() ? &ply_path : nullptr);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms" << std::endl;
     if (n < 0) {
         exit(EXIT_FAILURE);  // like every other device error of the reference (CudaSafeCall, APD.cpp:315-323)
     }
     std::cout << "Fused " << n << " points into " << ply_path << std::endl;
-    if (g_fusion_ply_vis) {
-        write_vis_beside(ply_path, points);
-    } else {
-        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter or --ply-estimate-normals alone
-    }
+    write_vis_beside(ply_path, points);
 }
 
 // The final maps are on `device` already (host/multi_device.cpp keeps every view's state there and gathers the other devices'
@@ -857,13 +716,13 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
     long long count = 0;
     apd_fusion_options fusion = call_options();
     apd_points_t points = nullptr;
-    if (g_fusion_ply_vis || ply_from_points()) {
+    const bool keep_points = g_ply.vis || g_ply.from_points();
+    if (keep_points) {
         fusion.result_on_device = 1;  // the maps are here already: the lists and the means are built here too and only they come down
     }
     const int st = apd_fuse_views_opt(&fusion, f->device, V, cams.data(), f->imgs.data(), f->channels, depths.data(), normals.data(), weaks.data(),
                                       f->any_block ? f->blocks.data() : nullptr, rws.data(), cls.data(), offs.data(), idx.data(), 1,
-                                      ply_from_points() ? nullptr : ply_path.string().c_str(), &count,
-                                      g_fusion_ply_vis || ply_from_points() ? &points : nullptr);
+                                      g_ply.from_points() ? nullptr : ply_path.string().c_str(), &count, keep_points ? &points : nullptr);
     double ms_setup = 0, ms_views = 0, ms_file = 0;
     apd_fusion_last_timing(&ms_setup, &ms_views, &ms_file);
     std::cout << "Fusion + PLY: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_fuse).count() << " ms (set-up "
@@ -874,15 +733,11 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
         std::cerr << err << std::endl;
         exit(EXIT_FAILURE);
     }
-    if (ply_from_points()) {
+    if (g_ply.from_points()) {
         rework_and_write(points, V, cams.data(), full.data(), depths.data(), normals.data(), rws.data(), cls.data(), 1, ply_path);
     }
     std::cout << "Fused " << count << " points into " << ply_path << std::endl;
-    if (g_fusion_ply_vis) {
-        write_vis_beside(ply_path, points);
-    } else {
-        apd_points_destroy(points);  // --ply-mean, --ply-voxel, --ply-stat-filter, --ply-radius-filter, --ply-component-filter or --ply-estimate-normals alone
-    }
+    write_vis_beside(ply_path, points);
 }
 
 // ---- --filtered-maps: the geometric filter (apd_filter_views, csrc/apd_filter.hip) ----

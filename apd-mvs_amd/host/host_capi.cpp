@@ -1,5 +1,6 @@
 // host_capi.cpp -- flat C entry points over the host-side file-format helpers, so the Python tests
 // can exercise ReadBinMat / WriteBinMat / ReadCamera / image decode / resampling without a GPU.
+#include <cstdio>
 #include <cstring>
 
 #include "APD.h"
@@ -158,6 +159,29 @@ int apdhost_wavefront_source_iteration(void *queue, int pass_index, int view, in
 }
 int apdhost_wavefront_lanes_per_pass(void) { return APD_GS_LANES_PER_PASS; }
 void apdhost_wavefront_destroy(void *queue) { delete static_cast<WavefrontQueue *>(queue); }
+
+// The value of a --ply-* flag as the command line reads it (host/ply_options.h), into options that are at their defaults.  0: the
+// value is good, and `fields` holds every option as a `name value` line, the floats as %.9g, the three file names last since they
+// end their lines; 1: it is bad, and `message` holds what the command line is told; -1: no such flag takes a value.
+int apdhost_parse_ply_option(const char *flag, const char *value, char *fields, size_t fields_cap, char *message, size_t message_cap)
+{
+    if (!FindPlyFlag(flag)) {
+        return -1;
+    }
+    PlyOptions o;
+    const std::string why = ParsePlyOption(flag, value, o);
+    snprintf(message, message_cap, "%s", why.c_str());
+    snprintf(fields, fields_cap,
+             "vis %d\nmean %d\nvoxel %.9g\nstat_radius %.9g\nstat_k %u\nstat_ratio %.9g\nradius %.9g\nradius_min %u\ncomponent_radius %.9g\ncomponent_min %u\n"
+             "smooth_radius %.9g\nsmooth_min %u\nsmooth_iterations %u\nnormals_radius %.9g\nnormals_min %u\nrender_splat %d\nrender_tolerance %.9g\n"
+             "register_radius %.9g\nregister_distance %.9g\nregister_trials %u\nregister_seed %llu\nalign_radius %.9g\nalign_iterations %u\nalign_scale %d\n"
+             "score_threshold %.9g\nregister_truth %s\nalign_truth %s\nscore_truth %s\n",
+             o.vis, o.mean, o.voxel, o.stat_radius, o.stat_k, o.stat_ratio, o.radius, o.radius_min, o.component_radius, o.component_min, o.smooth_radius,
+             o.smooth_min, o.smooth_iterations, o.normals_radius, o.normals_min, o.render_splat, o.render_tolerance, o.register_radius, o.register_distance,
+             o.register_trials, o.register_seed, o.align_radius, o.align_iterations, o.align_scale, o.score_threshold, o.register_truth.c_str(),
+             o.align_truth.c_str(), o.score_truth.c_str());
+    return why.empty() ? 0 : 1;
+}
 
 // HIP device of the fusion started by apdhost_fuse / RunFusion (default 0)
 void apdhost_set_fusion_device(int device) { SetFusionDevice(device); }

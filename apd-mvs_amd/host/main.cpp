@@ -109,7 +109,6 @@
 // --in-memory) when the folder fits it -- the files of the last pass are written with --keep-maps.
 // Not built: the debug JPEGs of show_medium_result.
 #include <algorithm>
-#include <cerrno>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -139,16 +138,7 @@ bool ParseOptions(int argc, char **argv, Options &o)
             dst = strtoull(argv[++i], nullptr, 10);
             return true;
         };
-        // a non-negative finite number that fills the whole token
-        auto real = [](const char *text, float &dst) {
-            char *end = nullptr;
-            const float f = strtof(text, &end);
-            if (end == text || *end != '\0' || !(f >= 0.0f) || f > 3.402823466e+38f) {
-                return false;
-            }
-            dst = f;
-            return true;
-        };
+        const auto real = ply_value::Real;   // a non-negative finite number that fills the whole token
         auto threshold = [&](float &dst) {
             const char *text = i + 1 < argc ? argv[++i] : "";
             if (!real(text, dst)) {
@@ -187,189 +177,15 @@ bool ParseOptions(int argc, char **argv, Options &o)
         } else if (a == "--ply-normals") {
             o.fusion.ply_normals = 1;
         } else if (a == "--ply-vis") {
-            o.ply_vis = true;
+            o.ply.vis = true;
         } else if (a == "--ply-mean") {
-            o.ply_mean = true;
-        } else if (a == "--ply-voxel") {
-            const char *text = i + 1 < argc ? argv[++i] : "";
-            if (!real(text, o.ply_voxel) || !(o.ply_voxel > 0.0f)) {
-                fprintf(stderr, "bad value '%s' of %s: a positive number\n", text, a.c_str());
+            o.ply.mean = true;
+        } else if (FindPlyFlag(a)) {   // every --ply-* flag with a value (host/ply_options.h)
+            const std::string why = ParsePlyOption(a, i + 1 < argc ? argv[++i] : "", o.ply);
+            if (!why.empty()) {
+                fprintf(stderr, "%s\n", why.c_str());
                 return false;
             }
-        } else if (a == "--ply-stat-filter") {
-            const std::string all = i + 1 < argc ? argv[++i] : "";
-            const size_t c1 = all.find(','), c2 = c1 == std::string::npos ? c1 : all.find(',', c1 + 1);
-            const std::string count = c2 == std::string::npos ? "" : all.substr(c1 + 1, c2 - c1 - 1), ratio = c2 == std::string::npos ? "" : all.substr(c2 + 1);
-            char *end = nullptr;
-            const unsigned long long k = strtoull(count.c_str(), &end, 10);
-            const bool digits = !count.empty() && count.size() <= 9 && count.find_first_not_of("0123456789") == std::string::npos && k >= 1 && k <= 64;
-            const float t = strtof(ratio.c_str(), &end);
-            const bool number = !ratio.empty() && end != ratio.c_str() && *end == '\0' && t >= -3.402823466e+38f && t <= 3.402823466e+38f;
-            float r = 0.0f;
-            if (!digits || !number || !real(all.substr(0, c1).c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
-                fprintf(stderr, "bad value '%s' of %s: RADIUS,K,RATIO, a positive number, a count of 1 .. 64 and a number\n", all.c_str(), a.c_str());
-                return false;
-            }
-            o.ply_stat_radius = r;
-            o.ply_stat_k = (unsigned)k;
-            o.ply_stat_ratio = t;
-        } else if (a == "--ply-radius-filter") {
-            const std::string both = i + 1 < argc ? argv[++i] : "";
-            const size_t comma = both.find(',');
-            const std::string count = comma == std::string::npos ? "" : both.substr(comma + 1);
-            char *end = nullptr;
-            const unsigned long long k = strtoull(count.c_str(), &end, 10);
-            const bool digits = !count.empty() && count.find_first_not_of("0123456789") == std::string::npos && *end == '\0' && k <= 0xffffffffull;
-            float r = 0.0f;
-            if (!digits || !real(both.substr(0, comma).c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
-                fprintf(stderr, "bad value '%s' of %s: RADIUS,MIN, a positive number and a count\n", both.c_str(), a.c_str());
-                return false;
-            }
-            o.ply_radius = r;
-            o.ply_radius_min = (unsigned)k;
-        } else if (a == "--ply-component-filter") {
-            const std::string both = i + 1 < argc ? argv[++i] : "";
-            const size_t comma = both.find(',');
-            const std::string count = comma == std::string::npos ? "" : both.substr(comma + 1);
-            char *end = nullptr;
-            const unsigned long long k = strtoull(count.c_str(), &end, 10);
-            const bool digits = !count.empty() && count.find_first_not_of("0123456789") == std::string::npos && *end == '\0' && k <= 0xffffffffull;
-            float r = 0.0f;
-            if (!digits || !real(both.substr(0, comma).c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
-                fprintf(stderr, "bad value '%s' of %s: RADIUS,MIN, a positive number and a count\n", both.c_str(), a.c_str());
-                return false;
-            }
-            o.ply_component_radius = r;
-            o.ply_component_min = (unsigned)k;
-        } else if (a == "--ply-smooth") {
-            const std::string all = i + 1 < argc ? argv[++i] : "";
-            const size_t c1 = all.find(','), c2 = c1 == std::string::npos ? c1 : all.find(',', c1 + 1);
-            const std::string count = c1 == std::string::npos ? "" : all.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
-            const std::string times = c2 == std::string::npos ? "1" : all.substr(c2 + 1);
-            char *end = nullptr;
-            const unsigned long long k = strtoull(count.c_str(), &end, 10);
-            const bool digits = !count.empty() && count.find_first_not_of("0123456789") == std::string::npos && *end == '\0' && k >= 2 && k <= 0x7fffffffull;
-            const unsigned long long n = strtoull(times.c_str(), &end, 10);
-            const bool iterations = !times.empty() && times.size() <= 2 && times.find_first_not_of("0123456789") == std::string::npos && n >= 1 && n <= 16;
-            float r = 0.0f;
-            if (!digits || !iterations || !real(all.substr(0, c1).c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
-                fprintf(stderr, "bad value '%s' of %s: RADIUS,MIN[,ITERATIONS], a positive number, a count of 2 or more and a count of 1 .. 16\n", all.c_str(),
-                        a.c_str());
-                return false;
-            }
-            o.ply_smooth_radius = r;
-            o.ply_smooth_min = (unsigned)k;
-            o.ply_smooth_iterations = (unsigned)n;
-        } else if (a == "--ply-estimate-normals") {
-            const std::string both = i + 1 < argc ? argv[++i] : "";
-            const size_t comma = both.find(',');
-            const std::string count = comma == std::string::npos ? "" : both.substr(comma + 1);
-            char *end = nullptr;
-            const unsigned long long k = strtoull(count.c_str(), &end, 10);
-            const bool digits = !count.empty() && count.find_first_not_of("0123456789") == std::string::npos && *end == '\0' && k >= 2 && k <= 0x7fffffffull;
-            float r = 0.0f;
-            if (!digits || !real(both.substr(0, comma).c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
-                fprintf(stderr, "bad value '%s' of %s: RADIUS,MIN, a positive number and a count of 2 or more\n", both.c_str(), a.c_str());
-                return false;
-            }
-            o.ply_normals_radius = r;
-            o.ply_normals_min = (unsigned)k;
-        } else if (a == "--ply-render-vis") {
-            const std::string both = i + 1 < argc ? argv[++i] : "";
-            const size_t comma = both.find(',');
-            const std::string count = comma == std::string::npos ? "" : both.substr(0, comma);
-            const bool digits = count.size() == 1 && count[0] >= '0' && count[0] <= '8';
-            float t = 0.0f;
-            if (!digits || !real(both.substr(comma + 1).c_str(), t)) {
-                fprintf(stderr, "bad value '%s' of %s: SPLAT,TOL, a count of 0 .. 8 and a non-negative number\n", both.c_str(), a.c_str());
-                return false;
-            }
-            o.ply_render_splat = count[0] - '0';
-            o.ply_render_tolerance = t;
-            o.ply_vis = true;
-        } else if (a == "--ply-score") {
-            const std::string both = i + 1 < argc ? argv[++i] : "";
-            const size_t comma = both.rfind(',');
-            float t = 0.0f;
-            if (comma == std::string::npos || comma == 0 || !real(both.substr(comma + 1).c_str(), t) || !(t * t > 0.0f) || t * t > 3.402823466e+38f) {
-                fprintf(stderr, "bad value '%s' of %s: TRUTH.ply,TAU, a file and a positive number\n", both.c_str(), a.c_str());
-                return false;
-            }
-            o.ply_score_truth = both.substr(0, comma);
-            o.ply_score_threshold = t;
-        } else if (a == "--ply-register") {
-            // read from the right, since the file's name may hold commas: the longest tail of four, three or two tokens that is
-            // RADIUS,DISTANCE[,TRIALS[,SEED]]
-            const std::string all = i + 1 < argc ? argv[++i] : "";
-            std::vector<size_t> commas;  // from the right
-            for (size_t at = all.rfind(','); at != std::string::npos && at > 0 && commas.size() < 4; at = all.rfind(',', at - 1)) {
-                commas.push_back(at);
-            }
-            const auto count = [](const std::string &text, unsigned long long lo, unsigned long long hi, unsigned long long &dst) {
-                char *end = nullptr;
-                errno = 0;
-                const unsigned long long n = strtoull(text.c_str(), &end, 10);
-                if (text.empty() || text.find_first_not_of("0123456789") != std::string::npos || *end != '\0' || errno != 0 || n < lo || n > hi) {
-                    return false;
-                }
-                dst = n;
-                return true;
-            };
-            bool found = false;
-            for (size_t tokens = commas.size(); tokens >= 2 && !found; --tokens) {
-                std::vector<std::string> token;
-                for (size_t k = tokens; k >= 1; --k) {
-                    const size_t from = commas[k - 1] + 1, to = k >= 2 ? commas[k - 2] : all.size();
-                    token.push_back(all.substr(from, to - from));
-                }
-                float r = 0.0f, d = 0.0f;
-                unsigned long long trials = 4096, seed = 0;
-                if (real(token[0].c_str(), r) && r * r > 0.0f && r * r <= 3.402823466e+38f && real(token[1].c_str(), d) && d * d > 0.0f &&
-                    d * d <= 3.402823466e+38f && (tokens < 3 || count(token[2], 1, 65536, trials)) && (tokens < 4 || count(token[3], 0, ~0ull, seed))) {
-                    found = true;
-                    o.ply_register_truth = all.substr(0, commas[tokens - 1]);
-                    o.ply_register_radius = r;
-                    o.ply_register_distance = d;
-                    o.ply_register_trials = (unsigned)trials;
-                    o.ply_register_seed = seed;
-                }
-            }
-            if (!found) {
-                fprintf(stderr,
-                        "bad value '%s' of %s: TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]], a file, two positive numbers, a count of 1 .. 65536 and a seed\n",
-                        all.c_str(), a.c_str());
-                return false;
-            }
-        } else if (a == "--ply-align") {
-            // read from the right, since the file's name may hold commas: [,scale], then [,ITERATIONS] when what stands before it is a
-            // radius too, then ,RADIUS
-            const std::string all = i + 1 < argc ? argv[++i] : "";
-            std::string rest = all;
-            const bool scale = rest.size() > 6 && rest.compare(rest.size() - 6, 6, ",scale") == 0;
-            rest = scale ? rest.substr(0, rest.size() - 6) : rest;
-            size_t comma = rest.rfind(',');
-            std::string last = comma == std::string::npos ? "" : rest.substr(comma + 1);
-            const size_t before = comma == std::string::npos || comma == 0 ? std::string::npos : rest.rfind(',', comma - 1);
-            char *end = nullptr;
-            const unsigned long long n = strtoull(last.c_str(), &end, 10);
-            float r = 0.0f;
-            unsigned long long iterations = 16;
-            if (before != std::string::npos && before > 0 && !last.empty() && last.find_first_not_of("0123456789") == std::string::npos && *end == '\0' &&
-                n >= 1 && n <= 64 && real(rest.substr(before + 1, comma - before - 1).c_str(), r) && r * r > 0.0f && r * r <= 3.402823466e+38f) {
-                iterations = n;
-                rest = rest.substr(0, comma);
-                comma = before;
-                last = rest.substr(comma + 1);
-            }
-            if (comma == std::string::npos || comma == 0 || !real(last.c_str(), r) || !(r * r > 0.0f) || r * r > 3.402823466e+38f) {
-                fprintf(stderr, "bad value '%s' of %s: TRUTH.ply,RADIUS[,ITERATIONS[,scale]], a file, a positive number and a count of 1 .. 64\n", all.c_str(),
-                        a.c_str());
-                return false;
-            }
-            o.ply_align_truth = rest.substr(0, comma);
-            o.ply_align_radius = r;
-            o.ply_align_iterations = (unsigned)iterations;
-            o.ply_align_scale = scale;
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
         } else if (a == "--seed") {
@@ -608,18 +424,7 @@ int main(int argc, char **argv)
     APD::SetDevice(opt.gpu_index);
     SetFusionDevice(opt.gpu_index);
     SetFusionOptions(opt.fusion);
-    SetFusionPlyVis(opt.ply_vis);
-    SetFusionPlyMean(opt.ply_mean);
-    SetFusionPlyVoxel(opt.ply_voxel);
-    SetFusionPlyStatFilter(opt.ply_stat_radius, opt.ply_stat_k, opt.ply_stat_ratio);
-    SetFusionPlyRadiusFilter(opt.ply_radius, opt.ply_radius_min);
-    SetFusionPlyComponentFilter(opt.ply_component_radius, opt.ply_component_min);
-    SetFusionPlySmooth(opt.ply_smooth_radius, opt.ply_smooth_min, opt.ply_smooth_iterations);
-    SetFusionPlyEstimateNormals(opt.ply_normals_radius, opt.ply_normals_min);
-    SetFusionPlyRenderVis(opt.ply_render_splat, opt.ply_render_tolerance);
-    SetFusionPlyScore(opt.ply_score_truth, opt.ply_score_threshold);
-    SetFusionPlyRegister(opt.ply_register_truth, opt.ply_register_radius, opt.ply_register_distance, opt.ply_register_trials, opt.ply_register_seed);
-    SetFusionPlyAlign(opt.ply_align_truth, opt.ply_align_radius, opt.ply_align_iterations, opt.ply_align_scale);
+    SetFusionPly(opt.ply);
 
     std::vector<Problem> problems;
     const std::string why = ReadPairFile(opt.dense_folder / "pair.txt", opt.dense_folder, problems);

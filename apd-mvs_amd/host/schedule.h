@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "APD.h"
+#include "ply_options.h"
 
 struct Options {
     path dense_folder;
@@ -35,34 +36,7 @@ struct Options {
         apd_fusion_default_options(&o);
         return o;
     }();
-    bool ply_vis = false;                 // --ply-vis: APD/APD.ply.vis beside APD.ply (apd_points_write_vis)
-    bool ply_mean = false;                // --ply-mean: APD.ply (and APD.ply.vis) of the points averaged over their agreeing views (apd_points_average)
-    float ply_voxel = 0.0f;               // --ply-voxel SIZE: APD.ply (and APD.ply.vis) of the points merged per cell of that size (apd_points_merge_voxels); 0: off
-    float ply_stat_radius = 0.0f;         // --ply-stat-filter RADIUS,K,RATIO: APD.ply (and APD.ply.vis) of the points whose mean distance to their K
-    unsigned ply_stat_k = 0;              // nearest neighbours within RADIUS is at most mean + RATIO * deviation (apd_points_remove_statistical), after
-    float ply_stat_ratio = 0.0f;          // --ply-mean and --ply-voxel, before --ply-radius-filter; radius 0: off
-    float ply_radius = 0.0f;              // --ply-radius-filter RADIUS,MIN: APD.ply (and APD.ply.vis) of the points with at least MIN others within
-    unsigned ply_radius_min = 0;          // RADIUS (apd_points_remove_sparse), after --ply-mean and --ply-voxel; radius 0: off
-    float ply_component_radius = 0.0f;    // --ply-component-filter RADIUS,MIN: APD.ply (and APD.ply.vis) of the points whose connected component within
-    unsigned ply_component_min = 0;       // RADIUS has at least MIN points (apd_points_remove_small_components), after --ply-radius-filter; radius 0: off
-    float ply_smooth_radius = 0.0f;       // --ply-smooth RADIUS,MIN[,ITERATIONS]: the points of APD.ply with each position projected on the weighted plane of
-    unsigned ply_smooth_min = 0;          // its neighbourhood within RADIUS where it has at least MIN others there, ITERATIONS (1 .. 16, default 1) times
-    unsigned ply_smooth_iterations = 1;   // (apd_points_with_smoothed_positions), after --ply-component-filter, before --ply-estimate-normals; radius 0: off
-    float ply_normals_radius = 0.0f;      // --ply-estimate-normals RADIUS,MIN: the points of APD.ply with normals estimated from the neighbourhood within
-    unsigned ply_normals_min = 0;         // RADIUS of each point that has at least MIN others there (apd_points_with_estimated_normals), last; radius 0: off
-    int ply_render_splat = -1;            // --ply-render-vis SPLAT,TOL: APD.ply.vis (the flag implies --ply-vis) lists per point the views that see it when the
-    float ply_render_tolerance = 0.0f;    // cloud is drawn into them with footprints of SPLAT (apd_points_rendered_visibility), last; splat -1: off
-    std::string ply_score_truth;          // --ply-score TRUTH.ply,TAU: the points of APD.ply scored against the cloud of TRUTH.ply at threshold TAU
-    float ply_score_threshold = 0.0f;     // (apd_points_score), after every other --ply-* flag: one printed line and APD.ply.score; empty: off
-    std::string ply_align_truth;          // --ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]: the points of APD.ply moved onto the cloud of TRUTH.ply by ICP
-    float ply_align_radius = 0.0f;        // within RADIUS (apd_points_align, apd_points_transformed), after every other --ply-* flag but --ply-score: one
-    unsigned ply_align_iterations = 16;   // printed line and APD.ply.align; empty: off
-    bool ply_align_scale = false;
-    std::string ply_register_truth;       // --ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]: the points of APD.ply moved onto the cloud of TRUTH.ply from
-    float ply_register_radius = 0.0f;     // any start (apd_points_register with descriptors at RADIUS and inliers within DISTANCE, apd_points_transformed),
-    float ply_register_distance = 0.0f;   // after every other --ply-* flag but --ply-align and --ply-score: one printed line and APD.ply.register; empty: off
-    unsigned ply_register_trials = 4096;
-    unsigned long long ply_register_seed = 0;
+    PlyOptions ply;                       // every other --ply-* flag: what becomes of the fused points before APD.ply is written (host/ply_options.h)
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)

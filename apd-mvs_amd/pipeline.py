@@ -566,224 +566,136 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     points as a Points object (numpy views, or torch tensors on `device` with result_on_device): (count, Points); ply_path may
     then be None and no file is written.  vis_path: also write COLMAP's fused.ply.vis of the same fusion there (per point the
     views that see it, as indices of the scene's views; Points.write_vis), with or without a PLY file or the points.
-    average: the mean geometry (average_points) -- the file (written by Points.write_ply, with normals when the options say
-    ply_normals), the returned points and the .vis file are those of the averaged points: positions and normals are means over
-    the agreeing views, and a source that did not contribute is no longer listed.
-    voxel: a cell size -- the file, the returned points and the .vis file are those of Points.merge_voxels(voxel, voxel_origin): one
-    point per occupied cell of the cubic grid, the mean of the cell's points (of the averaged ones with average=True) with the
-    union of their lists; the count returned is that of the cells.
-    radius_filter: (radius, min_neighbours) -- applied after `average`, `voxel` and `stat_filter`: the file, the returned points and the
-    .vis file are those of Points.remove_sparse(radius, min_neighbours), the points with at least that many other points within
-    the radius; the count returned is that of the points kept.
-    stat_filter: (radius, k, std_ratio) -- applied after `average` and `voxel` and before `radius_filter`: the points are those of
-    Points.remove_statistical(radius, k, std_ratio), whose mean distance to their k nearest neighbours within the radius is at most
-    the cloud's mean + std_ratio * deviation of that value; the count returned is that of the points kept.
-    component_filter: (radius, min_size) -- applied last, after `average`, `voxel`, `stat_filter` and `radius_filter`: the file, the
-    returned points and the .vis file are those of Points.remove_small_components(radius, min_size), the points whose connected
-    component within the radius has at least that many points; the count returned is that of the points kept.
-    smooth: (radius, min_neighbours, iterations) -- applied after `component_filter` and before `estimate_normals`: the file, the
-    returned points and the .vis file are those of Points.with_smoothed_positions(radius, min_neighbours, iterations), the same
+    The options below rework the fused points.  They are applied in this order, each to what the ones before it have produced:
+    average, voxel, stat_filter, radius_filter, component_filter, smooth, estimate_normals, render_visibility, register, align; score
+    comes after all of them.  With any of them but score alone, the file (written by Points.write_ply, with normals when the options
+    say ply_normals), the returned points, the .vis file and the count returned are those of the last step's points.
+    average: the mean geometry (average_points): positions and normals are means over the agreeing views, and a source that did
+    not contribute is no longer listed.
+    voxel: a cell size -- Points.merge_voxels(voxel, voxel_origin): one point per occupied cell of the cubic grid, the mean of the
+    cell's points with the union of their lists; the count returned is that of the cells.
+    stat_filter: (radius, k, std_ratio) -- Points.remove_statistical(radius, k, std_ratio): the points whose mean distance to their k
+    nearest neighbours within the radius is at most the cloud's mean + std_ratio * deviation of that value.
+    radius_filter: (radius, min_neighbours) -- Points.remove_sparse(radius, min_neighbours): the points with at least that many other
+    points within the radius.
+    component_filter: (radius, min_size) -- Points.remove_small_components(radius, min_size): the points whose connected component
+    within the radius has at least that many points.
+    smooth: (radius, min_neighbours, iterations) -- Points.with_smoothed_positions(radius, min_neighbours, iterations): the same
     points with each position projected on the weighted plane of its neighbourhood, `iterations` times; normals estimated and
     visibility rendered afterwards belong to the smoothed cloud.
-    estimate_normals: (radius, min_neighbours) -- applied after `average`, `voxel`, `stat_filter`, `radius_filter`,
-    `component_filter` and `smooth`, since normals belong to the cloud that is kept: the file, the returned points and the .vis file are those of
-    Points.with_estimated_normals(radius, min_neighbours), the same points with their normals re-estimated from the cloud's own
-    geometry.  Without ply_normals in the options the step changes no byte of the file; it still acts on the returned points.
-    render_visibility: (splat, rel_tolerance) -- applied last, after `estimate_normals`: the file, the returned points and the .vis
-    file are those of Points.with_rendered_visibility(scene.cameras, splat, rel_tolerance), the same points as a merged object whose
-    lists name the views that see each point of the cloud as it is then, occlusion included: the cloud is drawn into the scene's
-    full-resolution cameras, in view order.  The step changes no byte of the PLY file.
-    register: (truth, radius, inlier_distance[, trials[, seed]]) -- applied after every other option and before `align`:
-    Points.register(truth, radius, inlier_distance, trials=trials, seed=seed) of the points the other options have produced (4096
-    trials, seed 0, unless given) -- global registration from any start by FPFH descriptors of the STORED normals, their matches and
-    RANSAC -- and Points.transformed of them by its answer, as `align` moves them; the Registration is returned as one more value
-    before the Alignment: (count, Registration[, Alignment][, Score]), or (count, Points, Registration, ..) with return_points.
-    align: (truth, radius[, iterations[, with_scale]]) -- applied after every other option but `score`: Points.align(truth, radius,
-    iterations=iterations, with_scale=with_scale) of the points the other options have produced (16 iterations, rigid, unless given)
-    and Points.transformed of them by its answer: the file and the returned points are the moved ones -- positions and normals;
-    the .vis file is what it is without the option, since moving changes no list -- and the Alignment is returned as one more
-    value after the count and the points and before the score: (count, Alignment), (count, Points, Alignment), (count, Points,
-    Alignment, Score).
-    score: (truth, threshold) -- applied last, to the points every other option has produced, and changes none of them nor a byte of
-    a file: Points.score(truth, threshold) of those points against `truth` (a Points: Points.read_ply of a ground truth, or another
-    fusion's), the precision, recall and F-score at the threshold, returned as one more value after the others: (count, Score), or
-    (count, Points, Score) with return_points.  With `align` the points scored are the moved ones."""
-    import ctypes as C
-    from . import Points, default_fusion_options
+    estimate_normals: (radius, min_neighbours) -- Points.with_estimated_normals(radius, min_neighbours): the same points with their
+    normals re-estimated from the geometry of the cloud that is kept.  Without ply_normals in the options the step changes no byte
+    of the file; it still acts on the returned points.
+    render_visibility: (splat, rel_tolerance) -- Points.with_rendered_visibility(scene.cameras, splat, rel_tolerance): the same
+    points as a merged object whose lists name the views that see each point of the cloud as it is then, occlusion included: the
+    cloud is drawn into the scene's full-resolution cameras, in view order.  The step changes no byte of the PLY file.
+    register: (truth, radius, inlier_distance[, trials[, seed]]) -- Points.register(truth, radius, inlier_distance, trials=trials,
+    seed=seed) (4096 trials, seed 0, unless given) -- global registration from any start by FPFH descriptors of the STORED normals,
+    their matches and RANSAC -- and Points.transformed by its answer, as `align` moves them; the Registration is returned as one
+    more value before the Alignment: (count, Registration[, Alignment][, Score]), or (count, Points, Registration, ..) with
+    return_points.
+    align: (truth, radius[, iterations[, with_scale]]) -- Points.align(truth, radius, iterations=iterations, with_scale=with_scale)
+    (16 iterations, rigid, unless given) and Points.transformed by its answer: the file and the returned points are the moved ones
+    -- positions and normals; the .vis file is what it is without the option, since moving changes no list -- and the Alignment
+    is returned as one more value after the count and the points and before the score: (count, Alignment), (count, Points,
+    Alignment), (count, Points, Alignment, Score).
+    score: (truth, threshold) -- changes no point nor a byte of a file: Points.score(truth, threshold) of the final points against
+    `truth` (a Points: Points.read_ply of a ground truth, or another fusion's), the precision, recall and F-score at the threshold,
+    returned as one more value after the others: (count, Score), or (count, Points, Score) with return_points.  With `align` the
+    points scored are the moved ones."""
     if variant not in FUSION_VARIANTS:
         raise ValueError("unknown fusion variant %r: one of %s" % (variant, ", ".join(sorted(FUSION_VARIANTS))))
     if ply_path is None and not return_points and vis_path is None:
         raise ValueError("fuse: neither a PLY file nor the points nor the visibility file are asked for")
+    # The reworking steps, each `points -> (new points, value to return or None)`.  They are unpacked from the last applied to the
+    # first, the order in which a malformed option has always been refused, before any device work.
+    steps = []
+
+    def kept_by(name, method, *args):   # a step whose method returns (new points, figures..)
+        steps.append((name, lambda p: (getattr(p, method)(*args)[0], None)))
+
+    def moved_by(method, *args, **kw):  # register, align: the transform the method finds, and the points moved by it
+        def step(p):
+            found = getattr(p, method)(*args, **kw)
+            return p.transformed(found), found
+        steps.append((method, step))
+
     if score is not None:
         truth, threshold = score
-        n, whole, *alignment = fuse(scene, results, ply_path, device, colour_images, block_masks, variant, options, return_points=True,
-                                    vis_path=vis_path, average=average, voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter,
-                                    stat_filter=stat_filter, component_filter=component_filter, estimate_normals=estimate_normals,
-                                    render_visibility=render_visibility, smooth=smooth, align=align, register=register)
-        result = whole.score(truth, threshold)
-        if return_points:
-            return (n, whole, *alignment, result)
-        whole.close()
-        return (n, *alignment, result)
     if align is not None:
-        truth, radius, *rest = align
+        onto, radius, *rest = align
         if len(rest) > 2:
             raise ValueError("fuse: align=(truth, radius[, iterations[, with_scale]]), not %d values" % len(align))
         iterations, with_scale = (rest + [16, False][len(rest):])
-        _, whole, *registration = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                                       voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                                       component_filter=component_filter, estimate_normals=estimate_normals, render_visibility=render_visibility,
-                                       smooth=smooth, register=register)
-        alignment = whole.align(truth, radius, iterations=iterations, with_scale=with_scale)
-        moved = whole.transformed(alignment)
-        whole.close()
-        if ply_path is not None:
-            moved.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            moved.write_vis(vis_path)
-        if return_points:
-            return (moved.count, moved, *registration, alignment)
-        n = moved.count
-        moved.close()
-        return (n, *registration, alignment)
+        moved_by("align", onto, radius, iterations=iterations, with_scale=with_scale)
     if register is not None:
-        truth, radius, inlier_distance, *rest = register
+        onto, radius, inlier_distance, *rest = register
         if len(rest) > 2:
             raise ValueError("fuse: register=(truth, radius, inlier_distance[, trials[, seed]]), not %d values" % len(register))
         trials, seed = (rest + [4096, 0][len(rest):])
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                        component_filter=component_filter, estimate_normals=estimate_normals, render_visibility=render_visibility, smooth=smooth)
-        registration = whole.register(truth, radius, inlier_distance, trials=trials, seed=seed)
-        moved = whole.transformed(registration)
-        whole.close()
-        if ply_path is not None:
-            moved.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            moved.write_vis(vis_path)
-        if return_points:
-            return moved.count, moved, registration
-        n = moved.count
-        moved.close()
-        return n, registration
+        moved_by("register", onto, radius, inlier_distance, trials=trials, seed=seed)
     if render_visibility is not None:
         splat, rel_tolerance = render_visibility
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                        component_filter=component_filter, estimate_normals=estimate_normals, smooth=smooth)
-        kept, _ = whole.with_rendered_visibility([scene.cameras[v] for v in range(scene.num_views)], splat, rel_tolerance)
-        whole.close()
-        if ply_path is not None:
-            kept.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            kept.write_vis(vis_path)
-        if return_points:
-            return kept.count, kept
-        n = kept.count
-        kept.close()
-        return n
+        kept_by("render_visibility", "with_rendered_visibility", [scene.cameras[v] for v in range(scene.num_views)], splat, rel_tolerance)
     if estimate_normals is not None:
         radius, min_neighbours = estimate_normals
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                        component_filter=component_filter, smooth=smooth)
-        kept, _ = whole.with_estimated_normals(radius, min_neighbours)
-        whole.close()
-        if ply_path is not None:
-            kept.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            kept.write_vis(vis_path)
-        if return_points:
-            return kept.count, kept
-        n = kept.count
-        kept.close()
-        return n
+        kept_by("estimate_normals", "with_estimated_normals", radius, min_neighbours)
     if smooth is not None:
         radius, min_neighbours, iterations = smooth
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter,
-                        component_filter=component_filter)
-        kept, _ = whole.with_smoothed_positions(radius, min_neighbours, iterations)
-        whole.close()
-        if ply_path is not None:
-            kept.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            kept.write_vis(vis_path)
-        if return_points:
-            return kept.count, kept
-        n = kept.count
-        kept.close()
-        return n
+        kept_by("smooth", "with_smoothed_positions", radius, min_neighbours, iterations)
     if component_filter is not None:
         radius, min_size = component_filter
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                        voxel=voxel, voxel_origin=voxel_origin, radius_filter=radius_filter, stat_filter=stat_filter)
-        kept, _, _ = whole.remove_small_components(radius, min_size)
-        whole.close()
-        if ply_path is not None:
-            kept.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            kept.write_vis(vis_path)
-        if return_points:
-            return kept.count, kept
-        n = kept.count
-        kept.close()
-        return n
+        kept_by("component_filter", "remove_small_components", radius, min_size)
     if radius_filter is not None:
         radius, min_neighbours = radius_filter
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                        voxel=voxel, voxel_origin=voxel_origin, stat_filter=stat_filter)
-        kept, _ = whole.remove_sparse(radius, min_neighbours)
-        whole.close()
-        if ply_path is not None:
-            kept.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            kept.write_vis(vis_path)
-        if return_points:
-            return kept.count, kept
-        n = kept.count
-        kept.close()
-        return n
+        kept_by("radius_filter", "remove_sparse", radius, min_neighbours)
     if stat_filter is not None:
         radius, k, std_ratio = stat_filter
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average,
-                        voxel=voxel, voxel_origin=voxel_origin)
-        kept, _, _ = whole.remove_statistical(radius, k, std_ratio)
-        whole.close()
-        if ply_path is not None:
-            kept.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            kept.write_vis(vis_path)
-        if return_points:
-            return kept.count, kept
-        n = kept.count
-        kept.close()
-        return n
+        kept_by("stat_filter", "remove_statistical", radius, k, std_ratio)
     if voxel is not None:
-        _, whole = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True, average=average)
-        merged, _ = whole.merge_voxels(voxel, voxel_origin)
-        whole.close()
-        if ply_path is not None:
-            merged.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            merged.write_vis(vis_path)
-        if return_points:
-            return merged.count, merged
-        n = merged.count
-        merged.close()
-        return n
+        kept_by("voxel", "merge_voxels", voxel, voxel_origin)
     if average:
-        n, fused = fuse(scene, results, None, device, colour_images, block_masks, variant, options, return_points=True)
-        mean = average_points(scene, results, fused, device)
-        fused.close()
-        if ply_path is not None:
-            mean.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
-        if vis_path is not None:
-            mean.write_vis(vis_path)
-        if return_points:
-            return n, mean
-        mean.close()
+        steps.append(("average", lambda p: (average_points(scene, results, p, device), None)))
+    steps.reverse()
+
+    # With a reworking step the file is written from the final points; otherwise it is the fusion's own, and the points are wrapped
+    # only where they are returned or scored (the .vis file alone is written from the raw handle).
+    wrap = bool(return_points or steps or score is not None)
+    n, points = _fuse_views(scene, results, None if steps else ply_path, device, colour_images, block_masks, variant, options, wrap,
+                            None if wrap else vis_path)
+    if points is None:
         return n
+    values = []
+    try:
+        for _, step in steps:
+            new, value = step(points)
+            points.close()
+            points = new
+            if value is not None:
+                values.append(value)
+        if steps:
+            if [name for name, _ in steps] != ["average"]:   # averaging alone keeps every point: the fusion's own count
+                n = points.count
+            if ply_path is not None:
+                points.write_ply(ply_path, normals=bool(options is not None and options.ply_normals))
+        if vis_path is not None:
+            points.write_vis(vis_path)
+        if score is not None:
+            values.append(points.score(truth, threshold))
+    except BaseException:
+        points.close()
+        raise
+    if return_points:
+        return (n, points, *values)
+    points.close()
+    return (n, *values) if values else n
+
+
+def _fuse_views(scene, results, ply_path, device, colour_images, block_masks, variant, options, wrap, vis_path):
+    """The one fusion of fuse(): (count, Points or None).  ply_path: the fusion writes the file itself, unless None.  wrap: the points
+    come back as a Points on `device`; otherwise vis_path, unless None, is written from the raw handle, which is then released."""
+    import ctypes as C
+    from . import Points, default_fusion_options
     L = host_lib()
     L.apdhost_set_fusion_device(int(device))
     L.apdhost_set_fusion_variant(FUSION_VARIANTS[variant])
@@ -838,20 +750,19 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     handle = C.c_void_p()
     n = L.apdhost_fuse_opt(C.byref(opt), V, C.byref(cams), ptrs(imgs), channels, ptrs(deps), ptrs(nors), ptrs(weaks), blocks, rows, cols, offs,
                            idx, None if ply_path is None else str(ply_path).encode(),
-                           C.byref(handle) if return_points or vis_path is not None else None)
+                           C.byref(handle) if wrap or vis_path is not None else None)
     if n < 0:
         raise RuntimeError("device fusion failed (apd_fuse_views_opt, %s): see stderr" % variant)
-    points = Points(handle, device) if return_points else None
-    if vis_path is not None and points is not None:
-        points.write_vis(vis_path)
-    elif vis_path is not None:  # the file alone: no array is copied or wrapped
+    if wrap:
+        return int(n), Points(handle, device)
+    if vis_path is not None:  # the file alone: no array is copied or wrapped
         from . import ApdError, lib
         rc = lib().apd_points_write_vis(handle, str(vis_path).encode())
         why = lib().apd_fusion_last_error().decode() if rc != 0 else ""
         lib().apd_points_destroy(handle)
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, why))
-    return (int(n), points) if return_points else int(n)
+    return int(n), None
 
 
 class FilteredMaps:
