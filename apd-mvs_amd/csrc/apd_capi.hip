@@ -26,7 +26,7 @@ hipError_t launch_export_state(const FrameArgs &fa, float4 *planes4, uint8_t *we
 hipError_t launch_masked_download(const FrameArgs &fa, float4 *planes4, uint8_t *weak, uint32_t *views, hipStream_t s);
 hipError_t launch_mask_weak_info(const uint8_t *mask, uint8_t *weak, int n, hipStream_t s);
 hipError_t launch_mask_count(const uint8_t *mask, int n, int *count, hipStream_t s);
-hipError_t launch_check_u8(const float *img, int n, int *flag, hipStream_t s);
+hipError_t launch_check_u8(const float *img, int n, int *flag, int *outside, hipStream_t s);
 hipError_t launch_weak_index_map(const uint8_t *weak, size_t n, int *map, int *scratch, hipStream_t s);
 hipError_t launch_pack_pairs(const float *img, int W, int H, quad_t *quad, hipStream_t s);
 hipError_t launch_pack_quads_tiled(const float *img, int W, int H, quad_t *quad, hipStream_t s);
@@ -597,7 +597,7 @@ static int finish_upload(apd_context *c, int num_images, const apd_camera *camer
 // Image / camera upload shared by apd_upload_views and apd_upload_views_split.  defer_depths: a geometric pass whose depth
 // maps arrive later (apd_upload_depths): their buffers are allocated here, so that the per-view constants can point at them.
 static int upload_views_impl(apd_context *c, int num_images, const apd_camera *cameras, const float *const *images, const float *const *depths,
-                             bool defer_depths)
+                             bool defer_depths, const char *who)
 {
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->W * c->H;
@@ -626,16 +626,24 @@ static int upload_views_impl(apd_context *c, int num_images, const apd_camera *c
             }
         }
     }
-    // 8-bit input (integers 0..255 in every view)?  Then also keep the source views as texel quads.
-    HIP_TRY(c->flag_dev.ensure(sizeof(int)));
-    const int one = 1;
-    HIP_TRY(hipMemcpyAsync(c->flag_dev, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // 8-bit input (integers 0..255 in every view)?  Then also keep the source views as texel quads.  The same pass over the pixels
+    // raises one flag per view for a pixel outside the pixel domain (apd_device.h: kPixelLimit).
+    std::vector<int> flags((size_t)num_images + 1, 0);  // [0] all views 8-bit; [1 + i] view i has a pixel outside the domain
+    flags[0] = 1;
+    HIP_TRY(c->flag_dev.ensure(flags.size() * sizeof(int)));
+    HIP_TRY(hipMemcpyAsync(c->flag_dev, flags.data(), flags.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     for (int i = 0; i < num_images; ++i) {  // the reference view too: K9/K10 keep its sub-patch texels as bytes
-        LAUNCH_TRY("k_check_u8", apd::launch_check_u8(c->images[i].img, (int)n, c->flag_dev, c->stream));
+        LAUNCH_TRY("k_check_u8", apd::launch_check_u8(c->images[i].img, (int)n, c->flag_dev, (int *)c->flag_dev + 1 + i, c->stream));
     }
-    int all_u8 = 0;
-    HIP_TRY(hipMemcpyAsync(&all_u8, c->flag_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), c->flag_dev, flags.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < num_images; ++i) {
+        if (flags[(size_t)i + 1]) {  // the handle's image planes hold the refused upload: it is no longer armed with the one before
+            c->views_uploaded = false;
+            return set_error(g_last_error, APD_ERR_UNSUPPORTED, "%s: the image of view %d has a pixel that is not finite or lies outside [-2^20, 2^20]", who, i);
+        }
+    }
+    const int all_u8 = flags[0];
     choose_copies(c, all_u8 != 0);
     std::vector<const DeviceImage *> img(num_images);
     for (int i = 0; i < num_images; ++i) {
@@ -671,7 +679,7 @@ int apd_upload_views(apd_handle c, int num_images, const apd_camera *cameras, co
     if (c->params.geom_consistency && !depths) {
         return set_error(g_last_error, APD_ERR_INVALID, "apd_upload_views: geom_consistency needs depth maps");
     }
-    return upload_views_impl(c, num_images, cameras, images, depths, false);
+    return upload_views_impl(c, num_images, cameras, images, depths, false, "apd_upload_views");
 }
 
 int apd_upload_views_split(apd_handle c, int num_images, const apd_camera *cameras, const float *const *images)
@@ -680,7 +688,7 @@ int apd_upload_views_split(apd_handle c, int num_images, const apd_camera *camer
     if (rc) {
         return rc;
     }
-    return upload_views_impl(c, num_images, cameras, images, nullptr, c->params.geom_consistency != 0);
+    return upload_views_impl(c, num_images, cameras, images, nullptr, c->params.geom_consistency != 0, "apd_upload_views_split");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -726,19 +734,23 @@ int apd_image_create(apd_image_t *out, int device, int width, int height, const 
     im->H = height;
     const size_t n = (size_t)width * height;
     DevBuf<int> flag;
-    int all_u8 = 1;
+    int flags[2] = {1, 0};  // 8-bit; a pixel outside the pixel domain (apd_device.h: kPixelLimit)
     hipError_t e = im->img.ensure(n * sizeof(float));
     e = e != hipSuccess ? e : hipMemcpy(im->img, pixels, n * sizeof(float), hipMemcpyDefault);
-    e = e != hipSuccess ? e : flag.ensure(sizeof(int));
-    e = e != hipSuccess ? e : hipMemcpy(flag, &all_u8, sizeof(int), hipMemcpyHostToDevice);
-    e = e != hipSuccess ? e : apd::launch_check_u8(im->img, (int)n, flag, nullptr);
-    e = e != hipSuccess ? e : hipMemcpy(&all_u8, flag, sizeof(int), hipMemcpyDeviceToHost);
+    e = e != hipSuccess ? e : flag.ensure(sizeof(flags));
+    e = e != hipSuccess ? e : hipMemcpy(flag, flags, sizeof(flags), hipMemcpyHostToDevice);
+    e = e != hipSuccess ? e : apd::launch_check_u8(im->img, (int)n, flag, (int *)flag + 1, nullptr);
+    e = e != hipSuccess ? e : hipMemcpy(flags, flag, sizeof(flags), hipMemcpyDeviceToHost);
     flag.release();
     if (e != hipSuccess) {
         apd_image_destroy(im);
         return set_error(g_last_error, APD_ERR_HIP, "apd_image_create: %s", hipGetErrorString(e));
     }
-    im->is_u8 = all_u8 != 0;
+    if (flags[1]) {  // no shared image outside the domain exists, so apd_upload_views_shared never meets one
+        apd_image_destroy(im);
+        return set_error(g_last_error, APD_ERR_UNSUPPORTED, "apd_image_create: the image has a pixel that is not finite or lies outside [-2^20, 2^20]");
+    }
+    im->is_u8 = flags[0] != 0;
     const int rc = image_ensure(im, im->is_u8 ? DeviceImage::PAIRS : DeviceImage::FQUADS, nullptr);
     if (rc != APD_OK) {
         apd_image_destroy(im);

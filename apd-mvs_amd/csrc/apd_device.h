@@ -210,7 +210,12 @@ __device__ __forceinline__ float recip_rn(float z) { return recip_rn(z, recip_fa
 //                      the steps of the compiler's own sequence without its range scaling; 2^32 random pairs over the operand
 //                      ranges of an NCC checked against `/`, zero included.
 // tools/valu_rates.hip --check runs both comparisons on the device (tests/test_gpu_edge_cases.py::test_isa_contract_exhaustive).
-// Callers guarantee the ranges: x = var_ref * var_src with both in [1e-5, 1.7e4], b = sqrt of that, |a| <= 6.6e4.
+// The operand ranges are the upload's to guarantee, not the callers': every upload entry point (apd_upload_views,
+// apd_upload_views_split, apd_image_create and with it apd_upload_views_shared) refuses an image with a pixel that is not finite or
+// lies outside [-kPixelLimit, kPixelLimit] (k_check_u8, APD_ERR_UNSUPPORTED).  With |v| <= 2^20 a variance is at most 2^40 and the
+// callers have tested both against kMinVar = 1e-5 > 2^-17, so x = var_ref * var_src lies in [2^-34, 2^80] (biased exponents 93..207,
+// inside 31..223), b = sqrt(x) in [2^-17, 2^40] and |a| = |covariance| <= 2^41: no step of div_rn_mid over- or underflows.
+constexpr float kPixelLimit = 0x1p20f;
 __device__ __forceinline__ float sqrt_rn_mid(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

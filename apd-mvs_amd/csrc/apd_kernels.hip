@@ -551,14 +551,19 @@ __global__ __launch_bounds__(256) void k15_local_refine(FrameArgs fa)
 // texel-quad images (built once per upload)
 // ------------------------------------------------------------------------------------------------
 
-// *flag stays 1 only if every pixel is an integer in [0, 255] (8-bit input at scale 1)
-__global__ __launch_bounds__(256) void k_check_u8(const float *__restrict__ img, int n, int *flag)
+// *flag stays 1 only if every pixel is an integer in [0, 255] (8-bit input at scale 1; -0.0f counts as 0: every sum of an NCC
+// starts at +0.0f, so the sign of a zero texel never shows).  *outside is set to 1 by a pixel outside the domain the NCC tail is
+// exact in (kPixelLimit, apd_device.h): NaN, +-inf or |v| > 2^20.
+__global__ __launch_bounds__(256) void k_check_u8(const float *__restrict__ img, int n, int *flag, int *outside)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
         const float v = img[i];
         if (!(v >= 0.0f && v <= 255.0f && v == floorf(v))) {
             *flag = 0;
+        }
+        if (!(fabsf(v) <= kPixelLimit)) {
+            *outside = 1;
         }
     }
 }
@@ -611,9 +616,9 @@ hipError_t launch_pack_fquads(const float *img, int W, int H, fquad_t *fq, hipSt
     return hipGetLastError();
 }
 
-hipError_t launch_check_u8(const float *img, int n, int *flag, hipStream_t s)
+hipError_t launch_check_u8(const float *img, int n, int *flag, int *outside, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_check_u8, dim3((n + 255) / 256), dim3(256), 0, s, img, n, flag);
+    hipLaunchKernelGGL(k_check_u8, dim3((n + 255) / 256), dim3(256), 0, s, img, n, flag, outside);
     return hipGetLastError();
 }
 

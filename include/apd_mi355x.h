@@ -138,7 +138,12 @@ int apd_reset(apd_handle h, const apd_params *params);
 
 /* Image / depth / camera upload of CudaSpaceInitialization (APD.cpp:588-634).  images[0] is the
  * reference view; `depths` may be NULL unless params.geom_consistency.  All images are W*H floats,
- * row-major, no padding.  Sets params.num_images. */
+ * row-major, no padding.  Sets params.num_images.
+ * The pixel domain: every pixel finite and in [-2^20, 2^20] (8- and 16-bit images at any scale up to that, [0, 1] images, images
+ * centred on zero).  Inside it every NCC has the reference's bits; outside it the variance products leave the range the NCC tail is
+ * exact in.  apd_upload_views, apd_upload_views_split and apd_image_create test every pixel on the device and answer
+ * APD_ERR_UNSUPPORTED with the first offending view in apd_last_error; no kernel of a pass runs, and a handle whose upload was
+ * refused holds no views until the next accepted upload.  Depth maps may hold any float (0 and -0 mean "no depth"). */
 int apd_upload_views(apd_handle h, int num_images, const apd_camera *cameras, const float *const *images,
                      const float *const *depths);
 

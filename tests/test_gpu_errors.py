@@ -97,6 +97,62 @@ def test_rotate_time_outside_1_to_4_is_refused_by_apd_reset(gpu_pkg, ob, synth, 
     o.close()
 
 
+OUTSIDE_PIXELS = [float("nan"), float("inf"), float("-inf"), 2.0 ** 20 + 0.125, -(2.0 ** 20) - 0.125, 3.0e38]
+
+
+@pytest.mark.parametrize("value", OUTSIDE_PIXELS, ids=["nan", "inf", "-inf", "above_2^20", "below_-2^20", "3e38"])
+@pytest.mark.parametrize("view", [0, 2])
+def test_a_pixel_outside_the_domain_is_refused_by_every_upload(gpu_pkg, ob, synth, value, view):
+    """The NCC tail (csrc/apd_device.h: sqrt_rn_mid, div_rn_mid) is exact for finite pixels in [-2^20, 2^20]; one pixel outside, in the
+    reference view or a source, and apd_upload_views, apd_upload_views_split and apd_image_create answer APD_ERR_UNSUPPORTED and name the
+    view.  The test that finds it is the upload's own pass over the pixels; no kernel of a pass runs.  Afterwards the handle holds no
+    views, and takes a clean upload with the oracle's bits."""
+    W, H, N = 40, 33, 2
+    sc, imgs = common.scene_inputs(synth, W, H, N)
+    bad = [im.copy() for im in imgs]
+    bad[view][H - 1, W - 1] = np.float32(value)     # the last pixel of the plane
+    p = common.base_params(sc, N, max_iterations=1, weak_peak_radius=6)
+    L = gpu_pkg.lib()
+    cams = [gpu_pkg.make_camera(sc.K[i], sc.R[i], sc.t[i], W, H, sc.depth_min, sc.depth_max) for i in range(N + 1)]
+    cam_arr = (gpu_pkg.Camera * (N + 1))(*cams)
+    ptrs = (C.c_void_p * (N + 1))(*[im.ctypes.data for im in bad])
+    h = common.make_handle(gpu_pkg, sc, imgs, N, p)      # armed with a clean upload first
+    for name, args in (("apd_upload_views", (ptrs, None)), ("apd_upload_views_split", (ptrs,))):
+        assert getattr(L, name)(h._h, N + 1, cam_arr, *args) == APD_ERR_UNSUPPORTED
+        message = L.apd_last_error().decode()
+        assert message.startswith(name + ":") and "view %d" % view in message and "2^20" in message, message
+        with pytest.raises(gpu_pkg.ApdError, match="apd_upload_views"):
+            h.run()
+    out = C.c_void_p()
+    assert L.apd_image_create(C.byref(out), 0, W, H, C.c_void_p(bad[view].ctypes.data)) == APD_ERR_UNSUPPORTED
+    assert out.value is None and "apd_image_create" in L.apd_last_error().decode()
+    with pytest.raises(gpu_pkg.ApdError, match="2\\^20"):
+        gpu_pkg.SharedImage(W, H, bad[view])
+    h.upload_views(cams, imgs)
+    o = common.make_oracle(ob, sc, imgs, N, p)
+    h.run()
+    o.run()
+    common.assert_state_equal(gpu_pkg, h, o, "a clean upload after a refused one")
+    h.close()
+    o.close()
+
+
+def test_pixels_at_the_edge_of_the_domain_are_accepted(gpu_pkg, ob, synth):
+    """+-2^20 exactly, -0.0 and a denormal are inside the domain: the upload is accepted and the pass has the oracle's bits."""
+    W, H, N = 40, 33, 2
+    sc, imgs = common.scene_inputs(synth, W, H, N)
+    imgs = [im.copy() for im in imgs]
+    imgs[0][0, 0], imgs[1][5, 7], imgs[2][H - 1, W - 1], imgs[2][3, 3] = np.float32(2.0 ** 20), np.float32(-(2.0 ** 20)), np.float32(-0.0), np.float32(1e-40)
+    p = common.base_params(sc, N, max_iterations=1, weak_peak_radius=6)
+    h = common.make_handle(gpu_pkg, sc, imgs, N, p)
+    o = common.make_oracle(ob, sc, imgs, N, p)
+    h.run()
+    o.run()
+    common.assert_state_equal_nan_canonical(gpu_pkg, h, o, "pixels at +-2^20")
+    h.close()
+    o.close()
+
+
 def test_camera_size_mismatch(gpu_pkg, synth):
     W, H = 32, 32
     sc, imgs = common.scene_inputs(synth, W, H, 1)

@@ -77,7 +77,7 @@ def _ncc_old64(sc, imgs, px, py, src, plane):
     H = _homography(sc, src, plane)
     cx, cy = _warp(H, px, py)
     if not (0 <= cx < sc.width and 0 <= cy < sc.height):
-        return 2.0, 1.0
+        return 2.0, float("inf")    # no patch: no variance to be near the threshold
     return _patch_cost(imgs[0], imgs[src], H, px, py, 5, 2)
 
 
@@ -103,7 +103,20 @@ def test_ncc_old_against_float64_on_general_cameras(ob, synth, rig):
     _check_ncc_old(ob, *_general_scene(synth, rig, 96, 72, seed=5))
 
 
-def _check_ncc_old(ob, sc, imgs):
+def _risky(margin, var_scale, var_error=0.0):
+    """A patch variance at which binary32 may land on the other side of kMinVar, or at which its rounding is amplified: the file's
+    1e-3 grey levels^2 times the square of the image's scale (an absolute bound in grey levels scales with the image), and -- kMinVar
+    itself does not scale -- anything within the binary32 error of a variance (var_error: _variance_error of the images) of it."""
+    return margin < 1e-3 * var_scale or abs(margin - 1e-5) < var_error
+
+
+def _variance_error(imgs):
+    """Largest error of a binary32 patch variance of these images: a difference of two numbers of size up to max|v|^2, each the
+    result of at most 36 accumulations, one scaling and one fma (38 roundings of relative size 2^-24)."""
+    return 38.0 * 2.0 ** -24 * max(float(np.abs(im).max()) for im in imgs) ** 2
+
+
+def _check_ncc_old(ob, sc, imgs, var_scale=1.0, bound=(5e-3, 1e-4), var_error=0.0):
     W, H, N = 96, 72, 3
     o = common.make_oracle(ob, sc, imgs, N, common.base_params(sc, N))
     gt = sc.gt_depth.numpy()
@@ -115,13 +128,14 @@ def _check_ncc_old(ob, sc, imgs):
             for src in range(1, N + 1):
                 want, margin = _ncc_old64(sc, imgs, px, py, src, plane)
                 got = o.ncc_old(px, py, src, plane.astype(np.float32))
-                if margin < 1e-3:      # at the variance threshold the binary32 rounding may land on the other side
+                if _risky(margin, var_scale, var_error):      # at the variance threshold the binary32 rounding may land on the other side
                     continue
                 twos += want == 2.0
                 diffs.append(abs(got - want))
     diffs = np.array(diffs)
     assert len(diffs) > 800 and twos > 5
-    assert diffs.max() < 5e-3 and np.median(diffs) < 1e-4, (diffs.max(), np.median(diffs))
+    print("ncc_old vs float64: %d costs, largest difference %.3g, median %.3g, bound %s" % (len(diffs), diffs.max(), np.median(diffs), bound))
+    assert diffs.max() < bound[0] and np.median(diffs) < bound[1], (diffs.max(), np.median(diffs))
     o.close()
 
 
@@ -137,7 +151,7 @@ def test_ncc_new_against_float64_on_general_cameras(ob, synth, rig):
     _check_ncc_new(ob, *_general_scene(synth, rig, 96, 72, seed=3, textureless=0.3))
 
 
-def _check_ncc_new(ob, sc, imgs):
+def _check_ncc_new(ob, sc, imgs, var_scale=1.0, bound=(5e-3, 6e-4), var_error=0.0, pixels=80):
     W, H, N = 96, 72, 3
     p0 = common.base_params(sc, N, max_iterations=2, weak_peak_radius=6)
     o0 = common.make_oracle(ob, sc, imgs, N, p0)
@@ -154,7 +168,7 @@ def _check_ncc_new(ob, sc, imgs):
     rng = np.random.RandomState(1)
     sel = o.selected_views
     diffs = []
-    for (py, px) in weak[rng.permutation(len(weak))[:80]]:
+    for (py, px) in weak[rng.permutation(len(weak))[:pixels]]:
         py, px = int(py), int(px)
         nb = o.neighbours[o.neighbours_map[py, px]]
         for plane in _random_planes(rng, sc, gt, px, py, 2):
@@ -166,7 +180,7 @@ def _check_ncc_new(ob, sc, imgs):
                     want = 2.0
                 else:
                     centre, m = _patch_cost(imgs[0], imgs[src], Hm, px, py, 5, 2)
-                    risky |= m < 1e-3
+                    risky |= _risky(m, var_scale, var_error)
                     acc, cnt = 0.0, 0
                     for k in range(1, 9):
                         qx, qy = int(nb[k][0]), int(nb[k][1])
@@ -179,7 +193,7 @@ def _check_ncc_new(ob, sc, imgs):
                                 cnt += 1
                             continue
                         c, m = _patch_cost(imgs[0], imgs[src], Hm, qx, qy, 5, 5)
-                        risky |= m < 1e-3
+                        risky |= _risky(m, var_scale, var_error)
                         acc += c
                         cnt += 1
                     want = centre if cnt == 0 else 0.25 * centre + 0.75 * min(acc / cnt, 2.0)
@@ -189,7 +203,8 @@ def _check_ncc_new(ob, sc, imgs):
     diffs = np.array(diffs)
     assert len(diffs) > 200
     # textureless patches: variances of a few grey levels^2 amplify the binary32 rounding of the moments
-    assert diffs.max() < 5e-3 and np.median(diffs) < 6e-4, (diffs.max(), np.median(diffs))
+    print("ncc_new vs float64: %d costs, largest difference %.3g, median %.3g, bound %s" % (len(diffs), diffs.max(), np.median(diffs), bound))
+    assert diffs.max() < bound[0] and np.median(diffs) < bound[1], (diffs.max(), np.median(diffs))
     o.close()
 
 
@@ -237,3 +252,54 @@ def _check_geometric_cost(ob, sc, imgs):
     assert len(diffs) > 250 and threes >= 1
     assert diffs.max() < 2e-2 and np.median(diffs) < 2e-4, (diffs.max(), np.median(diffs))
     o.close()
+
+
+# ---- off the 8-bit value range (tests/value_space_cases.py) ------------------------------------------------------------------------
+
+def _value_images(name, imgs):
+    import value_space_cases as vc
+    return [np.ascontiguousarray(im, np.float32) for im in vc.BY_NAME[name].edit([im.copy() for im in imgs])]
+
+
+def _moment_bound(imgs, var_floor):
+    """What binary32 moments can cost an NCC at this input's mean, from the float64 restatement of their error: each of var_ref,
+    var_src and the covariance is a difference of two numbers of size mean^2 + var, each the result of at most 36 accumulations,
+    one scaling and one fma (38 roundings of relative size 2^-24), so each carries an absolute error up to e = 38 * 2^-24 *
+    (mean^2 + var); to first order 1 - cov / sqrt(var_ref * var_src) then moves by up to 2 e / var_floor, var_floor being the smallest
+    variance the comparison admits.  No cost lies outside [0, 2]: the bound is capped there, and a cap that is reached says that
+    binary32 moments -- the reference's -- resolve nothing at this mean."""
+    mean = max(float(np.abs(im.astype(np.float64)).mean()) for im in imgs)
+    var = max(float(im.astype(np.float64).var()) for im in imgs)
+    e = 38.0 * 2.0 ** -24 * (mean * mean + var)
+    return min(2.0, 2.0 * e / var_floor), mean, var
+
+
+# name, the image's scale (the file's absolute bounds are in grey levels of 0..255 images: the variance margin scales with its square)
+VALUE_INPUTS = [("scale_257", 257.0), ("unit", 1.0 / 255.0), ("offset_1e6", 1.0)]
+
+
+@pytest.mark.parametrize("name,scale", VALUE_INPUTS, ids=[n for n, _ in VALUE_INPUTS])
+def test_cost_functions_against_float64_off_the_8_bit_range(ob, synth, name, scale):
+    """The three cost functions on 16-bit replication (0..65535), on [0, 1] images and at a mean of 1e6.  The cost is a ratio: the
+    file's own bounds on it are relative and stand as they are for the two scalings.  At a mean of 1e6 the bound is what
+    _moment_bound derives from the input (it reaches the cap: about 2^20 * 2^-24 of each moment is lost, sixty times the texture's
+    variance).  The geometric term reads no pixel: its bound stands."""
+    var_floor = 1e-3 * scale * scale
+    bound_old, bound_new = (5e-3, 1e-4), (5e-3, 6e-4)
+    sc, imgs = common.scene_inputs(synth, 96, 72, 3, seed=5)
+    if name == "offset_1e6":
+        b, mean, var = _moment_bound(_value_images(name, imgs), var_floor)
+        print("offset_1e6: mean %.6g, variance %.4g, derived bound on a cost %.3g" % (mean, var, b))
+        assert b == 2.0      # as derived: the cap
+        bound_old = bound_new = (b + 1e-6, b + 1e-6)      # a cost in [0, 2] differs from another by at most 2: `<` needs room for equality
+    # at a mean of 1e6 a variance may land on either side of kMinVar anywhere and the bound is the whole range: nothing is set aside
+    err = (lambda im: 0.0) if name == "offset_1e6" else _variance_error
+    vimgs = _value_images(name, imgs)
+    _check_ncc_old(ob, sc, vimgs, var_scale=scale * scale, bound=bound_old, var_error=err(vimgs))
+    sc, imgs = common.scene_inputs(synth, 96, 72, 3, seed=3, textureless=0.3)
+    vimgs = _value_images(name, imgs)
+    # [0, 1] images: the WEAK pixels lie where synth's noise is the only texture, 0.75 grey levels^2 = 1.15e-5, inside the error band
+    # around kMinVar for three patches in four; three times the pixels keep the file's count of compared costs
+    _check_ncc_new(ob, sc, vimgs, var_scale=scale * scale, bound=bound_new, var_error=err(vimgs), pixels=240 if name == "unit" else 80)
+    sc, imgs = common.scene_inputs(synth, 96, 72, 3, seed=4)
+    _check_geometric_cost(ob, sc, _value_images(name, imgs))

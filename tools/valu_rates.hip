@@ -158,8 +158,9 @@ __global__ __launch_bounds__(256) void sqrt_check(uint32_t base, unsigned long l
     }
 }
 
-// 2^32 pseudo-random pairs over the operand ranges of an NCC epilogue and beyond: b = 2^-20 .. 2^20 (the code has 1e-5 .. 1.7e4),
-// a = +-2^-40 .. 2^30 with one pair in 64 a = +-0; [0] results whose bits differ from a / b (an exact zero may differ in sign: the
+// 2^32 pseudo-random pairs over the operand ranges of an NCC epilogue on the pixel domain the uploads admit (|v| <= 2^20,
+// csrc/apd_device.h: kPixelLimit) and beyond: b = 2^-20 .. 2^40 (the code has 2^-17 .. 2^40), a = +-2^-40 .. 2^41 (the code has
+// |a| <= 2^41) with one pair in 64 a = +-0; [0] results whose bits differ from a / b (an exact zero may differ in sign: the
 // caller only forms 1 - q), [2] pairs checked
 __global__ __launch_bounds__(256) void div_check(uint32_t base, unsigned long long *counts, uint32_t *examples)
 {
@@ -172,9 +173,9 @@ __global__ __launch_bounds__(256) void div_check(uint32_t base, unsigned long lo
     w1 ^= w1 >> 16;
     w1 *= 0x27D4EB2Fu;
     w1 ^= w1 >> 15;
-    const uint32_t eb = 107u + (w0 >> 23) % 41u;                   // biased exponent of b: 2^-20 .. 2^20
+    const uint32_t eb = 107u + (w0 >> 23) % 61u;                   // biased exponent of b: 2^-20 .. 2^40
     const float b = __uint_as_float((eb << 23) | (w0 & 0x7FFFFFu));
-    const uint32_t ea = 87u + (w1 >> 24) % 71u;                    // 2^-40 .. 2^30
+    const uint32_t ea = 87u + (w1 >> 24) % 82u;                    // 2^-40 .. 2^41
     float a = __uint_as_float((w1 & 0x80000000u) | (ea << 23) | (w1 & 0x7FFFFFu));
     if ((h & 63u) == 0u) {
         a = __uint_as_float(w1 & 0x80000000u);
@@ -438,7 +439,7 @@ static int run_checks()
     CHECK(hipDeviceSynchronize());
     CHECK(hipMemcpy(hcounts, dcounts, sizeof(hcounts), hipMemcpyDeviceToHost));
     CHECK(hipMemcpy(hex, dex, sizeof(hex), hipMemcpyDeviceToHost));
-    printf("div_rn_mid vs a / b over %llu pseudo-random pairs (b = 2^-20..2^20, a = +-2^-40..2^30 and +-0): mismatches=%llu\n", hcounts[2], hcounts[0]);
+    printf("div_rn_mid vs a / b over %llu pseudo-random pairs (b = 2^-20..2^40, a = +-2^-40..2^41 and +-0): mismatches=%llu\n", hcounts[2], hcounts[0]);
     printf("CHECK_div_midrange_mismatches=%llu\nCHECK_div_pairs=%llu\n", hcounts[0], hcounts[2]);
     for (int i = 0; i < 8 && (unsigned long long)i < hcounts[0]; ++i) {
         printf("   a=%08x b=%08x mine=%08x exact=%08x\n", hex[4 * i], hex[4 * i + 1], hex[4 * i + 2], hex[4 * i + 3]);
