@@ -204,6 +204,8 @@ def lib():
     L.apd_points_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     L.apd_points_score.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsScore)]
     L.apd_points_align.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsAlignOptions), C.POINTER(PointsAlignment)]
+    L.apd_points_align_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(PointsAlignPlanesOptions),
+                                          C.POINTER(PointsPlaneAlignment)]
     L.apd_points_transformed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_void_p)]
     L.apd_points_features.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_void_p, C.c_void_p]
     L.apd_points_match_features.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
@@ -273,6 +275,23 @@ Alignment = collections.namedtuple("Alignment", [n for n, _ in PointsAlignment._
 ALIGN_ITERATIONS, ALIGN_CONVERGED, ALIGN_TOO_FEW = 0, 1, 2
 
 
+class PointsAlignPlanesOptions(C.Structure):
+    """apd_points_align_planes_options."""
+    _fields_ = [("iterations", C.c_uint), ("tolerance", C.c_double)]
+
+
+class PointsPlaneAlignment(C.Structure):
+    """apd_points_plane_alignment_t: the fields of apd_points_alignment_t, then the plane figures."""
+    _fields_ = PointsAlignment._fields_ + [("planes_before", C.c_longlong), ("planes_after", C.c_longlong), ("plane_rms_before", C.c_double),
+                                           ("plane_rms_after", C.c_double)]
+
+
+# What Points.align_planes returns: the fields of Alignment, in its shapes, then the usable matches and the plane rms before and
+# after; `stopped` may also be ALIGN_DEGENERATE
+PlaneAlignment = collections.namedtuple("PlaneAlignment", [n for n, _ in PointsPlaneAlignment._fields_])
+ALIGN_DEGENERATE = 3
+
+
 class PointsRegisterOptions(C.Structure):
     """apd_points_register_options."""
     _fields_ = [("trials", C.c_uint), ("seed", C.c_ulonglong), ("inlier_distance", C.c_float), ("edge_ratio", C.c_float), ("min_neighbours", C.c_uint),
@@ -327,7 +346,8 @@ class Points:
     stored ones (apd_points_with_smoothed_positions), likewise: the one step that moves a point.  nearest() gives for every point
     the nearest point of another Points within a radius (apd_points_nearest), score() the precision, recall and F-score of these
     points against another Points at a threshold (apd_points_score), align() the rigid or similarity transform that brings these
-    points onto another Points by ICP within a radius (apd_points_align), transformed() these points moved by such a transform
+    points onto another Points by ICP within a radius (apd_points_align), align_planes() the rigid one onto the other's tangent
+    planes (apd_points_align_planes), transformed() these points moved by such a transform
     (apd_points_transformed), features() every point's FPFH descriptor from the stored normals (apd_points_features),
     match_features() the point of another Points with the nearest descriptor (apd_points_match_features), register() the transform
     that brings these points onto another Points from any start, by RANSAC over those matches (apd_points_register), and read_ply() makes a Points of a PLY file, a ground truth for instance (apd_points_read_ply).
@@ -666,7 +686,7 @@ class Points:
         (p_within of n_p), recall the share of `truth` that has one of these within it (q_within of n_q), fscore their harmonic
         mean, mean_p and mean_q the mean distances of those that have one (contract C17; nearest() with radius = threshold in
         both directions).  Nearest-neighbour precision and recall at one threshold: register() gives a registration from any start
-        and align() and transformed() refine it first, but there is no cropping volume, no point-to-plane refinement and no
+        and align(), align_planes() and transformed() refine it first, but there is no cropping volume and no
         occlusion-aware evaluation as ETH3D's: scores compare with each other.  Computed on these points' device."""
         if not self._p:
             raise ApdError("Points.score: the points are closed")
@@ -706,15 +726,43 @@ class Points:
         return Alignment(out.scale, np.array(out.rotation, np.float64).reshape(3, 3), np.array(out.translation, np.float64), out.matched_before,
                          out.matched_after, out.rms_before, out.rms_after, out.steps, out.stopped)
 
+    def align_planes(self, other, radius, origin=None, iterations=16, tolerance=1e-6):
+        """apd_points_align_planes: PlaneAlignment(the fields of Alignment, planes_before, planes_after, plane_rms_before,
+        plane_rms_after) -- the rigid transform x' = rotation @ x + translation that brings these points onto the tangent planes of
+        `other` (a Points with normals; with_estimated_normals() makes them) by point-to-plane ICP (contract C20): per step every
+        point is matched as in align(), the matches whose normal has a finite length > 0 are usable, and the small motion that
+        brings the points closest to the planes through their matches is solved from the 6 x 6 normal equations.  Prefer it to
+        align() once a start within about `radius` exists and `other` has normals: it slides along the surface where align()
+        settles on the sampling offset.  It ends as align() does, with ALIGN_TOO_FEW also for fewer than 6 usable matches, or with
+        stopped == ALIGN_DEGENERATE when the matched geometry does not constrain every motion (a plane, a cylinder along its
+        axis, a sphere about its centre): the steps taken until then are returned.  scale is 1.0; rms_* are the point rms,
+        plane_rms_* the rms distance to the planes over the planes_* usable matches.  Nothing is moved: transformed() does that.
+        Computed on these points' device."""
+        if not self._p:
+            raise ApdError("Points.align_planes: the points are closed")
+        if not isinstance(other, Points) or not other._p:
+            raise ApdError("Points.align_planes: the other points are closed or not a Points")
+        if not 0 <= int(iterations) <= 0xFFFFFFFF:
+            raise ValueError("Points.align_planes: %r iterations, not in 0 .. 2^32 - 1" % (iterations,))
+        L = lib()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        options, out = PointsAlignPlanesOptions(int(iterations), float(tolerance)), PointsPlaneAlignment()
+        rc = L.apd_points_align_planes(self._p, other._p, float(radius), org, C.byref(options), C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return PlaneAlignment(out.scale, np.array(out.rotation, np.float64).reshape(3, 3), np.array(out.translation, np.float64), out.matched_before,
+                              out.matched_after, out.rms_before, out.rms_after, out.steps, out.stopped, out.planes_before, out.planes_after,
+                              out.plane_rms_before, out.plane_rms_after)
+
     def transformed(self, scale, rotation=None, translation=None):
         """apd_points_transformed: these points in their order with xyz replaced by scale * rotation @ x + translation and normal by
         rotation @ n (not scaled, not renormalised), each component as (float)(((m0 x + m1 y) + m2 z) + t) in binary64, and every
-        other array and the lists as they are: transformed(alignment) with what align() or register() returned, or transformed(scale, rotation,
+        other array and the lists as they are: transformed(alignment) with what align(), align_planes() or register() returned, or transformed(scale, rotation,
         translation) with a positive scale, a rotation (3 x 3, row-major, orthonormal to 1e-6) and a translation.  A merged object
         gives a merged object.  Computed on these points' device; the result lives where they live."""
         if not self._p:
             raise ApdError("Points.transformed: the points are closed")
-        if isinstance(scale, (Alignment, Registration)):
+        if isinstance(scale, (Alignment, PlaneAlignment, Registration)):
             if rotation is not None or translation is not None:
                 raise TypeError("Points.transformed: an Alignment or a Registration, or scale, rotation and translation")
             scale, rotation, translation = scale.scale, scale.rotation, scale.translation

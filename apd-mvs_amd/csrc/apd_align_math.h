@@ -216,6 +216,35 @@ inline void align_rotate(double A[4][4], double V[4][4], int p, int q)
     }
 }
 
+// The quaternion (w, x, y, z) divided by its length, when that is > 0.0 (contract C18, step 4)
+inline void align_unit_quaternion(double &w, double &x, double &y, double &z)
+{
+    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
+    const double len = sqrt(((ww + xx) + yy) + zz);
+    if (len > 0.0) {
+        w = w / len;
+        x = x / len;
+        y = y / len;
+        z = z / len;
+    }
+}
+
+// The nine expressions of contract C18, step 4: R, row-major, from the unit quaternion (w, x, y, z)
+inline void align_rotation_of(double w, double x, double y, double z, double R[9])
+{
+    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
+    const double xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+    R[0] = (ww + xx) - (yy + zz);
+    R[1] = 2.0 * (xy - wz);
+    R[2] = 2.0 * (xz + wy);
+    R[3] = 2.0 * (xy + wz);
+    R[4] = (ww - xx) + (yy - zz);
+    R[5] = 2.0 * (yz - wx);
+    R[6] = 2.0 * (xz - wy);
+    R[7] = 2.0 * (yz + wx);
+    R[8] = (ww - xx) - (yy - zz);
+}
+
 // The step from the means (pm, then qm) and the ten sums of pass 2 (S[9] > 0).  sweeps (may be null): the sweeps taken;
 // quaternion (may be null): w, x, y, z as the rotation was expanded from them
 inline AlignTransform align_solve(const double mean[6], const double S[kAlignSums2], bool with_scale, unsigned *sweeps = nullptr,
@@ -273,32 +302,15 @@ inline AlignTransform align_solve(const double mean[6], const double S[kAlignSum
         y = -y;
         z = -z;
     }
-    const double ww0 = w * w, xx0 = x * x, yy0 = y * y, zz0 = z * z;
-    const double len = sqrt(((ww0 + xx0) + yy0) + zz0);
-    if (len > 0.0) {
-        w = w / len;
-        x = x / len;
-        y = y / len;
-        z = z / len;
-    }
+    align_unit_quaternion(w, x, y, z);
     if (quaternion) {
         quaternion[0] = w;
         quaternion[1] = x;
         quaternion[2] = y;
         quaternion[3] = z;
     }
-    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
-    const double xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
     AlignTransform step;
-    step.R[0] = (ww + xx) - (yy + zz);
-    step.R[1] = 2.0 * (xy - wz);
-    step.R[2] = 2.0 * (xz + wy);
-    step.R[3] = 2.0 * (xy + wz);
-    step.R[4] = (ww - xx) + (yy - zz);
-    step.R[5] = 2.0 * (yz - wx);
-    step.R[6] = 2.0 * (xz - wy);
-    step.R[7] = 2.0 * (yz + wx);
-    step.R[8] = (ww - xx) - (yy - zz);
+    align_rotation_of(w, x, y, z, step.R);
     if (with_scale) {
         const double r0 = align_row_dot(step.R, 0, S[0], S[3], S[6]);
         const double r1 = align_row_dot(step.R, 1, S[1], S[4], S[7]);

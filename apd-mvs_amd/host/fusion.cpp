@@ -119,7 +119,7 @@ void SetFusionPly(const PlyOptions &ply) { g_ply = ply; }
 
 namespace {
 
-// The cloud of a truth file of --ply-register, --ply-align and --ply-score (apd_points_read_ply into host memory): read once when
+// The cloud of a truth file of --ply-register, --ply-align, --ply-align-planes and --ply-score (apd_points_read_ply into host memory): read once when
 // several name the same file
 struct Truth {
     apd_points_t points = nullptr;
@@ -147,7 +147,7 @@ void write_lines_or_exit(const std::string &to, const std::string &lines)
     }
 }
 
-// What --ply-register, --ply-align and --ply-score report: every figure once in the printed line and once as a `name value` line of
+// What --ply-register, --ply-align, --ply-align-planes and --ply-score report: every figure once in the printed line and once as a `name value` line of
 // the file beside APD.ply
 struct Report {
     std::string line, lines;
@@ -252,6 +252,38 @@ int align_beside(apd_points_t &points, Truth &truth, const path &ply_path)
     return APD_OK;
 }
 
+// --ply-align-planes: replaces the points by themselves moved onto the tangent planes of the cloud of the truth file, whose stored
+// normals are used as they are -- a file without nx ny nz has none that is usable, which gives APD_ALIGN_TOO_FEW and the identity
+// (apd_points_align_planes on the fusion's device, apd_points_transformed by its answer): one line with every field, and the same
+// as `name value` lines in <ply_path>.align_planes
+int align_planes_beside(apd_points_t &points, Truth &truth, const path &ply_path)
+{
+    int st = truth.read(g_ply.planes_truth);
+    const apd_points_align_planes_options options = {g_ply.planes_iterations, 1e-6};
+    apd_points_plane_alignment_t a;
+    st = st != APD_OK ? st : apd_points_align_planes(points, truth.points, g_ply.planes_radius, nullptr, &options, &a);
+    apd_points_t moved = nullptr;
+    st = st != APD_OK ? st : apd_points_transformed(points, a.scale, a.rotation, a.translation, &moved);
+    if (!took(st, points, moved)) {
+        return st;
+    }
+    Report report;
+    report.transform(a.scale, a.rotation, a.translation);
+    report.integer("matched_before", a.matched_before);
+    report.integer("matched_after", a.matched_after);
+    report.real("rms_before", a.rms_before);
+    report.real("rms_after", a.rms_after);
+    report.integer("steps", a.steps);
+    report.integer("stopped", a.stopped);
+    report.integer("planes_before", a.planes_before);
+    report.integer("planes_after", a.planes_after);
+    report.real("plane_rms_before", a.plane_rms_before);
+    report.real("plane_rms_after", a.plane_rms_after);
+    std::cout << "Aligned to planes of " << g_ply.planes_truth << " within " << g_ply.planes_radius;
+    report.write(ply_path.string() + ".align_planes");
+    return APD_OK;
+}
+
 // --ply-score: the points ply_path was written from against the cloud of the truth file (apd_points_score on the fusion's
 // device): one line with the nine fields, and the same as `key value` lines in <ply_path>.score
 int score_beside(apd_points_t points, Truth &truth, const path &ply_path)
@@ -350,6 +382,9 @@ void rework_and_write(apd_points_t &points, int num_views, const apd_camera *cam
     }
     if (st == APD_OK && !o.align_truth.empty()) {
         st = align_beside(points, truth, ply_path);
+    }
+    if (st == APD_OK && !o.planes_truth.empty()) {
+        st = align_planes_beside(points, truth, ply_path);
     }
     st = st != APD_OK ? st : apd_points_write_ply(points, ply_path.string().c_str(), fusion_options().ply_normals);
     std::string err = st != APD_OK ? apd_fusion_last_error() : "";

@@ -162,7 +162,7 @@ void apdhost_wavefront_destroy(void *queue) { delete static_cast<WavefrontQueue 
 
 // The value of a --ply-* flag as the command line reads it (host/ply_options.h), into options that are at their defaults.  0: the
 // value is good, and `fields` holds every option as a `name value` line, the floats as %.9g, the three file names last since they
-// end their lines; 1: it is bad, and `message` holds what the command line is told; -1: no such flag takes a value.
+// end their lines, and for --ply-align-planes its own three fields after them; 1: it is bad, and `message` holds what the command line is told; -1: no such flag takes a value.
 int apdhost_parse_ply_option(const char *flag, const char *value, char *fields, size_t fields_cap, char *message, size_t message_cap)
 {
     if (!FindPlyFlag(flag)) {
@@ -180,6 +180,11 @@ int apdhost_parse_ply_option(const char *flag, const char *value, char *fields, 
              o.smooth_min, o.smooth_iterations, o.normals_radius, o.normals_min, o.render_splat, o.render_tolerance, o.register_radius, o.register_distance,
              o.register_trials, o.register_seed, o.align_radius, o.align_iterations, o.align_scale, o.score_threshold, o.register_truth.c_str(),
              o.align_truth.c_str(), o.score_truth.c_str());
+    if (std::string(flag) == "--ply-align-planes") {   // the fields of a flag are reported when it is the one asked for
+        const size_t used = strlen(fields);
+        snprintf(fields + used, fields_cap - used, "planes_radius %.9g\nplanes_iterations %u\nplanes_truth %s\n", o.planes_radius, o.planes_iterations,
+                 o.planes_truth.c_str());
+    }
     return why.empty() ? 0 : 1;
 }
 

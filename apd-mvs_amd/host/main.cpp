@@ -6,7 +6,8 @@
 //       [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN]
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
 //       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
-//       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-score TRUTH.ply,TAU] [--filtered-maps]
+//       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]]
+//       [--ply-score TRUTH.ply,TAU] [--filtered-maps]
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -72,6 +73,14 @@
 // One line "Aligned to ..." with every field of apd_points_alignment_t is printed -- rotation0 .. rotation8 row-major and
 // translation0 .. translation2 -- and APD.ply.align holds the same as one `name value` line per number, the doubles as %.17g.
 // The value is read from its end, since a file's name may hold commas; a bad one leaves the usage line as all that happens.
+// --ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]: the points that APD.ply holds are moved onto the tangent planes of the
+// vertices of the binary little-endian PLY file TRUTH.ply, which must hold nx ny nz, by point-to-plane ICP within RADIUS
+// (apd_points_read_ply, apd_points_align_planes with ITERATIONS steps at most -- 1 .. 64, 16 without -- and the tolerance 1e-6;
+// apd_points_transformed by its answer).  Applied after --ply-align, which brings the points within RADIUS first, and before
+// --ply-score; TRUTH.ply is read once when several flags name it.  The normals of TRUTH.ply are used as stored and are not
+// estimated here: a file without them has no usable match, and the line then shows stopped 2 and the identity.  One line "Aligned
+// to planes of ..." with every field of apd_points_plane_alignment_t is printed and APD.ply.align_planes holds the same as one
+// `name value` line per number, the doubles as %.17g.  APD.ply.vis keeps its bytes.  The value is read from its end.
 // --ply-score TRUTH.ply,TAU: the points that APD.ply holds are scored against the vertices of the binary little-endian PLY file
 // TRUTH.ply at the threshold TAU (apd_points_read_ply, apd_points_score, on the grid of cell size TAU at the origin): precision is
 // the share of the points that have a vertex of TRUTH.ply within TAU, recall the share of those vertices that have a point within
@@ -397,7 +406,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
@@ -409,6 +418,7 @@ int main(int argc, char **argv)
                         "  --ply-render-vis SPLAT,TOL: APD.ply.vis (implies --ply-vis) lists per point the views that see it when the points of APD.ply are drawn into every view with a z-buffer, each over the (2 SPLAT + 1)^2 pixels around its own (SPLAT 0 .. 8), within TOL times the nearest depth at its pixel; after every other --ply-* flag but --ply-register, --ply-align and --ply-score.\n"
                         "  --ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]: the points of APD.ply are moved onto the vertices of the binary PLY file TRUTH.ply from any start, at a scale that is about right: FPFH descriptors of the stored normals at RADIUS, their mutual matches, TRIALS (1 .. 65536, default 4096) RANSAC trials keyed by SEED (default 0) with inliers within DISTANCE, a refit; prints the transform and writes it to APD.ply.register; after every other --ply-* flag but --ply-align and --ply-score, which work on the moved points; APD.ply.vis is unchanged.\n"
                         "  --ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]: the points of APD.ply are moved onto the vertices of the binary PLY file TRUTH.ply by point-to-point ICP within RADIUS, at most ITERATIONS (1 .. 64, default 16) steps, rigid or with `scale` a similarity; prints the transform and writes it to APD.ply.align; after every other --ply-* flag but --ply-score, APD.ply.vis is unchanged.\n"
+                        "  --ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]: the points of APD.ply are moved onto the tangent planes of the vertices of the binary PLY file TRUTH.ply, which needs nx ny nz (its normals are used as stored, not estimated), by point-to-plane ICP within RADIUS, at most ITERATIONS (1 .. 64, default 16) steps, rigid; prints the transform and writes it to APD.ply.align_planes; after --ply-align and before --ply-score, APD.ply.vis is unchanged.\n"
                         "  --ply-score TRUTH.ply,TAU: prints, and writes to APD.ply.score, the precision, recall and F-score of the points of APD.ply against the vertices of the binary PLY file TRUTH.ply at the threshold TAU: the share of each cloud that has a point of the other within TAU; after every other --ply-* flag, --ply-align included (it then scores the aligned points, and TRUTH.ply is read once when both name it), APD.ply keeps its bytes.\n");
         return EXIT_FAILURE;
     }

@@ -10,8 +10,8 @@
 #include <string>
 #include <vector>
 
-// The steps are applied in the order of the fields: mean, voxel, stat, radius, component, smooth, normals, render, register, align;
-// APD.ply is then written, and score comes last.
+// The steps are applied in the order of the fields: mean, voxel, stat, radius, component, smooth, normals, render, register, align, align
+// to planes; APD.ply is then written, and score comes last.
 struct PlyOptions {
     bool vis = false;                 // --ply-vis: APD/APD.ply.vis beside APD.ply (apd_points_write_vis)
     bool mean = false;                // --ply-mean: APD.ply (and APD.ply.vis) of the points averaged over their agreeing views (apd_points_average)
@@ -39,6 +39,9 @@ struct PlyOptions {
     float align_radius = 0.0f;        // within RADIUS (apd_points_align, apd_points_transformed): one printed line and APD.ply.align; empty: off
     unsigned align_iterations = 16;
     bool align_scale = false;
+    std::string planes_truth;         // --ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]: the points of APD.ply moved onto the tangent planes of the cloud of
+    float planes_radius = 0.0f;       // TRUTH.ply, which must hold nx ny nz, by point-to-plane ICP within RADIUS (apd_points_align_planes,
+    unsigned planes_iterations = 16;  // apd_points_transformed): one printed line and APD.ply.align_planes; empty: off
     std::string score_truth;          // --ply-score TRUTH.ply,TAU: the points of APD.ply scored against the cloud of TRUTH.ply at threshold TAU
     float score_threshold = 0.0f;     // (apd_points_score): one printed line and APD.ply.score; empty: off
 
@@ -46,7 +49,8 @@ struct PlyOptions {
     bool from_points() const
     {
         return mean || voxel > 0.0f || stat_radius > 0.0f || radius > 0.0f || component_radius > 0.0f || smooth_radius > 0.0f || normals_radius > 0.0f ||
-               render_splat >= 0 || !register_truth.empty() || !align_truth.empty() || !score_truth.empty();
+               render_splat >= 0 || !register_truth.empty() || !align_truth.empty() || !planes_truth.empty() ||
+               !score_truth.empty();
     }
 };
 
@@ -236,6 +240,24 @@ inline const PlyFlag *FindPlyFlag(const std::string &name)
              o.align_radius = r;
              o.align_iterations = (unsigned)iterations;
              o.align_scale = scale;
+             return true;
+         }},
+        {"--ply-align-planes", "TRUTH.ply,RADIUS[,ITERATIONS], a file with nx ny nz, a positive number and a count of 1 .. 64",
+         [](const std::string &value, PlyOptions &o) {
+             // read from the right, as --ply-align: [,ITERATIONS] when what stands before it is a radius too, then ,RADIUS
+             std::vector<std::string> t = Split(value, 2, true);
+             float r = 0.0f;
+             unsigned long long iterations = 16;
+             if (t.empty() || !Count(t[2], 1, 64, iterations) || !Radius(t[1], r)) {
+                 iterations = 16;
+                 t = Split(value, 1, true);
+                 if (t.empty() || !Radius(t[1], r)) {
+                     return false;
+                 }
+             }
+             o.planes_truth = t[0];
+             o.planes_radius = r;
+             o.planes_iterations = (unsigned)iterations;
              return true;
          }},
         {"--ply-score", "TRUTH.ply,TAU, a file and a positive number",

@@ -552,7 +552,7 @@ def average_points(scene, results, points, device=0):
 
 def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=None, variant="eth", options=None, return_points=False,
          vis_path=None, average=False, voxel=None, voxel_origin=None, radius_filter=None, stat_filter=None, component_filter=None,
-         estimate_normals=None, render_visibility=None, smooth=None, score=None, align=None, register=None):
+         estimate_normals=None, render_visibility=None, smooth=None, score=None, align=None, register=None, align_planes=None):
     """RunFusion (APD.cpp:826-977) on the gathered maps: consistency check and merge into a binary PLY on GPU `device`
     (apd_fuse_views, csrc/apd_fusion.hip).  variant: "eth" (RunFusion), "tat_intermediate" or "tat_advanced" (the Tanks and
     Temples loops RunFusion_TAT_Intermediate / RunFusion_TAT_advanced, APD.cpp:979-1296, csrc/apd_fusion_tat.hip; they ignore
@@ -567,8 +567,8 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     then be None and no file is written.  vis_path: also write COLMAP's fused.ply.vis of the same fusion there (per point the
     views that see it, as indices of the scene's views; Points.write_vis), with or without a PLY file or the points.
     The options below rework the fused points.  They are applied in this order, each to what the ones before it have produced:
-    average, voxel, stat_filter, radius_filter, component_filter, smooth, estimate_normals, render_visibility, register, align; score
-    comes after all of them.  With any of them but score alone, the file (written by Points.write_ply, with normals when the options
+    average, voxel, stat_filter, radius_filter, component_filter, smooth, estimate_normals, render_visibility, register, align, align_planes;
+    score comes after all of them.  With any of them but score alone, the file (written by Points.write_ply, with normals when the options
     say ply_normals), the returned points, the .vis file and the count returned are those of the last step's points.
     average: the mean geometry (average_points): positions and normals are means over the agreeing views, and a source that did
     not contribute is no longer listed.
@@ -599,6 +599,10 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     -- positions and normals; the .vis file is what it is without the option, since moving changes no list -- and the Alignment
     is returned as one more value after the count and the points and before the score: (count, Alignment), (count, Points,
     Alignment), (count, Points, Alignment, Score).
+    align_planes: (truth, radius[, iterations]) -- Points.align_planes(truth, radius, iterations=iterations) (16 iterations unless
+    given) -- point-to-plane ICP onto the STORED normals of `truth`, the refinement to prefer once `register` or `align` has
+    brought the points within about a radius -- and Points.transformed by its answer, as `align` moves them; the PlaneAlignment is
+    returned as one more value after the Alignment and before the Score.
     score: (truth, threshold) -- changes no point nor a byte of a file: Points.score(truth, threshold) of the final points against
     `truth` (a Points: Points.read_ply of a ground truth, or another fusion's), the precision, recall and F-score at the threshold,
     returned as one more value after the others: (count, Score), or (count, Points, Score) with return_points.  With `align` the
@@ -614,7 +618,7 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
     def kept_by(name, method, *args):   # a step whose method returns (new points, figures..)
         steps.append((name, lambda p: (getattr(p, method)(*args)[0], None)))
 
-    def moved_by(method, *args, **kw):  # register, align: the transform the method finds, and the points moved by it
+    def moved_by(method, *args, **kw):  # register, align, align_planes: the transform the method finds, and the points moved by it
         def step(p):
             found = getattr(p, method)(*args, **kw)
             return p.transformed(found), found
@@ -622,6 +626,12 @@ def fuse(scene, results, ply_path, device=0, colour_images=None, block_masks=Non
 
     if score is not None:
         truth, threshold = score
+    if align_planes is not None:
+        onto, radius, *rest = align_planes
+        if len(rest) > 1:
+            raise ValueError("fuse: align_planes=(truth, radius[, iterations]), not %d values" % len(align_planes))
+        iterations, = (rest + [16][len(rest):])
+        moved_by("align_planes", onto, radius, iterations=iterations)
     if align is not None:
         onto, radius, *rest = align
         if len(rest) > 2:

@@ -762,6 +762,51 @@ typedef struct {
 int apd_points_align(apd_points_t p, apd_points_t q, float radius, const float *origin3, const apd_points_align_options *opt,
                      apd_points_alignment_t *out);
 int apd_points_transformed(apd_points_t p, double scale, const double *rotation9, const double *translation3, apd_points_t *out);
+/* Alignment to another cloud's tangent planes: point-to-plane ICP, the refinement to prefer over apd_points_align once a start
+ * within about a radius exists and q carries normals.  A fused cloud and a laser scan sample the same surfaces at different
+ * points: point-to-point ICP pulls every point towards the nearest SAMPLE, converges slowly along the surface and settles with
+ * the sampling offset as its residual; this call minimises the distances to the planes through the matched points of q
+ * perpendicular to q's STORED normals, which lets p slide along the surface.  A q without normals gets them from
+ * apd_points_with_estimated_normals first.  Rigid only.  IEEE operations in the order given (contract C20, DESIGN.md;
+ * csrc/apd_align_plane_math.h), binary64 with + - * / and sqrt alone.
+ *   Step k, matches, the total and the move: those of apd_points_align.  Its sums of pass 1 give m, the mean qm of the matches
+ *   and the point rms, as there.
+ *   Sums.  A matched point is usable when its match's normal n has a squared length, in binary64, that is finite and > 0; u is n
+ *   over its length, and its sign plays no part.  With c = qm, x = p - c, y = q - c, a = x cross u, g = (a, u) and
+ *   r = (x - y) . u: the 21 sums of g_i g_j (i <= j), the 6 of g_i r, those of r^2, of 1 (m_plane) and of |x|^2, through the same
+ *   tree over chunks of 256.  The plane rms is sqrt(sum r^2 / m_plane).
+ *   Solve.  (sum g g^T) z = -(sum g r) for z = (omega, tau) by LDL^T without pivoting, in binary64 on the host.  The geometry is
+ *   degenerate when a pivot d_j fails d_j > 2^-20 * bound_j, bound_j = sum |x|^2 for the three rotations and m_plane for the
+ *   three translations -- the largest value the entry can have: a plane, a cylinder along its axis, a sphere about its centre
+ *   do not constrain every motion, and no step is invented for them.  The rotation is that of the quaternion
+ *   (1, omega / 2) normalised, about c; the translation c + tau - R c.
+ *   Stop.  After opt->iterations steps (APD_ALIGN_ITERATIONS); before step k when m < 3 or m_plane < 6 (APD_ALIGN_TOO_FEW); when
+ *   k > 0 and |rms_k - rms_(k-1)| <= opt->tolerance * rms_(k-1), rms the point rms (APD_ALIGN_CONVERGED); when the solve is
+ *   degenerate or a component of z not finite (APD_ALIGN_DEGENERATE): the total of the steps before it is returned.
+ * *out begins with the fields of apd_points_alignment_t in their order and layout (scale is 1.0; rms_* are the point rms); then the
+ * usable matches and the plane rms before any step and under the returned transform (0 and 0.0 when nothing is matched).  It
+ * moves nothing: apd_points_transformed applies the answer.  opt NULL: 16 iterations, tolerance 1e-6.  Computed on p's device, on
+ * its null stream, whatever memory p is in; a host-resident q goes up for the call, positions and normals; a device-resident q must
+ * live on that device.  There is no host path.  p and q may be the same object.  When either has no points the answer is the
+ * identity, APD_ALIGN_TOO_FEW and 0 steps and no device is touched.  Not here: a cropping volume, ETH3D's occlusion-aware
+ * evaluation, robust kernels (every usable match weighs the same), the normals of p (only q's are read).
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_align_planes: ..." (apd_fusion_last_error): what
+ * apd_points_align refuses.  *out is untouched when the call fails. */
+enum { APD_ALIGN_DEGENERATE = 3 };
+typedef struct {
+    unsigned iterations;
+    double tolerance;
+} apd_points_align_planes_options;
+typedef struct {
+    double scale, rotation[9], translation[3];
+    long long matched_before, matched_after;
+    double rms_before, rms_after;
+    int steps, stopped;
+    long long planes_before, planes_after;
+    double plane_rms_before, plane_rms_after;
+} apd_points_plane_alignment_t;
+int apd_points_align_planes(apd_points_t p, apd_points_t q, float radius, const float *origin3, const apd_points_align_planes_options *opt,
+                            apd_points_plane_alignment_t *out);
 /* Global registration to another cloud: the first step of "register, refine with ICP, score" for a cloud that stands in an
  * arbitrary frame relative to the other, at a scale that is already about right.  FPFH descriptors from the STORED normals
  * (apd_points_with_estimated_normals gives a cloud that has none its normals), the nearest descriptor of the other cloud for
@@ -798,7 +843,7 @@ int apd_points_transformed(apd_points_t p, double scale, const double *rotation9
  * the host for the trials; of the trials only the admitted transforms go up and the counts come down.  When either object has no
  * points the answer is the identity and APD_REGISTER_TOO_FEW_MATCHES and no device is touched.
  * The cost of matching is the product of the two numbers of descriptors: registration is done on a thinned cloud
- * (apd_points_merge_voxels).  Not here: a cropping volume, point-to-plane refinement, ETH3D's occlusion-aware evaluation.
+ * (apd_points_merge_voxels).  Not here: a cropping volume, ETH3D's occlusion-aware evaluation.
  * Refused with APD_ERR_INVALID before any device is touched, message "apd_points_features: ...", "apd_points_match_features:
  * ..." or "apd_points_register: ..." (apd_fusion_last_error): what apd_points_neighbour_counts refuses for either object, a
  * min_neighbours < 3, trials outside 1 .. 65536, an inlier_distance that is not positive and finite with such a square, an
