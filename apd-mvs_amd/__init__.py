@@ -219,6 +219,19 @@ def lib():
     L.apd_sort_tile_sizes.argtypes = [ipp, ipp]
     L.apd_sort_tile_sizes.restype = None
     L.apd_points_destroy.argtypes = [C.c_void_p]
+    L.apd_volume_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int,
+                                    C.POINTER(C.c_void_p)]
+    L.apd_volume_destroy.argtypes = [C.c_void_p]
+    L.apd_volume_integrate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, fpp, fpp, C.c_int, C.POINTER(C.c_float), C.c_int]
+    L.apd_volume_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.apd_volume_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.apd_volume_extract_mesh.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.apd_volume_view_chunk.argtypes = []
+    L.apd_mesh_counts.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.apd_mesh_has_colour.argtypes = [C.c_void_p]
+    L.apd_mesh_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.apd_mesh_write_ply.argtypes = [C.c_void_p, C.c_char_p]
+    L.apd_mesh_destroy.argtypes = [C.c_void_p]
     L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     _lib = L
     return L
@@ -996,6 +1009,179 @@ class Points:
         if self._p:
             lib().apd_points_destroy(self._p)
             self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Mesh:
+    """An indexed triangle mesh (apd_mesh_t) as Volume.extract_mesh() makes it: vertices float32 [n, 3], colours uint8 [n, 3] (blue,
+    green, red; None for a volume without colour) and faces int32 [m, 3], numpy arrays that are copies and outlive the object;
+    write_ply() writes the library's file (apd_mesh_write_ply).  A mesh may be empty."""
+
+    def __init__(self, handle):
+        L = lib()
+        self._m = handle
+        nv, nf = C.c_longlong(0), C.c_longlong(0)
+        rc = L.apd_mesh_counts(handle, C.byref(nv), C.byref(nf))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        self.vertices, self.faces = np.zeros((nv.value, 3), np.float32), np.zeros((nf.value, 3), np.int32)
+        self.colours = np.zeros((nv.value, 3), np.uint8) if L.apd_mesh_has_colour(handle) else None
+        if nv.value or nf.value:
+            rc = L.apd_mesh_download(handle, C.c_void_p(self.vertices.ctypes.data), None if self.colours is None else C.c_void_p(self.colours.ctypes.data),
+                                     C.c_void_p(self.faces.ctypes.data))
+            if rc != 0:
+                raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+
+    def write_ply(self, path):
+        """apd_mesh_write_ply: binary little-endian, x y z float (and red green blue uchar), then the faces as lists of three ints.
+        Points.read_ply reads the file back as its vertices."""
+        if not self._m:
+            raise ApdError("Mesh.write_ply: the mesh is closed")
+        L = lib()
+        rc = L.apd_mesh_write_ply(self._m, os.fspath(path).encode())
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+
+    def close(self):
+        if self._m:
+            lib().apd_mesh_destroy(self._m)
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Volume:
+    """A truncated signed distance volume on GPU `device` (apd_volume_t; arithmetic contract C21): dims = (nx, ny, nz) samples, sample
+    (i, j, k) at origin + (i, j, k) * voxel with the linear index i + nx * (j + ny * k); per sample a distance in units of `trunc`,
+    clamped above at 1, and a weight that saturates at max_weight; with colour=True also blue, green, red and a colour weight.
+    integrate() adds views, extract_mesh() gives the marching-tetrahedra Mesh of the zero level, state() / set_state() copy the
+    samples to and from numpy.  Making one touches no device; its memory (8 bytes a sample, 24 with colour) is allocated by the
+    first call that needs it."""
+
+    def __init__(self, dims, origin, voxel, trunc, max_weight=64.0, colour=False, device=0):
+        L = lib()
+        nx, ny, nz = [int(d) for d in dims]
+        out = C.c_void_p()
+        rc = L.apd_volume_create(int(device), nx, ny, nz, (C.c_float * 3)(*[float(x) for x in origin]), float(voxel), float(trunc), float(max_weight),
+                                 int(bool(colour)), C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        self._v = out
+        self.dims, self.origin = (nx, ny, nz), np.array([float(x) for x in origin], np.float32)
+        self.voxel, self.trunc, self.max_weight = np.float32(voxel), np.float32(trunc), np.float32(max_weight)
+        self.colour, self.device = bool(colour), int(device)
+
+    @classmethod
+    def around(cls, lo, hi, voxel, trunc, margin=None, **kw):
+        """A Volume whose samples cover the box lo .. hi grown by `margin` (trunc unless given) on every side: origin = lo - margin
+        in binary32, and per axis the fewest samples, at least 2, whose last one is at or past hi + margin."""
+        margin = np.float32(trunc if margin is None else margin)
+        lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+            raise ValueError("Volume.around: a box from %r to %r" % (lo.tolist(), hi.tolist()))
+        origin = (lo - margin).astype(np.float32)
+        extent = ((hi + margin) - origin).astype(np.float64)
+        dims = np.maximum(2, np.ceil(extent / float(np.float32(voxel))).astype(np.int64) + 1)
+        return cls(tuple(int(d) for d in dims), origin, voxel, trunc, **kw)
+
+    @property
+    def samples(self):
+        return self.dims[0] * self.dims[1] * self.dims[2]
+
+    def integrate(self, cameras, depths, images=None, weights=None, maps_on_device=False):
+        """apd_volume_integrate: the views, in order, into the volume.  cameras: a ctypes array or a sequence of Camera whose K and
+        width / height are those of the maps; depths: per view float32 [height, width]; images: per view float32 [height, width] or
+        [height, width, 3] (blue, green, red), for a volume with colour; weights: per view, 1 unless given.  numpy arrays, or with
+        maps_on_device torch tensors on the volume's device."""
+        if not self._v:
+            raise ApdError("Volume.integrate: the volume is closed")
+        L = lib()
+        V = len(cameras)
+        if len(depths) != V or (images is not None and len(images) != V) or (weights is not None and len(weights) != V):
+            raise ValueError("Volume.integrate: %d cameras, %d depth maps%s%s" % (V, len(depths), "" if images is None else ", %d images" % len(images),
+                                                                                "" if weights is None else ", %d weights" % len(weights)))
+        cams = cameras if isinstance(cameras, C.Array) else (Camera * max(V, 1))(*[Camera.from_buffer_copy(c) for c in cameras])
+
+        def prepared(a):
+            if maps_on_device:
+                import torch
+                if not hasattr(a, "data_ptr") or a.device != torch.device("cuda", self.device):
+                    raise ValueError("Volume.integrate: with maps_on_device every map is a torch tensor on cuda:%d, not %s" % (
+                        self.device, "on %s" % a.device if hasattr(a, "device") else type(a).__name__))
+                return a.to(torch.float32).contiguous()
+            return np.ascontiguousarray(a, np.float32)
+
+        deps = [prepared(d) for d in depths]
+        imgs = None if images is None else [prepared(m) for m in images]
+        channels = 1
+        for s in range(V):
+            shape = (int(cams[s].height), int(cams[s].width))
+            if shape[0] > 0 and shape[1] > 0 and tuple(deps[s].shape) != shape:   # a camera without pixels is the library's to refuse
+                raise ValueError("Volume.integrate: view %d has a depth map of %r and a camera of %r" % (s, tuple(deps[s].shape), shape))
+            if imgs is not None:
+                channels = 3 if imgs[s].ndim == 3 else 1
+                if tuple(imgs[s].shape) != tuple(deps[s].shape) + ((3,) if channels == 3 else ()) or (imgs[s].ndim == 3) != (imgs[0].ndim == 3):
+                    raise ValueError("Volume.integrate: images are [H, W] or [H, W, 3] at the size of the depth maps, all alike")
+        if maps_on_device:
+            import torch
+            torch.cuda.synchronize(torch.device("cuda", self.device))  # the tensors' producers, before the library's stream reads them
+        table = lambda arrs: None if arrs is None else (C.c_void_p * max(V, 1))(*[_ptr(a) for a in arrs])
+        w = None if weights is None else (C.c_float * max(V, 1))(*[float(x) for x in weights])
+        rc = L.apd_volume_integrate(self._v, V, C.byref(cams), table(deps), table(imgs), channels, w, int(bool(maps_on_device)))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+
+    def state(self):
+        """apd_volume_download: (tsdf float32 [samples], weight float32 [samples], colour float32 [samples, 4] or None), in linear
+        order."""
+        if not self._v:
+            raise ApdError("Volume.state: the volume is closed")
+        L = lib()
+        tsdf, weight = np.zeros(self.samples, np.float32), np.zeros(self.samples, np.float32)
+        colour = np.zeros((self.samples, 4), np.float32) if self.colour else None
+        rc = L.apd_volume_download(self._v, C.c_void_p(tsdf.ctypes.data), C.c_void_p(weight.ctypes.data),
+                                   None if colour is None else C.c_void_p(colour.ctypes.data))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return tsdf, weight, colour
+
+    def set_state(self, tsdf, weight, colour=None):
+        """apd_volume_upload: the samples from arrays in the shapes of state(); None leaves an array as it is."""
+        if not self._v:
+            raise ApdError("Volume.set_state: the volume is closed")
+        L = lib()
+        arrays = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (tsdf, weight, colour)]
+        for a, width in zip(arrays, (1, 1, 4)):
+            if a is not None and a.size != self.samples * width:
+                raise ValueError("Volume.set_state: an array of %d elements for %d samples" % (a.size, self.samples))
+        rc = L.apd_volume_upload(self._v, *[None if a is None else C.c_void_p(a.ctypes.data) for a in arrays])
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+
+    def extract_mesh(self):
+        """apd_volume_extract_mesh: the Mesh of the volume as it is now."""
+        if not self._v:
+            raise ApdError("Volume.extract_mesh: the volume is closed")
+        L = lib()
+        out = C.c_void_p()
+        rc = L.apd_volume_extract_mesh(self._v, C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Mesh(out)   # the mesh is the object's from its first line on
+
+    def close(self):
+        if self._v:
+            lib().apd_volume_destroy(self._v)
+            self._v = None
 
     def __del__(self):
         try:

@@ -91,3 +91,12 @@ static __device__ unsigned long long g_weak_stats[8];
 #else
 #define APD_RENDER_LOAD_BEFORE_MIN 1
 #endif
+
+// -DAPD_LAB_VOLUME_LAUNCH_PER_VIEW (tools/volume_time.py --library): apd_volume_integrate of apd_volume.hip launches
+// k_volume_integrate once per view, so that the volume is read and written once per view, instead of once per 16 views with the
+// loop over the views inside the kernel: the form the one-launch loop is measured against.  Same results.
+#ifdef APD_LAB_VOLUME_LAUNCH_PER_VIEW
+#define APD_VOLUME_VIEW_CHUNK 1
+#else
+#define APD_VOLUME_VIEW_CHUNK 16
+#endif

@@ -433,17 +433,18 @@ void RunFusion(const path &dense_folder, const std::vector<Problem> &problems) {
 // indices.  maps: host maps (RunFusionWithMaps) or nullptr with map_cols x map_rows > 0 (the maps are on the device) or
 // nullptr with 0 x 0 (read the files).  for_filter: the inputs of the geometric filter (--filtered-maps) -- no colour image (its
 // size is the grey image's, which the passes have decoded), the weak maps whatever the fusion variant, and no progress lines.
+// with_weak: the weak maps whatever the fusion variant, beside the colour image (--mesh).
 namespace {
 
 // log: where the reference's progress lines go ("Reading image ...", "Fusing image ...", APD.cpp:855, :899); the prefetch worker
 // collects them and RunFusionOnDevice prints them where the reference would, after the passes' own lines.
 bool prepare_fusion_inputs(const path &dense_folder, const std::vector<Problem> &problems, const std::vector<FinalMaps> *maps, int map_cols,
                            int map_rows, std::vector<FusionView> &views, std::vector<std::vector<int>> &sources, unsigned threads = 0,
-                           std::ostream *log = nullptr, bool for_filter = false)
+                           std::ostream *log = nullptr, bool for_filter = false, bool with_weak = false)
 {
     std::ostringstream unheard;
     std::ostream &out = for_filter ? unheard : log ? *log : std::cout;
-    const bool need_weak = for_filter || g_fusion_variant == APD_FUSION_ETH;
+    const bool need_weak = for_filter || with_weak || g_fusion_variant == APD_FUSION_ETH;
     const bool on_device = !maps && map_cols > 0 && map_rows > 0;
     views.assign(problems.size(), FusionView());
     std::unordered_map<int, int> index_of_id;
@@ -779,6 +780,52 @@ void RunFusionOnDevice(FusionPrefetch *f, const std::vector<const float *> &dept
 
 namespace {
 
+// The filter of --filtered-maps and --mesh on the views whose maps are given: the three outputs per view in host memory
+struct Filtered {
+    std::vector<Mat> depth, votes, consistency;
+    std::vector<apd_camera> cams;
+    double ms_setup = 0, ms_views = 0;
+};
+
+void filter_views(const std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const float *const *depths,
+                  const float *const *normals, const uint8_t *const *weaks, const uint8_t *const *blocks, int cols, int rows, int maps_on_device,
+                  Filtered &out)
+{
+    const int V = (int)views.size();
+    out.cams.resize(V);
+    out.depth.resize(V);
+    out.votes.resize(V);
+    out.consistency.resize(V);
+    std::vector<int> rws(V), cls(V), offs(V + 1, 0), idx;
+    std::vector<float *> depth_out(V), consistency_out(V);
+    std::vector<uint8_t *> votes_out(V);
+    for (int i = 0; i < V; ++i) {
+        out.cams[i] = views[i].cam;
+        rws[i] = rows > 0 ? rows : views[i].depth.rows;
+        cls[i] = cols > 0 ? cols : views[i].depth.cols;
+        idx.insert(idx.end(), sources[i].begin(), sources[i].end());
+        offs[i + 1] = (int)idx.size();
+        out.depth[i].create(rws[i], cls[i], MAT_32FC1);
+        out.votes[i].create(rws[i], cls[i], MAT_8UC1);
+        out.consistency[i].create(rws[i], cls[i], MAT_32FC1);
+        depth_out[i] = out.depth[i].ptr<float>();
+        votes_out[i] = out.votes[i].ptr<uint8_t>();
+        consistency_out[i] = out.consistency[i].ptr<float>();
+    }
+    if (idx.empty()) {
+        idx.push_back(0);
+    }
+    apd_fusion_options rule = fusion_options();
+    rule.variant = APD_FUSION_ETH;
+    const int st = apd_filter_views(&rule, g_fusion_device, V, out.cams.data(), depths, normals, weaks, blocks, rws.data(), cls.data(), offs.data(),
+                                    idx.data(), maps_on_device, depth_out.data(), votes_out.data(), consistency_out.data(), 0);
+    if (st != APD_OK) {
+        std::cerr << apd_fusion_last_error() << std::endl;
+        exit(EXIT_FAILURE);
+    }
+    apd_fusion_last_timing(&out.ms_setup, &out.ms_views, nullptr);
+}
+
 // Filters the views whose maps are given (host pointers, or device pointers on the fusion device with maps_on_device; blocks may be
 // null) and writes depths_filtered.dmb, consistency.dmb and votes.bin into every view's result folder.  The rule is the fusion's
 // (--fusion-*); a Tanks and Temples variant has refused those flags, so the filter then runs the defaults.
@@ -788,50 +835,89 @@ void filter_and_write(const std::vector<Problem> &problems, const std::vector<Fu
 {
     const auto t0 = std::chrono::steady_clock::now();
     const int V = (int)views.size();
-    std::vector<apd_camera> cams(V);
-    std::vector<int> rws(V), cls(V), offs(V + 1, 0), idx;
-    std::vector<Mat> depth(V), votes(V), consistency(V);
-    std::vector<float *> depth_out(V), consistency_out(V);
-    std::vector<uint8_t *> votes_out(V);
-    for (int i = 0; i < V; ++i) {
-        cams[i] = views[i].cam;
-        rws[i] = rows > 0 ? rows : views[i].depth.rows;
-        cls[i] = cols > 0 ? cols : views[i].depth.cols;
-        idx.insert(idx.end(), sources[i].begin(), sources[i].end());
-        offs[i + 1] = (int)idx.size();
-        depth[i].create(rws[i], cls[i], MAT_32FC1);
-        votes[i].create(rws[i], cls[i], MAT_8UC1);
-        consistency[i].create(rws[i], cls[i], MAT_32FC1);
-        depth_out[i] = depth[i].ptr<float>();
-        votes_out[i] = votes[i].ptr<uint8_t>();
-        consistency_out[i] = consistency[i].ptr<float>();
-    }
-    if (idx.empty()) {
-        idx.push_back(0);
-    }
-    apd_fusion_options rule = fusion_options();
-    rule.variant = APD_FUSION_ETH;
-    const int st = apd_filter_views(&rule, g_fusion_device, V, cams.data(), depths, normals, weaks, blocks, rws.data(), cls.data(), offs.data(),
-                                    idx.data(), maps_on_device, depth_out.data(), votes_out.data(), consistency_out.data(), 0);
-    if (st != APD_OK) {
-        std::cerr << apd_fusion_last_error() << std::endl;
-        exit(EXIT_FAILURE);
-    }
-    double ms_setup = 0, ms_views = 0;
-    apd_fusion_last_timing(&ms_setup, &ms_views, nullptr);
+    Filtered f;
+    filter_views(views, sources, depths, normals, weaks, blocks, cols, rows, maps_on_device, f);
     for (int i = 0; i < V; ++i) {
         const path &folder = problems[i].result_folder;
         std::filesystem::create_directories(folder);
-        const std::pair<const char *, const Mat *> files[3] = {{"depths_filtered.dmb", &depth[i]}, {"consistency.dmb", &consistency[i]}, {"votes.bin", &votes[i]}};
-        for (const auto &f : files) {
-            if (!WriteBinMat(folder / f.first, *f.second)) {
-                std::cerr << "cannot write " << (folder / f.first).string() << std::endl;
+        const std::pair<const char *, const Mat *> files[3] = {{"depths_filtered.dmb", &f.depth[i]}, {"consistency.dmb", &f.consistency[i]}, {"votes.bin", &f.votes[i]}};
+        for (const auto &file : files) {
+            if (!WriteBinMat(folder / file.first, *file.second)) {
+                std::cerr << "cannot write " << (folder / file.first).string() << std::endl;
                 exit(EXIT_FAILURE);
             }
         }
     }
     std::cout << "Filtered maps of " << V << " views: " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count()
-              << " ms (set-up " << (long long)ms_setup << ", views " << (long long)ms_views << ")" << std::endl;
+              << " ms (set-up " << (long long)f.ms_setup << ", views " << (long long)f.ms_views << ")" << std::endl;
+}
+
+// --mesh: the filter, then the volume over the box of the finite points of ply_path grown by trunc -- origin = lo - trunc and per
+// axis the fewest samples, at least 2, whose last one is at or past hi + trunc, in the arithmetic of the Python binding's
+// Volume.around --, the filtered maps with the views' colour images (3 channels) into it, every view weighing 1, and the mesh
+// into <ply_path>.mesh.  A failure ends the program like every other device error.
+void mesh_and_write(const path &ply_path, const std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const float *const *depths,
+                    const float *const *normals, const uint8_t *const *weaks, const uint8_t *const *blocks, int cols, int rows, int maps_on_device,
+                    float voxel, float trunc)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const int V = (int)views.size();
+    Filtered f;
+    filter_views(views, sources, depths, normals, weaks, blocks, cols, rows, maps_on_device, f);
+    auto failed = [](const std::string &why) {
+        std::cerr << why << std::endl;
+        exit(EXIT_FAILURE);
+    };
+    apd_points_t cloud = nullptr;
+    if (apd_points_read_ply(ply_path.string().c_str(), g_fusion_device, 0, &cloud) != APD_OK) {
+        failed(apd_fusion_last_error());
+    }
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    const float *xyz = apd_points_xyz(cloud);
+    for (long long k = 0; k < apd_points_count(cloud); ++k) {
+        const float *P = xyz + 3 * k;
+        if (std::isfinite(P[0]) && std::isfinite(P[1]) && std::isfinite(P[2])) {
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::min(lo[a], P[a]);
+                hi[a] = std::max(hi[a], P[a]);
+            }
+        }
+    }
+    apd_points_destroy(cloud);
+    if (!(lo[0] <= hi[0])) {
+        failed("--mesh: " + ply_path.string() + " holds no point with a finite position: no box to mesh in");
+    }
+    float origin[3];
+    int dims[3];
+    for (int a = 0; a < 3; ++a) {
+        origin[a] = lo[a] - trunc;
+        const float top = hi[a] + trunc;
+        const float extent = top - origin[a];
+        const double samples = std::ceil((double)extent / (double)voxel) + 1.0;
+        if (!(samples < 2147483648.0)) {
+            failed("--mesh: a voxel of " + std::to_string(voxel) + " gives too many samples in the box of " + ply_path.string());
+        }
+        dims[a] = std::max(2, (int)samples);
+    }
+    std::vector<const float *> filtered(V), images(V);
+    for (int i = 0; i < V; ++i) {
+        filtered[i] = f.depth[i].ptr<float>();
+        images[i] = views[i].image.ptr<float>();
+    }
+    apd_volume_t volume = nullptr;
+    apd_mesh_t mesh = nullptr;
+    const std::string mesh_path = ply_path.string() + ".mesh";
+    long long vertices = 0, faces = 0;
+    if (apd_volume_create(g_fusion_device, dims[0], dims[1], dims[2], origin, voxel, trunc, 64.0f, 1, &volume) != APD_OK ||
+        apd_volume_integrate(volume, V, f.cams.data(), filtered.data(), images.data(), 3, nullptr, 0) != APD_OK ||
+        apd_volume_extract_mesh(volume, &mesh) != APD_OK || apd_mesh_counts(mesh, &vertices, &faces) != APD_OK ||
+        apd_mesh_write_ply(mesh, mesh_path.c_str()) != APD_OK) {
+        failed(apd_fusion_last_error());
+    }
+    apd_mesh_destroy(mesh);
+    apd_volume_destroy(volume);
+    std::cout << "Mesh of " << vertices << " vertices and " << faces << " faces on " << dims[0] << " x " << dims[1] << " x " << dims[2] << " samples in "
+              << mesh_path << ": " << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() << " ms" << std::endl;
 }
 
 }  // namespace
@@ -888,6 +974,68 @@ void RunFilterOnDevice(const path &dense_folder, const std::vector<Problem> &pro
     const int fusion_device = g_fusion_device;
     g_fusion_device = device;
     filter_and_write(problems, views, sources, depths.data(), normals.data(), weaks.data(), owned.empty() ? nullptr : blocks.data(), cols, rows, 1);
+    g_fusion_device = fusion_device;
+    for (void *p : owned) {
+        apd_device_free(device, p);
+    }
+}
+
+// --mesh from the four state files of every view, as RunFusion reads them, after it has written APD.ply
+void RunMesh(const path &dense_folder, const std::vector<Problem> &problems, float voxel, float trunc)
+{
+    std::vector<FusionView> views;
+    std::vector<std::vector<int>> sources;
+    std::ostringstream unheard;
+    if (!prepare_fusion_inputs(dense_folder, problems, nullptr, 0, 0, views, sources, 0, &unheard, false, true)) {
+        exit(EXIT_FAILURE);
+    }
+    const int V = (int)views.size();
+    std::vector<const float *> deps(V), nors(V);
+    std::vector<const uint8_t *> weaks(V), blocks(V, nullptr);
+    bool any_block = false;
+    for (int i = 0; i < V; ++i) {
+        deps[i] = views[i].depth.ptr<float>();
+        nors[i] = views[i].normal.ptr<float>();
+        weaks[i] = views[i].weak.ptr<uint8_t>();
+        if (!views[i].block.empty()) {
+            blocks[i] = views[i].block.ptr<uint8_t>();
+            any_block = true;
+        }
+    }
+    mesh_and_write(dense_folder / path("APD") / path("APD.ply"), views, sources, deps.data(), nors.data(), weaks.data(), any_block ? blocks.data() : nullptr,
+                   0, 0, 0, voxel, trunc);
+}
+
+// The final maps are on `device` (cols x rows each): colour images, cameras and block masks are read here, the masks go up
+void RunMeshOnDevice(const path &dense_folder, const std::vector<Problem> &problems, int device, int cols, int rows,
+                     const std::vector<const float *> &depths, const std::vector<const float *> &normals, const std::vector<const uint8_t *> &weaks,
+                     float voxel, float trunc)
+{
+    std::vector<FusionView> views;
+    std::vector<std::vector<int>> sources;
+    std::ostringstream unheard;
+    if (!prepare_fusion_inputs(dense_folder, problems, nullptr, cols, rows, views, sources, 0, &unheard, false, true)) {
+        exit(EXIT_FAILURE);
+    }
+    const int V = (int)views.size();
+    std::vector<const uint8_t *> blocks(V, nullptr);
+    std::vector<void *> owned;
+    for (int i = 0; i < V; ++i) {
+        if (views[i].block.empty()) {
+            continue;
+        }
+        void *p = nullptr;
+        if (apd_device_malloc(device, (size_t)rows * cols, &p) != APD_OK || apd_device_memcpy(device, p, views[i].block.data(), (size_t)rows * cols) != APD_OK) {
+            std::cerr << "mesh: upload of a block mask failed: " << apd_exchange_last_error() << std::endl;
+            exit(EXIT_FAILURE);
+        }
+        owned.push_back(p);
+        blocks[i] = (const uint8_t *)p;
+    }
+    const int fusion_device = g_fusion_device;
+    g_fusion_device = device;
+    mesh_and_write(dense_folder / path("APD") / path("APD.ply"), views, sources, depths.data(), normals.data(), weaks.data(),
+                   owned.empty() ? nullptr : blocks.data(), cols, rows, 1, voxel, trunc);
     g_fusion_device = fusion_device;
     for (void *p : owned) {
         apd_device_free(device, p);

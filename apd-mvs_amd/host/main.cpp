@@ -7,7 +7,13 @@
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
 //       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
 //       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]]
-//       [--ply-score TRUTH.ply,TAU] [--filtered-maps]
+//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]]
+//
+// --mesh VOXEL[,TRUNC]: besides everything else, APD/APD.ply.mesh: a binary PLY with faces, the marching-tetrahedra mesh of a signed
+// distance volume with samples VOXEL apart and a truncation distance of TRUNC (4 * VOXEL unless given) over the box of the points
+// of APD.ply, integrated from the filtered maps of --filtered-maps (which need not be given) with the views' colours
+// (apd_volume_create, apd_volume_integrate, apd_volume_extract_mesh; RunMesh, host/fusion.cpp).  Every driver takes it; refused
+// with --no-fusion, which leaves no cloud to take the box from.  Without the flag no output changes.
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -197,6 +203,16 @@ bool ParseOptions(int argc, char **argv, Options &o)
             }
         } else if (a == "--filtered-maps") {
             o.filtered_maps = true;
+        } else if (a == "--mesh") {
+            const std::string both = i + 1 < argc ? argv[++i] : "";
+            const std::vector<std::string> t = ply_value::Split(both, 1);
+            float voxel = 0.0f, trunc = 0.0f;
+            if (!ply_value::Radius(t.empty() ? both : t[0], voxel) || (!t.empty() && !ply_value::Radius(t[1], trunc))) {
+                fprintf(stderr, "bad value '%s' of %s: VOXEL[,TRUNC], positive numbers\n", both.c_str(), a.c_str());
+                return false;
+            }
+            o.mesh_voxel = voxel;
+            o.mesh_trunc = t.empty() ? 4.0f * voxel : trunc;
         } else if (a == "--seed") {
             if (!value(o.seed)) return false;
         } else if (a == "--iters") {
@@ -278,6 +294,10 @@ bool ParseOptions(int argc, char **argv, Options &o)
     }
     if (o.fusion_thresholds_set && o.fusion_variant != APD_FUSION_ETH) {
         fprintf(stderr, "--fusion-min-consistent, --fusion-reproj, --fusion-depth, --fusion-angle and --fusion-factors apply to --fusion eth only\n");
+        return false;
+    }
+    if (o.mesh_voxel > 0.0f && o.no_fusion) {
+        fprintf(stderr, "--mesh takes its box from the fused points: not with --no-fusion\n");
         return false;
     }
     o.fusion.variant = o.fusion_variant;
@@ -406,7 +426,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
@@ -558,6 +578,9 @@ int main(int argc, char **argv)
     }
     if (!opt.no_fusion) {
         RunFusion(opt.dense_folder, problems);  // main.cpp:219
+        if (opt.mesh_voxel > 0.0f) {
+            RunMesh(opt.dense_folder, problems, opt.mesh_voxel, opt.mesh_trunc);
+        }
         if (!opt.keep_maps) {                   // main.cpp:220-230
             for (const Problem &p : problems) {
                 for (const char *name : kStateFiles) {

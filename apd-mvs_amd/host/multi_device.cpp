@@ -328,6 +328,7 @@ struct Scheduler {
     void WriteKeptMaps();
     void PrintExchangeSummary();
     void Fuse();
+    void Mesh();
 };
 
 // ---- views: the reference views in pair.txt order, then the source-only images (main.cpp); images, cameras, masks ----
@@ -1028,6 +1029,17 @@ void Scheduler::Filter()
     RunFilterOnDevice(opt.dense_folder, problems, ranks[0].device, W0, H0, d, n, fuse_weak);
 }
 
+// --mesh: from the gathered maps, where they are, after the fusion has written the cloud
+void Scheduler::Mesh()
+{
+    std::vector<const float *> d(V), n(V);
+    for (int v = 0; v < V; ++v) {
+        d[v] = fuse_depth[v].as<float>();
+        n[v] = fuse_normal[v].as<float>();
+    }
+    RunMeshOnDevice(opt.dense_folder, problems, ranks[0].device, W0, H0, d, n, fuse_weak, opt.mesh_voxel, opt.mesh_trunc);
+}
+
 void Scheduler::Fuse()
 {
     std::filesystem::create_directories(opt.dense_folder / "APD");
@@ -1093,6 +1105,9 @@ int RunMultiDevice(const Options &opt, std::vector<Problem> &problems)
         }
         if (!opt.no_fusion) {
             s.Fuse();
+            if (opt.mesh_voxel > 0.0f) {
+                s.Mesh();
+            }
         }
         ms_fusion = stage.lap();
     } catch (const std::exception &e) {

@@ -855,3 +855,81 @@ def filter_maps(scene, results, device=0, block_masks=None, options=None, on_dev
     if rc != 0:
         raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
     return outs
+
+
+def mesh_views(scene, results, colour_images):
+    """What mesh() hands to Volume.integrate of every view besides its filtered depth map: the camera at the size of the maps, with
+    K scaled when the image has another size (RescaleImageAndCamera, APD.cpp:729-750), and the image resampled as fuse() does."""
+    cam_t = type(scene.cameras[0])
+    cams, imgs = [], []
+    for v in range(scene.num_views):
+        h, w = results[v].depth.shape
+        cam = cam_t.from_buffer_copy(scene.cameras[v])
+        img = scene.images[v] if colour_images is None else colour_images[v]
+        if img.shape[:2] != (h, w):
+            sx = np.float32(w) / np.float32(img.shape[1])
+            sy = np.float32(h) / np.float32(img.shape[0])
+            if img.ndim == 3:
+                img = np.stack([np.rint(resize_linear(img[..., k], w, h)) for k in range(3)], -1).astype(np.float32)
+            else:
+                img = np.rint(resize_linear(img, w, h)).astype(np.float32)
+            cam.K[0] = float(np.float32(cam.K[0]) * sx)
+            cam.K[2] = float(np.float32(cam.K[2]) * sx)
+            cam.K[4] = float(np.float32(cam.K[4]) * sy)
+            cam.K[5] = float(np.float32(cam.K[5]) * sy)
+        cam.width, cam.height = w, h
+        cams.append(cam)
+        imgs.append(np.ascontiguousarray(img, np.float32))
+    return cams, imgs
+
+
+def mesh_bounds(bounds):
+    """(lo, hi) float32 [3] of mesh()'s `bounds`: a pair of corners, or a Points whose finite positions give the box."""
+    if hasattr(bounds, "xyz"):
+        xyz = bounds.xyz
+        xyz = np.asarray(xyz.cpu().numpy() if hasattr(xyz, "cpu") else xyz, np.float32).reshape(-1, 3)
+        xyz = xyz[np.isfinite(xyz).all(1)]
+        if len(xyz) == 0:
+            raise ValueError("mesh: the points that should give the box have no finite position")
+        return xyz.min(0), xyz.max(0)
+    lo, hi = bounds
+    return np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+
+
+def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, colour_images=None, block_masks=None, options=None,
+         return_mesh=False):
+    """A surface from the gathered maps: filter_maps(..., on_device=True) leaves every view's consistent depth map on GPU `device`,
+    Volume.integrate fuses them, at each view's depth-map resolution, into a truncated signed distance volume with samples `voxel`
+    apart (apd_volume_integrate, contract C21), and Volume.extract_mesh takes the marching-tetrahedra mesh of its zero level, which
+    is written to ply_path (unless None).  trunc: the truncation distance, 4 * voxel unless given.  bounds: (lo, hi), the corners of
+    the box to cover, or a Points whose box is taken; None: the box of the points fuse(..., return_points=True) makes of the same
+    inputs.  The volume covers the box grown by trunc (Volume.around).  colour_images, block_masks, options: as in fuse() and
+    filter_maps(); the images are resampled as fuse() resamples them and colour the vertices.  Every view weighs 1.
+    Returns (vertices, faces), the counts, or with return_mesh (vertices, faces, Mesh)."""
+    from . import Volume
+    import torch
+    trunc = 4.0 * float(voxel) if trunc is None else trunc
+    if bounds is None:
+        _, points = fuse(scene, results, None, device=device, colour_images=colour_images, block_masks=block_masks, options=options, return_points=True)
+        try:
+            lo, hi = mesh_bounds(points)
+        finally:
+            points.close()
+    else:
+        lo, hi = mesh_bounds(bounds)
+    maps = filter_maps(scene, results, device=device, block_masks=block_masks, options=options, on_device=True)
+    cams, imgs = mesh_views(scene, results, colour_images)
+    dev = torch.device("cuda", int(device))
+    volume = Volume.around(lo, hi, voxel, trunc, colour=True, device=device)
+    try:
+        volume.integrate(cams, [m.depth for m in maps], [torch.from_numpy(a).to(dev) for a in imgs], maps_on_device=True)
+        found = volume.extract_mesh()
+    finally:
+        volume.close()
+    if ply_path is not None:
+        found.write_ply(ply_path)
+    counts = (len(found.vertices), len(found.faces))
+    if return_mesh:
+        return counts + (found,)
+    found.close()
+    return counts

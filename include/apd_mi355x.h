@@ -914,6 +914,72 @@ int apd_points_rendered_visibility(apd_points_t p, int num_views, const apd_came
 void apd_sort_tile_sizes(int *sort_tile, int *scan_tile);
 int apd_points_destroy(apd_points_t p);
 
+/* A surface: a truncated signed distance volume integrated from depth maps -- the filtered maps of apd_filter_views, left on the
+ * device, are the intended input -- and the indexed triangle mesh that marching tetrahedra takes from it.  Every cell is split into
+ * the same six tetrahedra (Kuhn), so neighbouring cells agree on every shared face, no case is ambiguous, and the mesh is
+ * watertight wherever the volume is known.  binary32, IEEE operations in the order given (contract C21, DESIGN.md;
+ * csrc/apd_volume_math.h).
+ *   Grid.  nx x ny x nz samples; sample (i, j, k) has the linear index i + nx * (j + ny * k) and the position
+ *   origin[a] + (float)index_a * voxel: one multiplication, one addition.  Per sample a distance D (initially 1.0f) and a weight W
+ *   (initially 0); with colour also blue, green, red and a colour weight CW (all initially 0).
+ *   Integrate.  A view is a camera (K, R, t, width, height; the other fields are not read), a depth map of height x width floats,
+ *   optionally an image of the same size with 1 or 3 interleaved float channels (blue, green, red, as apd_fuse_views takes them;
+ *   one channel feeds all three) and a weight w > 0.  The sample at P is observed when it is drawn into the camera as
+ *   apd_points_render draws a point (depth d > 0 and finite, c = int(u + 0.5f) and r = int(v + 0.5f) defined and inside the map),
+ *   z = depth[r * width + c] is > 0 and finite, and sdf = z - d >= -trunc.  Then v = sdf / trunc, 1.0f where v > 1.0f;
+ *   a = D * W; b = v * w; s = W + w; D = (a + b) / s; W = s > max_weight ? max_weight : s.  Where also sdf <= trunc each colour
+ *   channel becomes (C * CW + colour * w) / (CW + w) in that operation order, and then CW as W.  The views of a call are applied
+ *   to a sample in the call's order: two calls of k views equal one call of the 2k.  There is no culling.
+ *   Vertices.  A sample is known when W > 0 and inside when known and D < 0 (zero and -0 are outside).  From a sample seven edges
+ *   run, in the directions (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), numbered 0 .. 6, where the upper end exists.
+ *   An edge carries a vertex when both ends are known and exactly one is inside: with fa, pa at the lower end, t = fa / (fa - fb)
+ *   and per component pa + t * (pb - pa); per colour channel ca + t * (cb - ca) where both ends have CW > 0, the colour of the one
+ *   end that has, else 0; clamped to 0 .. 255 (a NaN is 0) and converted by (int)(x + 0.5f).  Vertex ids ascend with
+ *   (linear index * 7 + direction).  No two edges share a vertex: t = 0 gives coincident vertices and triangles without area,
+ *   which are kept.
+ *   Faces.  The cell with lower sample (i, j, k) has the tetrahedra q = 0 .. 5 along the axis permutations xyz, xzy, yxz, yzx,
+ *   zxy, zyx: corners v0 = (0,0,0), v1 = v0 + e_p1, v2 = v1 + e_p2, v3 = (1,1,1).  A tetrahedron with a corner that is not known
+ *   has no faces.  One corner a apart from the others b < c < d: the triangle (e_ab, e_ac, e_ad); two inside a < b and two outside
+ *   c < d: (e_ac, e_ad, e_bd) and (e_ac, e_bd, e_bc); each turned to (first, third, second) where that makes its right-hand normal
+ *   point from inside to outside, which a table fixed at compile time says.  Faces are ordered by cell index
+ *   i + (nx - 1) * (j + (ny - 1) * k), then q, then as above.
+ * apd_volume_create checks its arguments and touches no device: the volume's memory -- 8 bytes a sample, 24 with colour -- is
+ * allocated on `device` by the first call that needs it.  apd_volume_integrate: depths and images (may be NULL: no colour is
+ * updated) are num_views pointers each, host memory, or device memory on the volume's device with maps_on_device; weights NULL:
+ * all 1.  apd_volume_download / apd_volume_upload copy D (tsdf), W (weight) and the four colour floats of every sample
+ * (colour4) to or from host arrays in linear order; any may be NULL, not all: the way to save a volume, and to extract from any
+ * field.  apd_volume_extract_mesh: *mesh is a new mesh on the volume's device, released with apd_mesh_destroy; a volume without a
+ * crossing edge gives a mesh of 0 vertices and 0 faces.  Extraction takes 26 bytes a sample of scratch memory for the length of
+ * the call.  apd_mesh_download: xyz takes 3 floats and bgr (a mesh with colour only) 3 bytes per vertex, faces 3 ints per face, host
+ * memory; any may be NULL, not all.  apd_mesh_write_ply: binary little-endian, `vertex` with x y z float and, with colour, red green
+ * blue uchar, then `face` with `property list uchar int vertex_indices`; apd_points_read_ply reads such a file back as its
+ * vertices.  apd_volume_view_chunk: the views one kernel launch of apd_volume_integrate takes, for tests that go past it.
+ * Everything is computed on the volume's device, on its null stream; there is no host implementation.
+ * Refused with APD_ERR_INVALID before any device is touched, message "<function>: ..." (apd_fusion_last_error): a NULL volume,
+ * mesh, origin3, cameras, depths, path or output pointer, a NULL map, all arrays NULL; a dimension below 2 or 2^31 or more
+ * samples; a voxel, trunc or max_weight that is not positive and finite, max_weight < 1, an origin that is not finite, a negative
+ * device; num_views < 1; a weight that is not positive and finite; images or a colour array for a volume or mesh without colour;
+ * image_channels other than 1 or 3; a camera whose width or height is not positive or whose product is 2^31 or more.
+ * APD_ERR_UNSUPPORTED for 2^31 or more vertices or faces (known once they are counted on the device).  Outputs are untouched when
+ * a call fails.  apd_fusion_last_timing reports a call like the other points calls: set-up, the kernels and copies as "views",
+ * and for apd_mesh_write_ply the file. */
+typedef struct apd_volume *apd_volume_t;
+typedef struct apd_mesh *apd_mesh_t;
+int apd_volume_create(int device, int nx, int ny, int nz, const float *origin3, float voxel, float trunc, float max_weight, int with_colour,
+                      apd_volume_t *volume);
+int apd_volume_destroy(apd_volume_t volume);
+int apd_volume_integrate(apd_volume_t volume, int num_views, const apd_camera *cameras, const float *const *depths, const float *const *images,
+                         int image_channels, const float *weights, int maps_on_device);
+int apd_volume_download(apd_volume_t volume, float *tsdf, float *weight, float *colour4);
+int apd_volume_upload(apd_volume_t volume, const float *tsdf, const float *weight, const float *colour4);
+int apd_volume_extract_mesh(apd_volume_t volume, apd_mesh_t *mesh);
+int apd_volume_view_chunk(void);
+int apd_mesh_counts(apd_mesh_t mesh, long long *vertices, long long *faces);
+int apd_mesh_has_colour(apd_mesh_t mesh);
+int apd_mesh_download(apd_mesh_t mesh, float *xyz, uint8_t *bgr, int32_t *faces);
+int apd_mesh_write_ply(apd_mesh_t mesh, const char *path);
+int apd_mesh_destroy(apd_mesh_t mesh);
+
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
  * points in memory (*points, released with apd_points_destroy; untouched when the call fails), or both from one fusion.  With
  * ply_normals the file has the properties x y z nx ny nz (float) before the three colour bytes.  Refused with APD_ERR_INVALID
