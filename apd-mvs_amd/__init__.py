@@ -232,6 +232,13 @@ def lib():
     L.apd_mesh_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.apd_mesh_write_ply.argtypes = [C.c_void_p, C.c_char_p]
     L.apd_mesh_destroy.argtypes = [C.c_void_p]
+    L.apd_mesh_create.argtypes = [C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.apd_mesh_weld.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.apd_mesh_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+    L.apd_mesh_remove_small_components.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.apd_mesh_with_vertex_normals.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.apd_mesh_has_normals.argtypes = [C.c_void_p]
+    L.apd_mesh_download_normals.argtypes = [C.c_void_p, C.c_void_p]
     L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     _lib = L
     return L
@@ -1018,13 +1025,23 @@ class Points:
 
 
 class Mesh:
-    """An indexed triangle mesh (apd_mesh_t) as Volume.extract_mesh() makes it: vertices float32 [n, 3], colours uint8 [n, 3] (blue,
-    green, red; None for a volume without colour) and faces int32 [m, 3], numpy arrays that are copies and outlive the object;
-    write_ply() writes the library's file (apd_mesh_write_ply).  A mesh may be empty."""
+    """An indexed triangle mesh (apd_mesh_t) as Volume.extract_mesh() or Mesh.from_arrays() makes it: vertices float32 [n, 3], colours
+    uint8 [n, 3] (blue, green, red; None for a mesh without colour), normals float32 [n, 3] (None until with_vertex_normals() has
+    made them) and faces int32 [m, 3], numpy arrays that are copies and outlive the object; write_ply() writes the library's file
+    (apd_mesh_write_ply).  weld(), remove_small_components() and with_vertex_normals() each give a new Mesh and leave this one as it
+    is (arithmetic contract C22); components() labels the faces.  A mesh may be empty."""
 
     def __init__(self, handle):
-        L = lib()
         self._m = handle
+        self.refresh()
+
+    def refresh(self):
+        """Reads vertices, colours, normals and faces from the device again.  No call changes a mesh, so this changes nothing; it is
+        how a test shows that."""
+        if not self._m:
+            raise ApdError("Mesh.refresh: the mesh is closed")
+        L = lib()
+        handle = self._m
         nv, nf = C.c_longlong(0), C.c_longlong(0)
         rc = L.apd_mesh_counts(handle, C.byref(nv), C.byref(nf))
         if rc != 0:
@@ -1036,10 +1053,82 @@ class Mesh:
                                      C.c_void_p(self.faces.ctypes.data))
             if rc != 0:
                 raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        self.normals = None
+        if L.apd_mesh_has_normals(handle):
+            self.normals = np.zeros((nv.value, 3), np.float32)
+            rc = L.apd_mesh_download_normals(handle, C.c_void_p(self.normals.ctypes.data))
+            if rc != 0:
+                raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+
+    @classmethod
+    def from_arrays(cls, vertices, faces, colours=None, device=0):
+        """apd_mesh_create: a Mesh on GPU `device` of copies of the arrays: vertices [n, 3] float32, faces [m, 3] int32 with every index
+        in [0, n), colours [n, 3] uint8 (blue, green, red) or None.  A face may repeat an index."""
+        L = lib()
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        c = None if colours is None else np.ascontiguousarray(colours, np.uint8).reshape(-1, 3)
+        if c is not None and len(c) != len(v):
+            raise ValueError("Mesh.from_arrays: %d colours for %d vertices" % (len(c), len(v)))
+        out = C.c_void_p()
+        rc = L.apd_mesh_create(int(device), len(v), C.c_void_p(v.ctypes.data) if len(v) else None, None if c is None else C.c_void_p(c.ctypes.data),
+                               len(f), C.c_void_p(f.ctypes.data) if len(f) else None, 0, C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return cls(out)
+
+    def _open(self, what):
+        if not self._m:
+            raise ApdError("Mesh.%s: the mesh is closed" % what)
+        return lib()
+
+    def weld(self, tolerance, origin=None):
+        """apd_mesh_weld: the Mesh whose vertices within `tolerance` of each other, through chains, are the one of them with the
+        smallest index; faces that name a vertex twice after that and vertices no face names are gone.  origin: of the grid of cell
+        size `tolerance`, (0, 0, 0) unless given.  A tolerance far below the voxel size welds only coincident vertices."""
+        L = self._open("weld")
+        out = C.c_void_p()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        rc = L.apd_mesh_weld(self._m, float(tolerance), org, C.byref(out), None, None)
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Mesh(out)
+
+    def components(self):
+        """apd_mesh_components: (label uint32 [m], size uint32 [m], count) of the faces' connected components, two faces being
+        adjacent when they name a common vertex: the smallest face index of each face's component and its number of faces."""
+        L = self._open("components")
+        label, size = np.zeros(len(self.faces), np.uint32), np.zeros(len(self.faces), np.uint32)
+        count = C.c_longlong(0)
+        rc = L.apd_mesh_components(self._m, C.c_void_p(label.ctypes.data), C.c_void_p(size.ctypes.data), C.byref(count))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return label, size, count.value
+
+    def remove_small_components(self, min_faces):
+        """apd_mesh_remove_small_components: the Mesh of the faces whose component has at least min_faces faces, and of the vertices they
+        name."""
+        L = self._open("remove_small_components")
+        if not 0 <= int(min_faces) < 2 ** 32:
+            raise ValueError("Mesh.remove_small_components: min_faces %r" % (min_faces,))
+        out = C.c_void_p()
+        rc = L.apd_mesh_remove_small_components(self._m, int(min_faces), C.byref(out), None, None)
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Mesh(out)
+
+    def with_vertex_normals(self):
+        """apd_mesh_with_vertex_normals: the Mesh with area-weighted vertex normals (`normals`), summed in binary64 in a fixed order."""
+        L = self._open("with_vertex_normals")
+        out = C.c_void_p()
+        rc = L.apd_mesh_with_vertex_normals(self._m, C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Mesh(out)
 
     def write_ply(self, path):
-        """apd_mesh_write_ply: binary little-endian, x y z float (and red green blue uchar), then the faces as lists of three ints.
-        Points.read_ply reads the file back as its vertices."""
+        """apd_mesh_write_ply: binary little-endian, x y z float (with normals nx ny nz float; with colour red green blue uchar), then
+        the faces as lists of three ints.  Points.read_ply reads the file back as its vertices."""
         if not self._m:
             raise ApdError("Mesh.write_ply: the mesh is closed")
         L = lib()

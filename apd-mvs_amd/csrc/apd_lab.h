@@ -74,7 +74,7 @@ static __device__ unsigned long long g_weak_stats[8];
 
 #endif
 
-// -DAPD_LAB_CLUSTER_REDUCE_NAIVE (tools/points_clusters_time.py --library): k_cluster_reduce of apd_points_clusters.hip issues one
+// -DAPD_LAB_CLUSTER_REDUCE_NAIVE (tools/points_clusters_time.py --library): k_cluster_reduce of apd_union_find.h issues one
 // min and one add per lane, without combining the lanes of a wave that hold the same root first: the form the combining is
 // measured against.  Same results, the product build combines.
 #ifdef APD_LAB_CLUSTER_REDUCE_NAIVE

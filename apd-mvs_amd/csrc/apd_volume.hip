@@ -1,6 +1,6 @@
-// apd_volume.hip -- the apd_volume_* and apd_mesh_* calls of include/apd_mi355x.h: a truncated signed distance volume integrated
-// from depth maps, and the indexed triangle mesh that marching tetrahedra on the six-tetrahedra split of each cell takes from it
-// (arithmetic contract C21; the relation: apd_volume_math.h).
+// apd_volume.hip -- the apd_volume_* calls of include/apd_mi355x.h: a truncated signed distance volume integrated from depth maps,
+// and the indexed triangle mesh that marching tetrahedra on the six-tetrahedra split of each cell takes from it (arithmetic
+// contract C21; the relation: apd_volume_math.h).  The mesh object and everything done to one: apd_mesh.hip.
 //
 // The volume: per sample a distance D and a weight W, 4 bytes each, and with colour four more floats (blue, green, red, colour
 // weight) interleaved; allocated and set to (1, 0, 0 ..) on the first call that needs the device, so that apd_volume_create itself
@@ -35,6 +35,7 @@
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_device.h"
 #include "apd_lab.h"
+#include "apd_mesh_host.h"
 #include "apd_points_host.h"
 #include "apd_sort.h"
 #include "apd_volume_math.h"
@@ -46,15 +47,6 @@ struct apd_volume {
     size_t samples = 0;
     float *D = nullptr, *W = nullptr, *C = nullptr;  // device memory once `ready`
     bool ready = false;
-};
-
-struct apd_mesh {
-    int device = 0;
-    long long vertices = 0, faces = 0;
-    int colour = 0;
-    float *xyz = nullptr;     // device memory, or null without vertices
-    uint8_t *bgr = nullptr;
-    int32_t *index = nullptr;
 };
 
 namespace {
@@ -368,22 +360,6 @@ struct Call {
         return APD_OK;
     }
 
-    // The arrays of m in host memory; any pointer may be null
-    int download(const apd_mesh *m, float *xyz, uint8_t *bgr, int32_t *faces) const
-    {
-        HIP_TRY(hipSetDevice(m->device));
-        if (xyz && m->vertices > 0) {
-            HIP_TRY(hipMemcpy(xyz, m->xyz, (size_t)m->vertices * 12, hipMemcpyDeviceToHost));
-        }
-        if (bgr && m->vertices > 0) {
-            HIP_TRY(hipMemcpy(bgr, m->bgr, (size_t)m->vertices * 3, hipMemcpyDeviceToHost));
-        }
-        if (faces && m->faces > 0) {
-            HIP_TRY(hipMemcpy(faces, m->index, (size_t)m->faces * 12, hipMemcpyDeviceToHost));
-        }
-        return APD_OK;
-    }
-
     int copy(apd_volume *v, float *tsdf, float *weight, float *colour4, bool up) const
     {
         const auto t0 = std::chrono::steady_clock::now();
@@ -564,111 +540,5 @@ extern "C" int apd_volume_extract_mesh(apd_volume_t v, apd_mesh_t *mesh)
         return rc;
     }
     *mesh = m;
-    return APD_OK;
-}
-
-extern "C" int apd_mesh_counts(apd_mesh_t m, long long *vertices, long long *faces)
-{
-    const Call call{"apd_mesh_counts"};
-    err().clear();
-    if (!m || (!vertices && !faces)) {
-        return call.invalid("null argument");
-    }
-    if (vertices) {
-        *vertices = m->vertices;
-    }
-    if (faces) {
-        *faces = m->faces;
-    }
-    return APD_OK;
-}
-
-extern "C" int apd_mesh_has_colour(apd_mesh_t m) { return m ? m->colour : 0; }
-
-extern "C" int apd_mesh_download(apd_mesh_t m, float *xyz, uint8_t *bgr, int32_t *faces)
-{
-    const Call call{"apd_mesh_download"};
-    err().clear();
-    if (!m || (!xyz && !bgr && !faces)) {
-        return call.invalid("null argument");
-    }
-    if (bgr && !m->colour) {
-        return call.invalid("a colour array for a mesh without colour");
-    }
-    if (m->vertices == 0 && m->faces == 0) {
-        return APD_OK;
-    }
-    DeviceScope scope(true);
-    return call.download(m, xyz, bgr, faces);
-}
-
-extern "C" int apd_mesh_write_ply(apd_mesh_t m, const char *path)
-{
-    const Call call{"apd_mesh_write_ply"};
-    err().clear();
-    if (!m || !path) {
-        return call.invalid("null argument");
-    }
-    clear_timing();
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t nv = (size_t)m->vertices, nf = (size_t)m->faces;
-    std::vector<float> xyz(3 * nv);
-    std::vector<uint8_t> bgr(m->colour ? 3 * nv : 0);
-    std::vector<int32_t> index(3 * nf);
-    if (nv > 0 || nf > 0) {
-        DeviceScope scope(true);
-        if (const int rc = call.download(m, xyz.data(), m->colour ? bgr.data() : nullptr, index.data()); rc != APD_OK) {
-            return rc;
-        }
-    }
-    apd_fusion::g_fusion_ms[1] = ms_since(t0);
-    const auto t1 = std::chrono::steady_clock::now();
-    FILE *f = fopen(path, "wb");
-    if (!f) {
-        return apd::set_error(err(), APD_ERR_INVALID, "%s: cannot open %s for writing", call.who, path);
-    }
-    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n%s"
-               "element face %lld\nproperty list uchar int vertex_indices\nend_header\n", m->vertices,
-            m->colour ? "property uchar red\nproperty uchar green\nproperty uchar blue\n" : "", m->faces);
-    const size_t vertex_bytes = m->colour ? 15 : 12;
-    std::vector<uint8_t> packed(std::max(nv * vertex_bytes, nf * 13));
-    for (size_t k = 0; k < nv; ++k) {  // little endian, as the host's memcpy writes them
-        uint8_t *rec = packed.data() + k * vertex_bytes;
-        memcpy(rec, xyz.data() + 3 * k, 12);
-        if (m->colour) {
-            rec[12] = bgr[3 * k + 2];
-            rec[13] = bgr[3 * k + 1];
-            rec[14] = bgr[3 * k];
-        }
-    }
-    bool ok = fwrite(packed.data(), 1, nv * vertex_bytes, f) == nv * vertex_bytes;
-    for (size_t k = 0; k < nf; ++k) {
-        uint8_t *rec = packed.data() + k * 13;
-        rec[0] = 3;
-        memcpy(rec + 1, index.data() + 3 * k, 12);
-    }
-    ok = ok && fwrite(packed.data(), 1, nf * 13, f) == nf * 13;
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) {
-        return apd::set_error(err(), APD_ERR_INVALID, "%s: writing %s failed", call.who, path);
-    }
-    apd_fusion::g_fusion_ms[2] = ms_since(t1);
-    return APD_OK;
-}
-
-extern "C" int apd_mesh_destroy(apd_mesh_t m)
-{
-    if (!m) {
-        return APD_OK;
-    }
-    if (m->xyz || m->bgr || m->index) {
-        DeviceScope scope(true);
-        if (hipSetDevice(m->device) == hipSuccess) {
-            hipFree(m->xyz);
-            hipFree(m->bgr);
-            hipFree(m->index);
-        }
-    }
-    delete m;
     return APD_OK;
 }

@@ -855,10 +855,12 @@ void filter_and_write(const std::vector<Problem> &problems, const std::vector<Fu
 // --mesh: the filter, then the volume over the box of the finite points of ply_path grown by trunc -- origin = lo - trunc and per
 // axis the fewest samples, at least 2, whose last one is at or past hi + trunc, in the arithmetic of the Python binding's
 // Volume.around --, the filtered maps with the views' colour images (3 channels) into it, every view weighing 1, and the mesh
-// into <ply_path>.mesh.  A failure ends the program like every other device error.
+// into <ply_path>.mesh, after the steps of `clean` in their fixed order -- weld, small components, normals --, each a new mesh that
+// replaces the one before and a printed line with the counts before and after.  A failure ends the program like every other device
+// error.
 void mesh_and_write(const path &ply_path, const std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const float *const *depths,
                     const float *const *normals, const uint8_t *const *weaks, const uint8_t *const *blocks, int cols, int rows, int maps_on_device,
-                    float voxel, float trunc)
+                    float voxel, float trunc, const MeshClean &clean)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const int V = (int)views.size();
@@ -910,8 +912,38 @@ void mesh_and_write(const path &ply_path, const std::vector<FusionView> &views, 
     long long vertices = 0, faces = 0;
     if (apd_volume_create(g_fusion_device, dims[0], dims[1], dims[2], origin, voxel, trunc, 64.0f, 1, &volume) != APD_OK ||
         apd_volume_integrate(volume, V, f.cams.data(), filtered.data(), images.data(), 3, nullptr, 0) != APD_OK ||
-        apd_volume_extract_mesh(volume, &mesh) != APD_OK || apd_mesh_counts(mesh, &vertices, &faces) != APD_OK ||
-        apd_mesh_write_ply(mesh, mesh_path.c_str()) != APD_OK) {
+        apd_volume_extract_mesh(volume, &mesh) != APD_OK || apd_mesh_counts(mesh, &vertices, &faces) != APD_OK) {
+        failed(apd_fusion_last_error());
+    }
+    // one step of `clean`: `next` replaces the mesh, and a line tells what the step did to the counts
+    auto replaced = [&](int rc, apd_mesh_t next, const std::string &what) {
+        long long nv = 0, nf = 0;
+        if (rc != APD_OK || apd_mesh_counts(next, &nv, &nf) != APD_OK) {
+            failed(apd_fusion_last_error());
+        }
+        std::cout << "Mesh " << what << ": " << vertices << " vertices and " << faces << " faces -> " << nv << " vertices and " << nf << " faces" << std::endl;
+        apd_mesh_destroy(mesh);
+        mesh = next;
+        vertices = nv;
+        faces = nf;
+    };
+    if (clean.weld > 0.0f) {
+        apd_mesh_t next = nullptr;
+        const int rc = apd_mesh_weld(mesh, clean.weld, nullptr, &next, nullptr, nullptr);
+        replaced(rc, next, "welded within " + std::to_string(clean.weld));
+    }
+    if (clean.remove_small) {
+        apd_mesh_t next = nullptr;
+        long long components = 0;
+        const int rc = apd_mesh_remove_small_components(mesh, clean.min_component, &next, nullptr, &components);
+        replaced(rc, next, "without the components of fewer than " + std::to_string(clean.min_component) + " faces among " + std::to_string(components));
+    }
+    if (clean.normals) {
+        apd_mesh_t next = nullptr;
+        const int rc = apd_mesh_with_vertex_normals(mesh, &next);
+        replaced(rc, next, "with vertex normals");
+    }
+    if (apd_mesh_write_ply(mesh, mesh_path.c_str()) != APD_OK) {
         failed(apd_fusion_last_error());
     }
     apd_mesh_destroy(mesh);
@@ -981,7 +1013,7 @@ void RunFilterOnDevice(const path &dense_folder, const std::vector<Problem> &pro
 }
 
 // --mesh from the four state files of every view, as RunFusion reads them, after it has written APD.ply
-void RunMesh(const path &dense_folder, const std::vector<Problem> &problems, float voxel, float trunc)
+void RunMesh(const path &dense_folder, const std::vector<Problem> &problems, float voxel, float trunc, const MeshClean &clean)
 {
     std::vector<FusionView> views;
     std::vector<std::vector<int>> sources;
@@ -1003,13 +1035,13 @@ void RunMesh(const path &dense_folder, const std::vector<Problem> &problems, flo
         }
     }
     mesh_and_write(dense_folder / path("APD") / path("APD.ply"), views, sources, deps.data(), nors.data(), weaks.data(), any_block ? blocks.data() : nullptr,
-                   0, 0, 0, voxel, trunc);
+                   0, 0, 0, voxel, trunc, clean);
 }
 
 // The final maps are on `device` (cols x rows each): colour images, cameras and block masks are read here, the masks go up
 void RunMeshOnDevice(const path &dense_folder, const std::vector<Problem> &problems, int device, int cols, int rows,
                      const std::vector<const float *> &depths, const std::vector<const float *> &normals, const std::vector<const uint8_t *> &weaks,
-                     float voxel, float trunc)
+                     float voxel, float trunc, const MeshClean &clean)
 {
     std::vector<FusionView> views;
     std::vector<std::vector<int>> sources;
@@ -1035,7 +1067,7 @@ void RunMeshOnDevice(const path &dense_folder, const std::vector<Problem> &probl
     const int fusion_device = g_fusion_device;
     g_fusion_device = device;
     mesh_and_write(dense_folder / path("APD") / path("APD.ply"), views, sources, depths.data(), normals.data(), weaks.data(),
-                   owned.empty() ? nullptr : blocks.data(), cols, rows, 1, voxel, trunc);
+                   owned.empty() ? nullptr : blocks.data(), cols, rows, 1, voxel, trunc, clean);
     g_fusion_device = fusion_device;
     for (void *p : owned) {
         apd_device_free(device, p);

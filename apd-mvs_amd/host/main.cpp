@@ -7,13 +7,19 @@
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
 //       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
 //       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]]
-//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]]
+//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-normals]
 //
 // --mesh VOXEL[,TRUNC]: besides everything else, APD/APD.ply.mesh: a binary PLY with faces, the marching-tetrahedra mesh of a signed
 // distance volume with samples VOXEL apart and a truncation distance of TRUNC (4 * VOXEL unless given) over the box of the points
 // of APD.ply, integrated from the filtered maps of --filtered-maps (which need not be given) with the views' colours
 // (apd_volume_create, apd_volume_integrate, apd_volume_extract_mesh; RunMesh, host/fusion.cpp).  Every driver takes it; refused
 // with --no-fusion, which leaves no cloud to take the box from.  Without the flag no output changes.
+// --mesh-weld TOL, --mesh-min-component FACES, --mesh-normals: what becomes of that mesh before it is written, in this fixed order
+// whatever the order of the flags: vertices within TOL of each other, through chains, become the one with the smallest index and
+// the faces that collapse go (apd_mesh_weld; VOXEL * 1e-4 welds only coincident vertices); the connected components of fewer than
+// FACES faces go with the vertices only they name (apd_mesh_remove_small_components); the file carries nx ny nz, area-weighted
+// vertex normals (apd_mesh_with_vertex_normals).  One line per step is printed with the counts before and after.  Each is refused
+// without --mesh and on a malformed value, with the usage line, before anything is read.  Without them APD.ply.mesh keeps its bytes.
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -144,6 +150,7 @@ bool ParseOptions(int argc, char **argv, Options &o)
         return false;
     }
     o.dense_folder = path(argv[1]);
+    std::string mesh_flag;   // the last --mesh-* flag seen: each needs --mesh
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
         auto value = [&](uint64_t &dst) {
@@ -213,6 +220,26 @@ bool ParseOptions(int argc, char **argv, Options &o)
             }
             o.mesh_voxel = voxel;
             o.mesh_trunc = t.empty() ? 4.0f * voxel : trunc;
+        } else if (a == "--mesh-weld") {
+            const std::string text = i + 1 < argc ? argv[++i] : "";
+            if (!ply_value::Radius(text, o.mesh_clean.weld)) {
+                fprintf(stderr, "bad value '%s' of %s: TOL, a positive number\n", text.c_str(), a.c_str());
+                return false;
+            }
+            mesh_flag = a;
+        } else if (a == "--mesh-min-component") {
+            const std::string text = i + 1 < argc ? argv[++i] : "";
+            unsigned long long n = 0;
+            if (!ply_value::Count(text, 0, 0x7fffffffull, n)) {
+                fprintf(stderr, "bad value '%s' of %s: FACES, a count\n", text.c_str(), a.c_str());
+                return false;
+            }
+            o.mesh_clean.remove_small = true;
+            o.mesh_clean.min_component = (unsigned)n;
+            mesh_flag = a;
+        } else if (a == "--mesh-normals") {
+            o.mesh_clean.normals = true;
+            mesh_flag = a;
         } else if (a == "--seed") {
             if (!value(o.seed)) return false;
         } else if (a == "--iters") {
@@ -294,6 +321,10 @@ bool ParseOptions(int argc, char **argv, Options &o)
     }
     if (o.fusion_thresholds_set && o.fusion_variant != APD_FUSION_ETH) {
         fprintf(stderr, "--fusion-min-consistent, --fusion-reproj, --fusion-depth, --fusion-angle and --fusion-factors apply to --fusion eth only\n");
+        return false;
+    }
+    if (!mesh_flag.empty() && !(o.mesh_voxel > 0.0f)) {
+        fprintf(stderr, "%s changes the mesh of --mesh VOXEL[,TRUNC]: not without it\n", mesh_flag.c_str());
         return false;
     }
     if (o.mesh_voxel > 0.0f && o.no_fusion) {
@@ -426,7 +457,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"
@@ -579,7 +610,7 @@ int main(int argc, char **argv)
     if (!opt.no_fusion) {
         RunFusion(opt.dense_folder, problems);  // main.cpp:219
         if (opt.mesh_voxel > 0.0f) {
-            RunMesh(opt.dense_folder, problems, opt.mesh_voxel, opt.mesh_trunc);
+            RunMesh(opt.dense_folder, problems, opt.mesh_voxel, opt.mesh_trunc, opt.mesh_clean);
         }
         if (!opt.keep_maps) {                   // main.cpp:220-230
             for (const Problem &p : problems) {

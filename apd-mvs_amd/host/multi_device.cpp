@@ -1037,7 +1037,7 @@ void Scheduler::Mesh()
         d[v] = fuse_depth[v].as<float>();
         n[v] = fuse_normal[v].as<float>();
     }
-    RunMeshOnDevice(opt.dense_folder, problems, ranks[0].device, W0, H0, d, n, fuse_weak, opt.mesh_voxel, opt.mesh_trunc);
+    RunMeshOnDevice(opt.dense_folder, problems, ranks[0].device, W0, H0, d, n, fuse_weak, opt.mesh_voxel, opt.mesh_trunc, opt.mesh_clean);
 }
 
 void Scheduler::Fuse()

@@ -13,6 +13,15 @@
 #include "APD.h"
 #include "ply_options.h"
 
+// What --mesh does to its mesh between extraction and the file, in this fixed order: apd_mesh_weld, apd_mesh_remove_small_components,
+// apd_mesh_with_vertex_normals.  All off: the file has the bytes of the extracted mesh.
+struct MeshClean {
+    float weld = 0.0f;                 // --mesh-weld TOL: 0 is off
+    bool remove_small = false;         // --mesh-min-component FACES
+    unsigned min_component = 0;
+    bool normals = false;              // --mesh-normals
+};
+
 struct Options {
     path dense_folder;
     int gpu_index = 0;
@@ -40,6 +49,7 @@ struct Options {
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     float mesh_voxel = 0.0f;              // --mesh VOXEL[,TRUNC]: APD/APD.ply.mesh, the marching-tetrahedra mesh of the filtered maps fused into a signed
     float mesh_trunc = 0.0f;              // distance volume with samples VOXEL apart in the box of the points of APD.ply (apd_volume_*); voxel 0: off
+    MeshClean mesh_clean;                 // --mesh-weld TOL, --mesh-min-component FACES, --mesh-normals: what becomes of that mesh before it is written
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)
     bool clean_exit = false;          // --clean-exit: return from main() instead of _Exit (exit handlers run: profilers)
@@ -186,10 +196,11 @@ void RunFilterOnDevice(const path &dense_folder, const std::vector<Problem> &pro
 // --mesh VOXEL[,TRUNC], after the fusion has written APD/APD.ply: the filter above on every view's final maps (read from the result
 // folders, or resident on `device`), apd_volume_create over the box of the finite points of APD.ply grown by `trunc`,
 // apd_volume_integrate of the filtered maps with the views' colour images, every view weighing 1, apd_volume_extract_mesh, and
-// apd_mesh_write_ply into APD/APD.ply.mesh.  Honours <dense>/blocks and the --fusion-* rule like the filter.
-void RunMesh(const path &dense_folder, const std::vector<Problem> &problems, float voxel, float trunc);
+// the steps of `clean` on the mesh, one printed line each with the counts before and after, and apd_mesh_write_ply into
+// APD/APD.ply.mesh.  Honours <dense>/blocks and the --fusion-* rule like the filter.
+void RunMesh(const path &dense_folder, const std::vector<Problem> &problems, float voxel, float trunc, const MeshClean &clean);
 void RunMeshOnDevice(const path &dense_folder, const std::vector<Problem> &problems, int device, int cols, int rows,
                      const std::vector<const float *> &depths, const std::vector<const float *> &normals, const std::vector<const uint8_t *> &weaks,
-                     float voxel, float trunc);
+                     float voxel, float trunc, const MeshClean &clean);
 
 #endif  // APD_MI355X_HOST_SCHEDULE_H_

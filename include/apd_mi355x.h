@@ -979,6 +979,58 @@ int apd_mesh_has_colour(apd_mesh_t mesh);
 int apd_mesh_download(apd_mesh_t mesh, float *xyz, uint8_t *bgr, int32_t *faces);
 int apd_mesh_write_ply(apd_mesh_t mesh, const char *path);
 int apd_mesh_destroy(apd_mesh_t mesh);
+/* Cleaning a mesh: what every pipeline that builds a distance volume runs after extraction -- merge close vertices, drop small
+ * connected components, compute vertex normals (Open3D's merge_close_vertices, remove small clusters of connected triangles and
+ * compute_vertex_normals; MeshLab's filters of the same names) -- here on the mesh object, on its device.  Every call leaves its
+ * input as it is, gives a new mesh that shares nothing with it (released with apd_mesh_destroy), and its result is a function of
+ * the input alone: two runs write the same bytes (contract C22; csrc/apd_mesh_math.h, csrc/apd_mesh.hip).
+ *   apd_mesh_create.  A mesh on `device` from the caller's arrays: xyz 3 floats per vertex, bgr (may be NULL: a mesh without
+ *   colour) 3 bytes per vertex, index 3 ints per face, each in [0, vertices); host memory, or with on_device device memory on
+ *   `device`; the arrays are copied.  A face may repeat an index.  A mesh of 0 vertices and 0 faces is allowed and touches no device.
+ *   Weld.  apd_mesh_weld joins vertices that are connected by a chain of pairs within `tolerance` of each other: the components of
+ *   apd_points_components over the vertex positions with radius = tolerance, on the grid of cell size `tolerance` at origin3 (NULL:
+ *   0, 0, 0), with that call's neighbour relation and grid limits; a vertex outside the grid (a coordinate that is not finite, 2^20
+ *   cells from the origin) is joined to nothing.  The representative of a group is its smallest index; it keeps its own position,
+ *   colour and normal, nothing is averaged.  Every face index is replaced by its representative; a face with two equal indices
+ *   after that is dropped; a vertex that is no representative, or that no surviving face names, is dropped; surviving vertices and
+ *   faces keep their order and the faces are renumbered.  -0.0 and +0.0 are one position.  A tolerance far below the voxel size,
+ *   such as voxel * 1e-4, welds only the coincident vertices that t = 0 gives (see Vertices above) and drops their triangles
+ *   without area; a tolerance near the voxel size collapses the surface.  *removed_vertices and *removed_faces (may be NULL): how
+ *   many fewer the result has.
+ *   Components.  Two faces are adjacent when they name a common vertex index; a component is the closure of that.  label[f] is the
+ *   smallest face index of f's component, size[f] its number of faces; host memory, one entry per face, `size` may be NULL;
+ *   *components (may be NULL) their number.  apd_mesh_remove_small_components keeps the faces with size[f] >= min_faces in their
+ *   order (0 and 1 keep every face), drops the vertices no kept face names -- an unreferenced vertex goes whatever min_faces is --
+ *   and renumbers; *removed_faces and *components (of the input) may be NULL.
+ *   Vertex normals, area-weighted.  Face f with corners a, b, c at positions widened to binary64: u = b - a, w = c - a,
+ *   g = (u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x), every product and difference one binary64
+ *   operation.  The sum s of vertex v is that of g over the corners (f, c) with index[3 f + c] == v in ascending 3 f + c, in
+ *   binary64 from +0.0.  len = sqrt((s.x * s.x + s.y * s.y) + s.z * s.z); the normal is (float)(s / len) per component where len
+ *   is finite and > 0, else (0, 0, 0): a vertex no face names, a vertex whose faces cancel, a face with a position that is not
+ *   finite.  The sums are gathered through a stable sort of the corners by vertex and never added atomically, so their order, and
+ *   with it every bit, is fixed.  apd_mesh_with_vertex_normals gives the mesh with these normals (replacing any it had);
+ *   apd_mesh_has_normals tells; apd_mesh_download_normals takes 3 floats per vertex, host memory.  Weld and removal carry the
+ *   normals of the vertices they keep along, unchanged.
+ * apd_mesh_write_ply of a mesh with normals writes `property float nx`, ny, nz after z and before the colours, as the points'
+ * file orders them; a mesh without writes the bytes it always wrote.  apd_points_read_ply reads either back as its vertices.
+ * Everything is computed on the mesh's device, on its null stream; there is no host implementation.  A mesh without vertices
+ * gives a mesh without, and no labels, with no device touched.
+ * Refused with APD_ERR_INVALID before any device is touched, message "<function>: ...": a NULL mesh or output pointer (label for
+ * apd_mesh_components); for apd_mesh_create a negative count, 2^31 or more of either, a NULL array with a count that is not 0, a
+ * negative device and, for host arrays, an index outside [0, vertices) -- for device arrays a kernel checks the range and a
+ * failure returns the same code; for apd_mesh_weld a tolerance that is not positive and finite or whose square is not, an origin
+ * that is not finite; apd_mesh_download_normals of a mesh without normals.  APD_ERR_UNSUPPORTED from
+ * apd_mesh_with_vertex_normals for a mesh whose 3 * faces reach 2^32 (the sort carries a 32-bit corner id).  Outputs are untouched
+ * when a call fails.  apd_fusion_last_timing reports each call like the other mesh calls: set-up, the kernels and copies as
+ * "views", file 0. */
+int apd_mesh_create(int device, long long vertices, const float *xyz, const uint8_t *bgr, long long faces, const int32_t *index, int on_device,
+                    apd_mesh_t *mesh);
+int apd_mesh_weld(apd_mesh_t mesh, float tolerance, const float *origin3, apd_mesh_t *out, long long *removed_vertices, long long *removed_faces);
+int apd_mesh_components(apd_mesh_t mesh, uint32_t *label, uint32_t *size, long long *components);
+int apd_mesh_remove_small_components(apd_mesh_t mesh, unsigned min_faces, apd_mesh_t *out, long long *removed_faces, long long *components);
+int apd_mesh_with_vertex_normals(apd_mesh_t mesh, apd_mesh_t *out);
+int apd_mesh_has_normals(apd_mesh_t mesh);
+int apd_mesh_download_normals(apd_mesh_t mesh, float *nxyz);
 
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
  * points in memory (*points, released with apd_points_destroy; untouched when the call fails), or both from one fusion.  With
