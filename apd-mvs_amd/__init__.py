@@ -237,6 +237,8 @@ def lib():
     L.apd_mesh_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
     L.apd_mesh_remove_small_components.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.apd_mesh_with_vertex_normals.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.apd_mesh_simplify.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
+                                    C.POINTER(C.c_longlong)]
     L.apd_mesh_has_normals.argtypes = [C.c_void_p]
     L.apd_mesh_download_normals.argtypes = [C.c_void_p, C.c_void_p]
     L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -1028,8 +1030,10 @@ class Mesh:
     """An indexed triangle mesh (apd_mesh_t) as Volume.extract_mesh() or Mesh.from_arrays() makes it: vertices float32 [n, 3], colours
     uint8 [n, 3] (blue, green, red; None for a mesh without colour), normals float32 [n, 3] (None until with_vertex_normals() has
     made them) and faces int32 [m, 3], numpy arrays that are copies and outlive the object; write_ply() writes the library's file
-    (apd_mesh_write_ply).  weld(), remove_small_components() and with_vertex_normals() each give a new Mesh and leave this one as it
-    is (arithmetic contract C22); components() labels the faces.  A mesh may be empty."""
+    (apd_mesh_write_ply).  weld(), remove_small_components(), simplify() and with_vertex_normals() each give a new Mesh and leave this
+    one as it is (arithmetic contracts C22 and C23); components() labels the faces.  A mesh may be empty."""
+
+    PLACEMENTS = {"mean": 0, "quadric": 1}   # APD_SIMPLIFY_MEAN, APD_SIMPLIFY_QUADRIC
 
     def __init__(self, handle):
         self._m = handle
@@ -1113,6 +1117,21 @@ class Mesh:
             raise ValueError("Mesh.remove_small_components: min_faces %r" % (min_faces,))
         out = C.c_void_p()
         rc = L.apd_mesh_remove_small_components(self._m, int(min_faces), C.byref(out), None, None)
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Mesh(out)
+
+    def simplify(self, cell, origin=None, placement="quadric"):
+        """apd_mesh_simplify: the Mesh thinned by vertex clustering (arithmetic contract C23): the vertices of one cell of the grid of
+        cell size `cell` at `origin` ((0, 0, 0) unless given) become one vertex, at their mean ("mean") or where the quadric of the
+        faces around them puts it ("quadric": on the surface, on creases and corners); faces that collapse and all but the first
+        of equal faces go.  The result has colours as this mesh and no normals: with_vertex_normals() is the step to run after."""
+        L = self._open("simplify")
+        if placement not in self.PLACEMENTS:
+            raise ValueError("Mesh.simplify: placement %r, neither 'mean' nor 'quadric'" % (placement,))
+        out = C.c_void_p()
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        rc = L.apd_mesh_simplify(self._m, float(cell), org, self.PLACEMENTS[placement], C.byref(out), None, None)
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Mesh(out)

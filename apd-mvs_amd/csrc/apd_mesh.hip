@@ -7,7 +7,7 @@
 //   1. rep[v] by contract C13 over the positions: Labelling::label_points of apd_union_find.h, the labelling of
 //      apd_points_components -- cell order, k_cluster_link, flatten, reduce, emit.
 //   2. k_mesh_weld_faces: per face the three representatives and whether the face survives (no two equal).
-//   3. the compaction below.
+//   3. the compaction (MeshCall::compact, apd_mesh_compact.h, shared with apd_mesh_simplify.hip).
 // apd_mesh_components, on a parent array over the VERTICES:
 //   1. k_cluster_init; k_mesh_link, one lane per face: unite(v0, v1), unite(v0, v2) -- the lock-free union-find of apd_union_find.h.
 //   2. k_cluster_flatten, a launch of its own: root[v].
@@ -15,7 +15,7 @@
 //   4. k_cluster_reduce over the faces, the lanes of a wave that hold one root combined first -- a surface is one component of
 //      millions of faces --, integer min / add per root; k_cluster_emit: label[f], size[f]; the count of label[f] == f by a scan.
 // apd_mesh_remove_small_components: the flags size[f] >= min_faces, and the compaction.
-// The compaction (compact): used[v] = 1 for every index of a kept face (plain stores of the one value 1), a 64-bit scan of the
+// The compaction (apd_mesh_compact.h): used[v] = 1 for every index of a kept face (plain stores of the one value 1), a 64-bit scan of the
 // vertex flags and one of the face flags, a gather of the kept vertices' arrays and of the kept faces with their indices renumbered
 // by the vertex scan.  Every output element has one writer and every position is a scan's.
 // apd_mesh_with_vertex_normals -- a GATHER, so that the order of every binary64 sum is the contract's and not the order of arrival
@@ -39,6 +39,7 @@
 
 #include "../../include/apd_mi355x.h"
 #include "apd_fusion_device.h"
+#include "apd_mesh_compact.h"
 #include "apd_mesh_host.h"
 #include "apd_mesh_math.h"
 #include "apd_points_host.h"
@@ -48,6 +49,11 @@
 
 namespace {
 
+using apd_mesh_compact::clear_timing;
+using apd_mesh_compact::err;
+using apd_mesh_compact::into_new_mesh;
+using apd_mesh_compact::MeshCall;
+using apd_mesh_compact::new_mesh_like;
 using apd_points_grid::grid_of;
 using apd_points_host::DeviceScope;
 using apd_points_host::ms_since;
@@ -84,55 +90,6 @@ __global__ __launch_bounds__(256) void k_mesh_weld_faces(const int32_t *__restri
     mapped[3 * f + 1] = b;
     mapped[3 * f + 2] = c;
     keep[f] = apd_fusion::mesh_face_degenerate(a, b, c) ? 0u : 1u;
-}
-
-// used[v] = 1 for the indices of the kept faces; used: zeros before.  Every writer writes the same value
-__global__ __launch_bounds__(256) void k_mesh_mark_used(const int32_t *__restrict__ index, const uint32_t *__restrict__ keep, size_t faces,
-                                                         uint32_t *used)
-{
-    const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (f < faces && keep[f]) {
-        used[index[3 * f]] = 1u;
-        used[index[3 * f + 1]] = 1u;
-        used[index[3 * f + 2]] = 1u;
-    }
-}
-
-// Vertex v < vertices with used[v]: its arrays to position at[v]; bgr / normal null: the mesh has none
-__global__ __launch_bounds__(256) void k_mesh_gather_vertices(const uint32_t *__restrict__ used, const uint64_t *__restrict__ at, size_t vertices,
-                                                               const float *__restrict__ xyz, const uint8_t *__restrict__ bgr,
-                                                               const float *__restrict__ normal, float *__restrict__ out_xyz,
-                                                               uint8_t *__restrict__ out_bgr, float *__restrict__ out_normal)
-{
-    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= vertices || !used[v]) {
-        return;
-    }
-    const size_t to = (size_t)at[v];
-    for (int a = 0; a < 3; ++a) {
-        out_xyz[3 * to + a] = xyz[3 * v + a];
-        if (bgr) {
-            out_bgr[3 * to + a] = bgr[3 * v + a];
-        }
-        if (normal) {
-            out_normal[3 * to + a] = normal[3 * v + a];
-        }
-    }
-}
-
-// Face f < faces with keep[f]: to position at[f], its indices renumbered by vertex_at
-__global__ __launch_bounds__(256) void k_mesh_gather_faces(const int32_t *__restrict__ index, const uint32_t *__restrict__ keep,
-                                                            const uint64_t *__restrict__ at, size_t faces, const uint64_t *__restrict__ vertex_at,
-                                                            int32_t *__restrict__ out_index)
-{
-    const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= faces || !keep[f]) {
-        return;
-    }
-    const size_t to = (size_t)at[f];
-    for (int c = 0; c < 3; ++c) {
-        out_index[3 * to + c] = (int32_t)vertex_at[index[3 * f + c]];
-    }
 }
 
 // Face f < faces: its three vertices are in one tree of parent[] when the kernel ends
@@ -201,43 +158,8 @@ __global__ __launch_bounds__(256) void k_mesh_vertex_normals(const float *__rest
     normal[3 * v + 2] = n[2];
 }
 
-std::string &err() { return apd_fusion::g_fusion_error; }
-
-void clear_timing() { apd_fusion::g_fusion_ms[0] = apd_fusion::g_fusion_ms[1] = apd_fusion::g_fusion_ms[2] = 0.0; }
-
 // One call: its name, which starts every message; for welding the grid of the search
-struct Call : Search {
-    int invalid(const char *what) const { return apd::set_error(err(), APD_ERR_INVALID, "%s: %s", who, what); }
-
-    // Device arrays for `vertices` vertices and `faces` faces in m (which has none so far), owned by `scratch` until keep()
-    int alloc(Scratch &scratch, apd_mesh *m, size_t vertices, size_t faces) const
-    {
-        m->vertices = (long long)vertices;
-        m->faces = (long long)faces;
-        if (vertices > 0) {
-            HIP_TRY(scratch.alloc(vertices * 12, &m->xyz));
-            if (m->colour) {
-                HIP_TRY(scratch.alloc(vertices * 3, &m->bgr));
-            }
-            if (m->normals) {
-                HIP_TRY(scratch.alloc(vertices * 12, &m->normal));
-            }
-        }
-        if (faces > 0) {
-            HIP_TRY(scratch.alloc(faces * 12, &m->index));
-        }
-        return APD_OK;
-    }
-
-    static void keep(Scratch &scratch, const apd_mesh *m)
-    {
-        for (void *q : {(void *)m->xyz, (void *)m->bgr, (void *)m->normal, (void *)m->index}) {
-            if (q) {
-                scratch.keep(q);
-            }
-        }
-    }
-
+struct Call : MeshCall {
     // apd_mesh_create after its refusals: the arrays into m on its device, which is made the current one
     int create(apd_mesh *m, size_t vertices, const float *xyz, const uint8_t *bgr, size_t faces, const int32_t *index, bool on_device) const
     {
@@ -273,46 +195,6 @@ struct Call : Search {
         HIP_TRY(hipDeviceSynchronize());
         keep(scratch, m);
         apd_fusion::g_fusion_ms[1] = ms_since(t1);
-        return APD_OK;
-    }
-
-    // The faces f of m with keep[f] != 0, their indices read from `index` (m's own or a welded copy: 3 per face of m, each a vertex of
-    // m), and the vertices those faces name, both in m's order and renumbered, into `out` (no arrays so far; colour and normals
-    // as m).  m has vertices; its device is the current one
-    int compact(Scratch &scratch, const apd_mesh *m, const int32_t *index, const uint32_t *keep_face, apd_mesh *out) const
-    {
-        const size_t nv = (size_t)m->vertices, nf = (size_t)m->faces;
-        uint32_t *used = nullptr;
-        uint64_t *vertex_at = nullptr, *face_at = nullptr;
-        HIP_TRY(scratch.alloc(nv * 4, &used));
-        HIP_TRY(scratch.alloc((nv + 1) * 8, &vertex_at));
-        HIP_TRY(scratch.alloc((nf + 1) * 8, &face_at));
-        HIP_TRY(hipMemsetAsync(used, 0, nv * 4, 0));
-        if (nf > 0) {
-            hipLaunchKernelGGL(k_mesh_mark_used, grid_of(nf), dim3(256), 0, 0, index, keep_face, nf, used);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(apd_sort::exclusive_scan(used, vertex_at, nv));
-        HIP_TRY(apd_sort::exclusive_scan(keep_face, face_at, nf));
-        uint64_t vertices = 0, faces = 0;
-        HIP_TRY(hipMemcpy(&vertices, vertex_at + nv, 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&faces, face_at + nf, 8, hipMemcpyDeviceToHost));
-        Scratch made;
-        if (const int rc = alloc(made, out, (size_t)vertices, (size_t)faces); rc != APD_OK) {
-            return rc;
-        }
-        if (vertices > 0) {
-            hipLaunchKernelGGL(k_mesh_gather_vertices, grid_of(nv), dim3(256), 0, 0, (const uint32_t *)used, (const uint64_t *)vertex_at, nv,
-                               (const float *)m->xyz, (const uint8_t *)m->bgr, (const float *)m->normal, out->xyz, out->bgr, out->normal);
-            HIP_TRY(hipGetLastError());
-        }
-        if (faces > 0) {
-            hipLaunchKernelGGL(k_mesh_gather_faces, grid_of(nf), dim3(256), 0, 0, index, keep_face, (const uint64_t *)face_at, nf,
-                               (const uint64_t *)vertex_at, out->index);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipDeviceSynchronize());
-        keep(made, out);
         return APD_OK;
     }
 
@@ -496,33 +378,7 @@ struct Call : Search {
     }
 };
 
-Call call_of(const char *who) { return Call{{who}}; }
-
-// A new mesh like m without vertices or faces: its device and whether it carries colour and normals
-apd_mesh *new_mesh_like(const apd_mesh *m)
-{
-    apd_mesh *out = new apd_mesh();
-    out->device = m->device;
-    out->colour = m->colour;
-    out->normals = m->normals;
-    return out;
-}
-
-// The tail of an entry point that answers with a new mesh: body(result) fills it from m (which has vertices) or fails with its
-// message set; a mesh without vertices gives one without, and touches no device
-template <typename Body> int into_new_mesh(apd_mesh_t m, apd_mesh *result, apd_mesh_t *out, Body &&body)
-{
-    clear_timing();
-    if (m->vertices > 0) {
-        DeviceScope scope(true);
-        if (const int rc = body(result); rc != APD_OK) {
-            delete result;  // it holds nothing: what the call allocated went with its scratch
-            return rc;
-        }
-    }
-    *out = result;
-    return APD_OK;
-}
+Call call_of(const char *who) { return Call{{{who}}}; }
 
 }  // namespace
 

@@ -1,5 +1,5 @@
 // apd_mesh_host.h -- the mesh object (apd_mesh_t of include/apd_mi355x.h), seen by who makes one (apd_volume.hip: extraction) and by
-// who owns its life, its files and its cleaning (apd_mesh.hip).
+// who owns its life, its files and its cleaning (apd_mesh.hip) and its simplification (apd_mesh_simplify.hip).
 #pragma once
 
 #include <stdint.h>

@@ -16,7 +16,8 @@
 // product rounded before it is added.
 // Covariance (normal_solve): m_a = s[a] / n;  C_ab = q - r with q = S_ab / n and r = m_a * m_b, for the six a <= b.
 //
-// Eigen-solve.  Cyclic Jacobi on the symmetric 3 x 3 matrix A = C with V = I, in binary64, with + - * / and sqrt alone.  An
+// Eigen-solve (normal_jacobi, which contract C23 calls on its own matrix).  Cyclic Jacobi on the symmetric 3 x 3 matrix A = C with
+// V = I, in binary64, with + - * / and sqrt alone.  An
 // off-diagonal A_pq is SETTLED when g = |A_pq| changes neither diagonal: |A_pp| + g == |A_pp| and |A_qq| + g == |A_qq| (zero
 // is settled).  Before every sweep: if all three are settled, stop; if kNormalSweepCap sweeps are done, stop (`capped`, which
 // no point of the tests' clouds reaches: DESIGN.md section 4).  A sweep visits (0,1), (0,2), (1,2) in that order; a settled entry
@@ -129,13 +130,13 @@ APD_HD_FLAT void normal_rotate(double &app, double &aqq, double &apq, double &ar
 
 APD_HD double normal_clamped(double x) { return x > 0.0 ? x : 0.0; }
 
-// The estimate of a point with the sums m (m.n >= 1) and the stored normal N.  sweeps: the sweeps taken; capped: stopped by the cap
-APD_HD_FLAT void normal_solve(const NormalSums &m, const float N[3], float normal[3], float &variation, unsigned &sweeps, bool &capped)
+// The cyclic Jacobi of the contract on the symmetric matrix A (its six entries a_pq, p <= q) with V = I: on return the diagonal of A
+// holds the eigenvalues, unclamped and unsorted, and column k of V (v0k, v1k, v2k) the vector of a_kk.  The one loop of normal_solve
+// and of simplify_place (apd_simplify_math.h, contract C23).  sweeps: the sweeps taken; capped: stopped by the cap
+APD_HD_FLAT void normal_jacobi(double &a00, double &a01, double &a02, double &a11, double &a12, double &a22, double &v00, double &v01, double &v02,
+                               double &v10, double &v11, double &v12, double &v20, double &v21, double &v22, unsigned &sweeps, bool &capped)
 {
-    const double mx = m.s[0] / m.n, my = m.s[1] / m.n, mz = m.s[2] / m.n;
-    double a00 = normal_covariance(m.xx, mx, mx, m.n), a01 = normal_covariance(m.xy, mx, my, m.n), a02 = normal_covariance(m.xz, mx, mz, m.n);
-    double a11 = normal_covariance(m.yy, my, my, m.n), a12 = normal_covariance(m.yz, my, mz, m.n), a22 = normal_covariance(m.zz, mz, mz, m.n);
-    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+    v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
     sweeps = 0;
     capped = false;
     for (;;) {
@@ -163,6 +164,16 @@ APD_HD_FLAT void normal_solve(const NormalSums &m, const float N[3], float norma
         }
         ++sweeps;
     }
+}
+
+// The estimate of a point with the sums m (m.n >= 1) and the stored normal N.  sweeps: the sweeps taken; capped: stopped by the cap
+APD_HD_FLAT void normal_solve(const NormalSums &m, const float N[3], float normal[3], float &variation, unsigned &sweeps, bool &capped)
+{
+    const double mx = m.s[0] / m.n, my = m.s[1] / m.n, mz = m.s[2] / m.n;
+    double a00 = normal_covariance(m.xx, mx, mx, m.n), a01 = normal_covariance(m.xy, mx, my, m.n), a02 = normal_covariance(m.xz, mx, mz, m.n);
+    double a11 = normal_covariance(m.yy, my, my, m.n), a12 = normal_covariance(m.yz, my, mz, m.n), a22 = normal_covariance(m.zz, mz, mz, m.n);
+    double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+    normal_jacobi(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22, sweeps, capped);
     const double e0 = normal_clamped(a00), e1 = normal_clamped(a11), e2 = normal_clamped(a22);
     // the column of the smallest, the lowest among equals
     const bool second = e1 < e0;

@@ -7,18 +7,19 @@
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
 //       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
 //       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]]
-//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-normals]
+//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals]
 //
 // --mesh VOXEL[,TRUNC]: besides everything else, APD/APD.ply.mesh: a binary PLY with faces, the marching-tetrahedra mesh of a signed
 // distance volume with samples VOXEL apart and a truncation distance of TRUNC (4 * VOXEL unless given) over the box of the points
 // of APD.ply, integrated from the filtered maps of --filtered-maps (which need not be given) with the views' colours
 // (apd_volume_create, apd_volume_integrate, apd_volume_extract_mesh; RunMesh, host/fusion.cpp).  Every driver takes it; refused
 // with --no-fusion, which leaves no cloud to take the box from.  Without the flag no output changes.
-// --mesh-weld TOL, --mesh-min-component FACES, --mesh-normals: what becomes of that mesh before it is written, in this fixed order
-// whatever the order of the flags: vertices within TOL of each other, through chains, become the one with the smallest index and
+// --mesh-weld TOL, --mesh-min-component FACES, --mesh-simplify CELL[,mean|quadric], --mesh-normals: what becomes of that mesh before it
+// is written, in this fixed order whatever the order of the flags: vertices within TOL of each other, through chains, become the one with the smallest index and
 // the faces that collapse go (apd_mesh_weld; VOXEL * 1e-4 welds only coincident vertices); the connected components of fewer than
-// FACES faces go with the vertices only they name (apd_mesh_remove_small_components); the file carries nx ny nz, area-weighted
-// vertex normals (apd_mesh_with_vertex_normals).  One line per step is printed with the counts before and after.  Each is refused
+// FACES faces go with the vertices only they name (apd_mesh_remove_small_components); the vertices of one cell of size CELL become
+// one, placed by the quadric of the faces around them or at their mean (apd_mesh_simplify, contract C23); the file carries nx ny
+// nz, area-weighted vertex normals (apd_mesh_with_vertex_normals).  One line per step is printed with the counts before and after.  Each is refused
 // without --mesh and on a malformed value, with the usage line, before anything is read.  Without them APD.ply.mesh keeps its bytes.
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
@@ -236,6 +237,17 @@ bool ParseOptions(int argc, char **argv, Options &o)
             }
             o.mesh_clean.remove_small = true;
             o.mesh_clean.min_component = (unsigned)n;
+            mesh_flag = a;
+        } else if (a == "--mesh-simplify") {
+            const std::string both = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = both.find(',');
+            const std::string how = comma == std::string::npos ? "quadric" : both.substr(comma + 1);
+            if (!ply_value::Radius(both.substr(0, comma), o.mesh_clean.simplify) || (how != "mean" && how != "quadric")) {
+                o.mesh_clean.simplify = 0.0f;
+                fprintf(stderr, "bad value '%s' of %s: CELL[,mean|quadric], CELL a positive number\n", both.c_str(), a.c_str());
+                return false;
+            }
+            o.mesh_clean.simplify_mean = how == "mean";
             mesh_flag = a;
         } else if (a == "--mesh-normals") {
             o.mesh_clean.normals = true;
@@ -457,7 +469,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"

@@ -1032,6 +1032,45 @@ int apd_mesh_with_vertex_normals(apd_mesh_t mesh, apd_mesh_t *out);
 int apd_mesh_has_normals(apd_mesh_t mesh);
 int apd_mesh_download_normals(apd_mesh_t mesh, float *nxyz);
 
+/* apd_mesh_simplify: the mesh thinned by vertex clustering on the cubic grid of cell size `cell` at origin3 (NULL: 0, 0, 0), each
+ * cluster's vertex placed at its members' mean (APD_SIMPLIFY_MEAN) or on the surface, on creases and on corners by the quadric of
+ * the faces around its members (APD_SIMPLIFY_QUADRIC) -- arithmetic contract C23, the rules written once in
+ * csrc/apd_simplify_math.h.  Like the other mesh calls it leaves its input as it is, gives a new mesh on the input's device that
+ * shares nothing with it, is a function of the input alone (stable sorts and scans, every sum walked in a fixed order, no
+ * floating-point atomic) and has no host implementation.
+ *   Clusters.  Vertex v is inside the grid when the voxel key of contract C10 exists for (P_v, origin, cell).  A cluster is the set
+ *   of inside vertices with one key, its members in ascending vertex index; clusters are ordered by ascending key.  A vertex
+ *   outside the grid (a non-finite coordinate, a cell beyond +-2^20) belongs to no cluster.
+ *   Faces.  A face that names an outside vertex is dropped.  Every other face has each index replaced by its cluster; a face that
+ *   then names a cluster twice is dropped.  Of the rest two are duplicates when their triples are equal after each is rotated (not
+ *   reflected) so that its smallest cluster comes first -- reflected triples are different faces and both stay --, and of a set of
+ *   duplicates the face with the smallest input index survives.  Surviving faces keep the input order and their corner order.  A
+ *   cluster survives when a surviving face names it; surviving clusters are numbered in key order and the faces renumbered.
+ *   Colour, both placements: per channel (sum + m / 2) / m over the m members in unsigned 64-bit, the rule of the voxel merge.
+ *   Normals: the result has none, whatever the input had.  The normal of a simplified surface is that of its new faces:
+ *   apd_mesh_with_vertex_normals is the step to run after.
+ *   MEAN: per component the binary32 sum of the members' positions in member order, from the first member's value, divided by
+ *   (float)m -- the position rule of the voxel merge.
+ *   QUADRIC, all in binary64, every product and sum one IEEE operation in the order written.  (1) c_a = (double)origin_a +
+ *   ((double)i_a + 0.5) * (double)cell, the centre of the cluster's cell (i signed).  (2) mu_a = (sum over the members of
+ *   ((double)P_a - c_a), from +0.0) / (double)m.  (3) Over the corners (f, k) of the input faces whose three vertices are all
+ *   inside the grid -- whether or not the face survives -- with index[3 f + k] a member, in ascending 3 f + k (a face with two
+ *   corners in the cluster adds twice): g = the binary64 cross product of face f as for the vertex normals, a_a = (double)A_a - c_a
+ *   with A the face's first corner, d = -((g0 * a0 + g1 * a1) + g2 * a2); S_ij += g_i * g_j for the six i <= j and t_a += g_a * d,
+ *   from +0.0.  (4) q_a = (S_a0 * mu0 + S_a1 * mu1) + S_a2 * mu2, r_a = (-t_a) - q_a.  (5) The cyclic Jacobi of contract C14 on S:
+ *   eigenvalues lambda_k (unclamped) with vectors e_k, lmax the largest.  (6) x = mu; for k = 0, 1, 2 where lambda_k > 0 and
+ *   lambda_k > 1e-3 * lmax: p = ((e_0k * r0 + e_1k * r1) + e_2k * r2) / lambda_k, x_a = x_a + e_ak * p: the vertex moves only along
+ *   the directions the faces constrain.  (7) x is accepted when every |x_a| <= (double)cell (a NaN fails); otherwise, or when a
+ *   sum is not finite or lmax is not > 0, x = mu.  (8) The position is (float)(c_a + x_a).
+ * *removed_vertices and *removed_faces (may be NULL): how many fewer the result has.  A mesh without vertices gives a mesh
+ * without, with no device touched.  Refused with APD_ERR_INVALID before any device is touched, message "apd_mesh_simplify: ...":
+ * a NULL mesh or out, a cell that is not positive and finite, an origin that is not finite, a placement other than the two.
+ * APD_ERR_UNSUPPORTED where 3 * faces reaches 2^32, as for the normals.  Outputs are untouched on failure.
+ * apd_fusion_last_timing reports the call like the other mesh calls. */
+enum { APD_SIMPLIFY_MEAN = 0, APD_SIMPLIFY_QUADRIC = 1 };
+int apd_mesh_simplify(apd_mesh_t mesh, float cell, const float *origin3 /* NULL: 0,0,0 */, int placement, apd_mesh_t *out,
+                      long long *removed_vertices, long long *removed_faces);
+
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
  * points in memory (*points, released with apd_points_destroy; untouched when the call fails), or both from one fusion.  With
  * ply_normals the file has the properties x y z nx ny nz (float) before the three colour bytes.  Refused with APD_ERR_INVALID
