@@ -11,7 +11,9 @@ exception tests/test_gpu_edge_cases.py already makes: a float word that is NaN o
 and payload (tiny frames do produce NaN costs in the oracle); a NaN on one side only is a difference.  The oracle's own
 behaviour at the tiny shapes has its witnesses in tests/test_oracle_frame_limits.py.
 
-Lines starting with FRAME_LIMITS carry the non-vacuity figures the tests measured (profiles/frame_limits/test_times.txt)."""
+Lines starting with FRAME_LIMITS carry the non-vacuity figures the tests measured (profiles/frame_limits/test_times.txt).
+
+Frames with both axes large, 2^26 px up to 16384 x 16382, where 32-bit index products can wrap: tests/test_gpu_frame_area.py."""
 import ctypes as C
 
 import numpy as np

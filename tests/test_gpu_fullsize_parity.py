@@ -6,7 +6,9 @@ XCD-banded grids, LDS windows and 16/32-bit index arithmetic of the real size --
 windows from the HIP path's own pre-kernel state, and every state array is compared inside the windows as raw bits.
 Windows: the image corner (clamped patches, the 6-pixel UNKNOWN border), the centre, a window across the seam between the
 tile bands of two XCDs, the bottom-right corner (last partial tile, HALF-launch rows), and for the APD configs windows
-inside and on the rim of a textureless region, where K3's neighbour search walks hundreds of pixels (APD.cu:1750-1969)."""
+inside and on the rim of a textureless region, where K3's neighbour search walks hundreds of pixels (APD.cu:1750-1969).
+
+Frames with both axes large, 2^26 px up to 16384 x 16382, where 32-bit index products can wrap: tests/test_gpu_frame_area.py."""
 import numpy as np
 import pytest
 
