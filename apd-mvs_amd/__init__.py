@@ -239,6 +239,8 @@ def lib():
     L.apd_mesh_with_vertex_normals.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.apd_mesh_simplify.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
                                     C.POINTER(C.c_longlong)]
+    L.apd_mesh_adjacency.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.apd_mesh_smooth.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
     L.apd_mesh_has_normals.argtypes = [C.c_void_p]
     L.apd_mesh_download_normals.argtypes = [C.c_void_p, C.c_void_p]
     L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -1030,10 +1032,14 @@ class Mesh:
     """An indexed triangle mesh (apd_mesh_t) as Volume.extract_mesh() or Mesh.from_arrays() makes it: vertices float32 [n, 3], colours
     uint8 [n, 3] (blue, green, red; None for a mesh without colour), normals float32 [n, 3] (None until with_vertex_normals() has
     made them) and faces int32 [m, 3], numpy arrays that are copies and outlive the object; write_ply() writes the library's file
-    (apd_mesh_write_ply).  weld(), remove_small_components(), simplify() and with_vertex_normals() each give a new Mesh and leave this
-    one as it is (arithmetic contracts C22 and C23); components() labels the faces.  A mesh may be empty."""
+    (apd_mesh_write_ply).  weld(), remove_small_components(), smooth(), simplify() and with_vertex_normals() each give a new Mesh and
+    leave this one as it is (arithmetic contracts C22, C23 and C24); components() labels the faces, adjacency() tells every vertex's
+    valence and whether the mesh is closed and manifold.  `moved`: after smooth(), on this mesh and on the result, the vertices the first step moved.  A mesh may
+    be empty."""
 
     PLACEMENTS = {"mean": 0, "quadric": 1}   # APD_SIMPLIFY_MEAN, APD_SIMPLIFY_QUADRIC
+    BOUNDARIES = {"fixed": 0, "along": 1, "free": 2}   # APD_SMOOTH_BOUNDARY_FIXED, _ALONG, _FREE
+    moved = None
 
     def __init__(self, handle):
         self._m = handle
@@ -1120,6 +1126,37 @@ class Mesh:
         if rc != 0:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         return Mesh(out)
+
+    def adjacency(self):
+        """apd_mesh_adjacency: (valence uint32 [n], boundary bool [n], edges, boundary_edges, nonmanifold_edges) of the vertex-to-vertex
+        adjacency (contract C24): every vertex's number of distinct neighbours and whether one of its edges has a single face side, and
+        the numbers of undirected edges, of edges with one face side and of edges with three or more.  A closed mesh has no boundary
+        edge, a manifold one no non-manifold edge."""
+        L = self._open("adjacency")
+        valence, boundary = np.zeros(len(self.vertices), np.uint32), np.zeros(len(self.vertices), np.uint8)
+        counts = [C.c_longlong(0) for _ in range(3)]
+        rc = L.apd_mesh_adjacency(self._m, C.c_void_p(valence.ctypes.data), C.c_void_p(boundary.ctypes.data), *[C.byref(c) for c in counts])
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return (valence, boundary.astype(bool)) + tuple(c.value for c in counts)
+
+    def smooth(self, iterations, lam=0.5, mu=-0.53, boundary="along"):
+        """apd_mesh_smooth: the Mesh after `iterations` iterations of smoothing (arithmetic contract C24): every vertex moves by `lam`
+        towards the mean of its neighbours and then, unless mu is 0, by `mu` (negative: away from it).  lam = 0.5 with mu = -0.53 is
+        Taubin's pair, which does not shrink the surface; mu = 0 is plain Laplacian smoothing.  boundary: what becomes of the vertices
+        on an edge with a single face: "fixed" holds them, "along" moves them among their neighbours along the border, "free" treats
+        them as the rest.  Same faces, colours and vertex count; no normals: with_vertex_normals() is the step to run after.
+        `moved` of this Mesh and of the result is then the number of vertices the first step moved."""
+        L = self._open("smooth")
+        if boundary not in self.BOUNDARIES:
+            raise ValueError("Mesh.smooth: boundary %r, none of 'fixed', 'along' and 'free'" % (boundary,))
+        out, moved = C.c_void_p(), C.c_longlong(0)
+        rc = L.apd_mesh_smooth(self._m, int(iterations), float(lam), float(mu), self.BOUNDARIES[boundary], C.byref(out), C.byref(moved))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        result = Mesh(out)
+        self.moved = result.moved = moved.value
+        return result
 
     def simplify(self, cell, origin=None, placement="quadric"):
         """apd_mesh_simplify: the Mesh thinned by vertex clustering (arithmetic contract C23): the vertices of one cell of the grid of

@@ -855,7 +855,7 @@ void filter_and_write(const std::vector<Problem> &problems, const std::vector<Fu
 // --mesh: the filter, then the volume over the box of the finite points of ply_path grown by trunc -- origin = lo - trunc and per
 // axis the fewest samples, at least 2, whose last one is at or past hi + trunc, in the arithmetic of the Python binding's
 // Volume.around --, the filtered maps with the views' colour images (3 channels) into it, every view weighing 1, and the mesh
-// into <ply_path>.mesh, after the steps of `clean` in their fixed order -- weld, small components, simplification, normals --, each a new mesh that
+// into <ply_path>.mesh, after the steps of `clean` in their fixed order -- weld, small components, smoothing, simplification, normals --, each a new mesh that
 // replaces the one before and a printed line with the counts before and after.  A failure ends the program like every other device
 // error.
 void mesh_and_write(const path &ply_path, const std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const float *const *depths,
@@ -937,6 +937,20 @@ void mesh_and_write(const path &ply_path, const std::vector<FusionView> &views, 
         long long components = 0;
         const int rc = apd_mesh_remove_small_components(mesh, clean.min_component, &next, nullptr, &components);
         replaced(rc, next, "without the components of fewer than " + std::to_string(clean.min_component) + " faces among " + std::to_string(components));
+    }
+    if (clean.smooth > 0) {
+        apd_mesh_t next = nullptr;
+        long long moved = 0;
+        const int rc = apd_mesh_smooth(mesh, clean.smooth, clean.smooth_lambda, clean.smooth_mu, clean.smooth_boundary, &next, &moved);
+        if (rc != APD_OK) {
+            failed(apd_fusion_last_error());
+        }
+        static const char *const modes[3] = {"fixed", "along", "free"};
+        printf("Mesh smoothed in %d iterations (lambda %f, mu %f, %s boundary): %lld of %lld vertices moved\n", clean.smooth, (double)clean.smooth_lambda,
+               (double)clean.smooth_mu, modes[clean.smooth_boundary], moved, vertices);
+        fflush(stdout);
+        apd_mesh_destroy(mesh);
+        mesh = next;
     }
     if (clean.simplify > 0.0f) {
         apd_mesh_t next = nullptr;

@@ -7,17 +7,21 @@
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
 //       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
 //       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]]
-//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals]
+//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals]
 //
 // --mesh VOXEL[,TRUNC]: besides everything else, APD/APD.ply.mesh: a binary PLY with faces, the marching-tetrahedra mesh of a signed
 // distance volume with samples VOXEL apart and a truncation distance of TRUNC (4 * VOXEL unless given) over the box of the points
 // of APD.ply, integrated from the filtered maps of --filtered-maps (which need not be given) with the views' colours
 // (apd_volume_create, apd_volume_integrate, apd_volume_extract_mesh; RunMesh, host/fusion.cpp).  Every driver takes it; refused
 // with --no-fusion, which leaves no cloud to take the box from.  Without the flag no output changes.
-// --mesh-weld TOL, --mesh-min-component FACES, --mesh-simplify CELL[,mean|quadric], --mesh-normals: what becomes of that mesh before it
+// --mesh-weld TOL, --mesh-min-component FACES, --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify
+// CELL[,mean|quadric], --mesh-normals: what becomes of that mesh before it
 // is written, in this fixed order whatever the order of the flags: vertices within TOL of each other, through chains, become the one with the smallest index and
 // the faces that collapse go (apd_mesh_weld; VOXEL * 1e-4 welds only coincident vertices); the connected components of fewer than
-// FACES faces go with the vertices only they name (apd_mesh_remove_small_components); the vertices of one cell of size CELL become
+// FACES faces go with the vertices only they name (apd_mesh_remove_small_components); every vertex moves ITERATIONS times towards the
+// mean of its neighbours by LAMBDA (0.5) and then by MU (-0.53: Taubin's pair, which does not shrink; 0: plain Laplacian), the border
+// vertices held (fixed), moved along the border (along, the default) or treated like the rest (free) (apd_mesh_smooth, contract C24);
+// the vertices of one cell of size CELL become
 // one, placed by the quadric of the faces around them or at their mean (apd_mesh_simplify, contract C23); the file carries nx ny
 // nz, area-weighted vertex normals (apd_mesh_with_vertex_normals).  One line per step is printed with the counts before and after.  Each is refused
 // without --mesh and on a malformed value, with the usage line, before anything is read.  Without them APD.ply.mesh keeps its bytes.
@@ -237,6 +241,40 @@ bool ParseOptions(int argc, char **argv, Options &o)
             }
             o.mesh_clean.remove_small = true;
             o.mesh_clean.min_component = (unsigned)n;
+            mesh_flag = a;
+        } else if (a == "--mesh-smooth") {
+            const std::string all = i + 1 < argc ? argv[++i] : "";
+            std::vector<std::string> t;
+            for (size_t from = 0; t.size() < 5; ) {
+                const size_t comma = all.find(',', from);
+                t.push_back(all.substr(from, comma == std::string::npos ? std::string::npos : comma - from));
+                if (comma == std::string::npos) {
+                    break;
+                }
+                from = comma + 1;
+            }
+            MeshClean c = o.mesh_clean;
+            unsigned long long n = 0;
+            char *end = nullptr;
+            bool good = t.size() <= 4 && ply_value::Count(t[0], 1, 1000, n);
+            if (good && t.size() > 1) {
+                good = ply_value::Real(t[1], c.smooth_lambda) && c.smooth_lambda > 0.0f && c.smooth_lambda <= 1.0f;
+            }
+            if (good && t.size() > 2) {
+                c.smooth_mu = strtof(t[2].c_str(), &end);
+                good = end != t[2].c_str() && *end == '\0' && c.smooth_mu >= -2.0f && c.smooth_mu <= 0.0f;
+            }
+            if (good && t.size() > 3) {
+                c.smooth_boundary = t[3] == "fixed" ? APD_SMOOTH_BOUNDARY_FIXED : t[3] == "along" ? APD_SMOOTH_BOUNDARY_ALONG : t[3] == "free" ? APD_SMOOTH_BOUNDARY_FREE : -1;
+                good = c.smooth_boundary >= 0;
+            }
+            if (!good) {
+                fprintf(stderr, "bad value '%s' of %s: ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], a count of 1 .. 1000, LAMBDA in (0, 1], MU in [-2, 0]\n", all.c_str(),
+                        a.c_str());
+                return false;
+            }
+            c.smooth = (int)n;
+            o.mesh_clean = c;
             mesh_flag = a;
         } else if (a == "--mesh-simplify") {
             const std::string both = i + 1 < argc ? argv[++i] : "";
@@ -469,7 +507,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"

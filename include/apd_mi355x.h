@@ -1071,6 +1071,43 @@ enum { APD_SIMPLIFY_MEAN = 0, APD_SIMPLIFY_QUADRIC = 1 };
 int apd_mesh_simplify(apd_mesh_t mesh, float cell, const float *origin3 /* NULL: 0,0,0 */, int placement, apd_mesh_t *out,
                       long long *removed_vertices, long long *removed_faces);
 
+/* apd_mesh_adjacency and apd_mesh_smooth: the vertex-to-vertex adjacency of a mesh with its edge multiplicities, and Laplacian or
+ * Taubin lambda|mu smoothing of the vertex positions over it -- arithmetic contract C24, the rules written once in
+ * csrc/apd_mesh_smooth_math.h.  Like the other mesh calls they leave their input as it is, are functions of the input alone (a
+ * stable sort and scans, every sum walked by one lane in a fixed order, no atomic) and have no host implementation.
+ *   Adjacency (integers only).  Every face (a, b, c) gives the six directed pairs (a,b), (b,a), (b,c), (c,b), (c,a), (a,c); a pair
+ *   with equal ends is dropped (a face may repeat an index).  The neighbours of v are the distinct w of its pairs, ascending.  The
+ *   multiplicity of the edge {v, w} is the number of times the pair (v, w) occurs: the number of face sides on the edge.
+ *   Multiplicity 1 is a boundary edge, 3 or more a non-manifold edge; a vertex is a boundary vertex when one of its edges is a
+ *   boundary edge.  A vertex no face names has no neighbours and is not a boundary vertex.  Two equal faces give their edges
+ *   multiplicity 2.
+ *   One step with a factor k (a float, widened to binary64), positions p to p'.  Neighbour w of v contributes when the three
+ *   coordinates of p[w] are finite; under APD_SMOOTH_BOUNDARY_ALONG a boundary vertex takes only the neighbours across its boundary
+ *   edges, under _FIXED a boundary vertex does not move, under _FREE it is treated as any other.  A vertex moves when it is not held
+ *   fixed, its own position is finite and at least one neighbour contributes; then per coordinate s = the binary64 sum of
+ *   (double)p[w] over the contributing neighbours in ascending w from +0.0, m = s / (double)count, p'[v] = (float)((double)p[v] +
+ *   k * (m - (double)p[v])), every operation one IEEE operation.  For every other vertex p'[v] = p[v], the same bits.
+ *   An iteration is a step with lambda, followed, when mu != 0, by a step with mu: mu = 0 is plain Laplacian smoothing, lambda =
+ *   0.5 with mu = -0.53 is Taubin's pair, which does not shrink.  Every step reads only the positions of the step before it; the
+ *   adjacency is built once per call and the boundary flags, which come from the connectivity, stay.
+ * apd_mesh_adjacency: valence[v] = the number of neighbours of v and boundary[v] = 1 for a boundary vertex, 0 otherwise (host
+ * arrays, one entry per vertex); *edges = the undirected edges, *boundary_edges and *nonmanifold_edges those of multiplicity 1 and
+ * of 3 or more: a mesh is closed when it has no boundary edge and manifold along its edges when it has no non-manifold one.  Every
+ * output may be NULL, not all of them.
+ * apd_mesh_smooth: `iterations` iterations into *out, a new mesh on the input's device with the same faces, colours and vertex
+ * count, and no normals, whatever the input had: they would be stale, apd_mesh_with_vertex_normals is the step to run after.
+ * *moved (may be NULL): the vertices that move in the first step.  A mesh without faces or without vertices gives a copy without
+ * normals and *moved = 0.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_mesh_adjacency: ..." or "apd_mesh_smooth: ...": a NULL
+ * mesh or out, outputs all NULL, iterations outside 1 .. 1000, lambda not in (0, 1], mu not in [-2, 0] or not finite, a boundary
+ * mode other than the three.  APD_ERR_UNSUPPORTED where 6 * faces reaches 2^32: the positions of the neighbour lists are 32-bit, as
+ * the corners of the vertex normals are.  Outputs are untouched on failure.  apd_fusion_last_timing reports the calls like the
+ * other mesh calls. */
+enum { APD_SMOOTH_BOUNDARY_FIXED = 0, APD_SMOOTH_BOUNDARY_ALONG = 1, APD_SMOOTH_BOUNDARY_FREE = 2 };
+int apd_mesh_adjacency(apd_mesh_t mesh, uint32_t *valence, uint8_t *boundary, long long *edges, long long *boundary_edges,
+                       long long *nonmanifold_edges);
+int apd_mesh_smooth(apd_mesh_t mesh, int iterations, float lambda, float mu, int boundary, apd_mesh_t *out, long long *moved);
+
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
  * points in memory (*points, released with apd_points_destroy; untouched when the call fails), or both from one fusion.  With
  * ply_normals the file has the properties x y z nx ny nz (float) before the three colour bytes.  Refused with APD_ERR_INVALID
