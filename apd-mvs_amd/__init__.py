@@ -241,6 +241,12 @@ def lib():
                                     C.POINTER(C.c_longlong)]
     L.apd_mesh_adjacency.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.apd_mesh_smooth.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]
+    L.apd_mesh_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_void_p, C.c_void_p]
+    L.apd_mesh_face_visibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+    L.apd_mesh_remove_unseen.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_uint, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.apd_mesh_render_split.argtypes = [C.c_int]
+    L.apd_mesh_render_split.restype = None
     L.apd_mesh_has_normals.argtypes = [C.c_void_p]
     L.apd_mesh_download_normals.argtypes = [C.c_void_p, C.c_void_p]
     L.apd_device_memcpy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -1034,12 +1040,16 @@ class Mesh:
     made them) and faces int32 [m, 3], numpy arrays that are copies and outlive the object; write_ply() writes the library's file
     (apd_mesh_write_ply).  weld(), remove_small_components(), smooth(), simplify() and with_vertex_normals() each give a new Mesh and
     leave this one as it is (arithmetic contracts C22, C23 and C24); components() labels the faces, adjacency() tells every vertex's
-    valence and whether the mesh is closed and manifold.  `moved`: after smooth(), on this mesh and on the result, the vertices the first step moved.  A mesh may
+    valence and whether the mesh is closed and manifold.  render() rasterises the mesh into a camera, face_visibility() counts the
+    cameras that see each face and remove_unseen() drops the faces too few see (contract C25).  `moved`: after smooth(), on this mesh and on the result, the vertices the first step moved.  A mesh may
     be empty."""
 
     PLACEMENTS = {"mean": 0, "quadric": 1}   # APD_SIMPLIFY_MEAN, APD_SIMPLIFY_QUADRIC
     BOUNDARIES = {"fixed": 0, "along": 1, "free": 2}   # APD_SMOOTH_BOUNDARY_FIXED, _ALONG, _FREE
+    CULLS = {"none": 0, "back": 1}   # APD_RENDER_CULL_NONE, _BACK
     moved = None
+    unseen = None          # after face_visibility(): the faces no camera sees
+    removed_faces = None   # after remove_unseen(), on this mesh and on the result: the faces that went
 
     def __init__(self, handle):
         self._m = handle
@@ -1156,6 +1166,63 @@ class Mesh:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         result = Mesh(out)
         self.moved = result.moved = moved.value
+        return result
+
+    def _cull(self, what, cull):
+        if cull not in self.CULLS:
+            raise ValueError("Mesh.%s: cull %r, neither 'none' nor 'back'" % (what, cull))
+        return self.CULLS[cull]
+
+    def render(self, camera, cull="none"):
+        """apd_mesh_render: (depth float32 [height, width], face uint32 [height, width]) -- this mesh rasterised into `camera` (a
+        Camera: K, R, t, width, height) with a z-buffer (arithmetic contract C25): per pixel the perspective-correct depth of the
+        nearest face that covers the pixel centre and that face's index, the lowest among equal depths; 0 and 0xFFFFFFFF where no
+        face covers.  cull: "none" draws both sides, "back" only the faces whose right-hand normal points at the camera.  A face
+        with a corner behind the camera or beyond the guard band of 2^19 pixels is not drawn at all: there is no clipping."""
+        L = self._open("render")
+        cam = Camera.from_buffer_copy(camera)
+        shape = (max(int(cam.height), 0), max(int(cam.width), 0))
+        depth, face = np.zeros(shape, np.float32), np.zeros(shape, np.uint32)
+        nothing = (C.c_uint32 * 1)()   # where a camera without pixels gets its no maps: the library refuses the camera, not a NULL
+        rc = L.apd_mesh_render(self._m, C.byref(cam), self._cull("render", cull),
+                               *[C.c_void_p(a.ctypes.data if a.size else C.addressof(nothing)) for a in (depth, face)])
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return depth, face
+
+    @staticmethod
+    def _cameras(cameras):
+        return cameras if isinstance(cameras, C.Array) else (Camera * max(len(cameras), 1))(*[Camera.from_buffer_copy(c) for c in cameras])
+
+    def face_visibility(self, cameras, cull="back", min_pixels=1, rel_tolerance=0.01):
+        """apd_mesh_face_visibility: (views uint32 [m], pixels uint64 [m]) -- per face the number of `cameras` (a ctypes array or a
+        sequence of Camera) that see it and the pixels it owns in their face maps together; `unseen` of this Mesh is then the number
+        of faces no camera sees.  A camera sees a face that is drawn into it and either owns at least min_pixels pixels of
+        render(camera, cull)'s face map or has all three corners within rel_tolerance * z behind the depth z at their own pixels."""
+        L = self._open("face_visibility")
+        views, pixels = np.zeros(len(self.faces), np.uint32), np.zeros(len(self.faces), np.uint64)
+        unseen = C.c_longlong(0)
+        cams = self._cameras(cameras)
+        rc = L.apd_mesh_face_visibility(self._m, len(cameras), C.byref(cams), self._cull("face_visibility", cull), int(min_pixels), float(rel_tolerance),
+                                        C.c_void_p(views.ctypes.data), C.c_void_p(pixels.ctypes.data), C.byref(unseen))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        self.unseen = unseen.value
+        return views, pixels
+
+    def remove_unseen(self, cameras, min_views=1, cull="back", min_pixels=1, rel_tolerance=0.01):
+        """apd_mesh_remove_unseen: the Mesh of the faces that at least min_views of `cameras` see (face_visibility) and of the
+        vertices they name, colours and normals carried; `removed_faces` of this Mesh and of the result is then the number of faces
+        that went.  min_views = 0 keeps every face."""
+        L = self._open("remove_unseen")
+        out, faces = C.c_void_p(), C.c_longlong(0)
+        cams = self._cameras(cameras)
+        rc = L.apd_mesh_remove_unseen(self._m, len(cameras), C.byref(cams), self._cull("remove_unseen", cull), int(min_pixels), float(rel_tolerance),
+                                      int(min_views), C.byref(out), C.byref(faces), None)
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        result = Mesh(out)
+        self.removed_faces = result.removed_faces = faces.value
         return result
 
     def simplify(self, cell, origin=None, placement="quadric"):

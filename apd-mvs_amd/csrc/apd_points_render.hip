@@ -4,13 +4,12 @@
 // relation: apd_render_math.h).
 //
 // On the points' device, on its null stream, per camera:
-//   1. k_render_clear: the key image of the camera, width * height 64-bit keys, to the empty key.
+//   1. k_render_clear: the key image of the camera, width * height 64-bit keys, to the empty key (apd_render_device.h, shared with
+//      the mesh's rasteriser, as are render_offer and k_render_resolve).
 //   2. k_render_scatter: one lane per point; the point's key (depth bits, index) goes to every pixel of its footprint with a 64-bit
-//      unsigned atomic min, relaxed, agent scope.  The min of integers does not depend on the order of arrival: the image is a
-//      function of the input.  Before the atomic a relaxed load of the pixel skips it when the key held there is already smaller:
-//      keys only ever decrease, so a value read early can only be too large and a skip decided on it stays right.  The load is an
-//      agent-scope one, served by the L2 where the atomics execute: a plain load may be served by a line of the CU's L1 that no
-//      atomic ever updates.  In a cloud many layers deep all but the lanes of the front layer then end in a load.
+//      unsigned atomic min, relaxed, agent scope, after a relaxed load that skips it where the pixel already holds a smaller key
+//      (render_offer).  The min of integers does not depend on the order of arrival: the image is a function of the input.  In a
+//      cloud many layers deep all but the lanes of the front layer then end in a load.
 //   3. apd_points_render: k_render_resolve turns the keys into the depth and the index map.
 //      apd_points_rendered_visibility: k_render_test repeats the projection of every point, reads the key at its centre pixel and
 //      sets bit s of the point's row of a bitset (ceil(num_views / 32) words a point) when camera s sees it.  A row belongs to one
@@ -33,6 +32,7 @@
 #include "apd_lab.h"
 #include "apd_points_grid.h"
 #include "apd_points_host.h"
+#include "apd_render_device.h"
 #include "apd_render_math.h"
 #include "apd_sort.h"
 
@@ -44,14 +44,9 @@ using apd_points_grid::grid_of;
 using apd_points_host::DeviceScope;
 using apd_points_host::ms_since;
 using apd_points_host::Scratch;
-
-__global__ __launch_bounds__(256) void k_render_clear(uint64_t *__restrict__ keys, size_t px)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < px) {
-        keys[i] = apd_fusion::kRenderEmptyKey;
-    }
-}
+using apd_render_device::k_render_clear;
+using apd_render_device::k_render_resolve;
+using apd_render_device::render_offer;
 
 // Point k < n: its key to the pixels of its footprint.  keys: view.rows x view.cols, cleared.
 __global__ __launch_bounds__(256) void k_render_scatter(const float *__restrict__ xyz, uint32_t n, View view, int splat, uint64_t *keys)
@@ -73,30 +68,8 @@ __global__ __launch_bounds__(256) void k_render_scatter(const float *__restrict_
     for (int y = r0; y <= r1; ++y) {
         uint64_t *row = keys + (size_t)y * (size_t)view.cols;
         for (int x = c0; x <= c1; ++x) {
-#if APD_RENDER_LOAD_BEFORE_MIN
-            if (__hip_atomic_load(row + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= key) {
-                continue;
-            }
-#endif
-            __hip_atomic_fetch_min(row + x, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            render_offer(row + x, key);
         }
-    }
-}
-
-// depth and index (either may be null) of the px pixels of a key image
-__global__ __launch_bounds__(256) void k_render_resolve(const uint64_t *__restrict__ keys, size_t px, float *__restrict__ depth,
-                                                         uint32_t *__restrict__ index)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= px) {
-        return;
-    }
-    const uint64_t key = keys[i];
-    if (depth) {
-        depth[i] = apd_fusion::render_depth(key);
-    }
-    if (index) {
-        index[i] = apd_fusion::render_index(key);
     }
 }
 

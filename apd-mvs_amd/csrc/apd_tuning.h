@@ -81,3 +81,11 @@
 #ifndef APD_K910_WAVES
 #define APD_K910_WAVES 2  // waves per SIMD (profiles/r02/tune_k910_waves.txt, profiles/r03/ab_k910_list_order.txt)
 #endif
+
+// ---- apd_mesh_render.hip ----
+#ifndef APD_MESH_RENDER_SPLIT
+#define APD_MESH_RENDER_SPLIT 64  // pixels of a face's clipped bounding box above which waves draw it instead of a lane; work ms of a render into
+                                  // 3200 x 2400 at 64 / 256 / 1024: a million 5-pixel faces 2.10 / 2.09 / 2.08, 78 thousand 58-pixel faces 2.20 / 2.24 /
+                                  // 2.83, 12 thousand 359-pixel faces 2.13 / 2.38 / 3.47 (tools/mesh_render_time.py with apd_mesh_render_split,
+                                  // profiles/mesh_render/timing.txt)
+#endif

@@ -855,10 +855,11 @@ void filter_and_write(const std::vector<Problem> &problems, const std::vector<Fu
 // --mesh: the filter, then the volume over the box of the finite points of ply_path grown by trunc -- origin = lo - trunc and per
 // axis the fewest samples, at least 2, whose last one is at or past hi + trunc, in the arithmetic of the Python binding's
 // Volume.around --, the filtered maps with the views' colour images (3 channels) into it, every view weighing 1, and the mesh
-// into <ply_path>.mesh, after the steps of `clean` in their fixed order -- weld, small components, smoothing, simplification, normals --, each a new mesh that
-// replaces the one before and a printed line with the counts before and after.  A failure ends the program like every other device
-// error.
-void mesh_and_write(const path &ply_path, const std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const float *const *depths,
+// into <ply_path>.mesh, after the steps of `clean` in their fixed order -- weld, trimming of unseen faces, small components, smoothing,
+// simplification, normals --, each a new mesh that replaces the one before and a printed line with the counts before and after.  With
+// clean.depth_maps the final mesh is rendered into every view and written as depths_mesh.dmb into its result folder.  A failure ends
+// the program like every other device error.
+void mesh_and_write(const path &ply_path, const std::vector<Problem> &problems, const std::vector<FusionView> &views, const std::vector<std::vector<int>> &sources, const float *const *depths,
                     const float *const *normals, const uint8_t *const *weaks, const uint8_t *const *blocks, int cols, int rows, int maps_on_device,
                     float voxel, float trunc, const MeshClean &clean)
 {
@@ -932,6 +933,17 @@ void mesh_and_write(const path &ply_path, const std::vector<FusionView> &views, 
         const int rc = apd_mesh_weld(mesh, clean.weld, nullptr, &next, nullptr, nullptr);
         replaced(rc, next, "welded within " + std::to_string(clean.weld));
     }
+    std::vector<apd_camera> cams = f.cams;  // the views at the size of their maps: what the mesh is trimmed by and rendered into
+    for (int i = 0; i < V; ++i) {
+        cams[i].width = f.depth[i].cols;
+        cams[i].height = f.depth[i].rows;
+    }
+    if (clean.trim > 0) {
+        apd_mesh_t next = nullptr;
+        const int rc = apd_mesh_remove_unseen(mesh, V, cams.data(), APD_RENDER_CULL_BACK, clean.trim_pixels, clean.trim_tolerance, clean.trim, &next, nullptr,
+                                              nullptr);
+        replaced(rc, next, "without the faces that fewer than " + std::to_string(clean.trim) + " of " + std::to_string(V) + " views see");
+    }
     if (clean.remove_small) {
         apd_mesh_t next = nullptr;
         long long components = 0;
@@ -964,6 +976,18 @@ void mesh_and_write(const path &ply_path, const std::vector<FusionView> &views, 
     }
     if (apd_mesh_write_ply(mesh, mesh_path.c_str()) != APD_OK) {
         failed(apd_fusion_last_error());
+    }
+    for (int i = 0; clean.depth_maps && i < V; ++i) {
+        Mat rendered;
+        rendered.create(cams[i].height, cams[i].width, MAT_32FC1);
+        if (apd_mesh_render(mesh, &cams[i], APD_RENDER_CULL_NONE, rendered.ptr<float>(), nullptr) != APD_OK) {
+            failed(apd_fusion_last_error());
+        }
+        const path file = problems[i].result_folder / "depths_mesh.dmb";
+        std::filesystem::create_directories(problems[i].result_folder);
+        if (!WriteBinMat(file, rendered)) {
+            failed("cannot write " + file.string());
+        }
     }
     apd_mesh_destroy(mesh);
     apd_volume_destroy(volume);
@@ -1053,7 +1077,7 @@ void RunMesh(const path &dense_folder, const std::vector<Problem> &problems, flo
             any_block = true;
         }
     }
-    mesh_and_write(dense_folder / path("APD") / path("APD.ply"), views, sources, deps.data(), nors.data(), weaks.data(), any_block ? blocks.data() : nullptr,
+    mesh_and_write(dense_folder / path("APD") / path("APD.ply"), problems, views, sources, deps.data(), nors.data(), weaks.data(), any_block ? blocks.data() : nullptr,
                    0, 0, 0, voxel, trunc, clean);
 }
 
@@ -1085,7 +1109,7 @@ void RunMeshOnDevice(const path &dense_folder, const std::vector<Problem> &probl
     }
     const int fusion_device = g_fusion_device;
     g_fusion_device = device;
-    mesh_and_write(dense_folder / path("APD") / path("APD.ply"), views, sources, depths.data(), normals.data(), weaks.data(),
+    mesh_and_write(dense_folder / path("APD") / path("APD.ply"), problems, views, sources, depths.data(), normals.data(), weaks.data(),
                    owned.empty() ? nullptr : blocks.data(), cols, rows, 1, voxel, trunc, clean);
     g_fusion_device = fusion_device;
     for (void *p : owned) {

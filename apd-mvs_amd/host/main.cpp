@@ -7,17 +7,20 @@
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
 //       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
 //       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]]
-//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals]
+//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals]
 //
 // --mesh VOXEL[,TRUNC]: besides everything else, APD/APD.ply.mesh: a binary PLY with faces, the marching-tetrahedra mesh of a signed
 // distance volume with samples VOXEL apart and a truncation distance of TRUNC (4 * VOXEL unless given) over the box of the points
 // of APD.ply, integrated from the filtered maps of --filtered-maps (which need not be given) with the views' colours
 // (apd_volume_create, apd_volume_integrate, apd_volume_extract_mesh; RunMesh, host/fusion.cpp).  Every driver takes it; refused
 // with --no-fusion, which leaves no cloud to take the box from.  Without the flag no output changes.
-// --mesh-weld TOL, --mesh-min-component FACES, --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify
-// CELL[,mean|quadric], --mesh-normals: what becomes of that mesh before it
+// --mesh-weld TOL, --mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]], --mesh-min-component FACES, --mesh-smooth
+// ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify CELL[,mean|quadric], --mesh-normals: what becomes of that mesh before it
 // is written, in this fixed order whatever the order of the flags: vertices within TOL of each other, through chains, become the one with the smallest index and
-// the faces that collapse go (apd_mesh_weld; VOXEL * 1e-4 welds only coincident vertices); the connected components of fewer than
+// the faces that collapse go (apd_mesh_weld; VOXEL * 1e-4 welds only coincident vertices); the faces that fewer than MIN_VIEWS of
+// the views see go with the vertices only they name -- a view sees a front face that owns MIN_PIXELS (1) pixels of the mesh rasterised
+// into it or whose corners all lie within TOL (0.01) * depth behind that image (apd_mesh_remove_unseen, contract C25) --, before the
+// component filter, which then removes what the trimming detached; the connected components of fewer than
 // FACES faces go with the vertices only they name (apd_mesh_remove_small_components); every vertex moves ITERATIONS times towards the
 // mean of its neighbours by LAMBDA (0.5) and then by MU (-0.53: Taubin's pair, which does not shrink; 0: plain Laplacian), the border
 // vertices held (fixed), moved along the border (along, the default) or treated like the rest (free) (apd_mesh_smooth, contract C24);
@@ -25,6 +28,8 @@
 // one, placed by the quadric of the faces around them or at their mean (apd_mesh_simplify, contract C23); the file carries nx ny
 // nz, area-weighted vertex normals (apd_mesh_with_vertex_normals).  One line per step is printed with the counts before and after.  Each is refused
 // without --mesh and on a malformed value, with the usage line, before anything is read.  Without them APD.ply.mesh keeps its bytes.
+// --mesh-depth-maps: every view's depths_mesh.dmb beside depths_filtered.dmb, in the format of depths.dmb: the depth of the final
+// mesh rasterised into the view, both sides drawn, 0 where it covers nothing (apd_mesh_render).  Needs --mesh.
 //
 // --filtered-maps: besides everything else, every view's depths_filtered.dmb, consistency.dmb (float, as depths.dmb) and votes.bin
 // (bytes, as weak.bin) in <dense>/APD/<%08d>/: the geometric filter (apd_filter_views) on the final maps, with the --fusion-* rule
@@ -136,6 +141,7 @@
 // Not built: the debug JPEGs of show_medium_result.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -232,6 +238,39 @@ bool ParseOptions(int argc, char **argv, Options &o)
                 return false;
             }
             mesh_flag = a;
+        } else if (a == "--mesh-trim") {
+            const std::string all = i + 1 < argc ? argv[++i] : "";
+            std::vector<std::string> t;
+            for (size_t from = 0; t.size() < 4; ) {
+                const size_t comma = all.find(',', from);
+                t.push_back(all.substr(from, comma == std::string::npos ? std::string::npos : comma - from));
+                if (comma == std::string::npos) {
+                    break;
+                }
+                from = comma + 1;
+            }
+            MeshClean c = o.mesh_clean;
+            unsigned long long views = 0, pixels = 1;
+            bool good = t.size() <= 3 && ply_value::Count(t[0], 1, 0x7fffffffull, views);
+            if (good && t.size() > 1) {
+                good = ply_value::Count(t[1], 1, 0x7fffffffull, pixels);
+            }
+            if (good && t.size() > 2) {
+                char *end = nullptr;
+                c.trim_tolerance = strtof(t[2].c_str(), &end);
+                good = end != t[2].c_str() && *end == '\0' && std::isfinite(c.trim_tolerance) && c.trim_tolerance >= 0.0f;
+            }
+            if (!good) {
+                fprintf(stderr, "bad value '%s' of %s: MIN_VIEWS[,MIN_PIXELS[,TOL]], counts of at least 1 and a number that is not negative\n", all.c_str(),
+                        a.c_str());
+                return false;
+            }
+            c.trim = (unsigned)views;
+            c.trim_pixels = (unsigned)pixels;
+            o.mesh_clean = c;
+            mesh_flag = a;
+        } else if (a == "--mesh-depth-maps") {
+            o.mesh_clean.depth_maps = true;
         } else if (a == "--mesh-min-component") {
             const std::string text = i + 1 < argc ? argv[++i] : "";
             unsigned long long n = 0;
@@ -373,6 +412,10 @@ bool ParseOptions(int argc, char **argv, Options &o)
         fprintf(stderr, "--fusion-min-consistent, --fusion-reproj, --fusion-depth, --fusion-angle and --fusion-factors apply to --fusion eth only\n");
         return false;
     }
+    if (o.mesh_clean.depth_maps && !(o.mesh_voxel > 0.0f)) {
+        fprintf(stderr, "--mesh-depth-maps renders the mesh of --mesh VOXEL[,TRUNC]: not without it\n");
+        return false;
+    }
     if (!mesh_flag.empty() && !(o.mesh_voxel > 0.0f)) {
         fprintf(stderr, "%s changes the mesh of --mesh VOXEL[,TRUNC]: not without it\n", mesh_flag.c_str());
         return false;
@@ -507,7 +550,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"

@@ -13,10 +13,15 @@
 #include "APD.h"
 #include "ply_options.h"
 
-// What --mesh does to its mesh between extraction and the file, in this fixed order: apd_mesh_weld, apd_mesh_remove_small_components,
-// apd_mesh_smooth, apd_mesh_simplify, apd_mesh_with_vertex_normals.  All off: the file has the bytes of the extracted mesh.
+// What --mesh does to its mesh between extraction and the file, in this fixed order: apd_mesh_weld, apd_mesh_remove_unseen,
+// apd_mesh_remove_small_components, apd_mesh_smooth, apd_mesh_simplify, apd_mesh_with_vertex_normals.  All off: the file has the bytes
+// of the extracted mesh.
 struct MeshClean {
     float weld = 0.0f;                 // --mesh-weld TOL: 0 is off
+    unsigned trim = 0;                 // --mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]: 0 is off
+    unsigned trim_pixels = 1;
+    float trim_tolerance = 0.01f;
+    bool depth_maps = false;           // --mesh-depth-maps: depths_mesh.dmb of every view, the final mesh rendered into it
     bool remove_small = false;         // --mesh-min-component FACES
     unsigned min_component = 0;
     int smooth = 0;                    // --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]: 0 is off
@@ -54,7 +59,7 @@ struct Options {
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     float mesh_voxel = 0.0f;              // --mesh VOXEL[,TRUNC]: APD/APD.ply.mesh, the marching-tetrahedra mesh of the filtered maps fused into a signed
     float mesh_trunc = 0.0f;              // distance volume with samples VOXEL apart in the box of the points of APD.ply (apd_volume_*); voxel 0: off
-    MeshClean mesh_clean;                 // --mesh-weld TOL, --mesh-min-component FACES, --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify CELL[,mean|quadric], --mesh-normals: what becomes of that mesh before it is written
+    MeshClean mesh_clean;                 // --mesh-weld TOL, --mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]], --mesh-depth-maps, --mesh-min-component FACES, --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify CELL[,mean|quadric], --mesh-normals: what becomes of that mesh before it is written
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)
     bool clean_exit = false;          // --clean-exit: return from main() instead of _Exit (exit handlers run: profilers)

@@ -897,7 +897,7 @@ def mesh_bounds(bounds):
 
 
 def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, colour_images=None, block_masks=None, options=None,
-         return_mesh=False, weld=None, min_component=None, normals=False, simplify=None, smooth=None):
+         return_mesh=False, weld=None, min_component=None, normals=False, simplify=None, smooth=None, trim=None, depth_maps=False):
     """A surface from the gathered maps: filter_maps(..., on_device=True) leaves every view's consistent depth map on GPU `device`,
     Volume.integrate fuses them, at each view's depth-map resolution, into a truncated signed distance volume with samples `voxel`
     apart (apd_volume_integrate, contract C21), and Volume.extract_mesh takes the marching-tetrahedra mesh of its zero level, which
@@ -905,17 +905,26 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
     the box to cover, or a Points whose box is taken; None: the box of the points fuse(..., return_points=True) makes of the same
     inputs.  The volume covers the box grown by trunc (Volume.around).  colour_images, block_masks, options: as in fuse() and
     filter_maps(); the images are resampled as fuse() resamples them and colour the vertices.  Every view weighs 1.
-    weld (a tolerance), min_component (a number of faces), smooth (a number of iterations, or (iterations, lam, mu), or (iterations,
+    weld (a tolerance), trim (min_views, or (min_views, min_pixels, rel_tolerance); Mesh.remove_unseen's defaults: 1 pixel, 0.01, back
+    faces culled), min_component (a number of faces), smooth (a number of iterations, or (iterations, lam, mu), or (iterations,
     lam, mu, boundary); Mesh.smooth's defaults: Taubin's 0.5 and -0.53, "along"), simplify (a cell size, or (cell, placement) with
     placement "mean" or "quadric", the default) and normals, each off by default, clean the mesh after extraction in this fixed
-    order: Mesh.weld, Mesh.remove_small_components, Mesh.smooth, Mesh.simplify, Mesh.with_vertex_normals (contracts C22, C24 and C23):
-    smoothing goes before simplification so that the quadric reads denoised planes; the file and the counts are the final mesh's.
-    Returns (vertices, faces), the counts, or with return_mesh (vertices, faces, Mesh)."""
+    order: Mesh.weld, Mesh.remove_unseen, Mesh.remove_small_components, Mesh.smooth, Mesh.simplify, Mesh.with_vertex_normals
+    (contracts C22, C25, C24 and C23): trimming drops the faces that fewer than min_views of the views the volume was built from see
+    -- the sheets with which the extraction closes the surface at depth discontinuities and at the frame border -- and goes before
+    the component filter so that the fragments it detaches are removed; smoothing goes before simplification so that the quadric
+    reads denoised planes; the file and the counts are the final mesh's.  depth_maps: the final mesh is also rendered into every
+    view (Mesh.render, both sides), at the size of that view's maps.
+    Returns (vertices, faces), the counts, or with return_mesh (vertices, faces, Mesh); with depth_maps the list of the views'
+    rendered depth maps (float32 [h, w]) follows."""
     from . import Volume
     import torch
     smoothing = tuple(smooth) if isinstance(smooth, (tuple, list)) else (smooth,)
     if smooth is not None and len(smoothing) not in (1, 3, 4):
         raise ValueError("mesh: smooth %r, neither iterations nor (iterations, lam, mu) nor (iterations, lam, mu, boundary)" % (smooth,))
+    trimming = tuple(trim) if isinstance(trim, (tuple, list)) else (trim,)
+    if trim is not None and len(trimming) not in (1, 3):
+        raise ValueError("mesh: trim %r, neither min_views nor (min_views, min_pixels, rel_tolerance)" % (trim,))
     trunc = 4.0 * float(voxel) if trunc is None else trunc
     if bounds is None:
         _, points = fuse(scene, results, None, device=device, colour_images=colour_images, block_masks=block_masks, options=options, return_points=True)
@@ -935,6 +944,9 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
     finally:
         volume.close()
     steps = [] if weld is None else [lambda m: m.weld(weld)]
+    if trim is not None:
+        min_views, min_pixels, rel_tolerance = trimming if len(trimming) == 3 else (trimming[0], 1, 0.01)
+        steps += [lambda m: m.remove_unseen(cams, min_views, "back", min_pixels, rel_tolerance)]
     steps += [] if min_component is None else [lambda m: m.remove_small_components(min_component)]
     steps += [] if smooth is None else [lambda m: m.smooth(*smoothing)]
     if simplify is not None:
@@ -950,7 +962,8 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
     if ply_path is not None:
         found.write_ply(ply_path)
     counts = (len(found.vertices), len(found.faces))
+    rendered = ([found.render(cam)[0] for cam in cams],) if depth_maps else ()
     if return_mesh:
-        return counts + (found,)
+        return counts + (found,) + rendered
     found.close()
-    return counts
+    return counts + rendered

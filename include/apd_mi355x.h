@@ -1108,6 +1108,54 @@ int apd_mesh_adjacency(apd_mesh_t mesh, uint32_t *valence, uint8_t *boundary, lo
                        long long *nonmanifold_edges);
 int apd_mesh_smooth(apd_mesh_t mesh, int iterations, float lambda, float mu, int boundary, apd_mesh_t *out, long long *moved);
 
+/* apd_mesh_render, apd_mesh_face_visibility and apd_mesh_remove_unseen: the mesh rasterised into a camera with a z-buffer, the number
+ * of cameras that see each face, and the mesh without the faces too few cameras see -- arithmetic contract C25, the rules
+ * written once in csrc/apd_mesh_render_math.h.  Like the other mesh calls they leave their input as it is, are functions of the input
+ * alone (integer coverage, one IEEE operation per step of the depth, a 64-bit integer atomic min per pixel and integer atomic adds:
+ * none depends on the order of arrival, and there is no floating-point atomic) and have no host implementation.
+ *   Vertex.  The fusion's projection (ProjectCamera) gives u, w, d in binary32.  A vertex is usable when d > 0 and finite and
+ *   su = u * 256.0f + 0.5f, sw = w * 256.0f + 0.5f are finite with |floorf(.)| <= 2^27 (the guard band: 2^19 pixels either side of
+ *   the origin); X = (int)floorf(su), Y = (int)floorf(sw) are its position in 1/256 pixel.  Pixel (c, r) has its centre at
+ *   (256 c, 256 r): integer coordinates are pixel centres, as everywhere in the fusion.
+ *   Face.  Drawn when its three vertices are usable and A2 = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) is not 0.  Two stated limits:
+ *   there is NO NEAR-PLANE CLIPPING -- a face with a corner behind the camera is not drawn at all, rather than cut --, and a face
+ *   with a corner BEYOND THE GUARD BAND is not drawn at all.  A face is front-facing, its right-hand normal (the one
+ *   apd_mesh_with_vertex_normals sums) towards the camera, when A2 < 0; APD_RENDER_CULL_BACK draws front faces only,
+ *   APD_RENDER_CULL_NONE both sides.  With A2 < 0 corners 1 and 2 are exchanged for what follows.
+ *   Coverage (integers only).  Edge a -> b: dx = Xb - Xa, dy = Yb - Ya, E(p) = dx (py - Ya) - dy (px - Xa) in 64 bits.  A pixel
+ *   centre of the face's bounding box clipped to the image is covered when for all three edges E > 0, or E == 0 with dy < 0, or
+ *   E == 0 with dy == 0 and dx > 0 (the top-left rule): a centre on an edge two faces share belongs to exactly one of them.
+ *   Depth (binary64, one IEEE operation per step).  w_i: the edge function opposite corner i, S = w0 + w1 + w2,
+ *   q = (w0 / d0 + w1 / d1) + w2 / d2, z = (float)(S / q): perspective-correct.  The pixel takes the face only when z > 0 and finite.
+ *   Maps.  Per pixel the nearest face, among equal depth bits the lowest index: depth z or 0.0f, face f or 0xFFFFFFFF.
+ *   Seen.  A camera sees face f when f is drawn (and not culled) and (a) owns at least min_pixels pixels of the camera's face map
+ *   or (b) each of its corners passes the points' test (apd_points_rendered_visibility): the corner's own pixel is inside the image,
+ *   the map depth z there is > 0 and d - z <= rel_tolerance * z.  (a) alone loses faces smaller than a pixel, (b) alone large faces
+ *   whose corners are hidden or outside the frame.
+ * apd_mesh_render: depth and face take width * height entries each, host memory; either may be NULL, not both.
+ * apd_mesh_face_visibility: views[f] = the cameras that see face f, pixels[f] = the pixels f owns over all cameras (host arrays, one
+ * entry per face), *unseen = the faces no camera sees; each may be NULL, not all.
+ * apd_mesh_remove_unseen: *out is a new mesh on the input's device of the faces with views[f] >= min_views, in their order, and of
+ * the vertices they name, renumbered, with their colours and normals unchanged, as apd_mesh_remove_small_components gives its
+ * result; min_views 0 keeps every face (and draws nothing).  *removed_faces, *removed_vertices (may be NULL): what went.
+ * A mesh without faces gives empty maps, nothing to count and *unseen = 0, or a mesh without faces or vertices, with no device
+ * touched.  One image of keys is alive at a time, allocated once per call at the largest camera.
+ * apd_mesh_render_split: faces whose clipped bounding box has more than box_pixels pixels are drawn by a wave instead of a lane;
+ * 0 restores the built-in value.  The results do not depend on it: it exists for the timing tool and a same-bytes test.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_mesh_render: ...", "apd_mesh_face_visibility: ..." or
+ * "apd_mesh_remove_unseen: ...": a NULL mesh, camera, cameras or out, outputs all NULL, a cull other than the two, min_pixels < 1, a
+ * rel_tolerance that is negative or not finite, num_views < 1, a camera whose width or height is not positive or whose product is
+ * 2^31 or more.  APD_ERR_UNSUPPORTED where the faces drawn by waves need more waves than one launch holds (2^33 - 3 or more: every
+ * such face takes 1 to 64, one per 256 tiles of 8 x 8 pixels of its clipped bounding box).  Outputs are untouched on failure.
+ * apd_fusion_last_timing reports the calls like the other mesh calls: set-up (allocations), work, and 0 for the file. */
+enum { APD_RENDER_CULL_NONE = 0, APD_RENDER_CULL_BACK = 1 };
+int apd_mesh_render(apd_mesh_t mesh, const apd_camera *camera, int cull, float *depth, uint32_t *face);
+int apd_mesh_face_visibility(apd_mesh_t mesh, int num_views, const apd_camera *cameras, int cull, unsigned min_pixels, float rel_tolerance,
+                             uint32_t *views, uint64_t *pixels, long long *unseen);
+int apd_mesh_remove_unseen(apd_mesh_t mesh, int num_views, const apd_camera *cameras, int cull, unsigned min_pixels, float rel_tolerance,
+                           unsigned min_views, apd_mesh_t *out, long long *removed_faces, long long *removed_vertices);
+void apd_mesh_render_split(int box_pixels);
+
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
  * points in memory (*points, released with apd_points_destroy; untouched when the call fails), or both from one fusion.  With
  * ply_normals the file has the properties x y z nx ny nz (float) before the three colour bytes.  Refused with APD_ERR_INVALID
