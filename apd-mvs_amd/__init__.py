@@ -245,6 +245,8 @@ def lib():
     L.apd_mesh_face_visibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
     L.apd_mesh_remove_unseen.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_uint, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.apd_mesh_colour_from_views.argtypes = [C.c_void_p, C.c_int, C.c_void_p, fpp, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_void_p), C.c_void_p,
+                                             C.POINTER(C.c_longlong)]
     L.apd_mesh_render_split.argtypes = [C.c_int]
     L.apd_mesh_render_split.restype = None
     L.apd_mesh_has_normals.argtypes = [C.c_void_p]
@@ -1041,7 +1043,8 @@ class Mesh:
     (apd_mesh_write_ply).  weld(), remove_small_components(), smooth(), simplify() and with_vertex_normals() each give a new Mesh and
     leave this one as it is (arithmetic contracts C22, C23 and C24); components() labels the faces, adjacency() tells every vertex's
     valence and whether the mesh is closed and manifold.  render() rasterises the mesh into a camera, face_visibility() counts the
-    cameras that see each face and remove_unseen() drops the faces too few see (contract C25).  `moved`: after smooth(), on this mesh and on the result, the vertices the first step moved.  A mesh may
+    cameras that see each face and remove_unseen() drops the faces too few see (contract C25); colour_from_views() gives the Mesh whose
+    vertices have the colour of the images of the cameras that see them (contract C26).  `moved`: after smooth(), on this mesh and on the result, the vertices the first step moved.  A mesh may
     be empty."""
 
     PLACEMENTS = {"mean": 0, "quadric": 1}   # APD_SIMPLIFY_MEAN, APD_SIMPLIFY_QUADRIC
@@ -1050,6 +1053,8 @@ class Mesh:
     moved = None
     unseen = None          # after face_visibility(): the faces no camera sees
     removed_faces = None   # after remove_unseen(), on this mesh and on the result: the faces that went
+    uncoloured = None      # after colour_from_views(), on this mesh and on the result: the vertices no camera gave a colour
+    coloured_views = None  # on the result of colour_from_views(): uint32 [n], the views each vertex took a sample from
 
     def __init__(self, handle):
         self._m = handle
@@ -1223,6 +1228,50 @@ class Mesh:
             raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
         result = Mesh(out)
         self.removed_faces = result.removed_faces = faces.value
+        return result
+
+    def colour_from_views(self, cameras, images, rel_tolerance=0.01, min_cos=0.1):
+        """apd_mesh_colour_from_views: the Mesh with these vertices, faces and normals whose every vertex has the colour of the
+        `images` of the `cameras` (a ctypes array or a sequence of Camera) that see it (arithmetic contract C26): a view gives a vertex
+        a bilinear sample when the four pixels around its projection are inside the image and not more than rel_tolerance * z behind
+        the depth z of this mesh rendered into the view (both sides drawn), and the vertex normal (with_vertex_normals()'s, where
+        this mesh has none) makes a cosine above min_cos with the direction to the camera; that cosine weighs the sample.  images:
+        per view float32 [height, width] or [height, width, 3] (blue, green, red), all alike: numpy arrays, or torch tensors on the
+        mesh's device.  A vertex no view colours keeps its colour, (0, 0, 0) on a mesh without.  `coloured_views` of the result is
+        the number of views each vertex took a sample from, `uncoloured` of this Mesh and of the result the vertices with none."""
+        L = self._open("colour_from_views")
+        V = len(cameras)
+        if len(images) != V:
+            raise ValueError("Mesh.colour_from_views: %d cameras, %d images" % (V, len(images)))
+        cams = self._cameras(cameras)
+        on_device = V > 0 and all(hasattr(a, "data_ptr") for a in images)
+        if on_device:
+            import torch
+            imgs = [a.to(torch.float32).contiguous() for a in images]
+            for a in imgs:
+                if not a.is_cuda:
+                    raise ValueError("Mesh.colour_from_views: torch tensors are images on the mesh's device, not on %s" % a.device)
+            torch.cuda.synchronize(imgs[0].device)  # the tensors' producers, before the library's stream reads them
+        else:
+            if any(hasattr(a, "data_ptr") for a in images):
+                raise ValueError("Mesh.colour_from_views: the images are numpy arrays or torch tensors on the mesh's device, all alike")
+            imgs = [np.ascontiguousarray(a, np.float32) for a in images]
+        channels = 3 if V > 0 and imgs[0].ndim == 3 else 1
+        for s in range(V):
+            shape = (int(cams[s].height), int(cams[s].width))
+            if shape[0] > 0 and shape[1] > 0 and tuple(imgs[s].shape) != shape + ((3,) if channels == 3 else ()):   # a camera without pixels is the library's to refuse
+                raise ValueError("Mesh.colour_from_views: view %d has an image of %r and a camera of %r; images are [H, W] or [H, W, 3], all alike" % (
+                    s, tuple(imgs[s].shape), shape))
+        table = (C.c_void_p * max(V, 1))(*[_ptr(a) for a in imgs])
+        out, none = C.c_void_p(), C.c_longlong(0)
+        views = np.zeros(len(self.vertices), np.uint32)
+        rc = L.apd_mesh_colour_from_views(self._m, V, C.byref(cams), table, channels, int(on_device), float(rel_tolerance), float(min_cos), C.byref(out),
+                                          C.c_void_p(views.ctypes.data) if len(views) else None, C.byref(none))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        result = Mesh(out)
+        result.coloured_views = views
+        self.uncoloured = result.uncoloured = none.value
         return result
 
     def simplify(self, cell, origin=None, placement="quadric"):

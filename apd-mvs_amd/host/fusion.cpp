@@ -911,8 +911,9 @@ void mesh_and_write(const path &ply_path, const std::vector<Problem> &problems, 
     apd_mesh_t mesh = nullptr;
     const std::string mesh_path = ply_path.string() + ".mesh";
     long long vertices = 0, faces = 0;
-    if (apd_volume_create(g_fusion_device, dims[0], dims[1], dims[2], origin, voxel, trunc, 64.0f, 1, &volume) != APD_OK ||
-        apd_volume_integrate(volume, V, f.cams.data(), filtered.data(), images.data(), 3, nullptr, 0) != APD_OK ||
+    // --mesh-recolour: the colours come from the images at the end, so the volume carries none and is integrated without them
+    if (apd_volume_create(g_fusion_device, dims[0], dims[1], dims[2], origin, voxel, trunc, 64.0f, clean.recolour ? 0 : 1, &volume) != APD_OK ||
+        apd_volume_integrate(volume, V, f.cams.data(), filtered.data(), clean.recolour ? nullptr : images.data(), 3, nullptr, 0) != APD_OK ||
         apd_volume_extract_mesh(volume, &mesh) != APD_OK || apd_mesh_counts(mesh, &vertices, &faces) != APD_OK) {
         failed(apd_fusion_last_error());
     }
@@ -973,6 +974,19 @@ void mesh_and_write(const path &ply_path, const std::vector<Problem> &problems, 
         apd_mesh_t next = nullptr;
         const int rc = apd_mesh_with_vertex_normals(mesh, &next);
         replaced(rc, next, "with vertex normals");
+    }
+    if (clean.recolour) {
+        apd_mesh_t next = nullptr;
+        long long uncoloured = 0;
+        if (apd_mesh_colour_from_views(mesh, V, cams.data(), images.data(), 3, 0, clean.recolour_tolerance, clean.recolour_min_cos, &next, nullptr,
+                                       &uncoloured) != APD_OK) {
+            failed(apd_fusion_last_error());
+        }
+        printf("Mesh recoloured from %d views (tolerance %f, min_cos %f): %lld vertices, %lld left uncoloured\n", V, (double)clean.recolour_tolerance,
+               (double)clean.recolour_min_cos, vertices, uncoloured);
+        fflush(stdout);
+        apd_mesh_destroy(mesh);
+        mesh = next;
     }
     if (apd_mesh_write_ply(mesh, mesh_path.c_str()) != APD_OK) {
         failed(apd_fusion_last_error());

@@ -7,7 +7,7 @@
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
 //       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
 //       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]]
-//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals]
+//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--mesh-recolour [TOL[,MIN_COS]]]
 //
 // --mesh VOXEL[,TRUNC]: besides everything else, APD/APD.ply.mesh: a binary PLY with faces, the marching-tetrahedra mesh of a signed
 // distance volume with samples VOXEL apart and a truncation distance of TRUNC (4 * VOXEL unless given) over the box of the points
@@ -28,6 +28,11 @@
 // one, placed by the quadric of the faces around them or at their mean (apd_mesh_simplify, contract C23); the file carries nx ny
 // nz, area-weighted vertex normals (apd_mesh_with_vertex_normals).  One line per step is printed with the counts before and after.  Each is refused
 // without --mesh and on a malformed value, with the usage line, before anything is read.  Without them APD.ply.mesh keeps its bytes.
+// --mesh-recolour [TOL[,MIN_COS]]: the last step, after --mesh-normals: every vertex takes its colour from the images of the views that
+// see it through the final mesh's own z-buffer -- the four pixels around its projection within TOL (0.01) * depth of the rendered
+// mesh, its normal at a cosine above MIN_COS (0.1, in [0, 1)) to the view (apd_mesh_colour_from_views, contract C26) -- and the volume
+// is made without colour and integrated without the images: a third of its memory, the same geometry.  One line tells the vertices
+// and how many no view coloured.  Needs --mesh; a malformed value gives the usage line before anything is read.
 // --mesh-depth-maps: every view's depths_mesh.dmb beside depths_filtered.dmb, in the format of depths.dmb: the depth of the final
 // mesh rasterised into the view, both sides drawn, 0 where it covers nothing (apd_mesh_render).  Needs --mesh.
 //
@@ -329,6 +334,23 @@ bool ParseOptions(int argc, char **argv, Options &o)
         } else if (a == "--mesh-normals") {
             o.mesh_clean.normals = true;
             mesh_flag = a;
+        } else if (a == "--mesh-recolour") {
+            MeshClean c = o.mesh_clean;
+            if (i + 1 < argc && argv[i + 1][0] != '-') {   // the value is optional
+                const std::string both = argv[++i];
+                const size_t comma = both.find(',');
+                bool good = ply_value::Real(both.substr(0, comma), c.recolour_tolerance) && c.recolour_tolerance >= 0.0f;
+                if (good && comma != std::string::npos) {
+                    good = ply_value::Real(both.substr(comma + 1), c.recolour_min_cos) && c.recolour_min_cos >= 0.0f && c.recolour_min_cos < 1.0f;
+                }
+                if (!good) {
+                    fprintf(stderr, "bad value '%s' of %s: [TOL[,MIN_COS]], a number that is not negative and one in [0, 1)\n", both.c_str(), a.c_str());
+                    return false;
+                }
+            }
+            c.recolour = true;
+            o.mesh_clean = c;
+            mesh_flag = a;
         } else if (a == "--seed") {
             if (!value(o.seed)) return false;
         } else if (a == "--iters") {
@@ -550,7 +572,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--mesh-recolour [TOL[,MIN_COS]]] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"

@@ -14,7 +14,7 @@
 #include "ply_options.h"
 
 // What --mesh does to its mesh between extraction and the file, in this fixed order: apd_mesh_weld, apd_mesh_remove_unseen,
-// apd_mesh_remove_small_components, apd_mesh_smooth, apd_mesh_simplify, apd_mesh_with_vertex_normals.  All off: the file has the bytes
+// apd_mesh_remove_small_components, apd_mesh_smooth, apd_mesh_simplify, apd_mesh_with_vertex_normals, apd_mesh_colour_from_views.  All off: the file has the bytes
 // of the extracted mesh.
 struct MeshClean {
     float weld = 0.0f;                 // --mesh-weld TOL: 0 is off
@@ -30,6 +30,8 @@ struct MeshClean {
     float simplify = 0.0f;             // --mesh-simplify CELL[,mean|quadric]: 0 is off
     bool simplify_mean = false;        // ,mean: APD_SIMPLIFY_MEAN; otherwise APD_SIMPLIFY_QUADRIC
     bool normals = false;              // --mesh-normals
+    bool recolour = false;             // --mesh-recolour [TOL[,MIN_COS]]: the colours from the views' images, not from the volume
+    float recolour_tolerance = 0.01f, recolour_min_cos = 0.1f;
 };
 
 struct Options {
@@ -59,7 +61,7 @@ struct Options {
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     float mesh_voxel = 0.0f;              // --mesh VOXEL[,TRUNC]: APD/APD.ply.mesh, the marching-tetrahedra mesh of the filtered maps fused into a signed
     float mesh_trunc = 0.0f;              // distance volume with samples VOXEL apart in the box of the points of APD.ply (apd_volume_*); voxel 0: off
-    MeshClean mesh_clean;                 // --mesh-weld TOL, --mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]], --mesh-depth-maps, --mesh-min-component FACES, --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify CELL[,mean|quadric], --mesh-normals: what becomes of that mesh before it is written
+    MeshClean mesh_clean;                 // --mesh-weld TOL, --mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]], --mesh-depth-maps, --mesh-min-component FACES, --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify CELL[,mean|quadric], --mesh-normals, --mesh-recolour [TOL[,MIN_COS]]: what becomes of that mesh before it is written
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)
     bool clean_exit = false;          // --clean-exit: return from main() instead of _Exit (exit handlers run: profilers)

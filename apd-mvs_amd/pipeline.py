@@ -897,7 +897,8 @@ def mesh_bounds(bounds):
 
 
 def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, colour_images=None, block_masks=None, options=None,
-         return_mesh=False, weld=None, min_component=None, normals=False, simplify=None, smooth=None, trim=None, depth_maps=False):
+         return_mesh=False, weld=None, min_component=None, normals=False, simplify=None, smooth=None, trim=None, depth_maps=False,
+         recolour=None):
     """A surface from the gathered maps: filter_maps(..., on_device=True) leaves every view's consistent depth map on GPU `device`,
     Volume.integrate fuses them, at each view's depth-map resolution, into a truncated signed distance volume with samples `voxel`
     apart (apd_volume_integrate, contract C21), and Volume.extract_mesh takes the marching-tetrahedra mesh of its zero level, which
@@ -909,12 +910,15 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
     faces culled), min_component (a number of faces), smooth (a number of iterations, or (iterations, lam, mu), or (iterations,
     lam, mu, boundary); Mesh.smooth's defaults: Taubin's 0.5 and -0.53, "along"), simplify (a cell size, or (cell, placement) with
     placement "mean" or "quadric", the default) and normals, each off by default, clean the mesh after extraction in this fixed
-    order: Mesh.weld, Mesh.remove_unseen, Mesh.remove_small_components, Mesh.smooth, Mesh.simplify, Mesh.with_vertex_normals
-    (contracts C22, C25, C24 and C23): trimming drops the faces that fewer than min_views of the views the volume was built from see
+    order: Mesh.weld, Mesh.remove_unseen, Mesh.remove_small_components, Mesh.smooth, Mesh.simplify, Mesh.with_vertex_normals,
+    Mesh.colour_from_views (contracts C22, C25, C24, C23 and C26): trimming drops the faces that fewer than min_views of the views the volume was built from see
     -- the sheets with which the extraction closes the surface at depth discontinuities and at the frame border -- and goes before
     the component filter so that the fragments it detaches are removed; smoothing goes before simplification so that the quadric
     reads denoised planes; the file and the counts are the final mesh's.  depth_maps: the final mesh is also rendered into every
-    view (Mesh.render, both sides), at the size of that view's maps.
+    view (Mesh.render, both sides), at the size of that view's maps.  recolour (True, or (rel_tolerance, min_cos); Mesh.colour_from_views'
+    defaults: 0.01 and 0.1): the last step, after the normals: the vertices take their colour from the views' images through the final
+    mesh's own z-buffer (contract C26) instead of from the volume, which is then made without colour -- a third of the memory -- and
+    integrated without the images; the geometry is the same.  The images go to the device once.
     Returns (vertices, faces), the counts, or with return_mesh (vertices, faces, Mesh); with depth_maps the list of the views'
     rendered depth maps (float32 [h, w]) follows."""
     from . import Volume
@@ -925,6 +929,9 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
     trimming = tuple(trim) if isinstance(trim, (tuple, list)) else (trim,)
     if trim is not None and len(trimming) not in (1, 3):
         raise ValueError("mesh: trim %r, neither min_views nor (min_views, min_pixels, rel_tolerance)" % (trim,))
+    recolouring = () if recolour is True else tuple(recolour) if isinstance(recolour, (tuple, list)) else (recolour,)
+    if recolour is not None and (recolour is False or len(recolouring) not in (0, 2)):
+        raise ValueError("mesh: recolour %r, neither True nor (rel_tolerance, min_cos)" % (recolour,))
     trunc = 4.0 * float(voxel) if trunc is None else trunc
     if bounds is None:
         _, points = fuse(scene, results, None, device=device, colour_images=colour_images, block_masks=block_masks, options=options, return_points=True)
@@ -937,9 +944,10 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
     maps = filter_maps(scene, results, device=device, block_masks=block_masks, options=options, on_device=True)
     cams, imgs = mesh_views(scene, results, colour_images)
     dev = torch.device("cuda", int(device))
-    volume = Volume.around(lo, hi, voxel, trunc, colour=True, device=device)
+    volume = Volume.around(lo, hi, voxel, trunc, colour=recolour is None, device=device)
+    on_device = [torch.from_numpy(a).to(dev) for a in imgs]
     try:
-        volume.integrate(cams, [m.depth for m in maps], [torch.from_numpy(a).to(dev) for a in imgs], maps_on_device=True)
+        volume.integrate(cams, [m.depth for m in maps], on_device if recolour is None else None, maps_on_device=True)
         found = volume.extract_mesh()
     finally:
         volume.close()
@@ -953,6 +961,7 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
         cell, placement = simplify if isinstance(simplify, (tuple, list)) else (simplify, "quadric")
         steps += [lambda m: m.simplify(cell, placement=placement)]
     steps += [lambda m: m.with_vertex_normals()] if normals else []
+    steps += [] if recolour is None else [lambda m: m.colour_from_views(cams, on_device, *recolouring)]
     for step in steps:
         before = found
         try:

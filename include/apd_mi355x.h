@@ -1156,6 +1156,43 @@ int apd_mesh_remove_unseen(apd_mesh_t mesh, int num_views, const apd_camera *cam
                            unsigned min_views, apd_mesh_t *out, long long *removed_faces, long long *removed_vertices);
 void apd_mesh_render_split(int box_pixels);
 
+/* apd_mesh_colour_from_views: the mesh with every vertex coloured from the images of the cameras that see it, through the mesh's own
+ * z-buffer -- arithmetic contract C26, the rules written once in csrc/apd_mesh_colour_math.h.  Like the other mesh calls it
+ * leaves its input as it is, is a function of the input alone (one writer per vertex, the views in the call's order, no floating-point
+ * atomic) and has no host implementation.
+ *   Inputs.  num_views cameras and one image per view of the camera's height x width, of 1 or 3 interleaved float channels, blue
+ *   green red, as apd_volume_integrate takes them (one channel feeds all three); host memory, or with maps_on_device device memory on
+ *   the mesh's device.  The vertex normals are the mesh's own, or where it has none those apd_mesh_with_vertex_normals would give it.
+ *   Per view, in the call's order, Z = the depth map of apd_mesh_render(mesh, camera, APD_RENDER_CULL_NONE): both sides occlude.
+ *   Sample.  The vertex at P with normal n takes a sample from a view when (1) n is not (0, 0, 0); (2) the fusion's projection gives
+ *   d > 0 and finite; (3) the bilinear footprint is inside the image: c0 = (int)floorf(u), r0 = (int)floorf(w), 0 <= c0,
+ *   c0 + 1 <= width - 1, 0 <= r0, r0 + 1 <= height - 1 (so u == width - 1 takes none); (4) it is not occluded at any of the four
+ *   pixels (c0 | c0 + 1, r0 | r0 + 1): z = Z there is > 0 and d - z <= rel_tolerance * z, the points' test
+ *   (apd_points_rendered_visibility) on the whole footprint, which keeps a nearer surface's colour out of a vertex just behind its
+ *   silhouette and costs a mesh's border vertices some views; (5) it faces the camera: in binary64 e = centre - P,
+ *   c = (n . e) / sqrt(e . e), c > min_cos.  The weight of the sample is c.
+ *   Colour of a sample (binary32, one operation per step): fu = u - floorf(u), fw = w - floorf(w), per channel
+ *   top = a + fu * (b - a), bot = a' + fu * (b' - a'), value = top + fw * (bot - top).
+ *   Sums (binary64, in view order): S_k += c * value_k per channel, W += c, count += 1.
+ *   Result.  count > 0: per channel x = (float)(S_k / W) clamped to 0 .. 255 (a NaN is 0), (int)(x + 0.5f), the conversion of the
+ *   volume's vertex colours.  count == 0: the input's colour, (0, 0, 0) for a mesh without.
+ * *out is a new mesh on the input's device that always has colour, with the input's vertices, faces and normals bit for bit.
+ * views[v] (host, one entry per vertex, may be NULL) = the views vertex v took a sample from, *uncoloured (may be NULL) = the
+ * vertices with none.  rel_tolerance: 0.01 is apd_mesh_face_visibility's; min_cos: 0.1 drops the views that see a vertex at more
+ * than about 84 degrees, which contribute smear -- a design choice, not a measurement.  C25's two limits carry over: a face that is
+ * not drawn occludes nothing.
+ * A mesh without vertices gives an empty coloured mesh and *uncoloured = 0 with no device touched; a mesh with vertices and no
+ * faces renders nothing, so every vertex is uncoloured.  Alive on the device at a time: one image of keys, one depth map and (for
+ * host images, which go up one view at a time) one image buffer, each allocated once per call at the largest camera, and 36 bytes
+ * a vertex; for a mesh without normals also the mesh with them.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_mesh_colour_from_views: ...": a NULL mesh, cameras, images,
+ * image or out, num_views < 1, image_channels other than 1 or 3, a rel_tolerance that is negative or not finite, a min_cos outside
+ * [0, 1) or not finite, a camera whose width or height is not positive or whose product is 2^31 or more.  APD_ERR_UNSUPPORTED as
+ * apd_mesh_render and, for a mesh without normals, as apd_mesh_with_vertex_normals.  Outputs are untouched on failure.
+ * apd_fusion_last_timing reports the call like the other mesh calls: set-up (allocations), work, and 0 for the file. */
+int apd_mesh_colour_from_views(apd_mesh_t mesh, int num_views, const apd_camera *cameras, const float *const *images, int image_channels,
+                               int maps_on_device, float rel_tolerance, float min_cos, apd_mesh_t *out, uint32_t *views, long long *uncoloured);
+
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
  * points in memory (*points, released with apd_points_destroy; untouched when the call fails), or both from one fusion.  With
  * ply_normals the file has the properties x y z nx ny nz (float) before the three colour bytes.  Refused with APD_ERR_INVALID
