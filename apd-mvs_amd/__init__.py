@@ -247,6 +247,12 @@ def lib():
                                          C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.apd_mesh_colour_from_views.argtypes = [C.c_void_p, C.c_int, C.c_void_p, fpp, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_void_p), C.c_void_p,
                                              C.POINTER(C.c_longlong)]
+    L.apd_mesh_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.apd_mesh_device.argtypes = [C.c_void_p]
+    L.apd_mesh_nearest_pair_limit.argtypes = [C.c_longlong]
+    L.apd_mesh_nearest_pair_limit.restype = None
+    L.apd_mesh_sample_points.argtypes = [C.c_void_p, C.c_double, C.c_ulonglong, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+    L.apd_mesh_score.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_double, C.c_ulonglong, C.POINTER(PointsScore)]
     L.apd_mesh_render_split.argtypes = [C.c_int]
     L.apd_mesh_render_split.restype = None
     L.apd_mesh_has_normals.argtypes = [C.c_void_p]
@@ -1044,7 +1050,9 @@ class Mesh:
     leave this one as it is (arithmetic contracts C22, C23 and C24); components() labels the faces, adjacency() tells every vertex's
     valence and whether the mesh is closed and manifold.  render() rasterises the mesh into a camera, face_visibility() counts the
     cameras that see each face and remove_unseen() drops the faces too few see (contract C25); colour_from_views() gives the Mesh whose
-    vertices have the colour of the images of the cameras that see them (contract C26).  `moved`: after smooth(), on this mesh and on the result, the vertices the first step moved.  A mesh may
+    vertices have the colour of the images of the cameras that see them (contract C26).  nearest() gives the closest point of the
+    surface for every point of a Points, sample_points() a Points drawn on the surface by area and score() the precision, recall and
+    F-score of the surface against a ground-truth Points (contract C27).  `moved`: after smooth(), on this mesh and on the result, the vertices the first step moved.  A mesh may
     be empty."""
 
     PLACEMENTS = {"mean": 0, "quadric": 1}   # APD_SIMPLIFY_MEAN, APD_SIMPLIFY_QUADRIC
@@ -1273,6 +1281,83 @@ class Mesh:
         result.coloured_views = views
         self.uncoloured = result.uncoloured = none.value
         return result
+
+    def nearest(self, points, radius, origin=None):
+        """apd_mesh_nearest: (distance float32 [N], face int32 [N], closest float32 [N, 3]) -- per point of `points` (a Points) the
+        distance to the closest point of this mesh's surface within `radius`, the face it lies on and the point itself (arithmetic
+        contract C27: binary64 on the widened coordinates, among equally near faces the smallest index; the grid of cell size
+        `radius` with a corner at `origin`, 0, 0, 0 by default, bounds what is searched), +inf, -1 and NaN where there is none.
+        numpy arrays for host points, torch tensors on their device for device points.  Computed on the mesh's device: host points go
+        up for the call, device points must live there."""
+        L = self._open("nearest")
+        if not isinstance(points, Points) or not points._p:
+            raise ApdError("Mesh.nearest: the points are closed or not a Points")
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        nothing = (C.c_float * 3)()   # where an object without points gets its no results: the library refuses NULL for all three
+        n = points.count
+        if points.on_device:
+            import torch
+            dev = torch.device("cuda", points.device)
+            distance, face = torch.empty((n,), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+            closest = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)
+            addresses = [a.data_ptr() if n else C.addressof(nothing) for a in (distance, face, closest)]
+        else:
+            distance, face, closest = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros((n, 3), np.float32)
+            addresses = [a.ctypes.data if n else C.addressof(nothing) for a in (distance, face, closest)]
+        rc = L.apd_mesh_nearest(self._m, points._p, float(radius), org, *[C.c_void_p(a) for a in addresses])
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return distance, face, closest
+
+    def sample_points(self, density, seed=0, on_device=True):
+        """apd_mesh_sample_points: a Points of points drawn on the surface uniformly by area, `density` per unit of area in
+        expectation (face f gets floor(area * density + u) of them, u in [0, 1) from a counter-based generator keyed by seed and f),
+        each with the unit normal of its face and the barycentric mix of its face's vertex colours; faces ascending.  `face` of the
+        result is int32 [N]: the face each sample lies on.  A function of (mesh, density, seed) alone.  on_device: the points live on
+        the mesh's GPU; otherwise in host memory.  A Points like that of Points.read_ply: one view of 1 x 1 without sources."""
+        L = self._open("sample_points")
+        density, seed = float(density), int(seed)
+        if not (density > 0.0 and np.isfinite(density)):
+            raise ValueError("Mesh.sample_points: a density of %r, not a positive finite number" % (density,))
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("Mesh.sample_points: seed %r, not in 0 .. 2^64 - 1" % (seed,))
+        # room for every sample's face: per face at most floor(area * density) + 1, and 1 more for this estimate's own rounding
+        with np.errstate(all="ignore"):
+            v = self.vertices.astype(np.float64)
+            cross = np.cross(v[self.faces[:, 1]] - v[self.faces[:, 0]], v[self.faces[:, 2]] - v[self.faces[:, 0]]) if len(self.faces) else np.zeros((0, 3))
+            room = np.floor(0.5 * np.sqrt((cross * cross).sum(1)) * density) + 2.0
+        room = float(np.where(np.isfinite(room), room, 2.0).sum())
+        if room >= 2.0 ** 31 + 2.0 * len(self.faces):
+            raise ApdError("Mesh.sample_points: about %.3g samples at a density of %g, 2^31 or more" % (room, density))
+        face = np.zeros(int(room), np.int32)
+        out = C.c_void_p()
+        rc = L.apd_mesh_sample_points(self._m, density, seed, int(bool(on_device)), C.byref(out), C.c_void_p(face.ctypes.data) if face.size else None)
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        result = Points(out, int(L.apd_mesh_device(self._m)))
+        result.face = face[:result.count].copy()
+        return result
+
+    def score(self, truth, threshold, density=None, seed=0, origin=None):
+        """apd_mesh_score: Score(n_p, n_q, p_within, q_within, precision, recall, fscore, mean_p, mean_q) of this surface against
+        `truth` (a Points) at `threshold` (contract C27).  Precision: the share of sample_points(density, seed) that have a point of
+        `truth` within the threshold (p_within of n_p samples); recall: the share of `truth` whose closest point of the surface is
+        within it (q_within of n_q) -- exact, independent of the sampling; fscore their harmonic mean; mean_p and mean_q the mean
+        distances of those that have one.  density: None gives 4 / threshold^2.  As Points.score: no cropping volume and no
+        occlusion-aware evaluation; scores compare with each other.  Computed on the mesh's device."""
+        L = self._open("score")
+        if not isinstance(truth, Points) or not truth._p:
+            raise ApdError("Mesh.score: the truth is closed or not a Points")
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("Mesh.score: seed %r, not in 0 .. 2^64 - 1" % (seed,))
+        org = None if origin is None else (C.c_float * 3)(*[float(x) for x in origin])
+        out = PointsScore()
+        rc = L.apd_mesh_score(self._m, truth._p, float(threshold), org, 0.0 if density is None else float(density), seed, C.byref(out))
+        if rc != 0:
+            raise ApdError("apd error %d: %s" % (rc, L.apd_fusion_last_error().decode()))
+        return Score(*[getattr(out, n) for n in Score._fields])
 
     def simplify(self, cell, origin=None, placement="quadric"):
         """apd_mesh_simplify: the Mesh thinned by vertex clustering (arithmetic contract C23): the vertices of one cell of the grid of

@@ -14,8 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_build")
 LIB_PATH = os.path.join(OUT_DIR, "libapd_mi355x.so")
-SOURCES = ["apd_kernels.hip", "apd_kernels_k67w.hip", "apd_kernels_k1415w.hip", "apd_kernels_weak.hip", "apd_fusion.hip", "apd_fusion_call.hip", "apd_fusion_tat.hip", "apd_filter.hip", "apd_points.hip", "apd_points_vis.hip", "apd_points_average.hip", "apd_points_merge.hip", "apd_points_radius.hip", "apd_points_knn.hip", "apd_points_clusters.hip", "apd_points_normals.hip", "apd_points_smooth.hip", "apd_points_nearest.hip", "apd_points_align.hip", "apd_points_align_planes.hip", "apd_points_register.hip", "apd_points_render.hip", "apd_volume.hip", "apd_mesh.hip", "apd_mesh_simplify.hip", "apd_mesh_smooth.hip", "apd_mesh_render.hip", "apd_mesh_colour.hip", "apd_sort.hip", "apd_exchange.hip", "apd_capi.hip"]
-HEADERS = ["apd_device.h", "apd_sweep.h", "apd_window.h", "apd_tuning.h", "apd_lab.h", "apd_fusion_math.h", "apd_fusion_device.h", "apd_host_error.h", "apd_voxel_math.h", "apd_radius_math.h", "apd_knn_math.h", "apd_normal_math.h", "apd_smooth_math.h", "apd_nearest_math.h", "apd_align_math.h", "apd_align_plane_math.h", "apd_register_math.h", "apd_render_math.h", "apd_volume_math.h", "apd_mesh_math.h", "apd_simplify_math.h", "apd_mesh_smooth_math.h", "apd_mesh_render_math.h", "apd_mesh_colour_math.h", "apd_render_device.h", "apd_mesh_render_device.h", "apd_mesh_host.h", "apd_mesh_compact.h", "apd_union_find.h", "apd_points_grid.h", "apd_points_search.h", "apd_points_nearest.h", "apd_points_align_sums.h", "apd_points_host.h", "apd_sort.h", "apd_scan.h", os.path.join("..", "..", "include", "apd_mi355x.h")]
+SOURCES = ["apd_kernels.hip", "apd_kernels_k67w.hip", "apd_kernels_k1415w.hip", "apd_kernels_weak.hip", "apd_fusion.hip", "apd_fusion_call.hip", "apd_fusion_tat.hip", "apd_filter.hip", "apd_points.hip", "apd_points_vis.hip", "apd_points_average.hip", "apd_points_merge.hip", "apd_points_radius.hip", "apd_points_knn.hip", "apd_points_clusters.hip", "apd_points_normals.hip", "apd_points_smooth.hip", "apd_points_nearest.hip", "apd_points_align.hip", "apd_points_align_planes.hip", "apd_points_register.hip", "apd_points_render.hip", "apd_volume.hip", "apd_mesh.hip", "apd_mesh_simplify.hip", "apd_mesh_smooth.hip", "apd_mesh_render.hip", "apd_mesh_colour.hip", "apd_mesh_nearest.hip", "apd_sort.hip", "apd_exchange.hip", "apd_capi.hip"]
+HEADERS = ["apd_device.h", "apd_sweep.h", "apd_window.h", "apd_tuning.h", "apd_lab.h", "apd_fusion_math.h", "apd_fusion_device.h", "apd_host_error.h", "apd_voxel_math.h", "apd_radius_math.h", "apd_knn_math.h", "apd_normal_math.h", "apd_smooth_math.h", "apd_nearest_math.h", "apd_align_math.h", "apd_align_plane_math.h", "apd_register_math.h", "apd_render_math.h", "apd_volume_math.h", "apd_mesh_math.h", "apd_simplify_math.h", "apd_mesh_smooth_math.h", "apd_mesh_render_math.h", "apd_mesh_colour_math.h", "apd_mesh_nearest_math.h", "apd_render_device.h", "apd_mesh_render_device.h", "apd_mesh_host.h", "apd_mesh_compact.h", "apd_union_find.h", "apd_points_grid.h", "apd_points_search.h", "apd_points_nearest.h", "apd_points_align_sums.h", "apd_points_host.h", "apd_sort.h", "apd_scan.h", os.path.join("..", "..", "include", "apd_mi355x.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]

@@ -112,9 +112,10 @@ __device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ key
 // for_each_candidate_around is that walk around a cell given as three integers (each in [-2^20, 2^20)), which need not hold a
 // member of the cloud walked: keys / xyz may be another cloud's than the one the cell was taken from (apd_points_nearest.hip,
 // contract C17), and then no read reaches position `end` at all.  for_each_candidate is the walk around the cell of member i.
-template <typename F>
-__device__ __forceinline__ void for_each_candidate_around(const uint64_t *__restrict__ keys, const float *__restrict__ xyz, const int cell[3], uint32_t end,
-                                                          F &&f)
+//
+// for_each_position_around is the walk itself: f(at) for every such position, whatever stands there -- a point's xyz for
+// for_each_candidate_around, the face of a (cell, face) pair for apd_mesh_nearest.hip (contract C27).
+template <typename F> __device__ __forceinline__ void for_each_position_around(const uint64_t *__restrict__ keys, const int cell[3], uint32_t end, F &&f)
 {
     const int lo = -apd_fusion::kVoxelHalf, hi = apd_fusion::kVoxelHalf - 1;
     const int x0 = cell[0] > lo ? cell[0] - 1 : lo, x1 = cell[0] < hi ? cell[0] + 1 : hi;
@@ -132,13 +133,22 @@ __device__ __forceinline__ void for_each_candidate_around(const uint64_t *__rest
             const uint64_t last = apd_fusion::radius_key(x1, cy, cz);
             at = lower_bound(keys, at, end, apd_fusion::radius_key(x0, cy, cz));
             for (; at < end && keys[at] <= last; ++at) {
-                const float Q[3] = {xyz[3 * (size_t)at], xyz[3 * (size_t)at + 1], xyz[3 * (size_t)at + 2]};
-                if (f(at, Q)) {
+                if (f(at)) {
                     return;
                 }
             }
         }
     }
+}
+
+template <typename F>
+__device__ __forceinline__ void for_each_candidate_around(const uint64_t *__restrict__ keys, const float *__restrict__ xyz, const int cell[3], uint32_t end,
+                                                          F &&f)
+{
+    for_each_position_around(keys, cell, end, [&](uint32_t at) {
+        const float Q[3] = {xyz[3 * (size_t)at], xyz[3 * (size_t)at + 1], xyz[3 * (size_t)at + 2]};
+        return f(at, Q);
+    });
 }
 
 template <typename F>

@@ -1003,6 +1003,26 @@ void mesh_and_write(const path &ply_path, const std::vector<Problem> &problems, 
             failed("cannot write " + file.string());
         }
     }
+    if (!clean.score_truth.empty()) {   // --mesh-score: last, the file has its bytes
+        Truth truth;
+        apd_points_score_t s;
+        if (truth.read(clean.score_truth) != APD_OK ||
+            apd_mesh_score(mesh, truth.points, clean.score_threshold, nullptr, clean.score_density, clean.score_seed, &s) != APD_OK) {
+            failed(apd_fusion_last_error());
+        }
+        Report report;
+        report.integer("n_p", s.n_p);
+        report.integer("n_q", s.n_q);
+        report.integer("p_within", s.p_within);
+        report.integer("q_within", s.q_within);
+        report.real("precision", s.precision);
+        report.real("recall", s.recall);
+        report.real("fscore", s.fscore);
+        report.real("mean_p", s.mean_p);
+        report.real("mean_q", s.mean_q);
+        std::cout << "Mesh score against " << clean.score_truth << " at " << clean.score_threshold;
+        report.write(mesh_path + ".score");
+    }
     apd_mesh_destroy(mesh);
     apd_volume_destroy(volume);
     std::cout << "Mesh of " << vertices << " vertices and " << faces << " faces on " << dims[0] << " x " << dims[1] << " x " << dims[2] << " samples in "

@@ -7,7 +7,7 @@
 //       [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN]
 //       [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]]
 //       [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]]
-//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--mesh-recolour [TOL[,MIN_COS]]]
+//       [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--mesh-recolour [TOL[,MIN_COS]]] [--mesh-score TRUTH.ply,TAU[,DENSITY[,SEED]]]
 //
 // --mesh VOXEL[,TRUNC]: besides everything else, APD/APD.ply.mesh: a binary PLY with faces, the marching-tetrahedra mesh of a signed
 // distance volume with samples VOXEL apart and a truncation distance of TRUNC (4 * VOXEL unless given) over the box of the points
@@ -33,6 +33,10 @@
 // mesh, its normal at a cosine above MIN_COS (0.1, in [0, 1)) to the view (apd_mesh_colour_from_views, contract C26) -- and the volume
 // is made without colour and integrated without the images: a third of its memory, the same geometry.  One line tells the vertices
 // and how many no view coloured.  Needs --mesh; a malformed value gives the usage line before anything is read.
+// --mesh-score TRUTH.ply,TAU[,DENSITY[,SEED]]: after everything else of --mesh, and changing no byte of APD.ply.mesh: the final mesh is
+// scored against the vertices of the binary little-endian PLY file TRUTH.ply (apd_points_read_ply) at the threshold TAU
+// (apd_mesh_score, contract C27): precision from DENSITY (4 / TAU^2) points per unit of area drawn on the surface under SEED (0), recall
+// from every truth point's closest point of the surface.  One line in the format of --ply-score, and APD.ply.mesh.score.  Needs --mesh.
 // --mesh-depth-maps: every view's depths_mesh.dmb beside depths_filtered.dmb, in the format of depths.dmb: the depth of the final
 // mesh rasterised into the view, both sides drawn, 0 where it covers nothing (apd_mesh_render).  Needs --mesh.
 //
@@ -351,6 +355,29 @@ bool ParseOptions(int argc, char **argv, Options &o)
             c.recolour = true;
             o.mesh_clean = c;
             mesh_flag = a;
+        } else if (a == "--mesh-score") {
+            const std::string all = i + 1 < argc ? argv[++i] : "";
+            MeshClean c = o.mesh_clean;
+            bool good = false;
+            for (size_t cuts = 3; cuts >= 1 && !good; --cuts) {   // the file's name may hold commas: the most trailing numbers that parse
+                const std::vector<std::string> t = ply_value::Split(all, cuts, true);
+                unsigned long long seed = 0;
+                float density = 0.0f;
+                good = !t.empty() && ply_value::Radius(t[1], c.score_threshold) && (cuts < 2 || (ply_value::Real(t[2], density) && density > 0.0f)) &&
+                       (cuts < 3 || ply_value::Count(t[3], 0, ~0ull, seed));
+                if (good) {
+                    c.score_truth = t[0];
+                    c.score_density = cuts < 2 ? 0.0 : strtod(t[2].c_str(), nullptr);
+                    c.score_seed = seed;
+                }
+            }
+            if (!good) {
+                fprintf(stderr, "bad value '%s' of %s: TRUTH.ply,TAU[,DENSITY[,SEED]], a file, a positive number, a positive number and an integer\n", all.c_str(),
+                        a.c_str());
+                return false;
+            }
+            o.mesh_clean = c;
+            mesh_flag = a;
         } else if (a == "--seed") {
             if (!value(o.seed)) return false;
         } else if (a == "--iters") {
@@ -572,7 +599,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     Options opt;
     if (!ParseOptions(argc, argv, opt)) {
-        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--mesh-recolour [TOL[,MIN_COS]]] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
+        fprintf(stderr, "USAGE: APD dense_folder [gpu_index | gpu,gpu,...] [--seed S] [--iters K] [--single-level] [--max-src N] [--keep-maps] [--no-fusion] [--fusion eth|tat-intermediate|tat-advanced] [--fusion-min-consistent N] [--fusion-reproj PX] [--fusion-depth REL] [--fusion-angle RAD] [--fusion-factors STRONG,WEAK] [--ply-normals] [--ply-vis] [--ply-mean] [--ply-voxel SIZE] [--ply-stat-filter RADIUS,K,RATIO] [--ply-radius-filter RADIUS,MIN] [--ply-component-filter RADIUS,MIN] [--ply-smooth RADIUS,MIN[,ITERATIONS]] [--ply-estimate-normals RADIUS,MIN] [--ply-render-vis SPLAT,TOL] [--ply-register TRUTH.ply,RADIUS,DISTANCE[,TRIALS[,SEED]]] [--ply-align TRUTH.ply,RADIUS[,ITERATIONS[,scale]]] [--ply-align-planes TRUTH.ply,RADIUS[,ITERATIONS]] [--ply-score TRUTH.ply,TAU] [--filtered-maps] [--mesh VOXEL[,TRUNC]] [--mesh-weld TOL] [--mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]] [--mesh-depth-maps] [--mesh-min-component FACES] [--mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]]] [--mesh-simplify CELL[,mean|quadric]] [--mesh-normals] [--mesh-recolour [TOL[,MIN_COS]]] [--mesh-score TRUTH.ply,TAU[,DENSITY[,SEED]]] [--files | --in-memory] [--jacobi] [--ranks N] [--no-rccl] [--rccl] [--masks [DIR]] [--exchange-device-sync] [--late-fusion-inputs] [--copy-images] [--clean-exit]\n"
                         "  --ply-mean: APD.ply with every point's mean position (--ply-normals: and normal) over the views that agree on it; with every --fusion.\n"
                         "      A source that a Tanks and Temples loop counted through a stale entry and the point's own projection does not reach is skipped.\n"
                         "  --ply-voxel SIZE: APD.ply (and APD.ply.vis) with one point per cell of a cubic grid of cell size SIZE, after --ply-mean if both are given.\n"

@@ -15,7 +15,7 @@
 
 // What --mesh does to its mesh between extraction and the file, in this fixed order: apd_mesh_weld, apd_mesh_remove_unseen,
 // apd_mesh_remove_small_components, apd_mesh_smooth, apd_mesh_simplify, apd_mesh_with_vertex_normals, apd_mesh_colour_from_views.  All off: the file has the bytes
-// of the extracted mesh.
+// of the extracted mesh.  --mesh-score comes after the file and changes nothing of it.
 struct MeshClean {
     float weld = 0.0f;                 // --mesh-weld TOL: 0 is off
     unsigned trim = 0;                 // --mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]]: 0 is off
@@ -32,6 +32,10 @@ struct MeshClean {
     bool normals = false;              // --mesh-normals
     bool recolour = false;             // --mesh-recolour [TOL[,MIN_COS]]: the colours from the views' images, not from the volume
     float recolour_tolerance = 0.01f, recolour_min_cos = 0.1f;
+    std::string score_truth;           // --mesh-score TRUTH.ply,TAU[,DENSITY[,SEED]]: the final mesh scored against the cloud of TRUTH.ply; empty is off
+    float score_threshold = 0.0f;
+    double score_density = 0.0;        // 0: apd_mesh_score's own, 4 / TAU^2
+    unsigned long long score_seed = 0;
 };
 
 struct Options {
@@ -61,7 +65,7 @@ struct Options {
     bool filtered_maps = false;           // --filtered-maps: depths_filtered.dmb, consistency.dmb and votes.bin of every view (apd_filter_views)
     float mesh_voxel = 0.0f;              // --mesh VOXEL[,TRUNC]: APD/APD.ply.mesh, the marching-tetrahedra mesh of the filtered maps fused into a signed
     float mesh_trunc = 0.0f;              // distance volume with samples VOXEL apart in the box of the points of APD.ply (apd_volume_*); voxel 0: off
-    MeshClean mesh_clean;                 // --mesh-weld TOL, --mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]], --mesh-depth-maps, --mesh-min-component FACES, --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify CELL[,mean|quadric], --mesh-normals, --mesh-recolour [TOL[,MIN_COS]]: what becomes of that mesh before it is written
+    MeshClean mesh_clean;                 // --mesh-weld TOL, --mesh-trim MIN_VIEWS[,MIN_PIXELS[,TOL]], --mesh-depth-maps, --mesh-min-component FACES, --mesh-smooth ITERATIONS[,LAMBDA[,MU[,fixed|along|free]]], --mesh-simplify CELL[,mean|quadric], --mesh-normals, --mesh-recolour [TOL[,MIN_COS]]: what becomes of that mesh before it is written; --mesh-score TRUTH.ply,TAU[,DENSITY[,SEED]]: its score
     bool fusion_thresholds_set = false;   // one of the five threshold flags was given: the ETH loop only
     bool copy_images = false;         // --copy-images: handles copy and pack their images per (view, pass) instead of sharing the level images (A/B)
     bool clean_exit = false;          // --clean-exit: return from main() instead of _Exit (exit handlers run: profilers)

@@ -898,7 +898,7 @@ def mesh_bounds(bounds):
 
 def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, colour_images=None, block_masks=None, options=None,
          return_mesh=False, weld=None, min_component=None, normals=False, simplify=None, smooth=None, trim=None, depth_maps=False,
-         recolour=None):
+         score=None, recolour=None):
     """A surface from the gathered maps: filter_maps(..., on_device=True) leaves every view's consistent depth map on GPU `device`,
     Volume.integrate fuses them, at each view's depth-map resolution, into a truncated signed distance volume with samples `voxel`
     apart (apd_volume_integrate, contract C21), and Volume.extract_mesh takes the marching-tetrahedra mesh of its zero level, which
@@ -919,8 +919,11 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
     defaults: 0.01 and 0.1): the last step, after the normals: the vertices take their colour from the views' images through the final
     mesh's own z-buffer (contract C26) instead of from the volume, which is then made without colour -- a third of the memory -- and
     integrated without the images; the geometry is the same.  The images go to the device once.
+    score: (truth, threshold[, density[, seed]]) -- after every other step, changes no vertex nor a byte of the file:
+    Mesh.score(truth, threshold, density, seed) of the final mesh against `truth` (a Points: Points.read_ply of a ground truth, or a
+    fusion's), the precision, recall and F-score of the surface at the threshold (contract C27), as fuse(score=...) gives them for points.
     Returns (vertices, faces), the counts, or with return_mesh (vertices, faces, Mesh); with depth_maps the list of the views'
-    rendered depth maps (float32 [h, w]) follows."""
+    rendered depth maps (float32 [h, w]) follows, and with score the Score comes last."""
     from . import Volume
     import torch
     smoothing = tuple(smooth) if isinstance(smooth, (tuple, list)) else (smooth,)
@@ -932,6 +935,9 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
     recolouring = () if recolour is True else tuple(recolour) if isinstance(recolour, (tuple, list)) else (recolour,)
     if recolour is not None and (recolour is False or len(recolouring) not in (0, 2)):
         raise ValueError("mesh: recolour %r, neither True nor (rel_tolerance, min_cos)" % (recolour,))
+    scoring = tuple(score) if isinstance(score, (tuple, list)) else (score,)
+    if score is not None and len(scoring) not in (2, 3, 4):
+        raise ValueError("mesh: score %r, not (truth, threshold[, density[, seed]])" % (score,))
     trunc = 4.0 * float(voxel) if trunc is None else trunc
     if bounds is None:
         _, points = fuse(scene, results, None, device=device, colour_images=colour_images, block_masks=block_masks, options=options, return_points=True)
@@ -972,7 +978,12 @@ def mesh(scene, results, ply_path, voxel, trunc=None, bounds=None, device=0, col
         found.write_ply(ply_path)
     counts = (len(found.vertices), len(found.faces))
     rendered = ([found.render(cam)[0] for cam in cams],) if depth_maps else ()
+    try:
+        scored = () if score is None else (found.score(*scoring),)
+    except Exception:
+        found.close()
+        raise
     if return_mesh:
-        return counts + (found,) + rendered
+        return counts + (found,) + rendered + scored
     found.close()
-    return counts + rendered
+    return counts + rendered + scored

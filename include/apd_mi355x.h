@@ -1193,6 +1193,64 @@ void apd_mesh_render_split(int box_pixels);
 int apd_mesh_colour_from_views(apd_mesh_t mesh, int num_views, const apd_camera *cameras, const float *const *images, int image_channels,
                                int maps_on_device, float rel_tolerance, float min_cos, apd_mesh_t *out, uint32_t *views, long long *uncoloured);
 
+/* apd_mesh_nearest, apd_mesh_sample_points and apd_mesh_score: a mesh related to a cloud -- the closest point of the surface for
+ * every point of a points object, points drawn on the surface uniformly by area, and from the two the precision, recall and F-score
+ * of the surface against a ground-truth cloud, as Tanks and Temples and ETH3D evaluate a surface against a scan.  IEEE operations in
+ * the order given (contract C27; csrc/apd_mesh_nearest_math.h).  Like the other mesh calls they leave their inputs as they
+ * are, are functions of the inputs alone (two runs write the same bytes) and have no host implementation; they run on the mesh's
+ * device, on its null stream.  A host-resident points object goes up for the call; a device-resident one must live on the mesh's
+ * device (APD_ERR_UNSUPPORTED otherwise, before any device is touched).
+ *   apd_mesh_nearest.  Grid: that of apd_points_neighbour_counts, cell size `radius` at origin3 (NULL: 0, 0, 0).  Face f is a
+ *   candidate of point i of p when its three indices are distinct, its nine coordinates are finite and inside the grid, the binary64
+ *   squared length of (b - a) x (c - a) is > 0, the point is inside the grid, and the binary64 squared distance d2 from the point to
+ *   its closest point X on the face is <= (double)radius * (double)radius.  X is the Voronoi-region method of Ericson, Real-Time
+ *   Collision Detection 5.1.5 -- the vertex regions a, b, c, the edge regions ab, ac, bc and the interior, in that order -- in binary64
+ *   on the binary32 inputs widened, every dot product (x * x' + y * y') + z * z', and X held inside the face's bounding box.  The nearest face is the candidate of least d2,
+ *   among equal d2 the one of smallest index: a point over a shared edge or vertex has one answer.  distance[i] = (float)sqrt(d2),
+ *   face[i] = that face, closest3[3 i ..] = X rounded to binary32; without a candidate +inf, -1 and three NaNs.  The definition does
+ *   not depend on how the search is organised: a loop over all faces gives the same bits.  Each output takes apd_points_count(p)
+ *   entries (closest3 three times as many), host memory for a host-resident p, device memory on its device otherwise; any may be
+ *   NULL, not all.  A p without points gives nothing with no device touched; a mesh without faces gives +inf, -1 and NaN throughout.
+ *   The search puts every face into each cell of the grid that its bounding box overlaps and walks, per point, the 27 cells around
+ *   it; a side of the box whose corner stands within binary32 rounding of a cell boundary takes one cell more, so that the cells,
+ *   which are binary32 quotients, cannot hide a face that is within the radius (csrc/apd_mesh_nearest_math.h has the bound).  The work
+ *   is the number of (cell, face) pairs, one sort of them, and the pairs in the 27 cells of every point.  A radius far
+ *   below the size of the faces makes the pairs many: when they reach 2^31 the call is refused with APD_ERR_UNSUPPORTED after the
+ *   counting pass, the message names their number (a lower bound: one face counts for at most 2^31), the radius and the remedy --
+ *   a larger radius, or apd_mesh_simplify / a subdivision elsewhere.  apd_mesh_nearest_pair_limit sets another limit (at most 2^31;
+ *   0 restores it): it exists for a test of that refusal.  apd_fusion_last_timing reports the pair build, the two sorts and the search.
+ *   apd_mesh_sample_points.  *out is a new points object (released with apd_points_destroy) in device memory on the mesh's device
+ *   (on_device != 0) or in host memory, with apd_points_read_ply's convention: one view of 1 x 1 pixels without sources; support,
+ *   view, pixel and sources are 0.  A face with a repeated index, a non-finite coordinate or a cross product of squared length not
+ *   > 0 gets no sample; any other face f gets n_f = floor(area_f * density + u(seed, f)) of them, area_f = 0.5 * sqrt(|(b - a) x
+ *   (c - a)|^2) in binary64 and u in [0, 1): stochastic rounding, so that the expected total is density * area and a mesh of faces
+ *   far smaller than 1 / density is still sampled.  u and the two numbers r1, r2 of sample k of face f come from a counter-based
+ *   generator, two splitmix64 finalisers on (seed, f) and (k, c), the top 53 bits scaled by 2^-53; r1 + r2 > 1 folds them to 1 - r1
+ *   and 1 - r2.  Position a + r1 (b - a) + r2 (c - a) in binary64 rounded to binary32; normal the unit face normal (not the
+ *   vertex normals); colour the barycentric mix of the corners' colours rounded half up per channel, 0 for a mesh without colours.
+ *   Order: faces ascending, k ascending within a face.  face (host, may be NULL): one entry per sample, the face it lies on.  A
+ *   function of (mesh, density, seed) alone; no floating-point sum decides a position.
+ *   apd_mesh_score.  Fills the struct of apd_points_score at radius = threshold.  Precision side: the samples of
+ *   apd_mesh_sample_points(mesh, density, seed) against `truth` by apd_points_nearest's search (n_p = the samples, p_within those with a
+ *   point of truth within the threshold, mean_p their mean distance).  Recall side: `truth` against the surface by apd_mesh_nearest
+ *   (n_q, q_within, mean_q): exact, it does not depend on the sampling.  density <= 0: 4 / (threshold * threshold) in binary64, about four
+ *   samples per threshold-sized square.  Of the distances only the binary64 chunk sums leave the device.  As for apd_points_score there
+ *   is no cropping volume and no occlusion-aware evaluation: scores of two runs compare with each other.
+ * Refused with APD_ERR_INVALID before any device is touched, message "apd_mesh_nearest: ...", "apd_mesh_sample_points: ..." or
+ * "apd_mesh_score: ..." (apd_fusion_last_error): a NULL mesh, p, truth or out, all three outputs NULL, what apd_points_nearest refuses
+ * for the radius (the threshold) and origin3, a density that is not positive and finite (apd_mesh_score: not finite).
+ * APD_ERR_UNSUPPORTED: 2^31 or more points, the pair limit, and samples that would reach 2^31 (known after the scan of the counts,
+ * before they are allocated).  A refused call has written no output: the pair limit is held before the first of them is filled.  A
+ * HIP error in the middle of apd_mesh_nearest (APD_ERR_HIP) may leave device-resident outputs holding the fill values +inf, -1 and NaN.
+ * apd_mesh_device: the device the mesh lives on, where these calls compute and device-resident samples live; -1 for a NULL mesh. */
+int apd_mesh_device(apd_mesh_t mesh);
+int apd_mesh_nearest(apd_mesh_t mesh, apd_points_t p, float radius, const float *origin3, float *distance, int32_t *face, float *closest3);
+void apd_mesh_nearest_pair_limit(long long pairs);
+int apd_mesh_sample_points(apd_mesh_t mesh, double density, unsigned long long seed, int on_device, apd_points_t *out,
+                           int32_t *face /* may be NULL; host, one per sample */);
+int apd_mesh_score(apd_mesh_t mesh, apd_points_t truth, float threshold, const float *origin3,
+                   double density /* <= 0: 4 / (threshold * threshold) in binary64 */, unsigned long long seed, apd_points_score_t *out);
+
 /* apd_fuse_views_variant(options->variant, ...) with options.  ply_path and points may each be NULL, not both: a file, the
  * points in memory (*points, released with apd_points_destroy; untouched when the call fails), or both from one fusion.  With
  * ply_normals the file has the properties x y z nx ny nz (float) before the three colour bytes.  Refused with APD_ERR_INVALID
